@@ -3,6 +3,7 @@ reference (oracle/_ref/libcabac_ref.so, build container only) and random op/reco
 
 The oracle and the reference harness are TEST INFRASTRUCTURE; product code never loads them."""
 import ctypes
+import hashlib
 import os
 import subprocess
 import tempfile
@@ -362,30 +363,37 @@ def load_ref():
     return _ref
 
 
-HOST_ABI_DEPS = [os.path.join(ROOT, "entropy_coding_amd", "host", "cabac_hip_host.hpp"),
-                 os.path.join(ROOT, "entropy_coding_amd", "host", "cabac_rem_abs.hpp"),
-                 os.path.join(ROOT, "include", "cabac_hip.h"), os.path.join(ROOT, "integration", "reference_adapter.hpp"),
-                 os.path.join(ROOT, "integration", "reference_adapter_test.cpp"), os.path.join(ROOT, "oracle", "ref_rig.hpp"),
-                 os.path.join(ROOT, "oracle", "ref_harness.cpp")]
+def ref_library_current(so):
+    """True when every file of this repository that oracle/Makefile compiled `so` against still has the content it had then
+    (the `sha256sum` list written beside the library when it was linked)."""
+    try:
+        lines = open(so + ".sha256").read().splitlines()
+    except OSError:
+        return False
+    for line in lines:
+        digest, path = line.split(None, 1)
+        path = os.path.join(ORACLE_DIR, path.lstrip("*"))
+        if not os.path.exists(path) or hashlib.sha256(open(path, "rb").read()).hexdigest() != digest:
+            return False
+    return bool(lines)
 
 
 def ref_test_library(name):
     """Path of oracle/_ref/<name>, built by oracle/Makefile from the reference's sources and this repo's host headers.  A copy
-    that is older than those headers lays the shim's classes out differently from libcabac_hip.so and corrupts memory without a
-    diagnostic (the SIGABRT of round 2, a segfault in round 3): where the reference's sources are present
-    it is rebuilt, elsewhere (the GPU box, which runs the prebuilt file) a stale one fails the test instead of running."""
+    compiled against other host headers lays the shim's classes out differently from libcabac_hip.so and corrupts memory
+    without a diagnostic (the SIGABRT of round 2, a segfault in round 3): where the reference's sources
+    are present it is rebuilt; where only the prebuilt file is, a stale one fails the test instead of running."""
     import pytest
     so = os.path.join(ORACLE_DIR, "_ref", name)
     if not os.path.exists(so):
         pytest.skip("oracle/_ref/%s not built" % name)
-    deps = HOST_ABI_DEPS[-2:] if name.startswith("libcabac_ref") else HOST_ABI_DEPS   # the reference alone: harness + rig only
-    newest = max(os.path.getmtime(p) for p in deps if os.path.exists(p))
-    if os.path.getmtime(so) < newest:
-        if os.path.isdir("/root/reference/src"):
+    if not ref_library_current(so):
+        if subprocess.run(["make", "-s", "-C", ORACLE_DIR, "has-ref"], stderr=subprocess.DEVNULL).returncode == 0:
+            os.remove(so)
             subprocess.check_call(["make", "-C", ORACLE_DIR, "-j8", "all"], stdout=subprocess.DEVNULL)
-        if os.path.getmtime(so) < newest:
-            pytest.fail("oracle/_ref/%s is older than the host headers it was compiled from: run `make -C oracle` in the build "
-                        "container before sending the tree to the GPU box" % name)
+        if not ref_library_current(so):
+            pytest.fail("oracle/_ref/%s was compiled against other host headers than this tree's: run `make -C oracle` where "
+                        "the reference's sources are" % name)
     return so
 
 

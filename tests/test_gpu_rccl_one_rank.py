@@ -19,7 +19,7 @@ def test_bench_through_rccl_with_one_rank(mode):
     env = dict(os.environ, CABAC_BENCH_DIST_ONE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29541 + (mode == "strong")),
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     cmd = [sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "1", "--workload", "C3", "--steps", "1", "--warmup", "1",
-           "--no-cpu-baseline", "--no-end-to-end", "--no-co-scheduled", "--no-residual"]
+           "--full", "--no-cpu-baseline", "--no-end-to-end", "--no-co-scheduled", "--no-residual"]
     if mode == "strong":
         cmd.append("--strong")
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)

@@ -22,7 +22,7 @@ def adp():
     if not SAN:
         from entropy_coding_amd import capi
         capi.load_library()
-    so = SAN or H.ref_test_library("libadapter_test.so")   # rebuilt, or refused, when it is older than the host headers
+    so = SAN or H.ref_test_library("libadapter_test.so")   # rebuilt, or refused, when compiled against other host headers
     cwd = os.getcwd()
     os.chdir(tempfile.mkdtemp(prefix="cabac_ref_"))   # reference log.cpp:3-4 creates bin_log.txt/bit_log.txt in CWD
     try:

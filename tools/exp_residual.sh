@@ -8,7 +8,7 @@ from entropy_coding_amd.build import build_library
 build_library(force=True)
 " > /dev/null 2>&1
   echo "== flags: $f"
-  CABAC_EXTRA_FLAGS="$f" python3 bench.py --no-cpu-baseline --no-end-to-end --no-co-scheduled --steps 2 --warmup 1 2>/dev/null | python3 -c "
+  CABAC_EXTRA_FLAGS="$f" python3 bench.py --full --no-cpu-baseline --no-end-to-end --no-co-scheduled --steps 2 --warmup 1 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(d['residual']['kernel_ms'], d['residual']['records_match_reference'])
