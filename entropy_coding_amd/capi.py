@@ -44,6 +44,10 @@ EXPORTS = [
     "cabac_hip_encode_batch_residual16", "cabac_hip_decode_batch_packed", "cabac_hip_residual_parse16_device",
     "cabac_hip_residual_parse_batch16", "cabac_hip_gather_records_device",
 ]
+# include/cabac_hip_estimate.h (the fused residual estimator; tests/test_residual_estimate_abi.py compares that header with this list)
+EXPORTS_ESTIMATE = [
+    "cabac_hip_estimate_residual_device", "cabac_hip_estimate_residual16_device", "cabac_hip_estimate_residual_batch",
+]
 
 _lib = None
 vp = ctypes.c_void_p
@@ -125,6 +129,10 @@ def load_library():
     L.cabac_hip_estimate_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
     L.cabac_hip_estimate_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp]
     L.cabac_hip_estimate_from_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+    L.cabac_hip_estimate_residual_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.cabac_hip_estimate_residual16_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.cabac_hip_estimate_residual_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, ctypes.c_uint64, vp, vp,
+                                                    ctypes.c_uint32, vp, vp, vp, vp]
     L.cabac_hip_profile_enable.argtypes = [vp, ctypes.c_uint32]
     L.cabac_hip_profile_read.argtypes = [vp, vp, vp, ctypes.c_uint32]
     L.cabac_hip_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(vp)]
@@ -253,7 +261,8 @@ class CabacHip:
         self._prof_cap = capacity
 
     def profile_read(self):
-        """[(kind, ms)] of the device calls since the last read; kind 0 encode, 1 decode, 2 binarize."""
+        """[(kind, ms)] of the device calls since the last read; kind 0 encode, 1 decode, 2 binarize, ..., 12 residual estimate
+        (the list is at cabac_hip_profile_read in include/cabac_hip.h; 12 in cabac_hip_estimate.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -340,6 +349,41 @@ class CabacHip:
                                              bits.ctypes.data, flags.ctypes.data)
         self._check(rc, allow_substream=not check)
         return bits[: len(desc)], flags[: len(desc)]
+
+    def estimate_residual_device(self, n_cand, d_cand_first, d_tu, d_coeff, d_state, d_rate, d_set, d_frac_bits, d_tu_frac_bits=0,
+                                 d_tu_info=0, int16=False):
+        """cabac_hip_estimate_residual_device (int16: cabac_hip_estimate_residual16_device): coefficient blocks -> fractional
+        bits.  Candidate c = blocks d_cand_first[c] .. d_cand_first[c + 1] - 1 costed in order from context set d_set[c];
+        d_frac_bits[c] (uint64) = cost in 1/32768 bit, d_tu_frac_bits / d_tu_info (optional) per block."""
+        self._check((self.L.cabac_hip_estimate_residual16_device if int16 else self.L.cabac_hip_estimate_residual_device)(
+            self.h, n_cand, vp(d_cand_first), vp(d_tu), vp(d_coeff), vp(d_state), vp(d_rate), vp(d_set), vp(d_frac_bits),
+            vp(d_tu_frac_bits) if d_tu_frac_bits else None, vp(d_tu_info) if d_tu_info else None))
+
+    def estimate_residual_batch(self, cand_first, tus, coeff, state, rate, sets, int16=False, with_blocks=False, check=True):
+        """Host arrays through cabac_hip_estimate_residual_batch (synchronous).  state / rate: (n_sets, 379) context sets in
+        the format of ctx_init_device; sets[c]: the set candidate c starts from.  Returns frac_bits uint64[n_cand], with
+        with_blocks also (tu_frac_bits uint64[n_tu], tu_info uint32[n_tu]).  check=False: an empty block or a bad
+        descriptor does not raise (tu_info says which)."""
+        cand_first = np.ascontiguousarray(cand_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        coeff = np.ascontiguousarray(coeff, np.int16 if int16 else np.int32)
+        state = np.ascontiguousarray(state, np.uint32).reshape(-1)
+        rate = np.ascontiguousarray(rate, np.uint8).reshape(-1)
+        sets = np.ascontiguousarray(sets, np.uint32)
+        n_cand = len(cand_first) - 1
+        assert n_cand >= 0 and len(sets) == n_cand and len(state) == len(rate) and len(state) % NUM_CTX == 0
+        bits = np.zeros(max(n_cand, 1), np.uint64)
+        tu_bits = np.zeros(max(len(tus), 1), np.uint64)
+        info = np.zeros(max(len(tus), 1), np.uint32)
+        rc = self.L.cabac_hip_estimate_residual_batch(self.h, n_cand, cand_first.ctypes.data, tus.ctypes.data, coeff.ctypes.data,
+                                                      2 if int16 else 4, len(coeff), state.ctypes.data, rate.ctypes.data,
+                                                      len(state) // NUM_CTX, sets.ctypes.data, bits.ctypes.data,
+                                                      tu_bits.ctypes.data if with_blocks else None,
+                                                      info.ctypes.data if with_blocks else None)
+        self._check(rc, allow_substream=not check)
+        if with_blocks:
+            return bits[:n_cand], tu_bits[: len(tus)], info[: len(tus)]
+        return bits[:n_cand]
 
     def binarize_device(self, n_sub, d_se_offset, d_se, d_rec_offset, d_n_records, d_records):
         self._check(self.L.cabac_hip_binarize_device(self.h, n_sub, vp(d_se_offset), vp(d_se), vp(d_rec_offset),

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "cabac_hip.h"
+#include "cabac_hip_estimate.h"
 #include "cabac_kernels.h"
 
 #ifdef CABAC_PARSE_PROFILE
@@ -40,8 +41,8 @@ struct cabac_hip_ctx {
   uint32_t prof_n = 0;
   // device staging for the host-pointer entry points (grown on demand)
   // [5]: scratch of the residual binariser, [6]: compacted payload, [7]: payload offsets; [8..]: the spliced-residual path
-  // (kSp* below)
-  static constexpr int kSlots = 24;
+  // (kSp* below); [24..]: the fused residual estimator (kEst* below)
+  static constexpr int kSlots = 33;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -1260,6 +1261,107 @@ int cabac_hip_encode_batch_residual16(cabac_hip_ctx *c, uint32_t n_sub, const ca
 }
 
 // ---- pinned host memory for the caller's buffers ------------------------------------------------------------
+// ---- fused residual estimator (cabac_residual_estimate.hip) -------------------------------------------------------
+namespace {
+// device slots: the candidate order, and the staging of the host-pointer form
+enum { kEstScratch = 24, kEstInFirst = 25, kEstInTu = 26, kEstInCoeff = 27, kEstInState = 28, kEstInRate = 29, kEstInSet = 30,
+       kEstOutBits = 31, kEstOutInfo = 32 };
+}  // namespace
+
+static int estimate_residual_device_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
+                                         const void *d_coeff, int coeff_bytes, const uint32_t *d_state, const uint8_t *d_rate,
+                                         const uint32_t *d_set, uint64_t *d_frac_bits, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info) {
+  if (!c || (n_cand && (!d_cand_first || !d_tu || !d_coeff || !d_state || !d_rate || !d_set || !d_frac_bits)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_cand == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  if (int rc = ensure(c, kEstScratch, cabac::residual_estimate_scratch_bytes(n_cand))) return rc;
+  Bracket br = bracket_for(c, 12);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_residual_estimate(c->stream, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state, d_rate, d_set,
+                                             d_frac_bits, d_tu_frac_bits, d_tu_info, c->d_buf[kEstScratch]));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_estimate_residual_device(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
+                                       const int32_t *d_coeff, const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_set,
+                                       uint64_t *d_frac_bits, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info) {
+  return estimate_residual_device_impl(c, n_cand, d_cand_first, d_tu, d_coeff, 4, d_state, d_rate, d_set, d_frac_bits, d_tu_frac_bits,
+                                       d_tu_info);
+}
+
+int cabac_hip_estimate_residual16_device(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
+                                         const int16_t *d_coeff, const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_set,
+                                         uint64_t *d_frac_bits, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info) {
+  return estimate_residual_device_impl(c, n_cand, d_cand_first, d_tu, d_coeff, 2, d_state, d_rate, d_set, d_frac_bits, d_tu_frac_bits,
+                                       d_tu_info);
+}
+
+int cabac_hip_estimate_residual_batch(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus,
+                                      const void *coeff, int coeff_bytes, uint64_t n_coeff_total, const uint32_t *state,
+                                      const uint8_t *rate, uint32_t n_sets, const uint32_t *set, uint64_t *frac_bits,
+                                      uint64_t *tu_frac_bits, uint32_t *tu_info) {
+  if (!c || (n_cand && (!cand_first || !state || !rate || !set || !frac_bits))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_cand == 0) return CABAC_HIP_OK;
+  for (uint32_t k = 0; k < n_cand; k++) {
+    if (cand_first[k] > cand_first[k + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "cand_first is not non-decreasing");
+    if (set[k] >= n_sets) return fail(c, CABAC_HIP_ERR_INVALID, "set out of range");
+  }
+  const uint32_t n_tu = cand_first[n_cand];
+  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  for (uint32_t t = cand_first[0]; t < n_tu; t++) {
+    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, reads nothing
+    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
+    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
+  }
+  DeviceGuard g(c->device);
+  int rc;
+  const size_t set_words = size_t(n_sets) * CABAC_NUM_CONTEXTS;
+  if ((rc = ensure(c, kEstInFirst, (size_t(n_cand) + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kEstInTu, size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
+  if ((rc = ensure(c, kEstInCoeff, n_coeff_total * size_t(coeff_bytes)))) return rc;
+  if ((rc = ensure(c, kEstInState, set_words * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kEstInRate, set_words))) return rc;
+  if ((rc = ensure(c, kEstInSet, size_t(n_cand) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kEstOutBits, (size_t(n_cand) + n_tu) * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kEstOutInfo, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  uint64_t *d_bits = static_cast<uint64_t *>(c->d_buf[kEstOutBits]), *d_tu_bits = d_bits + n_cand;
+  uint32_t *d_info = static_cast<uint32_t *>(c->d_buf[kEstOutInfo]);
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInFirst], cand_first, (size_t(n_cand) + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  if (n_tu) HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInTu], tus, size_t(n_tu) * sizeof(cabac_tu_desc), hipMemcpyHostToDevice, c->stream));
+  if (n_coeff_total)
+    HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInState], state, set_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInRate], rate, set_words, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInSet], set, size_t(n_cand) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  if (n_tu) {  // blocks no candidate owns keep a defined value
+    HIP_TRY(c, hipMemsetAsync(d_tu_bits, 0, size_t(n_tu) * sizeof(uint64_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_info, 0, size_t(n_tu) * sizeof(uint32_t), c->stream));
+  }
+  rc = estimate_residual_device_impl(c, n_cand, (const uint32_t *)c->d_buf[kEstInFirst], (const cabac_tu_desc *)c->d_buf[kEstInTu],
+                                     c->d_buf[kEstInCoeff], coeff_bytes, (const uint32_t *)c->d_buf[kEstInState],
+                                     (const uint8_t *)c->d_buf[kEstInRate], (const uint32_t *)c->d_buf[kEstInSet], d_bits, d_tu_bits,
+                                     d_info);
+  if (rc) return rc;
+  std::vector<uint32_t> info(n_tu);
+  HIP_TRY(c, hipMemcpyAsync(frac_bits, d_bits, size_t(n_cand) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  if (n_tu && tu_frac_bits)
+    HIP_TRY(c, hipMemcpyAsync(tu_frac_bits, d_tu_bits, size_t(n_tu) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  if (n_tu) HIP_TRY(c, hipMemcpyAsync(info.data(), d_info, size_t(n_tu) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int status = CABAC_HIP_OK;
+  for (uint32_t t = 0; t < n_tu; t++) {
+    if (tu_info) tu_info[t] = info[t];
+    if (info[t] & (CABAC_TU_INFO_EMPTY | CABAC_TU_INFO_BAD_DESC)) status = CABAC_HIP_ERR_SUBSTREAM;
+  }
+  if (status) c->last_error = "empty block or bad descriptor (see tu_info[])";
+  return status;
+}
+
 int cabac_hip_host_alloc(size_t bytes, void **out) {
   if (!out) return CABAC_HIP_ERR_INVALID;
   *out = nullptr;

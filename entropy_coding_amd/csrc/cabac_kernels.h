@@ -50,6 +50,14 @@ hipError_t launch_residual(hipStream_t st, uint32_t n_tu, const cabac_tu_desc *t
                            const uint64_t *rec_offset, uint32_t *n_records, uint32_t *info, uint16_t *records,
                            void *scratch, bool order_ready = false);
 
+// fused residual estimator (cabac_residual_estimate.hip): candidate c = blocks [cand_first[c], cand_first[c+1]) costed in order from
+// context set start_set[c]; scratch: residual_estimate_scratch_bytes(n_cand) bytes the launch may overwrite (candidate ordering)
+size_t residual_estimate_scratch_bytes(uint32_t n_cand);
+hipError_t launch_residual_estimate(hipStream_t st, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus,
+                                    const void *coeff, int coeff_bytes /* 4 or 2 */, const uint32_t *start_state,
+                                    const uint8_t *start_rate, const uint32_t *start_set, uint64_t *frac_bits,
+                                    uint64_t *tu_frac_bits, uint32_t *tu_info, void *scratch);
+
 // residual parser (cabac_residual.hip): bytes -> coefficient blocks, one substream = blocks [tile_first[s], tile_first[s+1])
 // (cabac_residual_parse.hip); tu_info (may be null): per block scanPosLast | CABAC_TU_INFO_*
 hipError_t launch_residual_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
