@@ -1,4 +1,4 @@
-"""ctypes binding of include/cabac_hip.h — test/bench plumbing; the product is the shared library."""
+"""ctypes binding of include/cabac_hip.h and its extension headers — test/bench plumbing; the product is the shared library."""
 import ctypes
 import sys
 import os
@@ -48,6 +48,14 @@ EXPORTS = [
 EXPORTS_ESTIMATE = [
     "cabac_hip_estimate_residual_device", "cabac_hip_estimate_residual16_device", "cabac_hip_estimate_residual_batch",
 ]
+# include/cabac_hip_nal.h (emulation prevention; tests/test_nal_abi.py compares that header with this list)
+EXPORTS_NAL = [
+    "cabac_hip_nal_escape_bound", "cabac_hip_nal_escape_device", "cabac_hip_nal_unescape_device", "cabac_hip_nal_escape_batch",
+    "cabac_hip_nal_unescape_batch", "cabac_hip_encode_batch_nal",
+]
+NAL_STATUS_DTYPE = np.dtype([("out_bytes", "<u8"), ("n_changed", "<u4"), ("flags", "<u4")])   # cabac_nal_status
+assert NAL_STATUS_DTYPE.itemsize == 16
+NAL_OVERFLOW, NAL_TRAILING_ZERO, NAL_FORBIDDEN, NAL_BAD_ESCAPE, NAL_LOC_OVERFLOW, NAL_INPUT_CLIPPED = 1, 2, 4, 8, 16, 32
 
 _lib = None
 vp = ctypes.c_void_p
@@ -133,6 +141,15 @@ def load_library():
     L.cabac_hip_estimate_residual16_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_estimate_residual_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, ctypes.c_uint64, vp, vp,
                                                     ctypes.c_uint32, vp, vp, vp, vp]
+    L.cabac_hip_nal_escape_bound.restype = ctypes.c_size_t
+    L.cabac_hip_nal_escape_bound.argtypes = [ctypes.c_uint64]
+    L.cabac_hip_nal_escape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
+    L.cabac_hip_nal_unescape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp,
+                                                ctypes.c_uint64, ctypes.c_uint32, vp]
+    L.cabac_hip_nal_escape_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp]
+    L.cabac_hip_nal_unescape_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64,
+                                               ctypes.c_uint32, vp]
+    L.cabac_hip_encode_batch_nal.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp]
     L.cabac_hip_profile_enable.argtypes = [vp, ctypes.c_uint32]
     L.cabac_hip_profile_read.argtypes = [vp, vp, vp, ctypes.c_uint32]
     L.cabac_hip_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(vp)]
@@ -202,6 +219,11 @@ def encode_bound(n_ctx, n_ep, n_trm):
     return load_library().cabac_hip_encode_bound(n_ctx, n_ep, n_trm)
 
 
+def nal_escape_bound(n_bytes):
+    """cabac_hip_nal_escape_bound: the largest escape of n_bytes bytes."""
+    return load_library().cabac_hip_nal_escape_bound(n_bytes)
+
+
 class CabacHip:
     """One codec context = one device + one HIP stream (stream=None: a non-blocking stream of the ctx's own; otherwise the
     caller's stream handle, 0 being the device's default stream).  Raises if there is no GPU (no CPU fallback)."""
@@ -262,7 +284,8 @@ class CabacHip:
 
     def profile_read(self):
         """[(kind, ms)] of the device calls since the last read; kind 0 encode, 1 decode, 2 binarize, ..., 12 residual estimate
-        (the list is at cabac_hip_profile_read in include/cabac_hip.h; 12 in cabac_hip_estimate.h)."""
+        (the list is at cabac_hip_profile_read in include/cabac_hip.h; 12 in cabac_hip_estimate.h; 13 nal escape and 14 nal unescape in
+        cabac_hip_nal.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -488,3 +511,66 @@ class CabacHip:
 
     def ctx_init_device(self, n_sub, d_qp, d_init_id, d_state, d_rate):
         self._check(self.L.cabac_hip_ctx_init_device(self.h, n_sub, vp(d_qp), vp(d_init_id), vp(d_state), vp(d_rate)))
+
+    # ---- emulation prevention (include/cabac_hip_nal.h) ---------------------------------------
+    def nal_escape_device(self, n_seg, d_offsets, d_payload, payload_bytes_max, d_nal, nal_capacity, d_nal_offsets, d_status):
+        """cabac_hip_nal_escape_device: segmented payload -> NAL bytes (03 inserted), entry points and a cabac_nal_status, all in
+        device memory; payload_bytes_max bounds the length d_offsets[n_seg] that only the device reads."""
+        self._check(self.L.cabac_hip_nal_escape_device(self.h, n_seg, vp(d_offsets) if d_offsets else None,
+                                                       vp(d_payload) if d_payload else None, payload_bytes_max,
+                                                       vp(d_nal) if d_nal else None, nal_capacity,
+                                                       vp(d_nal_offsets) if d_nal_offsets else None, vp(d_status)))
+
+    def nal_unescape_device(self, n_seg, d_nal_offsets, d_nal, nal_bytes_max, d_payload, payload_capacity, d_offsets, d_status,
+                            d_locations=0, loc_capacity=0, loc_base=0):
+        """cabac_hip_nal_unescape_device: the inverse; d_locations (optional, uint32): the positions of the removed bytes."""
+        self._check(self.L.cabac_hip_nal_unescape_device(self.h, n_seg, vp(d_nal_offsets) if d_nal_offsets else None,
+                                                         vp(d_nal) if d_nal else None, nal_bytes_max,
+                                                         vp(d_payload) if d_payload else None, payload_capacity,
+                                                         vp(d_offsets) if d_offsets else None,
+                                                         vp(d_locations) if d_locations else None, loc_capacity, loc_base,
+                                                         vp(d_status)))
+
+    def nal_escape_batch(self, offsets, payload, nal):
+        """cabac_hip_nal_escape_batch (host arrays, synchronous): fills `nal` (uint8 array, its size is the capacity; e.g.
+        pinned) and returns (nal_offsets uint64[n_seg + 1], status record of NAL_STATUS_DTYPE)."""
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        payload = np.ascontiguousarray(payload, np.uint8)
+        nal_offsets = np.zeros(len(offsets), np.uint64)
+        status = np.zeros(1, NAL_STATUS_DTYPE)
+        self._check(self.L.cabac_hip_nal_escape_batch(self.h, len(offsets) - 1, offsets.ctypes.data, payload.ctypes.data,
+                                                      nal.ctypes.data, nal.nbytes, nal_offsets.ctypes.data, status.ctypes.data))
+        return nal_offsets, status[0]
+
+    def nal_unescape_batch(self, nal_offsets, nal, payload, locations=None, loc_base=0):
+        """cabac_hip_nal_unescape_batch: fills `payload` (and `locations`, a uint32 array, if given; their sizes are the
+        capacities) and returns (offsets uint64[n_seg + 1], status record)."""
+        nal_offsets = np.ascontiguousarray(nal_offsets, np.uint64)
+        nal = np.ascontiguousarray(nal, np.uint8)
+        offsets = np.zeros(len(nal_offsets), np.uint64)
+        status = np.zeros(1, NAL_STATUS_DTYPE)
+        self._check(self.L.cabac_hip_nal_unescape_batch(self.h, len(nal_offsets) - 1, nal_offsets.ctypes.data, nal.ctypes.data,
+                                                        payload.ctypes.data, payload.nbytes, offsets.ctypes.data,
+                                                        locations.ctypes.data if locations is not None else None,
+                                                        len(locations) if locations is not None else 0, loc_base,
+                                                        status.ctypes.data))
+        return offsets, status[0]
+
+    def encode_batch_nal(self, desc, records, nal, check=True):
+        """cabac_hip_encode_batch_nal: records -> NAL-ready payload in `nal` (uint8 array, e.g. pinned); returns (nal_offsets
+        uint64[n + 1] — the entry points —, results, status record).  A `nal` that is too small raises with status
+        CABAC_HIP_ERR_INVALID; the size needed is then in the error's `nal_status["out_bytes"]`."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        records = np.ascontiguousarray(records, np.uint16)
+        nal_offsets = np.zeros(len(desc) + 1, np.uint64)
+        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
+        status = np.zeros(1, NAL_STATUS_DTYPE)
+        rc = self.L.cabac_hip_encode_batch_nal(self.h, len(desc), desc.ctypes.data, records.ctypes.data, len(records),
+                                               nal.ctypes.data, nal.nbytes, nal_offsets.ctypes.data, res.ctypes.data,
+                                               status.ctypes.data)
+        try:
+            self._check(rc, allow_substream=not check)
+        except CabacHipError as e:
+            e.nal_status = status[0]
+            raise
+        return nal_offsets, res[: len(desc)], status[0]

@@ -18,7 +18,9 @@
 
 #include "cabac_hip.h"
 #include "cabac_hip_estimate.h"
+#include "cabac_hip_nal.h"
 #include "cabac_kernels.h"
+#include "cabac_nal_kernels.h"
 
 #ifdef CABAC_PARSE_PROFILE
 namespace cabac {
@@ -41,8 +43,8 @@ struct cabac_hip_ctx {
   uint32_t prof_n = 0;
   // device staging for the host-pointer entry points (grown on demand)
   // [5]: scratch of the residual binariser, [6]: compacted payload, [7]: payload offsets; [8..]: the spliced-residual path
-  // (kSp* below); [24..]: the fused residual estimator (kEst* below)
-  static constexpr int kSlots = 33;
+  // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below)
+  static constexpr int kSlots = 40;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -1360,6 +1362,182 @@ int cabac_hip_estimate_residual_batch(cabac_hip_ctx *c, uint32_t n_cand, const u
   }
   if (status) c->last_error = "empty block or bad descriptor (see tu_info[])";
   return status;
+}
+
+// ---- emulation prevention (cabac_nal.hip; declared in cabac_hip_nal.h) ---------------------------------------------------
+namespace {
+// device slots: the chunk summaries and scans, and the staging of the host-pointer forms
+enum { kNalScratch = 33, kNalIn = 34, kNalInOff = 35, kNalOut = 36, kNalOutOff = 37, kNalLoc = 38, kNalStatus = 39 };
+
+int check_offsets_host(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t *offsets) {
+  if (offsets[0] != 0) return fail(c, CABAC_HIP_ERR_INVALID, "offsets[0] must be 0");
+  for (uint32_t s = 0; s < n_seg; s++)
+    if (offsets[s] > offsets[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "offsets are not ascending");
+  return CABAC_HIP_OK;
+}
+}  // namespace
+
+size_t cabac_hip_nal_escape_bound(uint64_t n_bytes) { return (size_t)(n_bytes + n_bytes / 2); }
+
+int cabac_hip_nal_escape_device(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t *d_offsets, const uint8_t *d_payload,
+                                uint64_t payload_bytes_max, uint8_t *d_nal, uint64_t nal_capacity, uint64_t *d_nal_offsets,
+                                cabac_nal_status *d_status) {
+  if (!c || !d_status || (n_seg && !d_offsets) || (d_offsets && !d_nal_offsets) || (d_offsets && payload_bytes_max && !d_payload) ||
+      (nal_capacity && !d_nal))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  DeviceGuard g(c->device);
+  if (!d_offsets) {  // n_seg == 0 and no string at all
+    HIP_TRY(c, hipMemsetAsync(d_status, 0, sizeof(cabac_nal_status), c->stream));
+    return CABAC_HIP_OK;
+  }
+  if (int rc = ensure(c, kNalScratch, cabac::nal_scratch_bytes(payload_bytes_max))) return rc;
+  Bracket br = bracket_for(c, 13);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_nal_escape(c->stream, n_seg, d_offsets, d_payload, payload_bytes_max, d_nal, nal_capacity, d_nal_offsets,
+                                      d_status, c->d_buf[kNalScratch]));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_nal_unescape_device(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t *d_nal_offsets, const uint8_t *d_nal,
+                                  uint64_t nal_bytes_max, uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_offsets,
+                                  uint32_t *d_locations, uint64_t loc_capacity, uint32_t loc_base, cabac_nal_status *d_status) {
+  if (!c || !d_status || (n_seg && !d_nal_offsets) || (d_nal_offsets && !d_offsets) || (d_nal_offsets && nal_bytes_max && !d_nal) ||
+      (payload_capacity && !d_payload))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  DeviceGuard g(c->device);
+  if (!d_nal_offsets) {
+    HIP_TRY(c, hipMemsetAsync(d_status, 0, sizeof(cabac_nal_status), c->stream));
+    return CABAC_HIP_OK;
+  }
+  if (int rc = ensure(c, kNalScratch, cabac::nal_scratch_bytes(nal_bytes_max))) return rc;
+  Bracket br = bracket_for(c, 14);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_nal_unescape(c->stream, n_seg, d_nal_offsets, d_nal, nal_bytes_max, d_payload, payload_capacity, d_offsets,
+                                        d_locations, loc_capacity, loc_base, d_status, c->d_buf[kNalScratch]));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_nal_escape_batch(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t *offsets, const uint8_t *payload, uint8_t *nal,
+                               uint64_t nal_capacity, uint64_t *nal_offsets, cabac_nal_status *status) {
+  if (!c || !status || !offsets || !nal_offsets) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (int rc = check_offsets_host(c, n_seg, offsets)) return rc;
+  const uint64_t n = offsets[n_seg];
+  if ((n && !payload) || (nal_capacity && !nal)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  DeviceGuard g(c->device);
+  int rc;
+  const uint64_t cap = std::min<uint64_t>(nal_capacity, cabac_hip_nal_escape_bound(n));   // no result is longer
+  const size_t off_bytes = (size_t(n_seg) + 1) * sizeof(uint64_t);
+  if ((rc = ensure(c, kNalIn, n))) return rc;
+  if ((rc = ensure(c, kNalInOff, off_bytes))) return rc;
+  if ((rc = ensure(c, kNalOut, cap))) return rc;
+  if ((rc = ensure(c, kNalOutOff, off_bytes))) return rc;
+  if ((rc = ensure(c, kNalStatus, sizeof(cabac_nal_status)))) return rc;
+  auto *d_status = static_cast<cabac_nal_status *>(c->d_buf[kNalStatus]);
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kNalInOff], offsets, off_bytes, hipMemcpyHostToDevice, c->stream));
+  if (n) HIP_TRY(c, hipMemcpyAsync(c->d_buf[kNalIn], payload, n, hipMemcpyHostToDevice, c->stream));
+  rc = cabac_hip_nal_escape_device(c, n_seg, (const uint64_t *)c->d_buf[kNalInOff], (const uint8_t *)c->d_buf[kNalIn], n,
+                                   (uint8_t *)c->d_buf[kNalOut], cap, (uint64_t *)c->d_buf[kNalOutOff], d_status);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(status, d_status, sizeof(cabac_nal_status), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(nal_offsets, c->d_buf[kNalOutOff], off_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint64_t got = std::min<uint64_t>(status->out_bytes, cap);
+  if (got) HIP_TRY(c, hipMemcpyAsync(nal, c->d_buf[kNalOut], got, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_nal_unescape_batch(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t *nal_offsets, const uint8_t *nal, uint8_t *payload,
+                                 uint64_t payload_capacity, uint64_t *offsets, uint32_t *locations, uint64_t loc_capacity,
+                                 uint32_t loc_base, cabac_nal_status *status) {
+  if (!c || !status || !offsets || !nal_offsets) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (int rc = check_offsets_host(c, n_seg, nal_offsets)) return rc;
+  const uint64_t n = nal_offsets[n_seg];
+  if ((n && !nal) || (payload_capacity && !payload)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (locations && n && (n - 1) + loc_base > 0xffffffffull)
+    return fail(c, CABAC_HIP_ERR_INVALID, "locations are 32-bit: the NAL string plus loc_base passes 4 GiB");
+  DeviceGuard g(c->device);
+  int rc;
+  const uint64_t cap = std::min<uint64_t>(payload_capacity, n);
+  const uint64_t loc_cap = locations ? std::min<uint64_t>(loc_capacity, n / 3) : 0;   // a removal needs two zeros in front of it
+  const size_t off_bytes = (size_t(n_seg) + 1) * sizeof(uint64_t);
+  if ((rc = ensure(c, kNalIn, n))) return rc;
+  if ((rc = ensure(c, kNalInOff, off_bytes))) return rc;
+  if ((rc = ensure(c, kNalOut, cap))) return rc;
+  if ((rc = ensure(c, kNalOutOff, off_bytes))) return rc;
+  if ((rc = ensure(c, kNalLoc, loc_cap * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kNalStatus, sizeof(cabac_nal_status)))) return rc;
+  auto *d_status = static_cast<cabac_nal_status *>(c->d_buf[kNalStatus]);
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kNalInOff], nal_offsets, off_bytes, hipMemcpyHostToDevice, c->stream));
+  if (n) HIP_TRY(c, hipMemcpyAsync(c->d_buf[kNalIn], nal, n, hipMemcpyHostToDevice, c->stream));
+  // (loc_capacity as the caller gave it: CABAC_NAL_LOC_OVERFLOW is judged against that; no more than loc_cap can occur)
+  rc = cabac_hip_nal_unescape_device(c, n_seg, (const uint64_t *)c->d_buf[kNalInOff], (const uint8_t *)c->d_buf[kNalIn], n,
+                                     (uint8_t *)c->d_buf[kNalOut], cap, (uint64_t *)c->d_buf[kNalOutOff],
+                                     locations ? (uint32_t *)c->d_buf[kNalLoc] : nullptr, locations ? loc_capacity : 0, loc_base,
+                                     d_status);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(status, d_status, sizeof(cabac_nal_status), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(offsets, c->d_buf[kNalOutOff], off_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint64_t got = std::min<uint64_t>(status->out_bytes, cap), got_loc = std::min<uint64_t>(status->n_changed, loc_cap);
+  if (got) HIP_TRY(c, hipMemcpyAsync(payload, c->d_buf[kNalOut], got, hipMemcpyDeviceToHost, c->stream));
+  if (got_loc) HIP_TRY(c, hipMemcpyAsync(locations, c->d_buf[kNalLoc], got_loc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_encode_batch_nal(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                               uint64_t n_records_total, uint8_t *nal, uint64_t nal_capacity, uint64_t *nal_offsets,
+                               cabac_substream_result *results, cabac_nal_status *status) {
+  if (!c || !status || !nal_offsets || (nal_capacity && !nal) || (n_sub && (!desc || !results)) || (n_records_total && !records))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  *status = cabac_nal_status{0, 0, 0};
+  nal_offsets[0] = 0;
+  if (n_sub == 0) return CABAC_HIP_OK;
+  uint64_t slots_end = 0;  // the device-side slots follow the descriptors' byte_offset / byte_capacity, as in cabac_hip_encode_batch_payload
+  for (uint32_t s = 0; s < n_sub; s++) slots_end = std::max<uint64_t>(slots_end, desc[s].byte_offset + desc[s].byte_capacity);
+  int rc = check_desc_host(c, n_sub, desc, n_records_total, slots_end);
+  if (rc) return rc;
+  DeviceGuard g(c->device);
+  // device: [0] descriptors, [1] records, [2] byte slots, [3] results, [6] compacted payload, [7] payload offsets (the slots
+  // of cabac_hip_encode_batch), then the escape's own
+  const size_t off_bytes = (size_t(n_sub) + 1) * sizeof(uint64_t), res_bytes = size_t(n_sub) * sizeof(cabac_substream_result);
+  const uint64_t cap = std::min<uint64_t>(nal_capacity, cabac_hip_nal_escape_bound(slots_end));
+  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, 1, n_records_total * 2))) return rc;
+  if ((rc = ensure(c, 2, slots_end))) return rc;
+  if ((rc = ensure(c, 3, res_bytes))) return rc;
+  if ((rc = ensure(c, 6, slots_end))) return rc;
+  if ((rc = ensure(c, 7, off_bytes))) return rc;
+  if ((rc = ensure(c, kNalOut, cap))) return rc;
+  if ((rc = ensure(c, kNalOutOff, off_bytes))) return rc;
+  if ((rc = ensure(c, kNalStatus, sizeof(cabac_nal_status)))) return rc;
+  auto *d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[0]);
+  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[3]);
+  auto *d_status = static_cast<cabac_nal_status *>(c->d_buf[kNalStatus]);
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc), hipMemcpyHostToDevice, c->stream));
+  if (n_records_total) HIP_TRY(c, hipMemcpyAsync(c->d_buf[1], records, n_records_total * 2, hipMemcpyHostToDevice, c->stream));
+  if ((rc = cabac_hip_encode_device(c, n_sub, d_desc, (const uint16_t *)c->d_buf[1], (uint8_t *)c->d_buf[2], d_res))) return rc;
+  if ((rc = cabac_hip_assemble_device(c, n_sub, d_desc, d_res, (const uint8_t *)c->d_buf[2], (uint8_t *)c->d_buf[6], slots_end,
+                                      (uint64_t *)c->d_buf[7])))
+    return rc;
+  if ((rc = cabac_hip_nal_escape_device(c, n_sub, (const uint64_t *)c->d_buf[7], (const uint8_t *)c->d_buf[6], slots_end,
+                                        (uint8_t *)c->d_buf[kNalOut], cap, (uint64_t *)c->d_buf[kNalOutOff], d_status)))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(status, d_status, sizeof(cabac_nal_status), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(nal_offsets, c->d_buf[kNalOutOff], off_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(results, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (status->out_bytes > nal_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "nal_capacity too small (status->out_bytes is the size needed)");
+  if (status->out_bytes) HIP_TRY(c, hipMemcpyAsync(nal, c->d_buf[kNalOut], status->out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (uint32_t s = 0; s < n_sub; s++)
+    if (results[s].flags) return fail(c, CABAC_HIP_ERR_SUBSTREAM, "substream flag set (see results[].flags)");
+  return CABAC_HIP_OK;
 }
 
 int cabac_hip_host_alloc(size_t bytes, void **out) {
