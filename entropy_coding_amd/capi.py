@@ -53,6 +53,12 @@ EXPORTS_NAL = [
     "cabac_hip_nal_escape_bound", "cabac_hip_nal_escape_device", "cabac_hip_nal_unescape_device", "cabac_hip_nal_escape_batch",
     "cabac_hip_nal_unescape_batch", "cabac_hip_encode_batch_nal",
 ]
+# include/cabac_hip_search.h (search rounds; tests/test_search_abi.py compares that header with this list)
+EXPORTS_SEARCH = [
+    "cabac_hip_estimate_residual_ctx_device", "cabac_hip_estimate_residual_ctx16_device", "cabac_hip_search_select_device",
+    "cabac_hip_search_round_device", "cabac_hip_search_round_batch",
+]
+SEARCH_NO_SET = SEARCH_NONE = 0xFFFFFFFF                        # CABAC_SEARCH_NO_SET, CABAC_SEARCH_NONE
 NAL_STATUS_DTYPE = np.dtype([("out_bytes", "<u8"), ("n_changed", "<u4"), ("flags", "<u4")])   # cabac_nal_status
 assert NAL_STATUS_DTYPE.itemsize == 16
 NAL_OVERFLOW, NAL_TRAILING_ZERO, NAL_FORBIDDEN, NAL_BAD_ESCAPE, NAL_LOC_OVERFLOW, NAL_INPUT_CLIPPED = 1, 2, 4, 8, 16, 32
@@ -141,6 +147,13 @@ def load_library():
     L.cabac_hip_estimate_residual16_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_estimate_residual_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, ctypes.c_uint64, vp, vp,
                                                     ctypes.c_uint32, vp, vp, vp, vp]
+    L.cabac_hip_estimate_residual_ctx_device.argtypes = [vp, ctypes.c_uint32] + [vp] * 12
+    L.cabac_hip_estimate_residual_ctx16_device.argtypes = [vp, ctypes.c_uint32] + [vp] * 12
+    L.cabac_hip_search_select_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp]
+    L.cabac_hip_search_round_device.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp,
+                                                ctypes.c_uint64, vp, vp, vp, vp, vp]
+    L.cabac_hip_search_round_batch.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, ctypes.c_uint64, vp,
+                                               vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp]
     L.cabac_hip_nal_escape_bound.restype = ctypes.c_size_t
     L.cabac_hip_nal_escape_bound.argtypes = [ctypes.c_uint64]
     L.cabac_hip_nal_escape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
@@ -285,7 +298,8 @@ class CabacHip:
     def profile_read(self):
         """[(kind, ms)] of the device calls since the last read; kind 0 encode, 1 decode, 2 binarize, ..., 12 residual estimate
         (the list is at cabac_hip_profile_read in include/cabac_hip.h; 12 in cabac_hip_estimate.h; 13 nal escape and 14 nal unescape in
-        cabac_hip_nal.h)."""
+        cabac_hip_nal.h; 15 residual estimate with contexts, 16 search select, 17 / 18 a round's estimate / commit in
+        cabac_hip_search.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -407,6 +421,68 @@ class CabacHip:
         if with_blocks:
             return bits[:n_cand], tu_bits[: len(tus)], info[: len(tus)]
         return bits[:n_cand]
+
+    # ---- search rounds (include/cabac_hip_search.h) --------------------------------------------
+    def estimate_residual_ctx_device(self, n_cand, d_cand_first, d_tu, d_coeff, d_state, d_rate, d_set, d_frac_bits, d_out_set,
+                                     d_out_state, d_out_rate, d_tu_frac_bits=0, d_tu_info=0, int16=False):
+        """cabac_hip_estimate_residual_ctx_device (int16: _ctx16_device): estimate_residual_device, and candidate c with
+        d_out_set[c] != SEARCH_NO_SET writes the complete context set it leaves as set d_out_set[c] of d_out_state / d_out_rate
+        (which may be d_state / d_rate under the in-place rule of the header)."""
+        self._check((self.L.cabac_hip_estimate_residual_ctx16_device if int16 else self.L.cabac_hip_estimate_residual_ctx_device)(
+            self.h, n_cand, vp(d_cand_first), vp(d_tu), vp(d_coeff), vp(d_state), vp(d_rate), vp(d_set), vp(d_frac_bits),
+            vp(d_tu_frac_bits) if d_tu_frac_bits else None, vp(d_tu_info) if d_tu_info else None, vp(d_out_set), vp(d_out_state),
+            vp(d_out_rate)))
+
+    def search_select_device(self, n_group, d_group_first, d_frac_bits, d_dist, lambda_q16, d_pick, d_cost):
+        """cabac_hip_search_select_device: per group the candidate with the smallest d_dist + ((lambda_q16 * d_frac_bits) >> 31)
+        (d_dist = 0: no distortions) into d_pick (uint32, SEARCH_NONE for a group with nothing to pick) and d_cost (uint64)."""
+        self._check(self.L.cabac_hip_search_select_device(self.h, n_group, vp(d_group_first), vp(d_frac_bits),
+                                                          vp(d_dist) if d_dist else None, lambda_q16, vp(d_pick), vp(d_cost)))
+
+    def search_round_device(self, n_group, d_group_first, n_cand, d_cand_first, d_tu, d_coeff, d_state, d_rate, d_set,
+                            d_group_out_set, d_dist, lambda_q16, d_frac_bits, d_pick, d_cost, d_tu_frac_bits=0, d_tu_info=0,
+                            int16=False):
+        """cabac_hip_search_round_device: estimate, select, commit — the set the picked candidate of group g leaves is written
+        as set d_group_out_set[g] of d_state / d_rate."""
+        self._check(self.L.cabac_hip_search_round_device(
+            self.h, n_group, vp(d_group_first), n_cand, vp(d_cand_first), vp(d_tu), vp(d_coeff), 2 if int16 else 4, vp(d_state),
+            vp(d_rate), vp(d_set), vp(d_group_out_set) if d_group_out_set else None, vp(d_dist) if d_dist else None, lambda_q16,
+            vp(d_frac_bits), vp(d_pick), vp(d_cost), vp(d_tu_frac_bits) if d_tu_frac_bits else None,
+            vp(d_tu_info) if d_tu_info else None))
+
+    def search_round_batch(self, group_first, cand_first, tus, coeff, state, rate, sets, group_out_set, dist, lambda_q16,
+                           int16=False, with_blocks=False, check=True):
+        """Host arrays through cabac_hip_search_round_batch (synchronous).  state / rate: (n_sets, 379) context sets, updated IN
+        PLACE (they must be contiguous uint32 / uint8 arrays); group_out_set / dist may be None.  Returns (frac_bits uint64[n_cand],
+        pick uint32[n_group], cost uint64[n_group]), with with_blocks also (tu_frac_bits, tu_info)."""
+        group_first = np.ascontiguousarray(group_first, np.uint32)
+        cand_first = np.ascontiguousarray(cand_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        coeff = np.ascontiguousarray(coeff, np.int16 if int16 else np.int32)
+        sets = np.ascontiguousarray(sets, np.uint32)
+        assert state.dtype == np.uint32 and rate.dtype == np.uint8 and state.flags.c_contiguous and rate.flags.c_contiguous
+        assert state.size == rate.size and state.size % NUM_CTX == 0
+        n_group, n_cand = len(group_first) - 1, len(cand_first) - 1
+        assert n_group >= 0 and n_cand >= 0 and len(sets) == n_cand
+        out_set = None if group_out_set is None else np.ascontiguousarray(group_out_set, np.uint32)
+        dist = None if dist is None else np.ascontiguousarray(dist, np.uint64)
+        assert (out_set is None or len(out_set) == n_group) and (dist is None or len(dist) == n_cand)
+        bits = np.zeros(max(n_cand, 1), np.uint64)
+        pick = np.zeros(max(n_group, 1), np.uint32)
+        cost = np.zeros(max(n_group, 1), np.uint64)
+        tu_bits = np.zeros(max(len(tus), 1), np.uint64)
+        info = np.zeros(max(len(tus), 1), np.uint32)
+        rc = self.L.cabac_hip_search_round_batch(
+            self.h, n_group, group_first.ctypes.data, n_cand, cand_first.ctypes.data, tus.ctypes.data, coeff.ctypes.data,
+            2 if int16 else 4, len(coeff), state.ctypes.data, rate.ctypes.data, state.size // NUM_CTX, sets.ctypes.data,
+            out_set.ctypes.data if out_set is not None else None, dist.ctypes.data if dist is not None else None, lambda_q16,
+            bits.ctypes.data, pick.ctypes.data, cost.ctypes.data, tu_bits.ctypes.data if with_blocks else None,
+            info.ctypes.data if with_blocks else None)
+        self._check(rc, allow_substream=not check)
+        out = (bits[:n_cand], pick[:n_group], cost[:n_group])
+        if with_blocks:
+            out += (tu_bits[: len(tus)], info[: len(tus)])
+        return out
 
     def binarize_device(self, n_sub, d_se_offset, d_se, d_rec_offset, d_n_records, d_records):
         self._check(self.L.cabac_hip_binarize_device(self.h, n_sub, vp(d_se_offset), vp(d_se), vp(d_rec_offset),

@@ -19,6 +19,7 @@
 #include "cabac_hip.h"
 #include "cabac_hip_estimate.h"
 #include "cabac_hip_nal.h"
+#include "cabac_hip_search.h"
 #include "cabac_kernels.h"
 #include "cabac_nal_kernels.h"
 
@@ -43,8 +44,9 @@ struct cabac_hip_ctx {
   uint32_t prof_n = 0;
   // device staging for the host-pointer entry points (grown on demand)
   // [5]: scratch of the residual binariser, [6]: compacted payload, [7]: payload offsets; [8..]: the spliced-residual path
-  // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below)
-  static constexpr int kSlots = 40;
+  // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
+  // search rounds (kSearch* below)
+  static constexpr int kSlots = 45;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -1538,6 +1540,217 @@ int cabac_hip_encode_batch_nal(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
   for (uint32_t s = 0; s < n_sub; s++)
     if (results[s].flags) return fail(c, CABAC_HIP_ERR_SUBSTREAM, "substream flag set (see results[].flags)");
   return CABAC_HIP_OK;
+}
+
+// ---- search rounds (cabac_search.hip, cabac_residual_estimate.hip; declared in cabac_hip_search.h) -----------------------------
+namespace {
+// device slots: the staging of the host-pointer form (the rest of it goes through the estimator's kEst* slots)
+enum { kSearchInGroupFirst = 40, kSearchInOutSet = 41, kSearchInDist = 42, kSearchOutPick = 43, kSearchOutCost = 44 };
+
+int estimate_residual_ctx_device_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
+                                      const void *d_coeff, int coeff_bytes, const uint32_t *d_state, const uint8_t *d_rate,
+                                      const uint32_t *d_set, uint64_t *d_frac_bits, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info,
+                                      const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate) {
+  if (!c || (n_cand && (!d_cand_first || !d_tu || !d_coeff || !d_state || !d_rate || !d_set || !d_frac_bits || !d_out_set ||
+                        !d_out_state || !d_out_rate)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_cand == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  if (int rc = ensure(c, kEstScratch, cabac::residual_estimate_scratch_bytes(n_cand))) return rc;
+  Bracket br = bracket_for(c, 15);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_residual_estimate_export(c->stream, n_cand, nullptr, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state,
+                                                    d_rate, d_set, d_out_set, d_out_state, d_out_rate, d_frac_bits, d_tu_frac_bits,
+                                                    d_tu_info, c->d_buf[kEstScratch]));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+}  // namespace
+
+int cabac_hip_estimate_residual_ctx_device(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
+                                           const int32_t *d_coeff, const uint32_t *d_state, const uint8_t *d_rate,
+                                           const uint32_t *d_set, uint64_t *d_frac_bits, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info,
+                                           const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate) {
+  return estimate_residual_ctx_device_impl(c, n_cand, d_cand_first, d_tu, d_coeff, 4, d_state, d_rate, d_set, d_frac_bits,
+                                           d_tu_frac_bits, d_tu_info, d_out_set, d_out_state, d_out_rate);
+}
+
+int cabac_hip_estimate_residual_ctx16_device(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
+                                             const int16_t *d_coeff, const uint32_t *d_state, const uint8_t *d_rate,
+                                             const uint32_t *d_set, uint64_t *d_frac_bits, uint64_t *d_tu_frac_bits,
+                                             uint32_t *d_tu_info, const uint32_t *d_out_set, uint32_t *d_out_state,
+                                             uint8_t *d_out_rate) {
+  return estimate_residual_ctx_device_impl(c, n_cand, d_cand_first, d_tu, d_coeff, 2, d_state, d_rate, d_set, d_frac_bits,
+                                           d_tu_frac_bits, d_tu_info, d_out_set, d_out_state, d_out_rate);
+}
+
+int cabac_hip_search_select_device(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *d_group_first, const uint64_t *d_frac_bits,
+                                   const uint64_t *d_dist, uint64_t lambda_q16, uint32_t *d_pick, uint64_t *d_cost) {
+  if (!c || (n_group && (!d_group_first || !d_frac_bits || !d_pick || !d_cost))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_group == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  Bracket br = bracket_for(c, 16);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_search_select(c->stream, n_group, 0xffffffffu, d_group_first, d_frac_bits, d_dist, lambda_q16, d_pick, d_cost));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_search_round_device(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *d_group_first, uint32_t n_cand,
+                                  const uint32_t *d_cand_first, const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes,
+                                  uint32_t *d_state, uint8_t *d_rate, const uint32_t *d_set, const uint32_t *d_group_out_set,
+                                  const uint64_t *d_dist, uint64_t lambda_q16, uint64_t *d_frac_bits, uint32_t *d_pick,
+                                  uint64_t *d_cost, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info) {
+  if (!c || (n_cand && (!d_cand_first || !d_tu || !d_coeff || !d_state || !d_rate || !d_set || !d_frac_bits)) ||
+      (n_group && (!d_group_first || !d_pick || !d_cost)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_cand == 0 && n_group == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  if (int rc = ensure(c, kEstScratch, cabac::residual_estimate_scratch_bytes(std::max(n_cand, n_group)))) return rc;
+  c->timed = false;  // three brackets: read them with cabac_hip_profile_read
+  // estimate: every candidate from its start set; the sets are not modified
+  Bracket br = bracket_for(c, 17);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_residual_estimate(c->stream, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state, d_rate, d_set,
+                                             d_frac_bits, d_tu_frac_bits, d_tu_info, c->d_buf[kEstScratch]));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  if (n_group == 0) return CABAC_HIP_OK;
+  // select
+  br = bracket_for(c, 16);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_search_select(c->stream, n_group, n_cand, d_group_first, d_frac_bits, d_dist, lambda_q16, d_pick, d_cost));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  // commit: the picked candidates walked once more by the exporting kernel (d_pick is its index list, CABAC_SEARCH_NONE is
+  // skipped); the candidate order of the estimate pass is no longer needed, so the scratch is reused
+  br = bracket_for(c, 18);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  if (d_group_out_set && n_cand)
+    HIP_TRY(c, cabac::launch_residual_estimate_export(c->stream, n_group, d_pick, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes,
+                                                      d_state, d_rate, d_set, d_group_out_set, d_state, d_rate, nullptr, nullptr, nullptr,
+                                                      c->d_buf[kEstScratch]));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_search_round_batch(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *group_first, uint32_t n_cand,
+                                 const uint32_t *cand_first, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
+                                 uint64_t n_coeff_total, uint32_t *state, uint8_t *rate, uint32_t n_sets, const uint32_t *set,
+                                 const uint32_t *group_out_set, const uint64_t *dist, uint64_t lambda_q16, uint64_t *frac_bits,
+                                 uint32_t *pick, uint64_t *cost, uint64_t *tu_frac_bits, uint32_t *tu_info) {
+  if (!c || !group_first || !cand_first || (n_cand && (!state || !rate || !set || !frac_bits)) || (n_group && (!pick || !cost)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  for (uint32_t k = 0; k < n_cand; k++) {
+    if (cand_first[k] > cand_first[k + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "cand_first is not non-decreasing");
+    if (set[k] >= n_sets) return fail(c, CABAC_HIP_ERR_INVALID, "set out of range");
+  }
+  for (uint32_t g = 0; g < n_group; g++)
+    if (group_first[g] > group_first[g + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "group_first is not non-decreasing");
+  if (group_first[n_group] != n_cand) return fail(c, CABAC_HIP_ERR_INVALID, "group_first[n_group] must be n_cand");
+  const uint32_t n_tu = cand_first[n_cand];
+  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  for (uint32_t t = cand_first[0]; t < n_tu; t++) {
+    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, reads nothing
+    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
+    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
+  }
+  if (group_out_set) {  // the in-place rule of cabac_hip_search.h
+    std::vector<uint32_t> owner(n_sets, CABAC_SEARCH_NONE);  // set -> the group that writes it
+    for (uint32_t g = 0; g < n_group; g++) {
+      const uint32_t o = group_out_set[g];
+      if (o == CABAC_SEARCH_NO_SET) continue;
+      if (o >= n_sets) return fail(c, CABAC_HIP_ERR_INVALID, "out set out of range");
+      if (owner[o] != CABAC_SEARCH_NONE) return fail(c, CABAC_HIP_ERR_INVALID, "two groups name the same out set");
+      owner[o] = g;
+    }
+    uint32_t g = 0;
+    for (uint32_t k = 0; k < n_cand; k++) {
+      while (g < n_group && group_first[g + 1] <= k) g++;
+      const uint32_t mine = (g < n_group && group_first[g] <= k) ? g : CABAC_SEARCH_NONE;  // candidates before group 0 are in no group
+      const uint32_t w = owner[set[k]];
+      if (w != CABAC_SEARCH_NONE && w != mine) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "in-place rule: set %u is the out set of group %u and the start set of candidate %u of another group",
+                 set[k], w, k);
+        return fail(c, CABAC_HIP_ERR_INVALID, buf);
+      }
+    }
+  }
+  if (n_cand == 0 && n_group == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  int rc;
+  const size_t set_words = size_t(n_sets) * CABAC_NUM_CONTEXTS;
+  if ((rc = ensure(c, kEstInFirst, (size_t(n_cand) + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kEstInTu, size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
+  if ((rc = ensure(c, kEstInCoeff, n_coeff_total * size_t(coeff_bytes)))) return rc;
+  if ((rc = ensure(c, kEstInState, set_words * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kEstInRate, set_words))) return rc;
+  if ((rc = ensure(c, kEstInSet, size_t(n_cand) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kEstOutBits, (size_t(n_cand) + n_tu) * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kEstOutInfo, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kSearchInGroupFirst, (size_t(n_group) + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kSearchInOutSet, size_t(n_group) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kSearchInDist, size_t(n_cand) * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kSearchOutPick, size_t(n_group) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kSearchOutCost, size_t(n_group) * sizeof(uint64_t)))) return rc;
+  uint64_t *d_bits = static_cast<uint64_t *>(c->d_buf[kEstOutBits]), *d_tu_bits = d_bits + n_cand;
+  uint32_t *d_info = static_cast<uint32_t *>(c->d_buf[kEstOutInfo]);
+  auto up = [&](int slot, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(c->d_buf[slot], src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+  };
+  HIP_TRY(c, up(kEstInFirst, cand_first, (size_t(n_cand) + 1) * sizeof(uint32_t)));
+  HIP_TRY(c, up(kEstInTu, tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
+  HIP_TRY(c, up(kEstInCoeff, coeff, n_tu ? n_coeff_total * size_t(coeff_bytes) : 0));
+  HIP_TRY(c, up(kEstInState, state, n_cand ? set_words * sizeof(uint32_t) : 0));
+  HIP_TRY(c, up(kEstInRate, rate, n_cand ? set_words : 0));
+  HIP_TRY(c, up(kEstInSet, set, size_t(n_cand) * sizeof(uint32_t)));
+  HIP_TRY(c, up(kSearchInGroupFirst, group_first, (size_t(n_group) + 1) * sizeof(uint32_t)));
+  if (group_out_set) HIP_TRY(c, up(kSearchInOutSet, group_out_set, size_t(n_group) * sizeof(uint32_t)));
+  if (dist) HIP_TRY(c, up(kSearchInDist, dist, size_t(n_cand) * sizeof(uint64_t)));
+  if (n_tu) {  // blocks no candidate owns keep a defined value
+    HIP_TRY(c, hipMemsetAsync(d_tu_bits, 0, size_t(n_tu) * sizeof(uint64_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_info, 0, size_t(n_tu) * sizeof(uint32_t), c->stream));
+  }
+  rc = cabac_hip_search_round_device(c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand,
+                                     (const uint32_t *)c->d_buf[kEstInFirst], (const cabac_tu_desc *)c->d_buf[kEstInTu],
+                                     c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState], (uint8_t *)c->d_buf[kEstInRate],
+                                     (const uint32_t *)c->d_buf[kEstInSet],
+                                     group_out_set ? (const uint32_t *)c->d_buf[kSearchInOutSet] : nullptr,
+                                     dist ? (const uint64_t *)c->d_buf[kSearchInDist] : nullptr, lambda_q16, d_bits,
+                                     (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info);
+  if (rc) return rc;
+  std::vector<uint32_t> info(n_tu);
+  auto down = [&](void *dst, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  };
+  HIP_TRY(c, down(frac_bits, d_bits, size_t(n_cand) * sizeof(uint64_t)));
+  if (tu_frac_bits) HIP_TRY(c, down(tu_frac_bits, d_tu_bits, size_t(n_tu) * sizeof(uint64_t)));
+  HIP_TRY(c, down(info.data(), d_info, size_t(n_tu) * sizeof(uint32_t)));
+  HIP_TRY(c, down(pick, c->d_buf[kSearchOutPick], size_t(n_group) * sizeof(uint32_t)));
+  HIP_TRY(c, down(cost, c->d_buf[kSearchOutCost], size_t(n_group) * sizeof(uint64_t)));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // the written sets: those of the groups that picked a candidate
+  if (group_out_set && n_cand) {
+    for (uint32_t k = 0; k < n_group; k++) {
+      const uint32_t o = group_out_set[k];
+      if (o == CABAC_SEARCH_NO_SET || pick[k] == CABAC_SEARCH_NONE) continue;
+      const size_t at = size_t(o) * CABAC_NUM_CONTEXTS;
+      HIP_TRY(c, down(state + at, (const uint32_t *)c->d_buf[kEstInState] + at, CABAC_NUM_CONTEXTS * sizeof(uint32_t)));
+      HIP_TRY(c, down(rate + at, (const uint8_t *)c->d_buf[kEstInRate] + at, CABAC_NUM_CONTEXTS));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  int status = CABAC_HIP_OK;
+  for (uint32_t t = 0; t < n_tu; t++) {
+    if (tu_info) tu_info[t] = info[t];
+    if (info[t] & (CABAC_TU_INFO_EMPTY | CABAC_TU_INFO_BAD_DESC)) status = CABAC_HIP_ERR_SUBSTREAM;
+  }
+  if (status) c->last_error = "empty block or bad descriptor (see tu_info[])";
+  return status;
 }
 
 int cabac_hip_host_alloc(size_t bytes, void **out) {

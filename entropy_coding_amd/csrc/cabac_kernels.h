@@ -58,6 +58,21 @@ hipError_t launch_residual_estimate(hipStream_t st, uint32_t n_cand, const uint3
                                     const uint8_t *start_rate, const uint32_t *start_set, uint64_t *frac_bits,
                                     uint64_t *tu_frac_bits, uint32_t *tu_info, void *scratch);
 
+// the exporting variant (cabac_hip_search.h): walks the n_item candidates index[0 .. n_item) (index null: n_item == n_cand, every
+// candidate; an entry >= n_cand is skipped) and writes the contexts item i leaves as set out_set[i] (0xffffffff: none) of
+// out_state / out_rate, which may be the start arrays; frac_bits may be null here.  scratch: residual_estimate_scratch_bytes(n_item)
+hipError_t launch_residual_estimate_export(hipStream_t st, uint32_t n_item, const uint32_t *index, uint32_t n_cand,
+                                           const uint32_t *cand_first, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
+                                           const uint32_t *start_state, const uint8_t *start_rate, const uint32_t *start_set,
+                                           const uint32_t *out_set, uint32_t *out_state, uint8_t *out_rate, uint64_t *frac_bits,
+                                           uint64_t *tu_frac_bits, uint32_t *tu_info, void *scratch);
+
+// search rounds (cabac_search.hip): per group g = candidates [group_first[g], group_first[g+1]) (clipped to
+// min(group_first[n_group], n_cand_max)) the index and the value of the smallest dist + ((lambda_q16 * frac_bits) >> 31)
+hipError_t launch_search_select(hipStream_t st, uint32_t n_group, uint32_t n_cand_max, const uint32_t *group_first,
+                                const uint64_t *frac_bits, const uint64_t *dist /* may be null */, uint64_t lambda_q16, uint32_t *pick,
+                                uint64_t *cost);
+
 // residual parser (cabac_residual.hip): bytes -> coefficient blocks, one substream = blocks [tile_first[s], tile_first[s+1])
 // (cabac_residual_parse.hip); tu_info (may be null): per block scanPosLast | CABAC_TU_INFO_*
 hipError_t launch_residual_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,

@@ -26,6 +26,10 @@
 //
 // Reads 4 (2) B per coefficient plus template re-reads that hit L1 / L2, and the touched part of the start context set
 // per candidate (L2); writes 8 B per candidate (+ 12 B per block when the per-block outputs are asked for).  No MFMA.
+//
+// The exporting variant (kExport, cabac_hip_search.h) is the same walk over a list of candidates, which at its end unpacks
+// the row's context store into the set the candidate leaves (1.9 KB: 379 x 4 B states + 379 rate bytes): what a search
+// round commits for the candidate it picked.  The estimator's own entry points instantiate the kernel without it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -54,6 +58,13 @@ __device__ __forceinline__ uint64_t est_row_sum64(uint64_t v) {  // sum over the
   }
   return v;
 }
+
+struct EstExport {        // what the exporting variant of the kernel needs on top (all null / unused otherwise)
+  const uint32_t *index;    // item -> candidate (null: the identity)
+  const uint32_t *out_set;  // per item: the set to write, 0xffffffff = none
+  uint32_t *out_state;
+  uint8_t *out_rate;
+};
 
 struct EstRow {          // what a plane step needs of its row
   uint32_t *ctx;         // the row's context store (LDS)
@@ -185,21 +196,25 @@ __device__ __forceinline__ void est_cand_range(const uint32_t *cand_first, uint3
 
 // Ordering pre-pass (the idea of class_hist / class_scatter, cabac_residual.hip): the rows of a wave run as long as the
 // longest of them, so candidates are handed out by the log2 of their total group count, largest first.
-__global__ __launch_bounds__(256) void est_class_hist(uint32_t n_cand, const uint32_t *__restrict__ cand_first,
+// `index` (may be null): the pass orders the n_item candidates index[0 .. n_item) instead of candidates 0 .. n_cand - 1 (then
+// n_item == n_cand); an entry that names no candidate (>= n_cand) has no blocks.
+__global__ __launch_bounds__(256) void est_class_hist(uint32_t n_item, uint32_t n_cand, const uint32_t *__restrict__ index,
+                                                       const uint32_t *__restrict__ cand_first,
                                                        const cabac_tu_desc *__restrict__ tus, uint32_t *__restrict__ scratch) {
   __shared__ uint32_t h[kEstClasses];
   if (threadIdx.x < kEstClasses) h[threadIdx.x] = 0;
   __syncthreads();
   const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-  if (c < n_cand) {
-    uint32_t first, end, groups = 0;
-    est_cand_range(cand_first, n_cand, c, first, end);
+  if (c < n_item) {
+    uint32_t first = 0, end = 0, groups = 0;
+    const uint32_t cand = index ? index[c] : c;
+    if (cand < n_cand) est_cand_range(cand_first, n_cand, cand, first, end);
     for (uint32_t t = first; t < end; t++) {
       const uint64_t hi = reinterpret_cast<const uint64_t *>(tus)[2u * (uint64_t)t + 1u];  // log2_width, log2_height: its low bytes
       groups += est_groups((uint32_t)hi & 0xffu, (uint32_t)(hi >> 8) & 0xffu);
     }
     const uint32_t cls = groups ? min(32u - (uint32_t)__builtin_clz(groups), kEstClasses - 1u) : 0u;
-    scratch[kEstHeader + n_cand + c] = cls;
+    scratch[kEstHeader + n_item + c] = cls;
     atomicAdd(&h[cls], 1u);
   }
   __syncthreads();
@@ -226,14 +241,19 @@ __global__ __launch_bounds__(256) void est_class_scatter(uint32_t n_cand, uint32
   if (c < n_cand) scratch[kEstHeader + start[cls] + rank] = c;
 }
 
-template <class C>
-__global__ __launch_bounds__(256) void residual_estimate_kernel(uint32_t n_cand, const uint32_t *__restrict__ cand_first,
+// kExport: the variant that also writes the context set a candidate leaves (cabac_hip_search.h).  It walks the n_item
+// ITEMS of ex: item i is candidate ex.index[i] (i itself without an index; an entry >= n_cand is skipped) and writes its
+// final contexts as set ex.out_set[i] of ex.out_state / ex.out_rate, which may be the start arrays: every read of the start
+// set that feeds the walk happens before the __syncthreads() below, every store after the walk.  So the start arrays are not
+// __restrict__ here.  Without kExport n_item == n_cand, ex is not read and the code is the one the estimator always ran.
+template <class C, bool kExport>
+__global__ __launch_bounds__(256) void residual_estimate_kernel(uint32_t n_item, uint32_t n_cand, const uint32_t *__restrict__ cand_first,
                                                                  const cabac_tu_desc *__restrict__ tus, const C *__restrict__ coeff_all,
-                                                                 const uint32_t *__restrict__ start_state,
-                                                                 const uint8_t *__restrict__ start_rate,
+                                                                 const uint32_t *start_state, const uint8_t *start_rate,
                                                                  const uint32_t *__restrict__ start_set,
                                                                  const uint32_t *__restrict__ order, uint64_t *__restrict__ frac_bits,
-                                                                 uint64_t *__restrict__ tu_frac_bits, uint32_t *__restrict__ tu_info) {
+                                                                 uint64_t *__restrict__ tu_frac_bits, uint32_t *__restrict__ tu_info,
+                                                                 EstExport ex) {
   __shared__ uint32_t ctx_all[kEstRows * kEstCtxStride];
   __shared__ uint32_t frac[512];
   __shared__ uint32_t match_all[4 * kEstMatchWords];
@@ -242,8 +262,9 @@ __global__ __launch_bounds__(256) void residual_estimate_kernel(uint32_t n_cand,
   for (uint32_t k = threadIdx.x; k < 512u; k += 256u) frac[k] = c_est_frac_bits[k];
 
   const uint32_t slot = blockIdx.x * kEstRows + (threadIdx.x >> 4);
-  const uint32_t cand = slot < n_cand ? order[slot] : 0xffffffffu;
-  const bool has_cand = cand < n_cand;
+  const uint32_t item = slot < n_item ? order[slot] : 0xffffffffu;
+  const uint32_t cand = (kExport && ex.index && item < n_item) ? ex.index[item] : item;
+  const bool has_cand = item < n_item && cand < n_cand;
   uint32_t t = 0, t_end = 0;
   if (has_cand) est_cand_range(cand_first, n_cand, cand, t, t_end);
 
@@ -258,7 +279,7 @@ __global__ __launch_bounds__(256) void residual_estimate_kernel(uint32_t n_cand,
   // (m_state[0] | m_state[1] << 16, m_rate = 16 * rate0 + rate1).  Only what residual coding can touch is brought in:
   // SigCoeffGroup .. LastY (86..291), TransformSkipFlag (310, 311) and the transform-skip residual sets (357..378).
   if (l == 0u) r.ctx[kNumCtx] = 0u;
-  if (has_cand && t < t_end) {
+  if (has_cand && (kExport || t < t_end)) {
     const uint64_t set = (uint64_t)start_set[cand] * (uint64_t)kNumCtx;
     auto bring = [&](uint32_t k) {
       const uint32_t st = start_state[set + k], rt = start_rate[set + k];
@@ -608,31 +629,78 @@ __global__ __launch_bounds__(256) void residual_estimate_kernel(uint32_t n_cand,
     cand_total += blk ? share : 0ull;
     t += blk ? 1u : 0u;
   }
-  if (has_cand && l == 0u) frac_bits[cand] = cand_total;
+  if (has_cand && l == 0u && (!kExport || frac_bits)) frac_bits[cand] = cand_total;
+
+  // ---- the contexts the candidate leaves: the row's store unpacked into the format it was brought in from, and what
+  // residual coding cannot touch copied from the start set (the row's own lanes wrote the store: one wave, LDS in order)
+  if constexpr (kExport) {
+    const uint32_t oset = has_cand ? ex.out_set[item] : 0xffffffffu;
+    if (oset != 0xffffffffu) {
+      const uint64_t src = (uint64_t)start_set[cand] * (uint64_t)kNumCtx, dst = (uint64_t)oset * (uint64_t)kNumCtx;
+      for (uint32_t k = l; k < (uint32_t)kNumCtx; k += 16u) {
+        const bool held = (k >= 86u && k < 292u) || k == 310u || k == 311u || k >= 357u;
+        uint32_t st, rt;
+        if (held) {
+          const uint32_t w = r.ctx[k];
+          st = w & (kMask0 | 0xffff0000u);
+          rt = (((w & 3u) + 2u) << 4) | (((w >> 2) & 7u) + 5u);
+        } else {
+          st = start_state[src + k];
+          rt = start_rate[src + k];
+        }
+        ex.out_state[dst + k] = st;
+        ex.out_rate[dst + k] = (uint8_t)rt;
+      }
+    }
+  }
 }
 
 size_t residual_estimate_scratch_bytes(uint32_t n_cand) { return sizeof(uint32_t) * (kEstHeader + 2u * (size_t)n_cand); }
+
+namespace {
+
+template <bool kExport>
+hipError_t launch_estimate_items(hipStream_t st, uint32_t n_item, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus,
+                                 const void *coeff, int coeff_bytes, const uint32_t *start_state, const uint8_t *start_rate,
+                                 const uint32_t *start_set, uint64_t *frac_bits, uint64_t *tu_frac_bits, uint32_t *tu_info,
+                                 void *scratch, const EstExport &ex) {
+  if (n_item == 0) return hipSuccess;
+  if (coeff_bytes != 4 && coeff_bytes != 2) return hipErrorInvalidValue;
+  uint32_t *s32 = static_cast<uint32_t *>(scratch);
+  hipError_t e = hipMemsetAsync(s32, 0, sizeof(uint32_t) * kEstHeader, st);
+  if (e != hipSuccess) return e;
+  const dim3 sort_grid((n_item + 255u) / 256u), grid((n_item + kEstRows - 1u) / kEstRows);
+  hipLaunchKernelGGL(est_class_hist, sort_grid, dim3(256), 0, st, n_item, n_cand, ex.index, cand_first, tus, s32);
+  hipLaunchKernelGGL(est_class_scatter, sort_grid, dim3(256), 0, st, n_item, s32);
+  const uint32_t *order = s32 + kEstHeader;
+  if (coeff_bytes == 2)
+    hipLaunchKernelGGL((residual_estimate_kernel<int16_t, kExport>), grid, dim3(256), 0, st, n_item, n_cand, cand_first, tus,
+                       static_cast<const int16_t *>(coeff), start_state, start_rate, start_set, order, frac_bits, tu_frac_bits, tu_info,
+                       ex);
+  else
+    hipLaunchKernelGGL((residual_estimate_kernel<int32_t, kExport>), grid, dim3(256), 0, st, n_item, n_cand, cand_first, tus,
+                       static_cast<const int32_t *>(coeff), start_state, start_rate, start_set, order, frac_bits, tu_frac_bits, tu_info,
+                       ex);
+  return hipGetLastError();
+}
+
+}  // namespace
 
 hipError_t launch_residual_estimate(hipStream_t st, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus,
                                     const void *coeff, int coeff_bytes, const uint32_t *start_state, const uint8_t *start_rate,
                                     const uint32_t *start_set, uint64_t *frac_bits, uint64_t *tu_frac_bits, uint32_t *tu_info,
                                     void *scratch) {
-  if (n_cand == 0) return hipSuccess;
-  if (coeff_bytes != 4 && coeff_bytes != 2) return hipErrorInvalidValue;
-  uint32_t *s32 = static_cast<uint32_t *>(scratch);
-  hipError_t e = hipMemsetAsync(s32, 0, sizeof(uint32_t) * kEstHeader, st);
-  if (e != hipSuccess) return e;
-  const dim3 sort_grid((n_cand + 255u) / 256u), grid((n_cand + kEstRows - 1u) / kEstRows);
-  hipLaunchKernelGGL(est_class_hist, sort_grid, dim3(256), 0, st, n_cand, cand_first, tus, s32);
-  hipLaunchKernelGGL(est_class_scatter, sort_grid, dim3(256), 0, st, n_cand, s32);
-  const uint32_t *order = s32 + kEstHeader;
-  if (coeff_bytes == 2)
-    hipLaunchKernelGGL(residual_estimate_kernel<int16_t>, grid, dim3(256), 0, st, n_cand, cand_first, tus,
-                       static_cast<const int16_t *>(coeff), start_state, start_rate, start_set, order, frac_bits, tu_frac_bits, tu_info);
-  else
-    hipLaunchKernelGGL(residual_estimate_kernel<int32_t>, grid, dim3(256), 0, st, n_cand, cand_first, tus,
-                       static_cast<const int32_t *>(coeff), start_state, start_rate, start_set, order, frac_bits, tu_frac_bits, tu_info);
-  return hipGetLastError();
+  return launch_estimate_items<false>(st, n_cand, n_cand, cand_first, tus, coeff, coeff_bytes, start_state, start_rate, start_set,
+                                      frac_bits, tu_frac_bits, tu_info, scratch, EstExport{nullptr, nullptr, nullptr, nullptr});
+}
+
+hipError_t launch_residual_estimate_export(hipStream_t st, uint32_t n_item, const uint32_t *index, uint32_t n_cand,
+                                           const uint32_t *cand_first, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
+                                           const uint32_t *start_state, const uint8_t *start_rate, const uint32_t *start_set,
+                                           const uint32_t *out_set, uint32_t *out_state, uint8_t *out_rate, uint64_t *frac_bits,
+                                           uint64_t *tu_frac_bits, uint32_t *tu_info, void *scratch) {
+  return launch_estimate_items<true>(st, n_item, n_cand, cand_first, tus, coeff, coeff_bytes, start_state, start_rate, start_set,
+                                     frac_bits, tu_frac_bits, tu_info, scratch, EstExport{index, out_set, out_state, out_rate});
 }
 
 }  // namespace cabac
