@@ -726,9 +726,13 @@ __global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, 
   d.look = 16;
   d.rp = 4u;
   d.range = 510u;
-  uint32_t flags_out = 0;
+  // A substream that begins with the byte 0xFF is not one the arithmetic coder wrote: its first nine bits are the coder's
+  // value, which is below the initial range 510.  Decoding it would leave value >= range << 7, a state in which the
+  // reference's arithmetic and this one's part ways, so it is refused as a whole: no block is parsed, BAD_STOP.
+  const bool bad_start = d.cap >= 2u && (rl(d.in_cur, 0u) >> 24) == 0xffu;
+  uint32_t flags_out = bad_start ? CABAC_RES_BAD_STOP : 0u;
 
-  const uint32_t t_end = tile_first[sub + 1];
+  const uint32_t t_end = bad_start ? tile_first[sub] : tile_first[sub + 1];
   PP_TICK(k0);
   for (uint32_t t = tile_first[sub]; t < t_end; t++) {
     PP_TICK(b0);
@@ -801,7 +805,9 @@ __global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, 
 
   // encodeBinTrm(1) closes the substream (cabac_writer.cpp:104-107); decodeBinTrm, arith_codec.cpp:181-197
   uint32_t trm = 1;
-  const bool finish = (dsc.init_id & CABAC_SUB_FINISH) && !flags_out;
+  // (not after a refused block or a refused start: the parse stopped before the end of the substream.  CABAC_RES_RANGE does
+  // not stop anything.)
+  const bool finish = (dsc.init_id & CABAC_SUB_FINISH) && !(flags_out & (CABAC_RES_BAD_RECORD | CABAC_RES_BAD_STOP));
   if (finish) {
     pd_check(d);
     const uint32_t range = rfl(d.range) - 2u, hi = rfl(d.hi);
@@ -819,7 +825,8 @@ __global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, 
   const uint32_t bytes_read = 2u + (shifts >> 3);
   const int32_t bits_needed = (int32_t)(shifts & 7u) - 8;
   if (bytes_read > d.cap) {
-    flags_out |= CABAC_RES_UNDERRUN;  // an underrun throws before finish() is reached
+    // an underrun throws before finish() is reached — and before a block behind it could be refused: reported alone
+    flags_out = (flags_out & CABAC_RES_RANGE) | CABAC_RES_UNDERRUN;
   } else if (finish) {
     // finish(), arith_codec.cpp:68-73: the last byte read holds the stop bit where the decoder stands
     const uint32_t lastb = src[bytes_read - 1u];

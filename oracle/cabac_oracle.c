@@ -1408,8 +1408,10 @@ long orc_residual_records(int lw, int lh, int chroma, unsigned flags, int max_lo
  * descriptor's CABAC_TU_TRANSFORM_SKIP bit is then ignored); without it the descriptor's bit decides (BDPCM blocks: the
  * reference infers the flag).  info[t] (may be NULL): scanPosLast | CABAC_TU_INFO_MTS_VIOLATION for a regular block,
  * CABAC_TU_INFO_TS for a block parsed as transform skip.
- * Returns 0; -2 unsupported block (bad size, transform skip wider/taller than 32); -4 read past the end; -5 missing
- * terminate bin / stop pattern. */
+ * Returns 0; -2 unsupported block (bad size or max_log2_tr_range, transform skip wider/taller than 32; the parse stops there); -4 read past
+ * the end (checked after every block, the parse stops there; it also takes precedence over -5, as the reference's
+ * readByte throws before the terminate bin or finish() can be judged); -5 missing terminate bin / stop pattern.
+ * Defined for arbitrary input bytes: past the end zeros are read.  n_bits_read is set on every return. */
 static int parse_block_ts(bin_dec *d, const blk_geom *g, const uint32_t *scan, int bdpcm, int max_log2, int32_t *coeff) {
 #define SX(p) ((int)(scan[p] & 0xffff))
 #define SY(p) ((int)(scan[p] >> 16))
@@ -1507,13 +1509,13 @@ static int parse_block(bin_dec *d, const cabac_tu_desc *tu, int32_t *coeff, uint
   const int lw = tu->log2_width, lh = tu->log2_height, chroma = tu->channel;
   const unsigned flags = tu->flags;
   const int max_log2 = tu->max_log2_tr_range ? tu->max_log2_tr_range : 15;
-  if (lw > 6 || lh > 6 || chroma > 1) return -2;
+  if (lw > 6 || lh > 6 || chroma > 1 || max_log2 < 15 || max_log2 > 20) return -2;
   blk_geom g;
   blk_geom_init(&g, lw, lh);
   /* ts_flag, cabac_reader.cpp:2737-2752 */
   unsigned ts = (flags & CABAC_TU_TRANSFORM_SKIP) != 0;
   if (flags & CABAC_TU_TS_FLAG) ts = dec_bin(d, CABAC_CTX_TRANSFORM_SKIP_FLAG(chroma));
-  if (ts && (lw > 5 || lh > 5)) return -2;
+  if (ts && (lw > 5 || lh > 5)) return d->underrun ? -4 : -2; /* the flag's own read threw first */
   uint32_t *scan = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)(g.w * g.h));
   orc_scan_order(lw, lh, scan);
 #define SX(p) ((int)(scan[p] & 0xffff))
@@ -1662,15 +1664,27 @@ int orc_residual_decode(const uint8_t *in, long n_in, int qp, int init_id, const
   d.n_in = n_in;
   ctx_store_init(&d.ctx, qp, init_id);
   dec_start(&d);
+  if (!d.underrun && d.value >= (510u << 7)) {
+    /* first byte 0xFF: not a stream of the arithmetic coder (its first nine bits are the coder's value, below the initial
+     * range).  The reference does not check and decodes on with value >= range << 7; this parser and the device refuse the
+     * substream as a whole (include/cabac_hip_parse.h). */
+    if (n_bits_read) *n_bits_read = (uint32_t)(8 * d.idx + d.bits_needed);
+    return -5;
+  }
   for (long t = 0; t < n_tu; t++) {
     const int rc = parse_block(&d, &tus[t], coeff_out + tus[t].coeff_offset, info ? &info[t] : NULL);
-    if (rc) return rc;
+    if (rc) { /* bits read up to the stop (after an underrun: counting the bytes that were not there) */
+      if (n_bits_read) *n_bits_read = (uint32_t)(8 * d.idx + d.bits_needed);
+      return rc;
+    }
   }
   int rc = 0;
   if (finish) {
-    if (dec_trm(&d) != 1) rc = -5;
-    if (!rc && d.underrun) rc = -4;
-    if (!rc) rc = dec_finish(&d);
+    /* readByte throws where it runs out (bit_stream.cpp:268-274), also inside decodeBinTrm: the underrun comes first */
+    const unsigned trm = dec_trm(&d);
+    if (d.underrun) rc = -4;
+    else if (trm != 1) rc = -5;
+    else rc = dec_finish(&d);
   }
   if (n_bits_read) *n_bits_read = (uint32_t)(8 * d.idx + d.bits_needed);
   if (!rc && d.underrun) rc = -4;

@@ -247,11 +247,16 @@ class CodecLib:
         return out[:n].copy(), info
 
     def residual_decode(self, data, qp, blocks_meta, finish=True, with_info=False):
-        """blocks_meta: [(w, h, chroma, flags)] -> (rc, [coefficient blocks (h, w)], n_bits_read[, info]).
+        """blocks_meta: [(w, h, chroma, flags[, max_log2_tr_range])] -> (rc, [coefficient blocks (h, w)], n_bits_read[, info]).
+        max_log2_tr_range (0 or absent: 15) goes into the block's descriptor; the compiled reference's rig has no such knob and
+        refuses anything but 15.
         info: per block CABAC_TU_INFO_* as the device parser reports it (scanPosLast | MTS violation, or TS); for the
         compiled reference it is put together from the TransformUnit / CUCtx the reader leaves behind."""
         data = np.ascontiguousarray(data, np.uint8)
         i32p = ctypes.POINTER(ctypes.c_int32)
+        blocks_meta = [tuple(m) for m in blocks_meta]
+        ranges = [m[4] if len(m) > 4 else 0 for m in blocks_meta]
+        blocks_meta = [m[:4] for m in blocks_meta]
         total = sum(w * h for w, h, _, _ in blocks_meta)
         out = np.full(max(total, 1), 0x5A5A5A5A, np.int32)
         nbits = ctypes.c_uint32(0)
@@ -261,7 +266,7 @@ class CodecLib:
             off = 0
             for i, (w, h, ch, fl) in enumerate(blocks_meta):
                 tus[i]["coeff_offset"], tus[i]["log2_width"], tus[i]["log2_height"] = off, int(np.log2(w)), int(np.log2(h))
-                tus[i]["channel"], tus[i]["flags"] = ch, fl
+                tus[i]["channel"], tus[i]["flags"], tus[i]["max_log2_tr_range"] = ch, fl, ranges[i]
                 off += w * h
             info = np.zeros(max(n, 1), np.uint32)
             f = self.lib.orc_residual_decode
@@ -272,6 +277,7 @@ class CodecLib:
                    ctypes.byref(nbits), _ptr(info, u32p))
             info = info[:n]
         else:
+            assert all(r in (0, 15) for r in ranges), "the reference rig parses with max_log2_tr_range 15 only"
             # rig flags (oracle/ref_rig.hpp): bit0 dep_quant, bit1 sign hiding, bit2 transform skip enabled (flag coded),
             # bit4 the block is transform-skip coded, bit5 BDPCM
             rig = np.array([(fl & 3) | (4 if fl & TU_TS_FLAG else 0) | (0x10 if fl & TU_TRANSFORM_SKIP else 0) |

@@ -22,16 +22,23 @@ def hip(request):
     c.close()
 
 
-def build(rng, n_sub, flags_of, qps, max_blocks=12):
-    """n_sub substreams of random blocks -> (metas per substream, blocks per substream, bytes per substream)."""
+def random_regular(rng):
+    """A regular block of any shape up to 64 x 64 -> (w, h, coefficients)."""
+    w, h = SHAPES[int(rng.integers(0, len(SHAPES)))]
+    return w, h, H.random_block(rng, w, h, density=float(rng.choice([0.05, 0.3, 0.7, 1.0])), big=float(rng.choice([0.0, 0.05, 0.3])),
+                                huge=0.02 if rng.random() < 0.1 else 0.0, last_frac=float(rng.choice([1.0, 0.5, 0.2])))
+
+
+def build(rng, n_sub, flags_of, qps, max_blocks=12, n_blocks=None):
+    """n_sub substreams of random blocks (1..max_blocks each, or n_blocks) -> (metas per substream, blocks per substream,
+    bytes per substream)."""
     orc = H.load_oracle()
     subs = []
     for s in range(n_sub):
         blocks, metas = [], []
-        for k in range(int(rng.integers(1, max_blocks + 1))):
-            w, h = SHAPES[int(rng.integers(0, len(SHAPES)))]
-            blocks.append(H.random_block(rng, w, h, density=float(rng.choice([0.05, 0.3, 0.7, 1.0])), big=float(rng.choice([0.0, 0.05, 0.3])),
-                                         huge=0.02 if rng.random() < 0.1 else 0.0, last_frac=float(rng.choice([1.0, 0.5, 0.2]))))
+        for k in range(n_blocks if n_blocks else int(rng.integers(1, max_blocks + 1))):
+            w, h, c = random_regular(rng)
+            blocks.append(c)
             metas.append((w, h, int(rng.integers(0, 2)), flags_of(s)))
         rec = np.concatenate([orc.residual_records(c, metas[i][2], metas[i][3])[0] for i, c in enumerate(blocks)] + [np.array([0x81FF], np.uint16)])
         data, _ = orc.encode_records(rec, int(qps[s]), 2, 3)
@@ -39,15 +46,38 @@ def build(rng, n_sub, flags_of, qps, max_blocks=12):
     return subs
 
 
-def parse(hip, subs, qps, capacities=None, finish=True, mutate=None):
-    import torch
+def packed_layout(metas):
+    """coeff_offset of every block when the blocks lie back to back in list order -> (offsets, total)."""
+    sizes = np.array([m[0] * m[1] for m in metas], np.int64)
+    return np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64) if len(sizes) else np.zeros(0, np.int64), int(sizes.sum())
+
+
+def scattered_layout(rng, metas, pad=37):
+    """The blocks placed in a random order with 0..7 untouched elements between neighbours (so offsets are odd as often as
+    even) and `pad` + 0..7 elements in front of the first and behind the last -> (offsets, total)."""
+    offsets = np.zeros(len(metas), np.int64)
+    at = pad + int(rng.integers(0, 8))
+    for i in rng.permutation(len(metas)):
+        offsets[i] = at
+        at += metas[i][0] * metas[i][1] + int(rng.integers(0, 8))
+    return offsets, at + pad + int(rng.integers(0, 8))
+
+
+def sentinel(narrow):
+    """What parse() fills the coefficient buffer with before the parser runs."""
+    return 0x5A5A if narrow else 0x5A5A5A5A
+
+
+def pack(subs, qps, capacities=None, finish=True, layout=None):
+    """The host arrays of a parser call (see parse()) -> (desc, bytes, tile_first, tus, coeff_offset per block, elements in all)."""
     n_sub = len(subs)
     metas = [m for s in subs for m in s[0]]
-    tus = np.zeros(len(metas), H.TU_DTYPE)
-    off = 0
-    for i, (w, h, ch, fl) in enumerate(metas):
-        tus[i]["coeff_offset"], tus[i]["log2_width"], tus[i]["log2_height"], tus[i]["channel"], tus[i]["flags"] = off, int(np.log2(w)), int(np.log2(h)), ch, fl
-        off += w * h
+    offsets, total = packed_layout(metas) if layout is None else layout
+    tus = np.zeros(max(len(metas), 1), H.TU_DTYPE)
+    for i, m in enumerate(metas):
+        w, h, ch, fl = m[:4]
+        tus[i]["coeff_offset"], tus[i]["log2_width"], tus[i]["log2_height"], tus[i]["channel"], tus[i]["flags"] = int(offsets[i]), int(np.log2(w)), int(np.log2(h)), ch, fl
+        tus[i]["max_log2_tr_range"] = m[4] if len(m) > 4 else 0
     tile_first = np.concatenate([[0], np.cumsum([len(s[0]) for s in subs])]).astype(np.uint32)
     desc = np.zeros(n_sub, H.DESC_DTYPE)
     caps = np.array([len(s[2]) for s in subs], np.uint64) if capacities is None else np.asarray(capacities, np.uint64)
@@ -55,10 +85,22 @@ def parse(hip, subs, qps, capacities=None, finish=True, mutate=None):
     desc["byte_offset"] = np.concatenate([[0], np.cumsum(slots)[:-1]])
     desc["byte_capacity"] = caps
     desc["qp"] = qps
-    desc["init_id"] = 2 | (H.SUB_FINISH if finish else 0)
+    desc["init_id"] = 2 | np.where(np.broadcast_to(np.asarray(finish, bool), (n_sub,)), H.SUB_FINISH, 0).astype(np.uint32)
     buf = np.zeros(int(slots.sum()), np.uint8)
     for s in range(n_sub):
         buf[int(desc["byte_offset"][s]): int(desc["byte_offset"][s]) + len(subs[s][2])] = subs[s][2]
+    return desc, buf, tile_first, tus, offsets, total
+
+
+def parse(hip, subs, qps, capacities=None, finish=True, mutate=None, layout=None, raw=False):
+    """subs[s] = (metas, blocks, bytes), metas = [(w, h, channel, flags[, max_log2_tr_range])] — possibly none: a substream of
+    zero blocks.  finish: CABAC_SUB_FINISH for all substreams or one value each.  layout = (coeff_offset per block, elements in
+    all): where the blocks lie in the coefficient buffer (default: back to back from 0); the buffer is filled with sentinel()
+    first.  -> (blocks per substream, results), and with raw=True also the whole coefficient buffer as it came back."""
+    import torch
+    n_sub = len(subs)
+    metas = [m for s in subs for m in s[0]]
+    desc, buf, tile_first, tus, offsets, total = pack(subs, qps, capacities, finish, layout)
     if mutate:
         mutate(buf, desc)
     t_desc = torch.from_numpy(desc.view(np.uint8).copy()).cuda()
@@ -66,7 +108,7 @@ def parse(hip, subs, qps, capacities=None, finish=True, mutate=None):
     t_first = torch.from_numpy(tile_first.view(np.int32).copy()).cuda()
     t_tu = torch.from_numpy(tus.view(np.uint8).reshape(-1).copy()).cuda()
     narrow = getattr(hip, "parse_int16", False)
-    t_co = torch.full((max(off, 1),), 0x5A5A, dtype=torch.int16, device="cuda") if narrow else torch.full((max(off, 1),), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    t_co = torch.full((max(total, 1),), sentinel(narrow), dtype=torch.int16 if narrow else torch.int32, device="cuda")
     t_res = torch.full((2 * n_sub,), -1, dtype=torch.int32, device="cuda")
     t_info = torch.full((max(len(metas), 1),), -1, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
@@ -77,13 +119,16 @@ def parse(hip, subs, qps, capacities=None, finish=True, mutate=None):
     co = t_co.cpu().numpy()
     co = co.astype(np.int32)
     res = t_res.cpu().numpy().view(H.RESULT_DTYPE)
-    out, o = [], 0
+    out, t = [], 0
     for s in subs:
         blocks = []
-        for (w, h, _, _) in s[0]:
-            blocks.append(co[o:o + w * h].reshape(h, w))
-            o += w * h
+        for m in s[0]:
+            w, h = m[0], m[1]
+            blocks.append(co[int(offsets[t]): int(offsets[t]) + w * h].reshape(h, w))
+            t += 1
         out.append(blocks)
+    if raw:
+        return out, res, co
     return out, res
 
 

@@ -80,3 +80,28 @@ def test_reference_adapter_under_asan_ubsan():
     subprocess.check_call(["make", "-C", os.path.join(H.ROOT, "oracle"), "-j8", "_ref/libadapter_test_san.so"], stdout=subprocess.DEVNULL)
     so = os.path.abspath(os.path.join(H.ROOT, "oracle", "_ref", "libadapter_test_san.so"))
     _run_child({"CABAC_TEST_SANITIZED_ADAPTER": so}, "test_reference_adapter.py")
+
+
+def test_oracle_parser_on_damaged_streams_under_asan_ubsan():
+    """The oracle's residual parser is the expectation for damaged input (tests/test_gpu_residual_parse_large.py: flipped bits,
+    a wrong qp, random bytes, a reversed block list, truncation), so what it does there must itself be defined behaviour:
+    tests/parse_corpus.py builds that corpus and parses it — 3 600 substreams, same seed as the GPU test — with the oracle
+    compiled under AddressSanitizer / UBSan."""
+    asan = _libasan()
+    if not asan:
+        pytest.skip("no libasan for this gcc")
+    os.makedirs(SAN_DIR, exist_ok=True)
+    so = os.path.join(SAN_DIR, "libcabac_oracle_san.so")
+    c = os.path.join(H.ROOT, "oracle", "cabac_oracle.c")
+    if _stale(so, [c, os.path.join(H.ROOT, "oracle", "cabac_oracle.h"), os.path.join(H.ROOT, "include", "cabac_hip.h")]):
+        subprocess.check_call(["gcc", "-std=c11", "-D_POSIX_C_SOURCE=200809L", "-fPIC", "-shared", "-pthread"] + SAN_FLAGS + INC + [c, "-o", so])
+    env = dict(os.environ)
+    env["LD_PRELOAD"] = asan
+    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=1:halt_on_error=1:allocator_may_return_null=1"
+    env["UBSAN_OPTIONS"] = "halt_on_error=1:print_stacktrace=1"
+    r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "parse_corpus.py"), "--oracle", so], env=env, capture_output=True,
+                       text=True, timeout=900, cwd=H.ROOT)
+    log = r.stdout[-6000:] + r.stderr[-6000:]
+    assert "AddressSanitizer" not in log and "runtime error:" not in log, log
+    assert r.returncode == 0, log
+    assert "damaged corpus parsed: 3600 substreams" in r.stdout, log
