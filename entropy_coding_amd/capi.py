@@ -58,6 +58,10 @@ EXPORTS_SEARCH = [
     "cabac_hip_estimate_residual_ctx_device", "cabac_hip_estimate_residual_ctx16_device", "cabac_hip_search_select_device",
     "cabac_hip_search_round_device", "cabac_hip_search_round_batch",
 ]
+# include/cabac_hip_search_unit.h (search rounds over candidates with side records; tests/test_search_unit_abi.py compares)
+EXPORTS_SEARCH_UNIT = [
+    "cabac_hip_estimate_unit_device", "cabac_hip_search_unit_round_device", "cabac_hip_search_unit_round_batch",
+]
 SEARCH_NO_SET = SEARCH_NONE = 0xFFFFFFFF                        # CABAC_SEARCH_NO_SET, CABAC_SEARCH_NONE
 NAL_STATUS_DTYPE = np.dtype([("out_bytes", "<u8"), ("n_changed", "<u4"), ("flags", "<u4")])   # cabac_nal_status
 assert NAL_STATUS_DTYPE.itemsize == 16
@@ -154,6 +158,12 @@ def load_library():
                                                 ctypes.c_uint64, vp, vp, vp, vp, vp]
     L.cabac_hip_search_round_batch.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, ctypes.c_uint64, vp,
                                                vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp]
+    L.cabac_hip_estimate_unit_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int] + [vp] * 13
+    L.cabac_hip_search_unit_round_device.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int] + [vp] * 8 + \
+        [ctypes.c_uint64] + [vp] * 6
+    L.cabac_hip_search_unit_round_batch.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, ctypes.c_uint64,
+                                                    vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, ctypes.c_uint64,
+                                                    vp, vp, vp, vp, vp]
     L.cabac_hip_nal_escape_bound.restype = ctypes.c_size_t
     L.cabac_hip_nal_escape_bound.argtypes = [ctypes.c_uint64]
     L.cabac_hip_nal_escape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
@@ -299,7 +309,7 @@ class CabacHip:
         """[(kind, ms)] of the device calls since the last read; kind 0 encode, 1 decode, 2 binarize, ..., 12 residual estimate
         (the list is at cabac_hip_profile_read in include/cabac_hip.h; 12 in cabac_hip_estimate.h; 13 nal escape and 14 nal unescape in
         cabac_hip_nal.h; 15 residual estimate with contexts, 16 search select, 17 / 18 a round's estimate / commit in
-        cabac_hip_search.h)."""
+        cabac_hip_search.h; 19 unit estimate, 20 / 21 / 22 a unit round's estimate / select / commit in cabac_hip_search_unit.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -475,6 +485,69 @@ class CabacHip:
         rc = self.L.cabac_hip_search_round_batch(
             self.h, n_group, group_first.ctypes.data, n_cand, cand_first.ctypes.data, tus.ctypes.data, coeff.ctypes.data,
             2 if int16 else 4, len(coeff), state.ctypes.data, rate.ctypes.data, state.size // NUM_CTX, sets.ctypes.data,
+            out_set.ctypes.data if out_set is not None else None, dist.ctypes.data if dist is not None else None, lambda_q16,
+            bits.ctypes.data, pick.ctypes.data, cost.ctypes.data, tu_bits.ctypes.data if with_blocks else None,
+            info.ctypes.data if with_blocks else None)
+        self._check(rc, allow_substream=not check)
+        out = (bits[:n_cand], pick[:n_group], cost[:n_group])
+        if with_blocks:
+            out += (tu_bits[: len(tus)], info[: len(tus)])
+        return out
+
+    # ---- search rounds over candidates with side records (include/cabac_hip_search_unit.h) ------
+    def estimate_unit_device(self, n_cand, d_cand_first, d_tu, d_coeff, d_state, d_rate, d_set, d_rec_first, d_records, d_tu_at,
+                             d_frac_bits, d_tu_frac_bits=0, d_tu_info=0, d_flags=0, d_out_set=0, d_out_state=0, d_out_rate=0,
+                             int16=False):
+        """cabac_hip_estimate_unit_device: candidate c = side records d_records[d_rec_first[c] .. d_rec_first[c + 1]) (d_rec_first
+        uint64) with its blocks spliced in front of index d_tu_at[t] of that run (d_tu_at = 0: behind the run), costed in one walk;
+        d_flags[c] = RES_BAD_RECORD for a side record that is none; d_out_set = 0 writes no set, else as
+        estimate_residual_ctx_device with all 379 entries taken from the walk."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_estimate_unit_device(
+            self.h, n_cand, vp(d_cand_first), vp(d_tu), vp(d_coeff), 2 if int16 else 4, vp(d_state), vp(d_rate), vp(d_set),
+            vp(d_rec_first), opt(d_records), opt(d_tu_at), vp(d_frac_bits), opt(d_tu_frac_bits), opt(d_tu_info), opt(d_flags),
+            opt(d_out_set), opt(d_out_state), opt(d_out_rate)))
+
+    def search_unit_round_device(self, n_group, d_group_first, n_cand, d_cand_first, d_tu, d_coeff, d_state, d_rate, d_set,
+                                 d_rec_first, d_records, d_tu_at, d_group_out_set, d_dist, lambda_q16, d_frac_bits, d_pick, d_cost,
+                                 d_tu_frac_bits=0, d_tu_info=0, d_flags=0, int16=False):
+        """cabac_hip_search_unit_round_device: search_round_device over candidates with side records (see estimate_unit_device)."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_search_unit_round_device(
+            self.h, n_group, vp(d_group_first), n_cand, vp(d_cand_first), vp(d_tu), vp(d_coeff), 2 if int16 else 4, vp(d_state),
+            vp(d_rate), vp(d_set), vp(d_rec_first), opt(d_records), opt(d_tu_at), opt(d_group_out_set), opt(d_dist), lambda_q16,
+            vp(d_frac_bits), vp(d_pick), vp(d_cost), opt(d_tu_frac_bits), opt(d_tu_info), opt(d_flags)))
+
+    def search_unit_round_batch(self, group_first, cand_first, tus, coeff, state, rate, sets, records, rec_first, tu_at, group_out_set,
+                                dist, lambda_q16, int16=False, with_blocks=False, check=True):
+        """Host arrays through cabac_hip_search_unit_round_batch (synchronous): search_round_batch with the side records
+        `records` (uint16), `rec_first` (uint64[n_cand + 1]) and `tu_at` (uint32 per block, or None).  state / rate are updated IN
+        PLACE.  Returns (frac_bits, pick, cost), with with_blocks also (tu_frac_bits, tu_info)."""
+        group_first = np.ascontiguousarray(group_first, np.uint32)
+        cand_first = np.ascontiguousarray(cand_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        coeff = np.ascontiguousarray(coeff, np.int16 if int16 else np.int32)
+        sets = np.ascontiguousarray(sets, np.uint32)
+        records = np.ascontiguousarray(records, np.uint16)
+        rec_first = np.ascontiguousarray(rec_first, np.uint64)
+        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
+        assert state.dtype == np.uint32 and rate.dtype == np.uint8 and state.flags.c_contiguous and rate.flags.c_contiguous
+        assert state.size == rate.size and state.size % NUM_CTX == 0
+        n_group, n_cand = len(group_first) - 1, len(cand_first) - 1
+        assert n_group >= 0 and n_cand >= 0 and len(sets) == n_cand and len(rec_first) == n_cand + 1
+        assert tu_at is None or len(tu_at) == len(tus)
+        out_set = None if group_out_set is None else np.ascontiguousarray(group_out_set, np.uint32)
+        dist = None if dist is None else np.ascontiguousarray(dist, np.uint64)
+        assert (out_set is None or len(out_set) == n_group) and (dist is None or len(dist) == n_cand)
+        bits = np.zeros(max(n_cand, 1), np.uint64)
+        pick = np.zeros(max(n_group, 1), np.uint32)
+        cost = np.zeros(max(n_group, 1), np.uint64)
+        tu_bits = np.zeros(max(len(tus), 1), np.uint64)
+        info = np.zeros(max(len(tus), 1), np.uint32)
+        rc = self.L.cabac_hip_search_unit_round_batch(
+            self.h, n_group, group_first.ctypes.data, n_cand, cand_first.ctypes.data, tus.ctypes.data, coeff.ctypes.data,
+            2 if int16 else 4, len(coeff), state.ctypes.data, rate.ctypes.data, state.size // NUM_CTX, sets.ctypes.data,
+            records.ctypes.data, len(records), rec_first.ctypes.data, tu_at.ctypes.data if tu_at is not None else None,
             out_set.ctypes.data if out_set is not None else None, dist.ctypes.data if dist is not None else None, lambda_q16,
             bits.ctypes.data, pick.ctypes.data, cost.ctypes.data, tu_bits.ctypes.data if with_blocks else None,
             info.ctypes.data if with_blocks else None)

@@ -20,6 +20,7 @@
 #include "cabac_hip_estimate.h"
 #include "cabac_hip_nal.h"
 #include "cabac_hip_search.h"
+#include "cabac_hip_search_unit.h"
 #include "cabac_kernels.h"
 #include "cabac_nal_kernels.h"
 
@@ -45,8 +46,8 @@ struct cabac_hip_ctx {
   // device staging for the host-pointer entry points (grown on demand)
   // [5]: scratch of the residual binariser, [6]: compacted payload, [7]: payload offsets; [8..]: the spliced-residual path
   // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
-  // search rounds (kSearch* below)
-  static constexpr int kSlots = 45;
+  // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included)
+  static constexpr int kSlots = 48;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -1545,7 +1546,16 @@ int cabac_hip_encode_batch_nal(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
 // ---- search rounds (cabac_search.hip, cabac_residual_estimate.hip; declared in cabac_hip_search.h) -----------------------------
 namespace {
 // device slots: the staging of the host-pointer form (the rest of it goes through the estimator's kEst* slots)
-enum { kSearchInGroupFirst = 40, kSearchInOutSet = 41, kSearchInDist = 42, kSearchOutPick = 43, kSearchOutCost = 44 };
+enum { kSearchInGroupFirst = 40, kSearchInOutSet = 41, kSearchInDist = 42, kSearchOutPick = 43, kSearchOutCost = 44,
+       kSearchInRecords = 45, kSearchInRecFirst = 46, kSearchInTuAt = 47 };
+
+// the side records of the host-pointer form of cabac_hip_search_unit.h (null: the round of cabac_hip_search.h)
+struct HostSide {
+  const uint16_t *records;
+  uint64_t n_records_total;
+  const uint64_t *rec_first;
+  const uint32_t *tu_at;
+};
 
 int estimate_residual_ctx_device_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
                                       const void *d_coeff, int coeff_bytes, const uint32_t *d_state, const uint8_t *d_rate,
@@ -1635,11 +1645,11 @@ int cabac_hip_search_round_device(cabac_hip_ctx *c, uint32_t n_group, const uint
   return CABAC_HIP_OK;
 }
 
-int cabac_hip_search_round_batch(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *group_first, uint32_t n_cand,
-                                 const uint32_t *cand_first, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
-                                 uint64_t n_coeff_total, uint32_t *state, uint8_t *rate, uint32_t n_sets, const uint32_t *set,
-                                 const uint32_t *group_out_set, const uint64_t *dist, uint64_t lambda_q16, uint64_t *frac_bits,
-                                 uint32_t *pick, uint64_t *cost, uint64_t *tu_frac_bits, uint32_t *tu_info) {
+static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *group_first, uint32_t n_cand,
+                                   const uint32_t *cand_first, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
+                                   uint64_t n_coeff_total, uint32_t *state, uint8_t *rate, uint32_t n_sets, const uint32_t *set,
+                                   const uint32_t *group_out_set, const uint64_t *dist, uint64_t lambda_q16, uint64_t *frac_bits,
+                                   uint32_t *pick, uint64_t *cost, uint64_t *tu_frac_bits, uint32_t *tu_info, const HostSide *side) {
   if (!c || !group_first || !cand_first || (n_cand && (!state || !rate || !set || !frac_bits)) || (n_group && (!pick || !cost)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
@@ -1680,6 +1690,31 @@ int cabac_hip_search_round_batch(cabac_hip_ctx *c, uint32_t n_group, const uint3
       }
     }
   }
+  if (side) {  // what cabac_hip_search_unit.h refuses on top
+    if (!side->rec_first || (side->n_records_total && !side->records)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+    for (uint32_t k = 0; k < n_cand; k++)
+      if (side->rec_first[k] > side->rec_first[k + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "rec_first is not non-decreasing");
+    if (side->rec_first[n_cand] > side->n_records_total) return fail(c, CABAC_HIP_ERR_INVALID, "rec_first ends past n_records_total");
+    for (uint32_t k = 0; k < n_cand; k++) {
+      const uint64_t n_rec = side->rec_first[k + 1] - side->rec_first[k];
+      if (n_rec > 0xffffffffull) return fail(c, CABAC_HIP_ERR_INVALID, "rec_first: a run longer than 2^32 - 1 records");
+      uint32_t at = 0;
+      for (uint32_t t = cand_first[k]; side->tu_at && t < cand_first[k + 1]; t++) {
+        if (side->tu_at[t] < at) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at decreases inside a candidate");
+        if (side->tu_at[t] > n_rec) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at exceeds the candidate's run length");
+        at = side->tu_at[t];
+      }
+      for (uint64_t i = side->rec_first[k]; i < side->rec_first[k + 1]; i++) {
+        const uint32_t id = side->records[i] & CABAC_REC_ID_MASK;
+        if (id >= CABAC_NUM_CONTEXTS && id < CABAC_REC_ALIGN) {
+          char buf[160];
+          snprintf(buf, sizeof buf, "bad side record: candidate %u, record %llu of its run (id 0x%x)", k,
+                   (unsigned long long)(i - side->rec_first[k]), id);
+          return fail(c, CABAC_HIP_ERR_INVALID, buf);
+        }
+      }
+    }
+  }
   if (n_cand == 0 && n_group == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
   int rc;
@@ -1711,17 +1746,34 @@ int cabac_hip_search_round_batch(cabac_hip_ctx *c, uint32_t n_group, const uint3
   HIP_TRY(c, up(kSearchInGroupFirst, group_first, (size_t(n_group) + 1) * sizeof(uint32_t)));
   if (group_out_set) HIP_TRY(c, up(kSearchInOutSet, group_out_set, size_t(n_group) * sizeof(uint32_t)));
   if (dist) HIP_TRY(c, up(kSearchInDist, dist, size_t(n_cand) * sizeof(uint64_t)));
+  if (side) {
+    if ((rc = ensure(c, kSearchInRecords, size_t(side->n_records_total) * sizeof(uint16_t)))) return rc;
+    if ((rc = ensure(c, kSearchInRecFirst, (size_t(n_cand) + 1) * sizeof(uint64_t)))) return rc;
+    if ((rc = ensure(c, kSearchInTuAt, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+    HIP_TRY(c, up(kSearchInRecords, side->records, size_t(side->n_records_total) * sizeof(uint16_t)));
+    HIP_TRY(c, up(kSearchInRecFirst, side->rec_first, (size_t(n_cand) + 1) * sizeof(uint64_t)));
+    if (side->tu_at) HIP_TRY(c, up(kSearchInTuAt, side->tu_at, size_t(n_tu) * sizeof(uint32_t)));
+  }
   if (n_tu) {  // blocks no candidate owns keep a defined value
     HIP_TRY(c, hipMemsetAsync(d_tu_bits, 0, size_t(n_tu) * sizeof(uint64_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(d_info, 0, size_t(n_tu) * sizeof(uint32_t), c->stream));
   }
-  rc = cabac_hip_search_round_device(c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand,
-                                     (const uint32_t *)c->d_buf[kEstInFirst], (const cabac_tu_desc *)c->d_buf[kEstInTu],
-                                     c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState], (uint8_t *)c->d_buf[kEstInRate],
-                                     (const uint32_t *)c->d_buf[kEstInSet],
-                                     group_out_set ? (const uint32_t *)c->d_buf[kSearchInOutSet] : nullptr,
-                                     dist ? (const uint64_t *)c->d_buf[kSearchInDist] : nullptr, lambda_q16, d_bits,
-                                     (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info);
+  if (side)
+    rc = cabac_hip_search_unit_round_device(
+        c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand, (const uint32_t *)c->d_buf[kEstInFirst],
+        (const cabac_tu_desc *)c->d_buf[kEstInTu], c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState],
+        (uint8_t *)c->d_buf[kEstInRate], (const uint32_t *)c->d_buf[kEstInSet], (const uint64_t *)c->d_buf[kSearchInRecFirst],
+        (const uint16_t *)c->d_buf[kSearchInRecords], side->tu_at ? (const uint32_t *)c->d_buf[kSearchInTuAt] : nullptr,
+        group_out_set ? (const uint32_t *)c->d_buf[kSearchInOutSet] : nullptr, dist ? (const uint64_t *)c->d_buf[kSearchInDist] : nullptr,
+        lambda_q16, d_bits, (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info, nullptr);
+  else
+    rc = cabac_hip_search_round_device(c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand,
+                                       (const uint32_t *)c->d_buf[kEstInFirst], (const cabac_tu_desc *)c->d_buf[kEstInTu],
+                                       c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState], (uint8_t *)c->d_buf[kEstInRate],
+                                       (const uint32_t *)c->d_buf[kEstInSet],
+                                       group_out_set ? (const uint32_t *)c->d_buf[kSearchInOutSet] : nullptr,
+                                       dist ? (const uint64_t *)c->d_buf[kSearchInDist] : nullptr, lambda_q16, d_bits,
+                                       (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info);
   if (rc) return rc;
   std::vector<uint32_t> info(n_tu);
   auto down = [&](void *dst, const void *src, size_t bytes) {
@@ -1751,6 +1803,87 @@ int cabac_hip_search_round_batch(cabac_hip_ctx *c, uint32_t n_group, const uint3
   }
   if (status) c->last_error = "empty block or bad descriptor (see tu_info[])";
   return status;
+}
+
+int cabac_hip_search_round_batch(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *group_first, uint32_t n_cand,
+                                 const uint32_t *cand_first, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
+                                 uint64_t n_coeff_total, uint32_t *state, uint8_t *rate, uint32_t n_sets, const uint32_t *set,
+                                 const uint32_t *group_out_set, const uint64_t *dist, uint64_t lambda_q16, uint64_t *frac_bits,
+                                 uint32_t *pick, uint64_t *cost, uint64_t *tu_frac_bits, uint32_t *tu_info) {
+  return search_round_batch_impl(c, n_group, group_first, n_cand, cand_first, tus, coeff, coeff_bytes, n_coeff_total, state, rate,
+                                 n_sets, set, group_out_set, dist, lambda_q16, frac_bits, pick, cost, tu_frac_bits, tu_info, nullptr);
+}
+
+// ---- search rounds over candidates with side records (declared in cabac_hip_search_unit.h) -------------------------------------
+int cabac_hip_estimate_unit_device(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
+                                   const void *d_coeff, int coeff_bytes, const uint32_t *d_state, const uint8_t *d_rate,
+                                   const uint32_t *d_set, const uint64_t *d_rec_first, const uint16_t *d_records,
+                                   const uint32_t *d_tu_at, uint64_t *d_frac_bits, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info,
+                                   uint32_t *d_flags, const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate) {
+  if (!c || (n_cand && (!d_cand_first || !d_tu || !d_coeff || !d_state || !d_rate || !d_set || !d_rec_first || !d_frac_bits ||
+                        (d_out_set && (!d_out_state || !d_out_rate)))))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_cand == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  if (int rc = ensure(c, kEstScratch, cabac::residual_estimate_scratch_bytes(n_cand))) return rc;
+  Bracket br = bracket_for(c, 19);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_unit_estimate(c->stream, n_cand, nullptr, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state, d_rate,
+                                         d_set, d_rec_first, d_records, d_tu_at, d_out_set, d_out_state, d_out_rate, d_frac_bits,
+                                         d_tu_frac_bits, d_tu_info, d_flags, c->d_buf[kEstScratch]));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_search_unit_round_device(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *d_group_first, uint32_t n_cand,
+                                       const uint32_t *d_cand_first, const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes,
+                                       uint32_t *d_state, uint8_t *d_rate, const uint32_t *d_set, const uint64_t *d_rec_first,
+                                       const uint16_t *d_records, const uint32_t *d_tu_at, const uint32_t *d_group_out_set,
+                                       const uint64_t *d_dist, uint64_t lambda_q16, uint64_t *d_frac_bits, uint32_t *d_pick,
+                                       uint64_t *d_cost, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info, uint32_t *d_flags) {
+  if (!c || (n_cand && (!d_cand_first || !d_tu || !d_coeff || !d_state || !d_rate || !d_set || !d_rec_first || !d_frac_bits)) ||
+      (n_group && (!d_group_first || !d_pick || !d_cost)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_cand == 0 && n_group == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  if (int rc = ensure(c, kEstScratch, cabac::residual_estimate_scratch_bytes(std::max(n_cand, n_group)))) return rc;
+  c->timed = false;  // three brackets: read them with cabac_hip_profile_read
+  // estimate: every candidate's expanded string from its start set; no set is written
+  Bracket br = bracket_for(c, 20);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_unit_estimate(c->stream, n_cand, nullptr, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state, d_rate,
+                                         d_set, d_rec_first, d_records, d_tu_at, nullptr, nullptr, nullptr, d_frac_bits, d_tu_frac_bits,
+                                         d_tu_info, d_flags, c->d_buf[kEstScratch]));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  if (n_group == 0) return CABAC_HIP_OK;
+  // select: the kernel of cabac_hip_search_select_device, unchanged
+  br = bracket_for(c, 21);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_search_select(c->stream, n_group, n_cand, d_group_first, d_frac_bits, d_dist, lambda_q16, d_pick, d_cost));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  // commit: the picked candidates walked once more with their side records (d_pick is the index list)
+  br = bracket_for(c, 22);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  if (d_group_out_set && n_cand)
+    HIP_TRY(c, cabac::launch_unit_estimate(c->stream, n_group, d_pick, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state, d_rate,
+                                           d_set, d_rec_first, d_records, d_tu_at, d_group_out_set, d_state, d_rate, nullptr, nullptr,
+                                           nullptr, nullptr, c->d_buf[kEstScratch]));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_search_unit_round_batch(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *group_first, uint32_t n_cand,
+                                      const uint32_t *cand_first, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
+                                      uint64_t n_coeff_total, uint32_t *state, uint8_t *rate, uint32_t n_sets, const uint32_t *set,
+                                      const uint16_t *records, uint64_t n_records_total, const uint64_t *rec_first,
+                                      const uint32_t *tu_at, const uint32_t *group_out_set, const uint64_t *dist, uint64_t lambda_q16,
+                                      uint64_t *frac_bits, uint32_t *pick, uint64_t *cost, uint64_t *tu_frac_bits, uint32_t *tu_info) {
+  const HostSide side{records, n_records_total, rec_first, tu_at};
+  return search_round_batch_impl(c, n_group, group_first, n_cand, cand_first, tus, coeff, coeff_bytes, n_coeff_total, state, rate,
+                                 n_sets, set, group_out_set, dist, lambda_q16, frac_bits, pick, cost, tu_frac_bits, tu_info, &side);
 }
 
 int cabac_hip_host_alloc(size_t bytes, void **out) {

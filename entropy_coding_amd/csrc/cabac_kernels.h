@@ -67,6 +67,17 @@ hipError_t launch_residual_estimate_export(hipStream_t st, uint32_t n_item, cons
                                            const uint32_t *out_set, uint32_t *out_state, uint8_t *out_rate, uint64_t *frac_bits,
                                            uint64_t *tu_frac_bits, uint32_t *tu_info, void *scratch);
 
+// the variant with side records (cabac_hip_search_unit.h): the exporting walk over candidates that are record strings with blocks
+// spliced in — candidate c owns records[rec_first[c] .. rec_first[c+1]) and block t goes in front of index tu_at[t] of its
+// candidate's run (tu_at null: behind the run).  out_set null: no set is written; flags (may be null): CABAC_RES_BAD_RECORD or 0
+// per candidate.  scratch: residual_estimate_scratch_bytes(n_item)
+hipError_t launch_unit_estimate(hipStream_t st, uint32_t n_item, const uint32_t *index, uint32_t n_cand, const uint32_t *cand_first,
+                                const cabac_tu_desc *tus, const void *coeff, int coeff_bytes, const uint32_t *start_state,
+                                const uint8_t *start_rate, const uint32_t *start_set, const uint64_t *rec_first,
+                                const uint16_t *records, const uint32_t *tu_at, const uint32_t *out_set, uint32_t *out_state,
+                                uint8_t *out_rate, uint64_t *frac_bits, uint64_t *tu_frac_bits, uint32_t *tu_info, uint32_t *flags,
+                                void *scratch);
+
 // search rounds (cabac_search.hip): per group g = candidates [group_first[g], group_first[g+1]) (clipped to
 // min(group_first[n_group], n_cand_max)) the index and the value of the smallest dist + ((lambda_q16 * frac_bits) >> 31)
 hipError_t launch_search_select(hipStream_t st, uint32_t n_group, uint32_t n_cand_max, const uint32_t *group_first,

@@ -30,6 +30,13 @@
 // The exporting variant (kExport, cabac_hip_search.h) is the same walk over a list of candidates, which at its end unpacks
 // the row's context store into the set the candidate leaves (1.9 KB: 379 x 4 B states + 379 rate bytes): what a search
 // round commits for the candidate it picked.  The estimator's own entry points instantiate the kernel without it.
+//
+// The variant with side records (kSide, cabac_hip_search_unit.h) costs a candidate that is a record string with blocks
+// spliced in: in front of every block, and once more behind the last one, a row costs its own side records up to the
+// block's position, 16 per step with lane = record — a context-coded record through the same plane step as a block's
+// flags, a bypass bin 1 << 15, a terminate bin its constant, and an align record rounds the row's running total (blocks
+// included) up to a whole bit, formed in order only in a step that holds one.  Any of the 379 contexts can be named, so
+// this variant brings all of them in and exports all of them from the store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -64,6 +71,13 @@ struct EstExport {        // what the exporting variant of the kernel needs on t
   const uint32_t *out_set;  // per item: the set to write, 0xffffffff = none
   uint32_t *out_state;
   uint8_t *out_rate;
+};
+
+struct EstSide {           // what the variant with side records needs on top (unused otherwise)
+  const uint64_t *rec_first;  // candidate -> its run of side records (n_cand + 1 entries)
+  const uint16_t *records;
+  const uint32_t *tu_at;      // block -> the index in its candidate's run it is inserted in front of (null: behind the run)
+  uint32_t *flags;            // per candidate: CABAC_RES_BAD_RECORD or 0 (may be null)
 };
 
 struct EstRow {          // what a plane step needs of its row
@@ -192,15 +206,26 @@ __device__ __forceinline__ void est_cand_range(const uint32_t *cand_first, uint3
   end = max(end, first);
 }
 
+// side records [first, first + n) of candidate c, clipped to the rec_first[n_cand] records there are as est_cand_range clips
+// blocks; a run longer than 2^32 - 1 records (positions are uint32) is cut there
+__device__ __forceinline__ void est_side_range(const uint64_t *rec_first, uint32_t n_cand, uint32_t c, uint64_t &first, uint32_t &n) {
+  const uint64_t n_all = rec_first[n_cand];
+  first = min(rec_first[c], n_all);
+  const uint64_t end = max(min(rec_first[c + 1u], n_all), first);
+  n = (uint32_t)min(end - first, (uint64_t)0xffffffffu);
+}
+
 }  // namespace
 
 // Ordering pre-pass (the idea of class_hist / class_scatter, cabac_residual.hip): the rows of a wave run as long as the
 // longest of them, so candidates are handed out by the log2 of their total group count, largest first.
 // `index` (may be null): the pass orders the n_item candidates index[0 .. n_item) instead of candidates 0 .. n_cand - 1 (then
-// n_item == n_cand); an entry that names no candidate (>= n_cand) has no blocks.
+// n_item == n_cand); an entry that names no candidate (>= n_cand) has no blocks.  `rec_first` (may be null): the candidates' side
+// records; a step of 16 of them weighs as much as a coefficient group.
 __global__ __launch_bounds__(256) void est_class_hist(uint32_t n_item, uint32_t n_cand, const uint32_t *__restrict__ index,
                                                        const uint32_t *__restrict__ cand_first,
-                                                       const cabac_tu_desc *__restrict__ tus, uint32_t *__restrict__ scratch) {
+                                                       const cabac_tu_desc *__restrict__ tus, const uint64_t *__restrict__ rec_first,
+                                                       uint32_t *__restrict__ scratch) {
   __shared__ uint32_t h[kEstClasses];
   if (threadIdx.x < kEstClasses) h[threadIdx.x] = 0;
   __syncthreads();
@@ -212,6 +237,12 @@ __global__ __launch_bounds__(256) void est_class_hist(uint32_t n_item, uint32_t 
     for (uint32_t t = first; t < end; t++) {
       const uint64_t hi = reinterpret_cast<const uint64_t *>(tus)[2u * (uint64_t)t + 1u];  // log2_width, log2_height: its low bytes
       groups += est_groups((uint32_t)hi & 0xffu, (uint32_t)(hi >> 8) & 0xffu);
+    }
+    if (rec_first && cand < n_cand) {
+      uint64_t rec0;
+      uint32_t n_rec;
+      est_side_range(rec_first, n_cand, cand, rec0, n_rec);
+      groups += (uint32_t)min(((uint64_t)n_rec + 15ull) >> 4, (uint64_t)(0xffffffffu - groups));
     }
     const uint32_t cls = groups ? min(32u - (uint32_t)__builtin_clz(groups), kEstClasses - 1u) : 0u;
     scratch[kEstHeader + n_item + c] = cls;
@@ -246,14 +277,17 @@ __global__ __launch_bounds__(256) void est_class_scatter(uint32_t n_cand, uint32
 // final contexts as set ex.out_set[i] of ex.out_state / ex.out_rate, which may be the start arrays: every read of the start
 // set that feeds the walk happens before the __syncthreads() below, every store after the walk.  So the start arrays are not
 // __restrict__ here.  Without kExport n_item == n_cand, ex is not read and the code is the one the estimator always ran.
-template <class C, bool kExport>
+// kSide (with kExport only): the candidates carry side records (sd, see the top of the file); ex.out_set may then be null (no
+// set is written).  Without kSide sd is not read.
+template <class C, bool kExport, bool kSide>
 __global__ __launch_bounds__(256) void residual_estimate_kernel(uint32_t n_item, uint32_t n_cand, const uint32_t *__restrict__ cand_first,
                                                                  const cabac_tu_desc *__restrict__ tus, const C *__restrict__ coeff_all,
                                                                  const uint32_t *start_state, const uint8_t *start_rate,
                                                                  const uint32_t *__restrict__ start_set,
                                                                  const uint32_t *__restrict__ order, uint64_t *__restrict__ frac_bits,
                                                                  uint64_t *__restrict__ tu_frac_bits, uint32_t *__restrict__ tu_info,
-                                                                 EstExport ex) {
+                                                                 EstExport ex, EstSide sd) {
+  static_assert(kExport || !kSide, "side records come with the exporting variant");
   __shared__ uint32_t ctx_all[kEstRows * kEstCtxStride];
   __shared__ uint32_t frac[512];
   __shared__ uint32_t match_all[4 * kEstMatchWords];
@@ -285,15 +319,63 @@ __global__ __launch_bounds__(256) void residual_estimate_kernel(uint32_t n_item,
       const uint32_t st = start_state[set + k], rt = start_rate[set + k];
       r.ctx[k] = (st & kMask0) | (st & 0xffff0000u) | (((rt >> 4) - 2u) & 3u) | ((((rt & 15u) - 5u) & 7u) << 2);
     };
-    for (uint32_t k = 86u + l; k < 292u; k += 16u) bring(k);
-    if (l < 2u) bring(310u + l);
-    for (uint32_t k = 357u + l; k < (uint32_t)kNumCtx; k += 16u) bring(k);
+    if constexpr (kSide) {  // a side record can name any context
+      for (uint32_t k = l; k < (uint32_t)kNumCtx; k += 16u) bring(k);
+    } else {
+      for (uint32_t k = 86u + l; k < 292u; k += 16u) bring(k);
+      if (l < 2u) bring(310u + l);
+      for (uint32_t k = 357u + l; k < (uint32_t)kNumCtx; k += 16u) bring(k);
+    }
+  }
+  // the row's side records: rec[0 .. n_rec), costed up to rec_pos; rec_next holds lane l's record of the next step (rec_pos + l),
+  // loaded a step ahead — across a block's walk too
+  const uint16_t *rec = nullptr;
+  uint32_t n_rec = 0, rec_pos = 0, rec_next = 0;
+  uint64_t side_acc = 0;  // this lane's share of the side records' cost since the row's total was last formed
+  bool side_bad = false;
+  if constexpr (kSide) {
+    if (has_cand) {
+      uint64_t rec0;
+      est_side_range(sd.rec_first, n_cand, cand, rec0, n_rec);
+      rec = sd.records + rec0;
+      if (l < n_rec) rec_next = rec[l];
+    }
   }
   __syncthreads();
 
   uint64_t cand_total = 0;  // row-uniform
-  while (__ballot(t < t_end) != 0ull) {
+  while (__ballot(t < t_end || (kSide && rec_pos < n_rec)) != 0ull) {
     const bool blk = t < t_end;
+    if constexpr (kSide) {
+      // ---- the side records in front of this block (behind the last one: all that are left), 16 per step -----------
+      uint32_t seg_end = n_rec;
+      if (blk && sd.tu_at) seg_end = min(max(sd.tu_at[t], rec_pos), n_rec);
+      while (__ballot(rec_pos < seg_end) != 0ull) {
+        const uint32_t n_here = min(seg_end - rec_pos, 16u);
+        const bool active = l < n_here;
+        const uint32_t rr = rec_next;
+        rec_pos += n_here;
+        rec_next = (l < n_rec - rec_pos) ? rec[rec_pos + l] : 0u;
+        const uint32_t id = rr & CABAC_REC_ID_MASK, bin = rr >> 15;
+        uint32_t cost = est_plane<false>(r, active && id < (uint32_t)kNumCtx, id, bin);
+        if (active && id == CABAC_REC_EP) cost = 1u << 15;                  // estFracBitsEP, contexts.cpp:880-882
+        if (active && id == CABAC_REC_TRM) cost = bin ? 0x3bfbbu : 0x0010cu;  // estFracBitsTrm, contexts.cpp:931-933
+        const bool aln = active && id == CABAC_REC_ALIGN;
+        side_bad = side_bad || (active && id >= (uint32_t)kNumCtx && id < CABAC_REC_ALIGN);
+        if (__builtin_expect(__ballot(aln) != 0ull, 0)) {  // align(), arith_codec.cpp:679-684: the total in order, as estimate_kernel
+          uint64_t total = cand_total + est_row_sum64(side_acc);
+          for (int k = 0; k < 16; k++) {
+            total += (uint32_t)__shfl((int)cost, (int)(row * 16u + (uint32_t)k));
+            if (__shfl((int)aln, (int)(row * 16u + (uint32_t)k))) total = (total + 0x7fffull) & ~0x7fffull;
+          }
+          cand_total = total;
+          side_acc = 0;
+        } else {
+          side_acc += cost;
+        }
+      }
+      if (__ballot(blk) == 0ull) continue;  // the iteration behind the last block of every row
+    }
     bool live = blk;
     // ---- geometry (row-uniform), as residual_rows --------------------------------------------------
     uint32_t lw = 0, lh = 0, chroma = 0, flags = 0, max_log2 = 15;
@@ -629,16 +711,22 @@ __global__ __launch_bounds__(256) void residual_estimate_kernel(uint32_t n_item,
     cand_total += blk ? share : 0ull;
     t += blk ? 1u : 0u;
   }
+  if constexpr (kSide) {
+    cand_total += est_row_sum64(side_acc);
+    const bool bad_rec = row_bits(side_bad, row_shift) != 0u;
+    if (bad_rec) cand_total = ~0ull;
+    if (has_cand && l == 0u && sd.flags) sd.flags[cand] = bad_rec ? CABAC_RES_BAD_RECORD : 0u;
+  }
   if (has_cand && l == 0u && (!kExport || frac_bits)) frac_bits[cand] = cand_total;
 
   // ---- the contexts the candidate leaves: the row's store unpacked into the format it was brought in from, and what
   // residual coding cannot touch copied from the start set (the row's own lanes wrote the store: one wave, LDS in order)
   if constexpr (kExport) {
-    const uint32_t oset = has_cand ? ex.out_set[item] : 0xffffffffu;
+    const uint32_t oset = (has_cand && (!kSide || ex.out_set)) ? ex.out_set[item] : 0xffffffffu;
     if (oset != 0xffffffffu) {
       const uint64_t src = (uint64_t)start_set[cand] * (uint64_t)kNumCtx, dst = (uint64_t)oset * (uint64_t)kNumCtx;
       for (uint32_t k = l; k < (uint32_t)kNumCtx; k += 16u) {
-        const bool held = (k >= 86u && k < 292u) || k == 310u || k == 311u || k >= 357u;
+        const bool held = kSide || (k >= 86u && k < 292u) || k == 310u || k == 311u || k >= 357u;
         uint32_t st, rt;
         if (held) {
           const uint32_t w = r.ctx[k];
@@ -659,28 +747,29 @@ size_t residual_estimate_scratch_bytes(uint32_t n_cand) { return sizeof(uint32_t
 
 namespace {
 
-template <bool kExport>
+template <bool kExport, bool kSide = false>
 hipError_t launch_estimate_items(hipStream_t st, uint32_t n_item, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus,
                                  const void *coeff, int coeff_bytes, const uint32_t *start_state, const uint8_t *start_rate,
                                  const uint32_t *start_set, uint64_t *frac_bits, uint64_t *tu_frac_bits, uint32_t *tu_info,
-                                 void *scratch, const EstExport &ex) {
+                                 void *scratch, const EstExport &ex, const EstSide &sd = EstSide{nullptr, nullptr, nullptr, nullptr}) {
   if (n_item == 0) return hipSuccess;
   if (coeff_bytes != 4 && coeff_bytes != 2) return hipErrorInvalidValue;
   uint32_t *s32 = static_cast<uint32_t *>(scratch);
   hipError_t e = hipMemsetAsync(s32, 0, sizeof(uint32_t) * kEstHeader, st);
   if (e != hipSuccess) return e;
   const dim3 sort_grid((n_item + 255u) / 256u), grid((n_item + kEstRows - 1u) / kEstRows);
-  hipLaunchKernelGGL(est_class_hist, sort_grid, dim3(256), 0, st, n_item, n_cand, ex.index, cand_first, tus, s32);
+  hipLaunchKernelGGL(est_class_hist, sort_grid, dim3(256), 0, st, n_item, n_cand, ex.index, cand_first, tus,
+                     kSide ? sd.rec_first : nullptr, s32);
   hipLaunchKernelGGL(est_class_scatter, sort_grid, dim3(256), 0, st, n_item, s32);
   const uint32_t *order = s32 + kEstHeader;
   if (coeff_bytes == 2)
-    hipLaunchKernelGGL((residual_estimate_kernel<int16_t, kExport>), grid, dim3(256), 0, st, n_item, n_cand, cand_first, tus,
+    hipLaunchKernelGGL((residual_estimate_kernel<int16_t, kExport, kSide>), grid, dim3(256), 0, st, n_item, n_cand, cand_first, tus,
                        static_cast<const int16_t *>(coeff), start_state, start_rate, start_set, order, frac_bits, tu_frac_bits, tu_info,
-                       ex);
+                       ex, sd);
   else
-    hipLaunchKernelGGL((residual_estimate_kernel<int32_t, kExport>), grid, dim3(256), 0, st, n_item, n_cand, cand_first, tus,
+    hipLaunchKernelGGL((residual_estimate_kernel<int32_t, kExport, kSide>), grid, dim3(256), 0, st, n_item, n_cand, cand_first, tus,
                        static_cast<const int32_t *>(coeff), start_state, start_rate, start_set, order, frac_bits, tu_frac_bits, tu_info,
-                       ex);
+                       ex, sd);
   return hipGetLastError();
 }
 
@@ -701,6 +790,17 @@ hipError_t launch_residual_estimate_export(hipStream_t st, uint32_t n_item, cons
                                            uint64_t *tu_frac_bits, uint32_t *tu_info, void *scratch) {
   return launch_estimate_items<true>(st, n_item, n_cand, cand_first, tus, coeff, coeff_bytes, start_state, start_rate, start_set,
                                      frac_bits, tu_frac_bits, tu_info, scratch, EstExport{index, out_set, out_state, out_rate});
+}
+
+hipError_t launch_unit_estimate(hipStream_t st, uint32_t n_item, const uint32_t *index, uint32_t n_cand, const uint32_t *cand_first,
+                                const cabac_tu_desc *tus, const void *coeff, int coeff_bytes, const uint32_t *start_state,
+                                const uint8_t *start_rate, const uint32_t *start_set, const uint64_t *rec_first,
+                                const uint16_t *records, const uint32_t *tu_at, const uint32_t *out_set, uint32_t *out_state,
+                                uint8_t *out_rate, uint64_t *frac_bits, uint64_t *tu_frac_bits, uint32_t *tu_info, uint32_t *flags,
+                                void *scratch) {
+  return launch_estimate_items<true, true>(st, n_item, n_cand, cand_first, tus, coeff, coeff_bytes, start_state, start_rate, start_set,
+                                           frac_bits, tu_frac_bits, tu_info, scratch, EstExport{index, out_set, out_state, out_rate},
+                                           EstSide{rec_first, records, tu_at, flags});
 }
 
 }  // namespace cabac
