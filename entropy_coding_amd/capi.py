@@ -62,6 +62,20 @@ EXPORTS_SEARCH = [
 EXPORTS_SEARCH_UNIT = [
     "cabac_hip_estimate_unit_device", "cabac_hip_search_unit_round_device", "cabac_hip_search_unit_round_batch",
 ]
+# include/cabac_hip_search_emit.h (the winner log; tests/test_search_emit_abi.py compares that header with this list)
+EXPORTS_SEARCH_EMIT = [
+    "cabac_hip_search_log_create", "cabac_hip_search_log_destroy", "cabac_hip_search_log_reset_device",
+    "cabac_hip_search_log_append_device", "cabac_hip_search_log_view", "cabac_hip_search_log_encode_device",
+]
+SEARCH_NO_CHAIN = 0xFFFFFFFF                                     # CABAC_SEARCH_NO_CHAIN
+SEARCH_LOG_OVERFLOW = 0x1                                        # CABAC_SEARCH_LOG_OVERFLOW and the capacity that was too small
+SEARCH_LOG_OVER_ENTRIES, SEARCH_LOG_OVER_RECORDS, SEARCH_LOG_OVER_BLOCKS, SEARCH_LOG_OVER_COEFFS = 0x10, 0x20, 0x40, 0x80
+SEARCH_LOG_OVER_CHAIN_RECORDS = 0x100
+LOG_COUNTERS_DTYPE = np.dtype([("n_entry", "<u8"), ("n_record", "<u8"), ("n_tu", "<u8"), ("n_coeff", "<u8"), ("flags", "<u4"),
+                               ("reserved", "<u4")])             # cabac_search_log_counters
+LOG_ENTRY_DTYPE = np.dtype([("rec_first", "<u8"), ("chain", "<u4"), ("n_rec", "<u4"), ("n_tu", "<u4"), ("tu_first", "<u4"),
+                            ("chain_rec_first", "<u4"), ("chain_tu_first", "<u4")])   # cabac_search_log_entry
+assert LOG_COUNTERS_DTYPE.itemsize == 40 and LOG_ENTRY_DTYPE.itemsize == 32
 SEARCH_NO_SET = SEARCH_NONE = 0xFFFFFFFF                        # CABAC_SEARCH_NO_SET, CABAC_SEARCH_NONE
 NAL_STATUS_DTYPE = np.dtype([("out_bytes", "<u8"), ("n_changed", "<u4"), ("flags", "<u4")])   # cabac_nal_status
 assert NAL_STATUS_DTYPE.itemsize == 16
@@ -69,6 +83,15 @@ NAL_OVERFLOW, NAL_TRAILING_ZERO, NAL_FORBIDDEN, NAL_BAD_ESCAPE, NAL_LOC_OVERFLOW
 
 _lib = None
 vp = ctypes.c_void_p
+
+
+class SearchLogView(ctypes.Structure):
+    """cabac_search_log_view: const device pointers into a winner log and what it was created with."""
+    _fields_ = [("d_counters", vp), ("d_entries", vp), ("d_records", vp), ("d_tu", vp), ("d_tu_at", vp), ("d_coeff", vp),
+                ("record_capacity", ctypes.c_uint64), ("coeff_capacity", ctypes.c_uint64), ("n_chain", ctypes.c_uint32),
+                ("entry_capacity", ctypes.c_uint32), ("tu_capacity", ctypes.c_uint32), ("coeff_bytes", ctypes.c_int32)]
+
+
 # every CabacHip / PinnedArray that has not been closed yet: close_all() ends them in a defined order (contexts first, then
 # the pinned buffers they may still have been copying from) while the HIP runtime is certainly alive
 _live = weakref.WeakSet()
@@ -164,6 +187,13 @@ def load_library():
     L.cabac_hip_search_unit_round_batch.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, ctypes.c_uint64,
                                                     vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, ctypes.c_uint64,
                                                     vp, vp, vp, vp, vp]
+    L.cabac_hip_search_log_create.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
+                                              ctypes.c_int, ctypes.POINTER(vp)]
+    L.cabac_hip_search_log_destroy.argtypes = [vp]
+    L.cabac_hip_search_log_reset_device.argtypes = [vp]
+    L.cabac_hip_search_log_append_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, vp, vp, vp]
+    L.cabac_hip_search_log_view.argtypes = [vp, ctypes.POINTER(SearchLogView)]
+    L.cabac_hip_search_log_encode_device.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp]
     L.cabac_hip_nal_escape_bound.restype = ctypes.c_size_t
     L.cabac_hip_nal_escape_bound.argtypes = [ctypes.c_uint64]
     L.cabac_hip_nal_escape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
@@ -267,6 +297,8 @@ class CabacHip:
 
     def close(self):
         if getattr(self, "h", None):
+            for log in list(getattr(self, "_logs", ())):   # the winner logs of this ctx go first (close_all() closes them this way)
+                log.close()
             self.L.cabac_hip_destroy(self.h)   # waits for the ctx's streams, then releases them
             self.h = None
             _live.discard(self)
@@ -309,7 +341,8 @@ class CabacHip:
         """[(kind, ms)] of the device calls since the last read; kind 0 encode, 1 decode, 2 binarize, ..., 12 residual estimate
         (the list is at cabac_hip_profile_read in include/cabac_hip.h; 12 in cabac_hip_estimate.h; 13 nal escape and 14 nal unescape in
         cabac_hip_nal.h; 15 residual estimate with contexts, 16 search select, 17 / 18 a round's estimate / commit in
-        cabac_hip_search.h; 19 unit estimate, 20 / 21 / 22 a unit round's estimate / select / commit in cabac_hip_search_unit.h)."""
+        cabac_hip_search.h; 19 unit estimate, 20 / 21 / 22 a unit round's estimate / select / commit in cabac_hip_search_unit.h; 23 log append and
+        24 log place in cabac_hip_search_emit.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -557,6 +590,11 @@ class CabacHip:
             out += (tu_bits[: len(tus)], info[: len(tus)])
         return out
 
+    # ---- the winner log (include/cabac_hip_search_emit.h) ------
+    def search_log(self, n_chain, entry_capacity, record_capacity, tu_capacity, coeff_capacity, int16=False):
+        """cabac_hip_search_log_create: a SearchLog of this ctx (closed with it at the latest)."""
+        return SearchLog(self, n_chain, entry_capacity, record_capacity, tu_capacity, coeff_capacity, int16)
+
     def binarize_device(self, n_sub, d_se_offset, d_se, d_rec_offset, d_n_records, d_records):
         self._check(self.L.cabac_hip_binarize_device(self.h, n_sub, vp(d_se_offset), vp(d_se), vp(d_rec_offset),
                                                      vp(d_n_records), vp(d_records)))
@@ -723,3 +761,88 @@ class CabacHip:
             e.nal_status = status[0]
             raise
         return nal_offsets, res[: len(desc)], status[0]
+
+
+class SearchLog:
+    """A winner log (include/cabac_hip_search_emit.h): the candidates the search rounds picked, copied on the device round by
+    round, coded into one substream per chain by encode_device().  Owned by its CabacHip, which closes it when it is closed."""
+
+    def __init__(self, hip, n_chain, entry_capacity, record_capacity, tu_capacity, coeff_capacity, int16=False):
+        self.hip, self.L, self.n_chain, self.int16 = hip, hip.L, n_chain, bool(int16)
+        h = vp()
+        hip._check(self.L.cabac_hip_search_log_create(hip.h, n_chain, entry_capacity, record_capacity, tu_capacity, coeff_capacity,
+                                                      2 if int16 else 4, ctypes.byref(h)))
+        self.h = h
+        if not hasattr(hip, "_logs"):
+            hip._logs = []
+        hip._logs.append(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.cabac_hip_search_log_destroy(self.h)   # waits for the ctx's stream
+            self.h = None
+            self.hip._logs.remove(self)
+
+    @staticmethod
+    def validate(pick, group_chain, n_cand, n_chain):
+        """What the device form cannot see: among the groups that append (a pick below n_cand, a chain below n_chain) no chain
+        may be named twice in one call.  Raises ValueError."""
+        pick, group_chain = np.asarray(pick, np.uint32), np.asarray(group_chain, np.uint32)
+        if pick.shape != group_chain.shape or pick.ndim != 1:
+            raise ValueError("pick and group_chain must be one word per group")
+        chains = group_chain[(pick < n_cand) & (group_chain < n_chain)]
+        uniq, count = np.unique(chains, return_counts=True)
+        if (count > 1).any():
+            raise ValueError("chain %d is named by %d appending groups of one call (one group per chain)"
+                             % (int(uniq[count > 1][0]), int(count.max())))
+
+    def append_device(self, n_group, d_pick, d_group_chain, n_cand, d_cand_first, d_tu, d_coeff, d_rec_first, d_records=0, d_tu_at=0,
+                      int16=None, check=True, pick=None, group_chain=None):
+        """cabac_hip_search_log_append_device (asynchronous): group g appends candidate d_pick[g] to chain d_group_chain[g].  An
+        array-backed call — the host copies `pick` and `group_chain` of the two device arrays are passed too — is validated on
+        the host first with check=True (see validate); what only exists on the device cannot be."""
+        if check and pick is not None and group_chain is not None:
+            self.validate(pick, group_chain, n_cand, self.n_chain)
+        opt = lambda p: vp(p) if p else None
+        narrow = self.int16 if int16 is None else bool(int16)
+        self.hip._check(self.L.cabac_hip_search_log_append_device(
+            self.h, n_group, opt(d_pick), opt(d_group_chain), n_cand, opt(d_cand_first), opt(d_tu), opt(d_coeff), 2 if narrow else 4,
+            opt(d_rec_first), opt(d_records), opt(d_tu_at)))
+
+    def reset(self):
+        """cabac_hip_search_log_reset_device (asynchronous): the log is empty again."""
+        self.hip._check(self.L.cabac_hip_search_log_reset_device(self.h))
+
+    def view(self):
+        """cabac_hip_search_log_view: a SearchLogView of device pointers (counters, entries, records, descriptors, positions,
+        coefficients) and the capacities."""
+        v = SearchLogView()
+        self.hip._check(self.L.cabac_hip_search_log_view(self.h, ctypes.byref(v)))
+        return v
+
+    def read(self):
+        """The log's content on the host, after waiting for the ctx's stream: a dict of numpy arrays cut to the counters
+        (counters, entries, records, tu, tu_at, coeff)."""
+        v = self.view()
+        self.hip.synchronize()
+        copy = self.L.hipMemcpy          # the HIP runtime this library is linked with
+        copy.argtypes, copy.restype = [vp, vp, ctypes.c_size_t, ctypes.c_int], ctypes.c_int
+
+        def fetch(ptr, n, dtype):
+            out = np.zeros(n, dtype)
+            if out.nbytes and copy(out.ctypes.data, ptr, out.nbytes, 2) != 0:   # hipMemcpyDeviceToHost
+                raise CabacHipError(-3, "hipMemcpy of the log failed")
+            return out
+
+        cnt = fetch(v.d_counters, 1, LOG_COUNTERS_DTYPE)[0]
+        return {"counters": cnt, "entries": fetch(v.d_entries, int(cnt["n_entry"]), LOG_ENTRY_DTYPE),
+                "records": fetch(v.d_records, int(cnt["n_record"]), np.uint16), "tu": fetch(v.d_tu, int(cnt["n_tu"]), TU_DTYPE),
+                "tu_at": fetch(v.d_tu_at, int(cnt["n_tu"]), np.uint32),
+                "coeff": fetch(v.d_coeff, int(cnt["n_coeff"]), np.int16 if v.coeff_bytes == 2 else np.int32)}
+
+    def encode_device(self, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info=0, d_bin_counts=0):
+        """cabac_hip_search_log_encode_device: every chain's entries coded into its substream (d_desc: n_chain descriptors, qp and
+        init_id | SUB_* read); waits for the ctx's stream twice.  Raises CabacHipError(-2) for a log that overflowed."""
+        self.hip._check(self.L.cabac_hip_search_log_encode_device(
+            self.h, vp(d_desc), vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results),
+            vp(d_tu_info) if d_tu_info else None, vp(d_bin_counts) if d_bin_counts else None))

@@ -20,6 +20,7 @@
 #include "cabac_hip_estimate.h"
 #include "cabac_hip_nal.h"
 #include "cabac_hip_search.h"
+#include "cabac_hip_search_emit.h"
 #include "cabac_hip_search_unit.h"
 #include "cabac_kernels.h"
 #include "cabac_nal_kernels.h"
@@ -46,8 +47,8 @@ struct cabac_hip_ctx {
   // device staging for the host-pointer entry points (grown on demand)
   // [5]: scratch of the residual binariser, [6]: compacted payload, [7]: payload offsets; [8..]: the spliced-residual path
   // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
-  // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included)
-  static constexpr int kSlots = 48;
+  // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included); [48..]: the winner log (kLog* below)
+  static constexpr int kSlots = 53;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -69,6 +70,14 @@ struct cabac_hip_ctx {
   size_t h_cap[2] = {0, 0};
   bool pipe_ready = false;
   int chunks_override = 0;  // CABAC_HIP_CHUNKS (experiments); 0 = by batch size
+  std::vector<cabac_search_log *> logs;  // the winner logs that are alive (cabac_hip_search_emit.h): destroyed with the ctx
+};
+
+// a winner log: fixed device arrays (one allocation each, never grown) and the ctx whose stream orders everything done to them
+struct cabac_search_log {
+  cabac_hip_ctx *ctx = nullptr;
+  cabac::SearchLogArrays a = {};
+  int coeff_bytes = 4;
 };
 
 namespace {
@@ -431,6 +440,7 @@ void cabac_hip_destroy(cabac_hip_ctx *c) {
   if (!c) return;
   DeviceGuard g(c->device);
   (void)hipStreamSynchronize(c->stream);
+  while (!c->logs.empty()) (void)cabac_hip_search_log_destroy(c->logs.back());
   for (int i = 0; i < cabac_hip_ctx::kSlots; i++)
     if (c->d_buf[i]) (void)hipFree(c->d_buf[i]);
   if (c->h_totals) (void)hipHostFree(c->h_totals);
@@ -1884,6 +1894,150 @@ int cabac_hip_search_unit_round_batch(cabac_hip_ctx *c, uint32_t n_group, const 
   const HostSide side{records, n_records_total, rec_first, tu_at};
   return search_round_batch_impl(c, n_group, group_first, n_cand, cand_first, tus, coeff, coeff_bytes, n_coeff_total, state, rate,
                                  n_sets, set, group_out_set, dist, lambda_q16, frac_bits, pick, cost, tu_frac_bits, tu_info, &side);
+}
+
+// ---- the winner log (declared in cabac_hip_search_emit.h; kernels in cabac_search_emit.hip) -------------------------------------
+namespace {
+enum { kLogScratch = 48, kLogDesc = 49, kLogFirst = 50, kLogRec = 51, kLogSplice = 52 };
+
+void log_free(cabac_search_log *log) {
+  void *p[] = {log->a.counters, log->a.entries, log->a.records, log->a.tu, log->a.tu_at, log->a.coeff, log->a.chain_rec, log->a.chain_tu};
+  for (void *q : p)
+    if (q) (void)hipFree(q);
+  delete log;
+}
+}  // namespace
+
+int cabac_hip_search_log_create(cabac_hip_ctx *c, uint32_t n_chain, uint32_t entry_capacity, uint64_t record_capacity,
+                                uint32_t tu_capacity, uint64_t coeff_capacity, int coeff_bytes, cabac_search_log **out) {
+  if (!c || !out) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  *out = nullptr;
+  if (n_chain == 0) return fail(c, CABAC_HIP_ERR_INVALID, "a log needs at least one chain");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (record_capacity > (uint64_t(1) << 60) || coeff_capacity > (uint64_t(1) << 60)) return fail(c, CABAC_HIP_ERR_INVALID, "capacity");
+  DeviceGuard g(c->device);
+  cabac_search_log *log = new (std::nothrow) cabac_search_log;
+  if (!log) return fail(c, CABAC_HIP_ERR_NOMEM, "out of host memory");
+  log->ctx = c;
+  log->coeff_bytes = coeff_bytes;
+  cabac::SearchLogArrays &a = log->a;
+  a.n_chain = n_chain;
+  a.entry_cap = entry_capacity;
+  a.record_cap = record_capacity;
+  a.tu_cap = tu_capacity;
+  a.coeff_cap = coeff_capacity;
+  auto alloc = [](auto **p, size_t bytes) { return hipMalloc(reinterpret_cast<void **>(p), bytes + 16) == hipSuccess; };  // + 16: never empty
+  if (!alloc(&a.counters, sizeof(cabac_search_log_counters)) || !alloc(&a.entries, size_t(entry_capacity) * sizeof(cabac_search_log_entry)) ||
+      !alloc(&a.records, record_capacity * sizeof(uint16_t)) || !alloc(&a.tu, size_t(tu_capacity) * sizeof(cabac_tu_desc)) ||
+      !alloc(&a.tu_at, size_t(tu_capacity) * sizeof(uint32_t)) || !alloc(&a.coeff, coeff_capacity * size_t(coeff_bytes)) ||
+      !alloc(&a.chain_rec, size_t(n_chain) * sizeof(uint32_t)) || !alloc(&a.chain_tu, size_t(n_chain) * sizeof(uint32_t))) {
+    (void)hipGetLastError();
+    log_free(log);
+    return fail(c, CABAC_HIP_ERR_NOMEM, "hipMalloc failed");
+  }
+  hipError_t e = cabac::launch_search_log_reset(c->stream, a);
+  if (e != hipSuccess) {
+    log_free(log);
+    return fail_hip(c, e, "cabac_hip_search_log_create");
+  }
+  c->logs.push_back(log);
+  *out = log;
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_search_log_destroy(cabac_search_log *log) {
+  if (!log) return CABAC_HIP_OK;
+  cabac_hip_ctx *c = log->ctx;
+  DeviceGuard g(c->device);
+  (void)hipStreamSynchronize(c->stream);  // what is queued may still read or write the log
+  c->logs.erase(std::remove(c->logs.begin(), c->logs.end(), log), c->logs.end());
+  log_free(log);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_search_log_reset_device(cabac_search_log *log) {
+  if (!log) return CABAC_HIP_ERR_INVALID;
+  cabac_hip_ctx *c = log->ctx;
+  DeviceGuard g(c->device);
+  HIP_TRY(c, cabac::launch_search_log_reset(c->stream, log->a));
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_search_log_append_device(cabac_search_log *log, uint32_t n_group, const uint32_t *d_pick, const uint32_t *d_group_chain,
+                                       uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu, const void *d_coeff,
+                                       int coeff_bytes, const uint64_t *d_rec_first, const uint16_t *d_records, const uint32_t *d_tu_at) {
+  if (!log) return CABAC_HIP_ERR_INVALID;
+  cabac_hip_ctx *c = log->ctx;
+  if (n_group && (!d_pick || !d_group_chain || !d_cand_first || !d_rec_first)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != log->coeff_bytes) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes is not the log's");
+  if (n_group == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  if (int rc = ensure(c, kLogScratch, cabac::search_log_scratch_bytes(n_group))) return rc;
+  c->timed = false;
+  Timed t(c, 23);
+  HIP_TRY(c, cabac::launch_search_log_append(c->stream, log->a, n_group, d_pick, d_group_chain, n_cand, d_cand_first, d_tu, d_coeff,
+                                             coeff_bytes, d_rec_first, d_records, d_tu_at, c->d_buf[kLogScratch]));
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_search_log_view(const cabac_search_log *log, cabac_search_log_view *view) {
+  if (!log || !view) return CABAC_HIP_ERR_INVALID;
+  const cabac::SearchLogArrays &a = log->a;
+  view->d_counters = a.counters;
+  view->d_entries = a.entries;
+  view->d_records = a.records;
+  view->d_tu = a.tu;
+  view->d_tu_at = a.tu_at;
+  view->d_coeff = a.coeff;
+  view->record_capacity = a.record_cap;
+  view->coeff_capacity = a.coeff_cap;
+  view->n_chain = a.n_chain;
+  view->entry_capacity = a.entry_cap;
+  view->tu_capacity = a.tu_cap;
+  view->coeff_bytes = log->coeff_bytes;
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_search_log_encode_device(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
+                                       uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
+                                       uint32_t *d_tu_info, uint32_t *d_bin_counts) {
+  if (!log) return CABAC_HIP_ERR_INVALID;
+  cabac_hip_ctx *c = log->ctx;
+  if (!d_desc || !d_payload || !d_payload_offsets || !d_results) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  DeviceGuard g(c->device);
+  const cabac::SearchLogArrays &a = log->a;
+  if (!c->h_totals) HIP_TRY(c, hipHostMalloc(&c->h_totals, 64, hipHostMallocDefault));
+  static_assert(sizeof(cabac_search_log_counters) <= 64, "the pinned block of the ctx holds the counters");
+  HIP_TRY(c, hipMemcpyAsync(c->h_totals, a.counters, sizeof(cabac_search_log_counters), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the first wait: the counters size everything below
+  const cabac_search_log_counters cnt = *static_cast<const cabac_search_log_counters *>(c->h_totals);
+  if (cnt.flags & CABAC_SEARCH_LOG_OVERFLOW) {
+    std::string msg = "the log overflowed (an append was dropped):";
+    if (cnt.flags & CABAC_SEARCH_LOG_OVER_ENTRIES) msg += " entry_capacity";
+    if (cnt.flags & CABAC_SEARCH_LOG_OVER_RECORDS) msg += " record_capacity";
+    if (cnt.flags & CABAC_SEARCH_LOG_OVER_BLOCKS) msg += " tu_capacity";
+    if (cnt.flags & CABAC_SEARCH_LOG_OVER_COEFFS) msg += " coeff_capacity";
+    if (cnt.flags & CABAC_SEARCH_LOG_OVER_CHAIN_RECORDS) msg += " 2^32 - 1 records of one chain";
+    return fail(c, CABAC_HIP_ERR_INVALID, msg.c_str());
+  }
+  if (cnt.n_entry > a.entry_cap || cnt.n_record > a.record_cap || cnt.n_tu > a.tu_cap || cnt.n_coeff > a.coeff_cap)
+    return fail(c, CABAC_HIP_ERR_INVALID, "the log's counters are damaged");
+  const uint32_t n_entry = (uint32_t)cnt.n_entry, n_tu = (uint32_t)cnt.n_tu;
+  int rc;
+  if ((rc = ensure(c, kLogDesc, size_t(a.n_chain) * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kLogFirst, (size_t(a.n_chain) + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kLogRec, (cnt.n_record + 8) * sizeof(uint16_t)))) return rc;
+  if ((rc = ensure(c, kLogSplice, size_t(n_tu ? n_tu : 1) * sizeof(cabac_splice)))) return rc;
+  auto *desc2 = static_cast<cabac_substream_desc *>(c->d_buf[kLogDesc]);
+  auto *first = static_cast<uint32_t *>(c->d_buf[kLogFirst]);
+  auto *rec = static_cast<uint16_t *>(c->d_buf[kLogRec]);
+  auto *splices = static_cast<cabac_splice *>(c->d_buf[kLogSplice]);
+  {
+    Timed t(c, 24);
+    HIP_TRY(c, cabac::launch_search_log_place(c->stream, a, d_desc, n_entry, cnt.n_record, n_tu, desc2, first, rec, splices));
+  }
+  return encode_residual_device_impl(c, a.n_chain, desc2, rec, first, splices, n_tu, n_tu, a.tu, a.coeff, log->coeff_bytes, d_payload,
+                                     payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts);
 }
 
 int cabac_hip_host_alloc(size_t bytes, void **out) {

@@ -6,6 +6,9 @@
 
 #include "cabac_hip.h"
 
+struct cabac_search_log_counters;  // cabac_hip_search_emit.h
+struct cabac_search_log_entry;
+
 namespace cabac {
 
 hipError_t launch_ctx_init(hipStream_t st, uint32_t n_sub, const int32_t *qp, const uint32_t *init_id, uint32_t *state,
@@ -83,6 +86,56 @@ hipError_t launch_unit_estimate(hipStream_t st, uint32_t n_item, const uint32_t 
 hipError_t launch_search_select(hipStream_t st, uint32_t n_group, uint32_t n_cand_max, const uint32_t *group_first,
                                 const uint64_t *frac_bits, const uint64_t *dist /* may be null */, uint64_t lambda_q16, uint32_t *pick,
                                 uint64_t *cost);
+
+// the winner log (cabac_search_emit.hip; cabac_hip_search_emit.h): the device arrays of one log and what they hold at most
+struct SearchLogArrays {
+  cabac_search_log_counters *counters;
+  cabac_search_log_entry *entries;
+  uint16_t *records;
+  cabac_tu_desc *tu;
+  uint32_t *tu_at;
+  void *coeff;
+  uint32_t *chain_rec, *chain_tu;  // per chain: the records / blocks of its entries so far
+  uint64_t record_cap, coeff_cap;
+  uint32_t n_chain, entry_cap, tu_cap;
+};
+// the scratch of one append, carved out of one allocation that depends on n_group only: per group what the sizes pass found
+// (chain 0xffffffff: the group appends nothing) and where the scan put it; hdr = {the call fits, the log's coefficient cursor in
+// front of the call, the call's coefficients}
+struct SearchLogScratch {
+  uint64_t *hdr, *rec_src, *n_coeff, *rec_dst, *co_dst /* n_group + 1, relative to the call */;
+  uint32_t *chain, *n_rec, *n_tu, *tu_src, *tu_dst, *entry;
+  size_t bytes;
+};
+inline SearchLogScratch search_log_scratch(void *p, uint32_t n_group) {
+  SearchLogScratch s;
+  const size_t n = n_group;
+  s.hdr = static_cast<uint64_t *>(p);
+  s.rec_src = s.hdr + 4;
+  s.n_coeff = s.rec_src + n;
+  s.rec_dst = s.n_coeff + n;
+  s.co_dst = s.rec_dst + n;
+  s.chain = reinterpret_cast<uint32_t *>(s.co_dst + n + 1);
+  s.n_rec = s.chain + n;
+  s.n_tu = s.n_rec + n;
+  s.tu_src = s.n_tu + n;
+  s.tu_dst = s.tu_src + n;
+  s.entry = s.tu_dst + n;
+  s.bytes = (4 + 4 * n + 1) * sizeof(uint64_t) + 6 * n * sizeof(uint32_t);
+  return s;
+}
+size_t search_log_scratch_bytes(uint32_t n_group);
+hipError_t launch_search_log_reset(hipStream_t st, const SearchLogArrays &log);
+// the three launches of an append: sizes, scan (capacity, entries, cursors), copy; scratch: search_log_scratch_bytes(n_group)
+hipError_t launch_search_log_append(hipStream_t st, const SearchLogArrays &log, uint32_t n_group, const uint32_t *pick,
+                                    const uint32_t *group_chain, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus,
+                                    const void *coeff, int coeff_bytes, const uint64_t *rec_first, const uint16_t *records,
+                                    const uint32_t *tu_at, void *scratch);
+// the chains' entries laid out for launch_splice_plan: desc_out / splice_first (n_chain, n_chain + 1), records (n_record), splices
+// (n_tu); n_entry, n_record, n_tu: the log's counters as the host read them
+hipError_t launch_search_log_place(hipStream_t st, const SearchLogArrays &log, const cabac_substream_desc *desc, uint32_t n_entry,
+                                   uint64_t n_record, uint32_t n_tu, cabac_substream_desc *desc_out, uint32_t *splice_first,
+                                   uint16_t *records, cabac_splice *splices);
 
 // residual parser (cabac_residual.hip): bytes -> coefficient blocks, one substream = blocks [tile_first[s], tile_first[s+1])
 // (cabac_residual_parse.hip); tu_info (may be null): per block scanPosLast | CABAC_TU_INFO_*
