@@ -67,6 +67,10 @@ EXPORTS_SEARCH_EMIT = [
     "cabac_hip_search_log_create", "cabac_hip_search_log_destroy", "cabac_hip_search_log_reset_device",
     "cabac_hip_search_log_append_device", "cabac_hip_search_log_view", "cabac_hip_search_log_encode_device",
 ]
+# include/cabac_hip_parse_unit.h (spliced substreams read back; tests/test_parse_unit_abi.py compares that header with this list)
+EXPORTS_PARSE_UNIT = [
+    "cabac_hip_parse_unit_device", "cabac_hip_parse_unit_batch",
+]
 SEARCH_NO_CHAIN = 0xFFFFFFFF                                     # CABAC_SEARCH_NO_CHAIN
 SEARCH_LOG_OVERFLOW = 0x1                                        # CABAC_SEARCH_LOG_OVERFLOW and the capacity that was too small
 SEARCH_LOG_OVER_ENTRIES, SEARCH_LOG_OVER_RECORDS, SEARCH_LOG_OVER_BLOCKS, SEARCH_LOG_OVER_COEFFS = 0x10, 0x20, 0x40, 0x80
@@ -83,6 +87,16 @@ NAL_OVERFLOW, NAL_TRAILING_ZERO, NAL_FORBIDDEN, NAL_BAD_ESCAPE, NAL_LOC_OVERFLOW
 
 _lib = None
 vp = ctypes.c_void_p
+
+
+def splices_to_tu_at(splices):
+    """One substream's sorted cabac_splice list (SPLICE_DTYPE: at, tu) -> (block order, tu_at): the indices into tus[] in coded
+    order and the position of each in the substream's side run — with the records and descriptors handed to
+    encode_residual_device everything parse_unit_device needs to read that substream back."""
+    splices = np.ascontiguousarray(splices, SPLICE_DTYPE)
+    if len(splices) > 1 and (np.diff(splices["at"].astype(np.int64)) < 0).any():
+        raise ValueError("the splice list is not sorted by `at`")
+    return splices["tu"].astype(np.uint32), splices["at"].astype(np.uint32)
 
 
 class SearchLogView(ctypes.Structure):
@@ -187,6 +201,9 @@ def load_library():
     L.cabac_hip_search_unit_round_batch.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, ctypes.c_uint64,
                                                     vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, ctypes.c_uint64,
                                                     vp, vp, vp, vp, vp]
+    L.cabac_hip_parse_unit_device.argtypes = [vp, ctypes.c_uint32] + [vp] * 7 + [ctypes.c_int] + [vp] * 3
+    L.cabac_hip_parse_unit_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, ctypes.c_uint64, vp,
+                                             ctypes.c_int, ctypes.c_uint64, vp, vp, vp]
     L.cabac_hip_search_log_create.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                               ctypes.c_int, ctypes.POINTER(vp)]
     L.cabac_hip_search_log_destroy.argtypes = [vp]
@@ -342,7 +359,7 @@ class CabacHip:
         (the list is at cabac_hip_profile_read in include/cabac_hip.h; 12 in cabac_hip_estimate.h; 13 nal escape and 14 nal unescape in
         cabac_hip_nal.h; 15 residual estimate with contexts, 16 search select, 17 / 18 a round's estimate / commit in
         cabac_hip_search.h; 19 unit estimate, 20 / 21 / 22 a unit round's estimate / select / commit in cabac_hip_search_unit.h; 23 log append and
-        24 log place in cabac_hip_search_emit.h)."""
+        24 log place in cabac_hip_search_emit.h; 25 unit parse in cabac_hip_parse_unit.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -628,6 +645,43 @@ class CabacHip:
         if with_info:
             return coeff[: int(n_coeff_total)], res[: len(desc)], info[: len(tus)]
         return coeff[: int(n_coeff_total)], res[: len(desc)]
+
+    # ---- spliced substreams read back (include/cabac_hip_parse_unit.h) ------
+    def parse_unit_device(self, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_records, d_coeff, d_side_bins, d_results,
+                          d_tu_info=0, int16=False):
+        """cabac_hip_parse_unit_device: substream s = its side run d_records[rec_offset .. + n_records) with the blocks
+        d_tu[d_tile_first[s] .. d_tile_first[s + 1]) coded in front of index d_tu_at[t] of that run (d_tu_at = 0: behind it), read
+        back in one walk on one context store: blocks to d_coeff, side bins to d_side_bins[rec_offset + i]."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_parse_unit_device(
+            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), opt(d_tu), opt(d_tu_at), opt(d_records), opt(d_coeff),
+            2 if int16 else 4, opt(d_side_bins), opt(d_tu_info), vp(d_results)))
+
+    def parse_unit_batch(self, desc, data, tile_first, tus, tu_at, records, n_coeff_total, check=True, int16=False, coeff=None,
+                         side_bins=None, with_info=False):
+        """Host arrays through cabac_hip_parse_unit_batch (synchronous): (coeff, side_bins, results[, info]).  `coeff` /
+        `side_bins` (optional): the caller's arrays, written in place; tu_at may be None."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        data = np.ascontiguousarray(data, np.uint8)
+        tile_first = np.ascontiguousarray(tile_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        records = np.ascontiguousarray(records, np.uint16)
+        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
+        assert len(tile_first) == len(desc) + 1 and (tu_at is None or len(tu_at) == len(tus))
+        if coeff is None:
+            coeff = np.zeros(max(int(n_coeff_total), 1), np.int16 if int16 else np.int32)
+        if side_bins is None:
+            side_bins = np.zeros(max(len(records), 1), np.uint8)
+        assert coeff.dtype == (np.int16 if int16 else np.int32) and side_bins.dtype == np.uint8
+        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
+        info = np.zeros(max(len(tus), 1), np.uint32)
+        rc = self.L.cabac_hip_parse_unit_batch(
+            self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data,
+            tu_at.ctypes.data if tu_at is not None else None, records.ctypes.data, len(records), coeff.ctypes.data,
+            2 if int16 else 4, int(n_coeff_total), side_bins.ctypes.data, info.ctypes.data, res.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        out = (coeff[: int(n_coeff_total)], side_bins[: len(records)], res[: len(desc)])
+        return out + (info[: len(tus)],) if with_info else out
 
     def residual_batch(self, tus, coeff, check=True):
         """Host arrays in, (records, offsets, info) out (cabac_hip_residual_batch: both passes, synchronous)."""

@@ -19,6 +19,7 @@
 #include "cabac_hip.h"
 #include "cabac_hip_estimate.h"
 #include "cabac_hip_nal.h"
+#include "cabac_hip_parse_unit.h"
 #include "cabac_hip_search.h"
 #include "cabac_hip_search_emit.h"
 #include "cabac_hip_search_unit.h"
@@ -47,8 +48,9 @@ struct cabac_hip_ctx {
   // device staging for the host-pointer entry points (grown on demand)
   // [5]: scratch of the residual binariser, [6]: compacted payload, [7]: payload offsets; [8..]: the spliced-residual path
   // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
-  // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included); [48..]: the winner log (kLog* below)
-  static constexpr int kSlots = 53;
+  // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included); [48..]: the winner log (kLog* below); [53..]: the
+  // unit parse (kUnit* below)
+  static constexpr int kSlots = 56;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -1051,6 +1053,117 @@ int cabac_hip_residual_parse_batch16(cabac_hip_ctx *c, uint32_t n_sub, const cab
                                      uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, int16_t *coeff,
                                      uint64_t n_coeff_total, uint32_t *tu_info, cabac_substream_result *results) {
   return residual_parse_batch_impl(c, n_sub, desc, bytes, bytes_total, tile_first, tus, coeff, 2, n_coeff_total, tu_info, results);
+}
+
+// ---- spliced substreams read back (declared in cabac_hip_parse_unit.h; the side-walking instantiation of the parser) ----------
+namespace {
+enum { kUnitRecords = 53, kUnitTuAt = 54, kUnitBins = 55 };
+}
+
+int cabac_hip_parse_unit_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                const uint16_t *d_records, void *d_coeff, int coeff_bytes, uint8_t *d_side_bins, uint32_t *d_tu_info,
+                                cabac_substream_result *d_results) {
+  // d_tu / d_coeff belong to the blocks, d_records / d_side_bins to the runs: either kind may be absent altogether
+  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  Bracket br = bracket_for(c, 25);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_unit_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_records, d_coeff, coeff_bytes,
+                                      d_side_bins, d_tu_info, d_results));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_parse_unit_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                               uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                               const uint16_t *records, uint64_t n_records_total, void *coeff, int coeff_bytes, uint64_t n_coeff_total,
+                               uint8_t *side_bins, uint32_t *tu_info, cabac_substream_result *results) {
+  if (!c || (n_sub && (!desc || !bytes || !tile_first || !results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  const uint32_t n_tu = tile_first[n_sub];
+  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_records_total && (!records || !side_bins)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  for (uint32_t s = 0; s < n_sub; s++) {
+    if (tile_first[s] > tile_first[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "tile_first must not decrease");
+    if (desc[s].byte_offset > bytes_total || desc[s].byte_capacity > bytes_total - desc[s].byte_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "bytes out of range");
+    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
+    const uint64_t n_rec = desc[s].n_records;
+    if (desc[s].rec_offset > n_records_total || n_rec > n_records_total - desc[s].rec_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "a side run leaves n_records_total");
+    uint32_t at = 0;
+    for (uint32_t t = tile_first[s]; tu_at && t < tile_first[s + 1]; t++) {
+      if (tu_at[t] < at) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at decreases inside a substream");
+      if (tu_at[t] > n_rec) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at exceeds the substream's run length");
+      at = tu_at[t];
+    }
+    for (uint64_t i = 0; i < n_rec; i++) {
+      const uint32_t id = records[desc[s].rec_offset + i] & CABAC_REC_ID_MASK;
+      if (id >= CABAC_NUM_CONTEXTS && id < CABAC_REC_ALIGN) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "bad side record: substream %u, record %llu of its run (id 0x%x)", s, (unsigned long long)i, id);
+        return fail(c, CABAC_HIP_ERR_INVALID, buf);
+      }
+    }
+  }
+  for (uint32_t t = 0; t < n_tu; t++) {
+    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, writes nothing
+    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
+    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
+  }
+  DeviceGuard g(c->device);
+  int rc;
+  // staging as cabac_hip_residual_parse_batch: [0] substream descriptors, [2] bytes, [3] tile_first then block descriptors, [1]
+  // coefficients, [4] results, [6] info words; the runs, the positions and the side bins in slots of their own
+  const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), first_pad = (first_bytes + 15) / 16 * 16;
+  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, 2, bytes_total + 4))) return rc;
+  if ((rc = ensure(c, 3, first_pad + size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
+  if ((rc = ensure(c, 1, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
+  if ((rc = ensure(c, 4, n_sub * sizeof(cabac_substream_result)))) return rc;
+  if ((rc = ensure(c, 6, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kUnitRecords, size_t(n_records_total) * sizeof(uint16_t)))) return rc;
+  if ((rc = ensure(c, kUnitTuAt, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kUnitBins, size_t(n_records_total)))) return rc;
+  uint8_t *d_first = static_cast<uint8_t *>(c->d_buf[3]);
+  auto up = [&](void *dst, const void *src, size_t n) {
+    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+  };
+  auto down = [&](void *dst, const void *src, size_t n) {
+    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  };
+  HIP_TRY(c, up(c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc)));
+  HIP_TRY(c, up(c->d_buf[2], bytes, bytes_total));
+  HIP_TRY(c, up(d_first, tile_first, first_bytes));
+  HIP_TRY(c, up(d_first + first_pad, tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
+  HIP_TRY(c, up(c->d_buf[kUnitRecords], records, size_t(n_records_total) * sizeof(uint16_t)));
+  if (tu_at) HIP_TRY(c, up(c->d_buf[kUnitTuAt], tu_at, size_t(n_tu) * sizeof(uint32_t)));
+  // what the walk does not write keeps the caller's values (int32 blocks, side bins) or is zero (int16 blocks: output only)
+  HIP_TRY(c, up(c->d_buf[kUnitBins], side_bins, size_t(n_records_total)));
+  if (n_tu && coeff_bytes == 4) HIP_TRY(c, up(c->d_buf[1], coeff, n_coeff_total * sizeof(int32_t)));
+  if (n_tu && n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(c->d_buf[1], 0, n_coeff_total * sizeof(int16_t), c->stream));
+  rc = cabac_hip_parse_unit_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
+                                   (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad),
+                                   tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr, (const uint16_t *)c->d_buf[kUnitRecords],
+                                   c->d_buf[1], coeff_bytes, (uint8_t *)c->d_buf[kUnitBins], (uint32_t *)c->d_buf[6],
+                                   (cabac_substream_result *)c->d_buf[4]);
+  if (rc) return rc;
+  if (tu_info) HIP_TRY(c, down(tu_info, c->d_buf[6], size_t(n_tu) * sizeof(uint32_t)));
+  if (n_tu) HIP_TRY(c, down(coeff, c->d_buf[1], n_coeff_total * size_t(coeff_bytes)));
+  HIP_TRY(c, down(side_bins, c->d_buf[kUnitBins], size_t(n_records_total)));
+  HIP_TRY(c, down(results, c->d_buf[4], n_sub * sizeof(cabac_substream_result)));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int status = CABAC_HIP_OK;
+  for (uint32_t s = 0; s < n_sub; s++)
+    if (results[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
+  if (status) c->last_error = "substream flag set (see results[].flags)";
+  return status;
 }
 
 // ---- coefficients -> bytes (cabac_splice.hip) -------------------------------------------------------------------

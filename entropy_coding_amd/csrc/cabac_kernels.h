@@ -142,6 +142,13 @@ hipError_t launch_search_log_place(hipStream_t st, const SearchLogArrays &log, c
 hipError_t launch_residual_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
                                  const uint32_t *tile_first, const cabac_tu_desc *tus, void *coeff, int coeff_bytes /* 4 or 2 */,
                                  uint32_t *tu_info, cabac_substream_result *results);
+// its side-walking instantiation (cabac_hip_parse_unit.h): substream s = the side records records[desc[s].rec_offset .. +
+// n_records) with block t spliced in front of index tu_at[t] of that run (tu_at null: behind the run), all on one context store;
+// side_bins[rec_offset + i] receives the bin of side record i
+hipError_t launch_unit_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                             const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint16_t *records,
+                             void *coeff, int coeff_bytes /* 4 or 2 */, uint8_t *side_bins, uint32_t *tu_info,
+                             cabac_substream_result *results);
 
 // residual records spliced into host-recorded substreams (cabac_splice.hip); array sizes: pre n_splice + n_sub + 1,
 // sub_n / sub_cap / rec_base / byte_base n_sub, seen n_tu, err 1, totals 3 ({records, bytes, error})

@@ -61,9 +61,12 @@ constexpr uint32_t kCtxSlots = 232;
 constexpr uint32_t kBlkWords = 1024;   // coded region of a block, pitch = its coded width
 __host__ __device__ constexpr uint32_t slot_of(uint32_t id) { return id < 292u ? id - 86u : id < 312u ? id - 310u + 206u : id - 357u + 208u; }
 __device__ __forceinline__ uint32_t id_of_slot(uint32_t s) { return s < 206u ? s + 86u : s < 208u ? s - 206u + 310u : s - 208u + 357u; }
-#define SL_A(id) ((id) - 86u)            /* ids 86..291 */
-#define SL_TS(id) ((id) - 357u + 208u)   /* ids 357..378 */
-#define SL_TS_FLAG(ch) (206u + (ch))
+// D: the decoder type of the walk.  The side-walking instantiation (unit parse, below) keeps all 379 contexts and uses the id as
+// the slot; either way a block's slots are compile-time arithmetic on the ids.
+#define SL_A(id) (D::kIdSlots ? (id) : (id) - 86u)                    /* ids 86..291 */
+#define SL_TS(id) (D::kIdSlots ? (id) : (id) - 357u + 208u)           /* ids 357..378 */
+#define SL_TS_FLAG(ch) (D::kIdSlots ? 310u + (ch) : 206u + (ch))
+constexpr uint32_t kSideCtxSlots = 380;  // the side walk's store: slot = ctxId, 0..378
 
 // Per coefficient-group shape: which scan positions of the group lie in the five-sample template of each position
 // (context_modelling.hpp:71-117: right, right+1, below-right, below, below+1), and for transform-skip blocks the
@@ -115,10 +118,11 @@ __device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) { return (uint
 // ---------------------------------------------------------------------------------------------------------------
 // arithmetic decoder
 
-template <bool kS>
+template <bool kS, bool kIds = false>
 struct PDecT {
-  // kS: this wave keeps the decoder on the SCALAR unit (see pd_bin)
+  // kS: this wave keeps the decoder on the SCALAR unit (see pd_bin); kIds: the context store is indexed by ctxId (SL_A)
   static constexpr bool kScalar = kS;
+  static constexpr bool kIdSlots = kIds;
   uint32_t hi, lo;   // window (wave-uniform, kept in vector registers): value in bits 62..47
   uint32_t range;    //   "
   int32_t look;      //   "   valid look-ahead bits below bit 47
@@ -656,14 +660,22 @@ __device__ __forceinline__ void parse_ts(D &d, uint4 *ctx, int32_t *blk, const L
 
 // C: the type the coefficients are stored as — int32_t (the reference's TCoeff) or int16_t (streams of 15-bit dynamic range: half
 // the bytes back over PCIe for the host-pointer path; a level that does not fit sets CABAC_RES_RANGE and is stored truncated)
-template <int W, class C>
-__global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
-                                                                  const uint8_t *__restrict__ bytes,
-                                                                  const uint32_t *__restrict__ tile_first,
-                                                                  const cabac_tu_desc *__restrict__ tus, C *__restrict__ coeff_all,
-                                                                  uint32_t *__restrict__ tu_info,
-                                                                  cabac_substream_result *__restrict__ results) {
-  __shared__ uint4 ctx_all[W * kCtxSlots];
+//
+// kSide (cabac_hip_parse_unit.h): the substream is a run of side records with the blocks spliced in at positions.  The walk then
+// alternates between the block walk above and a record walk in the manner of cabac_hip_decode_device on ONE context store of all
+// 379 contexts (slot = ctxId).  The records are fetched as the input bytes are: 64 at a time, one coalesced 2-byte load per
+// lane, the next 64 a step ahead, a record reaching the scalar side by v_readlane; the decoded bins are collected in the lanes
+// (lane i holds the bin of record i of the group) and stored 64 at a time, a partial group in front of every block and at a stop.
+template <int W, class C, bool kSide>
+__device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+                                           const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ tile_first,
+                                           const cabac_tu_desc *__restrict__ tus, C *__restrict__ coeff_all,
+                                           uint32_t *__restrict__ tu_info, cabac_substream_result *__restrict__ results,
+                                           const uint32_t *__restrict__ tu_at, const uint16_t *__restrict__ records,
+                                           uint8_t *__restrict__ side_bins) {
+  constexpr uint32_t kSlots = kSide ? kSideCtxSlots : kCtxSlots;
+  __shared__ uint4 ctx_all[W * kSlots];
+  __shared__ uint32_t side_park[kSide ? W : 1];  // the record cursor while a block is walked: out of the block walk's scalar registers
   __shared__ int32_t blk_all[W * kBlkWords];
   __shared__ LdsTables tab;
   // Placement: the walk is bound by what the waves of a CU share (instruction issue, the scalar unit), so the waves must
@@ -685,14 +697,14 @@ __global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, 
   }
   const uint32_t sub = rfl(blockIdx.x * W + wave);
   const bool live = sub < n_sub;
-  uint4 *ctx = ctx_all + wave * kCtxSlots;
+  uint4 *ctx = ctx_all + wave * kSlots;
   int32_t *blk = blk_all + wave * kBlkWords;
   const cabac_substream_desc dsc = desc[live ? sub : 0];
   {
     const int qp = dsc.qp < 0 ? 0 : (dsc.qp > 63 ? 63 : dsc.qp);
     const uint32_t iid = dsc.init_id & 3u;
-    for (uint32_t k = lane; k < 230u; k += 64u) {
-      const uint32_t id = id_of_slot(k);
+    for (uint32_t k = lane; k < (kSide ? (uint32_t)CABAC_NUM_CONTEXTS : 230u); k += 64u) {
+      const uint32_t id = kSide ? k : id_of_slot(k);
       const uint32_t packed = ctx2_init(qp, c_init_tables[iid * kNumCtx + id], c_init_tables[3 * kNumCtx + id]);
       const uint32_t r0 = (packed & 3u) + 2u, r1 = ((packed >> 2) & 7u) + 5u;
       ctx[k] = make_uint4(packed & ~31u, r0 | (r1 << 16), ((0x7fffu >> r0) & kMask0) | (((0x7fffu >> r1) & kMask1) << 16), 0u);
@@ -710,7 +722,8 @@ __global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, 
   const bool scalar_wave = CABAC_PARSE_SCALAR_WAVES == 2 ||
                            (CABAC_PARSE_SCALAR_WAVES == 1 && (__builtin_amdgcn_s_getreg((4) | (0 << 6) | (3 << 11)) & 1u) != 0u);   // HW_ID.wave_id[3:0]
   auto walk = [&](auto kind) {
-  PDecT<decltype(kind)::value> d;
+  typedef PDecT<decltype(kind)::value, kSide> D;
+  D d;
   d.lane = lane;
   d.cap = dsc.byte_capacity;
   const uint8_t *src = bytes + dsc.byte_offset;
@@ -734,7 +747,73 @@ __global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, 
 
   const uint32_t t_end = bad_start ? tile_first[sub] : tile_first[sub + 1];
   PP_TICK(k0);
-  for (uint32_t t = tile_first[sub]; t < t_end; t++) {
+  // side walk: i = the next record of the run, n_rec its length; rec_cur / rec_nxt = records 64 * (i >> 6) + lane and the 64
+  // behind them; bins_v = the bins of the current group, stored from record `stored` on
+  const uint32_t n_rec = (kSide && !bad_start) ? dsc.n_records : 0u;
+  uint32_t rec_i = 0, stored = 0, rec_cur = 0, rec_nxt = 0, bins_v = 0;
+  auto load_records = [&](uint32_t group) {
+    const uint32_t k = 64u * group + lane;
+    return k < n_rec ? (uint32_t)records[dsc.rec_offset + k] : 0u;
+  };
+  auto store_bins = [&](uint32_t upto) {  // lane = record of the current group: the bins of records [stored, upto)
+    const uint32_t k = ((upto - 1u) & ~63u) + lane;
+    if (k >= stored && k < upto) side_bins[dsc.rec_offset + k] = (uint8_t)bins_v;
+  };
+  if (kSide && n_rec != 0u) {
+    rec_cur = load_records(0u);
+    rec_nxt = load_records(1u);
+  }
+  for (uint32_t t = tile_first[sub]; kSide || t < t_end; t++) {
+    if (kSide) {
+      // at(t) = min(max(tu_at[t], at(t - 1)), n_rec); behind the last block the rest of the run
+      uint32_t upto = n_rec;
+      if (t < t_end && tu_at) upto = min(max(tu_at[t], rec_i), n_rec);
+      bool bad = false;
+      while (rec_i < upto) {
+        pd_check(d);  // 32 look-ahead bits; a record consumes at most 7
+        const uint32_t id = rl(rec_cur, rec_i & 63u) & CABAC_REC_ID_MASK;
+        uint32_t bin = 0;
+        if (id < (uint32_t)CABAC_NUM_CONTEXTS) {
+          bin = pd_bin(d, ctx, id);
+        } else if (id == CABAC_REC_EP) {
+          bin = pd_ep(d);
+        } else if (id == CABAC_REC_TRM) {  // decodeBinTrm, arith_codec.cpp:181-197: decoding goes on whatever the bin is
+          const uint32_t range = rfl(d.range) - 2u;
+          bin = rfl(d.hi) >= (range << 22) ? 1u : 0u;
+          d.range = range;
+          if (!bin && range < 256u) {
+            const uint64_t v = (((uint64_t)d.hi << 32) | d.lo) << 1;
+            d.hi = (uint32_t)(v >> 32);
+            d.lo = (uint32_t)v;
+            d.look -= 1;
+            d.range = range << 1;
+          }
+        } else if (id == CABAC_REC_ALIGN) {
+          d.range = 256u;
+        } else {
+          bad = true;  // no record of the codec: the substream stops in front of it
+          break;
+        }
+        bins_v = lane == (rec_i & 63u) ? bin : bins_v;
+        rec_i++;
+        if ((rec_i & 63u) == 0u) {
+          store_bins(rec_i);
+          stored = rec_i;
+          rec_cur = rec_nxt;
+          rec_nxt = load_records((rec_i >> 6) + 1u);
+        }
+      }
+      if (stored < rec_i) {  // a partial group: in front of every block and at a stop
+        store_bins(rec_i);
+        stored = rec_i;
+      }
+      if (bad) {
+        flags_out |= CABAC_RES_BAD_RECORD;
+        break;
+      }
+      if (t >= t_end) break;
+      if (lane == 0u) side_park[wave] = rec_i;
+    }
     PP_TICK(b0);
     const cabac_tu_desc tu = tus[t];
     BlockGeom g;
@@ -786,6 +865,7 @@ __global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, 
 #ifdef CABAC_PARSE_PROFILE
     if (blockIdx.x == 0 && threadIdx.x == 0) g_parse_prof[12] += 1;  // blocks
 #endif
+    if (kSide) stored = rec_i = rfl(side_park[wave]);  // (the barriers of the write-out order the lanes' accesses)
   }
   PP_TICK(k1);
   PP_ADD(8, k0, k1);
@@ -807,8 +887,9 @@ __global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, 
   uint32_t trm = 1;
   // (not after a refused block or a refused start: the parse stopped before the end of the substream.  CABAC_RES_RANGE does
   // not stop anything.)
+  // (the side walk has no implied terminate bin: it is a side record; CABAC_SUB_FINISH is the stop check alone)
   const bool finish = (dsc.init_id & CABAC_SUB_FINISH) && !(flags_out & (CABAC_RES_BAD_RECORD | CABAC_RES_BAD_STOP));
-  if (finish) {
+  if (finish && !kSide) {
     pd_check(d);
     const uint32_t range = rfl(d.range) - 2u, hi = rfl(d.hi);
     trm = hi >= (range << 22) ? 1u : 0u;
@@ -844,6 +925,26 @@ __global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, 
   else walk(std::false_type{});
 }
 
+template <int W, class C>
+__global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+                                                                  const uint8_t *__restrict__ bytes,
+                                                                  const uint32_t *__restrict__ tile_first,
+                                                                  const cabac_tu_desc *__restrict__ tus, C *__restrict__ coeff_all,
+                                                                  uint32_t *__restrict__ tu_info,
+                                                                  cabac_substream_result *__restrict__ results) {
+  parse_walk<W, C, false>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, nullptr, nullptr, nullptr);
+}
+
+template <int W, class C>
+__global__ __launch_bounds__(64 * W) void unit_parse_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+                                                              const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ tile_first,
+                                                              const cabac_tu_desc *__restrict__ tus, const uint32_t *__restrict__ tu_at,
+                                                              const uint16_t *__restrict__ records, C *__restrict__ coeff_all,
+                                                              uint8_t *__restrict__ side_bins, uint32_t *__restrict__ tu_info,
+                                                              cabac_substream_result *__restrict__ results) {
+  parse_walk<W, C, true>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, tu_at, records, side_bins);
+}
+
 #ifdef CABAC_PARSE_PROFILE
 hipError_t debug_read_parse_waves(unsigned long long *out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_parse_wave), sizeof(unsigned long long) * 3 * 8192);
@@ -869,6 +970,32 @@ static hipError_t launch_residual_parse_as(hipStream_t st, uint32_t n_sub, const
     hipLaunchKernelGGL((residual_parse_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, coeff, tu_info,
                        results);
   return hipGetLastError();
+}
+
+template <class C>
+static hipError_t launch_unit_parse_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                       const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                                       const uint16_t *records, C *coeff, uint8_t *side_bins, uint32_t *tu_info,
+                                       cabac_substream_result *results) {
+  // the parser's geometry and threshold
+  if (n_sub >= 1024u)
+    hipLaunchKernelGGL((unit_parse_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at,
+                       records, coeff, side_bins, tu_info, results);
+  else
+    hipLaunchKernelGGL((unit_parse_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at, records,
+                       coeff, side_bins, tu_info, results);
+  return hipGetLastError();
+}
+
+hipError_t launch_unit_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                             const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint16_t *records,
+                             void *coeff, int coeff_bytes, uint8_t *side_bins, uint32_t *tu_info, cabac_substream_result *results) {
+  if (n_sub == 0) return hipSuccess;
+  if (coeff_bytes == 2)
+    return launch_unit_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, records, static_cast<int16_t *>(coeff), side_bins, tu_info, results);
+  if (coeff_bytes == 4)
+    return launch_unit_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, records, static_cast<int32_t *>(coeff), side_bins, tu_info, results);
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_residual_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
