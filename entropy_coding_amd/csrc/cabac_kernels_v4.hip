@@ -8,7 +8,7 @@
 // the chain is written with per-lane (row-uniform) vector arithmetic, so one instruction advances FOUR bins;
 // the record of step i is delivered to its row with a DPP row broadcast (v_mov_b32_dpp row_newbcast:i — one
 // instruction, no LDS, no scalar round trip).  Everything row-divergent is mask arithmetic; the only
-// branches are the rare ones (output of whole 16-bit units, input refill).
+// branches are the rare ones (output of whole 16-bit units; the decoder's input has none).
 //
 //  encode: per 16-bin step  (a) quad_resolve: the context state each of the 16 bins of a row sees (match-any
 //          on ctxId, then every lane applies the earlier bins of its context itself);  (b) 16 unrolled
@@ -19,7 +19,8 @@
 //          outstanding 0xFF) is the same algorithm in base 2^16 (buffered unit + count of outstanding
 //          0xFFFF).  The emitted stream is the identical number: the top S+1 bits of low >> 8 with
 //          carries resolved (S = bits shifted), which is what finish() (:339-357) leaves.
-//  decode: a 64-bit look-ahead window per row; after each bin every lane applies it to its own
+//  decode: a 64-bit look-ahead window per row, topped up from a bit cursor every fourth bin without a
+//          branch; after each bin every lane applies it to its own
 //          copy of the context state and the lanes of that row holding the same ctxId keep it.
 //  estimate: BitEstimator_Std on the same records — quad_resolve plus a table lookup, no chain.
 //
@@ -1304,10 +1305,13 @@ struct QuadDec {   // row-uniform values
   uint32_t hi, lo;   // 64-bit window: value in [62:47] (see v2)
   int32_t look;
   uint32_t range;
-  uint32_t rp;       // byte offset of the next unread 16-bit unit
-  uint32_t q_hi, q_lo;  // the two ring dwords from the one that holds that unit (big-endian: first unit on top),
-                     // fetched by the previous check
-  uint32_t *ring;    // this row's input ring in LDS: 64 byte-swapped dwords (+ dword 64 = a copy of dword 0)
+  uint32_t npos;     // bit cursor, complemented: ~pos, pos = the substream bits moved into the window so far (bits 5..10 of
+                     // ~pos are 63 - the ring dword that holds bit pos: the ring runs backwards, see below)
+  uint32_t q_hi, q_lo;  // the two ring dwords from the one that holds bit `pos` (big-endian: first bit on top),
+                     // fetched by the previous top-up
+  uint32_t *ring;    // this row's input ring in LDS: 64 byte-swapped dwords, BACKWARDS — dword k of the substream at
+                     // 64 - (k & 63), so that an ascending pair of LDS words is (q_lo, q_hi), a 64-bit register pair as it
+                     // is read — and word 0 = a copy of word 64 (the pair that starts at dword 63 ends with dword 64 = 0)
   uint32_t filled;   // bytes of the substream staged into the ring so far (a multiple of 64)
   uint32_t pf_data, pf_off, pf_mask;  // a 64-byte block on its way: this lane's dword, its byte offset, wanted or not
   const uint8_t *src;
@@ -1331,34 +1335,30 @@ struct QuadDecInfo {
 };
 
 // Input.  The substream is staged into an LDS ring in 64-byte blocks — one dword per lane, byte-swapped so that
-// the first of its two 16-bit units is on top — by quad_dec_stage_load / _store below (every 4th step, a block
-// whenever fewer than 128 bytes are staged ahead; 4 steps consume at most 48).  A check takes its units from
-// (q_hi, q_lo), two ring dwords read by the PREVIOUS check, and reads the two dwords for the next one: no global
-// memory and no wait anywhere near the chain.
+// the first bit is on top — by quad_dec_stage_load / _store below (every 4th step, a block whenever fewer than
+// 128 bytes are staged ahead of the cursor; 4 steps consume at most 48).
 //
-// Append one 16-bit unit to the window of every row that has fewer than 32 valid look-ahead bits: mask
-// arithmetic for all rows at once, no branch (the callers branch on scalar masks computed a step earlier).
-template <bool kSecond>
-__device__ __forceinline__ void quad_dec_refill(QuadDec &w, uint32_t units) {  // units: the next two, first on top
-  // look is 2..47 here, so "fewer than 32" is bit 5 clear
-  const uint32_t take = ~(uint32_t)((int32_t)(w.look << 26) >> 31);
-  const uint32_t unit = (kSecond ? (units & 0xffffu) : (units >> 16)) & take;
-  const uint64_t add = (uint64_t)unit << ((31 - w.look) & 63);
-  w.hi |= (uint32_t)(add >> 32);
-  w.lo |= (uint32_t)add;
-  w.look += (int32_t)(16u & take);
-  w.rp += 2u & take;
-}
-
-// one check: up to two units per row, then the ring dwords for the next check
-__device__ __forceinline__ void quad_dec_check(QuadDec &w, bool second) {
-  const uint64_t q = (((uint64_t)w.q_hi << 32) | w.q_lo) << ((w.rp & 2u) << 3);  // rp odd unit: skip the first one
-  const uint32_t units = (uint32_t)(q >> 32);
-  quad_dec_refill<false>(w, units);
-  if (second) quad_dec_refill<true>(w, units);  // look >= 2 here, so two units always reach 32
-  const uint32_t at = (w.rp >> 2) & 63u;
-  w.q_hi = w.ring[at];
-  w.q_lo = w.ring[at + 1u];  // at == 63: dword 64 mirrors dword 0
+// Top-up, every fourth bin, without a question asked: the window is filled to all 63 bits below the sign bit
+// (look = 47).  Four bins consume at most 24 bits, so look is 23..47 here, the 47 - look missing bits lie wholly
+// in `lo`, and they are the top of the 32 stream bits at `pos` — cut out of (q_hi, q_lo), two ring dwords read
+// by the PREVIOUS top-up, which also reads the two dwords for the next one: no global memory, no compare, no
+// branch and no wait anywhere near the chain.  Both shift counts have an edge that the hardware takes modulo 32:
+// pos & 31 == 0 (the 64-bit shift by 0 leaves q_hi on top) and look == 47 (offset 32, but v_bfe_u32 with a width
+// of 0 returns 0 whatever its offset).  Reading ahead never changes a decision: a bit enters the comparison only
+// when it reaches bit 54 of the window, and it is the same bit of the stream whenever it was appended (past the
+// end of the substream: a zero, as the staging feeds them).
+__device__ __forceinline__ void quad_dec_topup(QuadDec &w) {
+  const uint64_t q = (((uint64_t)w.q_hi << 32) | w.q_lo) << (~w.npos & 31u);
+  const uint32_t next32 = (uint32_t)(q >> 32);      // stream bits pos .. pos + 31
+  const uint32_t want = 47u - (uint32_t)w.look;     // 0..24
+  uint32_t add;                                     // next32 >> (32 - want), 0 for want == 0
+  asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(add) : "v"(next32), "v"((uint32_t)w.look - 15u), "v"(want));
+  w.lo |= add;
+  w.npos -= want;
+  w.look = 47;
+  const uint32_t *p = w.ring + ((w.npos >> 5) & 63u);  // 63 - dword: the second of the pair (dword 64 = dword 0 sits at 0)
+  w.q_lo = p[0];
+  w.q_hi = p[1];
 }
 
 // staging, part 1 (a step whose number is 0 mod 4): request the next block (one dword per lane of the substream: 64 bytes
@@ -1366,7 +1366,7 @@ __device__ __forceinline__ void quad_dec_check(QuadDec &w, bool second) {
 template <int L = 16>
 __device__ __forceinline__ void quad_dec_stage_load(QuadDec &w, uint32_t j) {
   constexpr uint32_t kLanes = L > 16 ? 16u : (uint32_t)L;  // a block is at most 64 bytes (the ring holds 256)
-  const uint32_t wanted = neg_mask(w.filled - w.rp - 128u);  // fewer than 128 bytes ahead (filled >= rp always)
+  const uint32_t wanted = neg_mask(w.filled - (~w.npos >> 3) - 128u);  // fewer than 128 bytes ahead of the cursor (never behind it)
   w.pf_mask = L > 16 ? wanted & neg_mask(j - kLanes) : wanted;  // (with 64 lanes per substream the first 16 fetch)
   w.pf_off = w.filled + 4u * (j & (kLanes - 1u));
   w.pf_data = *reinterpret_cast<const uint32_t *>(w.src_safe + min(w.pf_off, w.last_dword));
@@ -1376,8 +1376,8 @@ __device__ __forceinline__ void quad_dec_stage_load(QuadDec &w, uint32_t j) {
 __device__ __forceinline__ void quad_dec_stage_store(QuadDec &w) {
   const uint32_t v = __builtin_bswap32(w.pf_data) & neg_mask(w.pf_off - w.cap);
   const uint32_t at = (w.pf_off >> 2) & 63u;
-  w.ring[sel(w.pf_mask, at, 65u)] = v;                                  // dword 65: nobody reads it
-  w.ring[sel(w.pf_mask & neg_mask(at - 1u), 64u, 65u)] = v;             // at == 0: also the mirror
+  w.ring[sel(w.pf_mask, 64u - at, 65u)] = v;                            // word 65: nobody reads it
+  w.ring[sel(w.pf_mask & neg_mask(at - 1u), 0u, 65u)] = v;              // at == 0: also the mirror
 }
 
 constexpr uint32_t kRingStride = 66;  // 64 ring dwords + the mirror of dword 0 + a dump word
@@ -1423,17 +1423,6 @@ template <int I, bool kSpecial, int L = 16>
 __device__ __forceinline__ void quad_dec_step(const QuadDecInfo &f, const QuadDecRow<L> &u, uint32_t r0_v, uint32_t a_v, uint32_t &st_v,
                                               uint32_t (&bits)[2], QuadDec &w) {
   constexpr int J = I % QuadDecRow<L>::kN;  // where bin I's fields sit in u
-  // Input check only every 4th bin (4 bins consume at most 24 bits): 16-bit units are appended while fewer than
-  // 32 look-ahead bits are valid.  The question is asked here, the answer acted upon at the END of this step: a
-  // branch right behind the compare would stall ~55 cycles, and the step in between cannot be hurt — a decision
-  // only depends on the nine bits of value that are compared with the range (window bits 62..54), and the
-  // look-ahead is never short of them by more than this one step's 6 bits below bit 47.
-  uint64_t refill = 0, refill2 = 0;
-  if ((I & 3) == 0) {
-    refill = __ballot(w.look <= 31);
-    refill2 = __ballot(w.look <= 21);  // 15 + the 6 bits this step can consume: a second unit may be needed
-    asm volatile("" : "+s"(refill), "+s"(refill2));
-  }
   // the state of this bin's context, from the lane that holds the record; state() / getLPS, contexts.cpp:939-950
   uint32_t sum;  // the two estimators added: the low half carries no rate bits here (see the kernel)
   if constexpr (L == 64) {
@@ -1454,13 +1443,13 @@ __device__ __forceinline__ void quad_dec_step(const QuadDecInfo &f, const QuadDe
   // multiplication, because v_lshlrev_b32 with DPP on its shift-amount operand returned wrong results on gfx950 — bisected
   // with the parity tests.)
   // value - scaledRange in ONE instruction: the record's field is MINUS the scale, a signed 24-bit factor (v_mad_i32_i24)
-  uint32_t e;
-  asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(e) : "v"(rm), "v"(u.srmul[J]), "v"(w.hi));
   // 0: value >= scaledRange (LPS / bin 1), ~0: MPS / bin 0.  Through asm so that hipcc sees an opaque mask: written
   // as (int)e >> 31 it turns every use back into v_cmp + v_cndmask pairs, two instructions where a v_bfi /
   // v_bitop3 on the mask is one.
-  uint32_t ngem;
-  asm("v_ashrrev_i32 %0, 31, %1" : "=v"(ngem) : "v"(e));
+  // (Both in ONE statement: hipcc pads every asm statement whose result the next instruction reads with an s_nop,
+  // an issue slot like any other, and the shift reads the difference at once.)
+  uint32_t e, ngem;
+  asm("v_mad_i32_i24 %0, %2, %3, %4\n\tv_ashrrev_i32 %1, 31, %0" : "=v"(e), "=v"(ngem) : "v"(rm), "v"(u.srmul[J]), "v"(w.hi));
   const uint32_t bin = ~(ngem ^ sx) & 1u;                        // LPS ? !mps : mps; sx is the MPS as a mask (0 if st == 0)
   const uint32_t gc = u.ctxm[J] & ~ngem;
   // One renormalisation rule for both paths: the chosen sub-range shifted up to [256, 511].  LPS (context bins only):
@@ -1502,13 +1491,12 @@ __device__ __forceinline__ void quad_dec_step(const QuadDecInfo &f, const QuadDe
   const u16x2 dlt2 = (st2 >> __builtin_bit_cast(u16x2, r0_v)) & __builtin_bit_cast(u16x2, (kMask1 << 16) | kMask0);
   const uint32_t rest = __builtin_bit_cast(uint32_t, (u16x2)(st2 - dlt2));
   uint32_t upd;  // both halves: rest + a * bin, the low half of `bin` feeding both lanes of the packed mad (op_sel_hi)
-  asm("v_pk_mad_u16 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(upd) : "v"(a_v), "v"(bin), "v"(rest));
-  asm volatile("" : "+v"(upd));   // keep the update unconditional: hipcc would otherwise wrap it in an exec
-  st_v = (f.key == u.key[J]) ? upd : st_v;
-  asm volatile("" : "+v"(st_v));  // region (SALU round trip + branch per bin)
-  if ((I & 3) == 0 && refill != 0) {
-    quad_dec_check(w, refill2 != 0);
-  }
+  // The update and its selection in one volatile statement (the padding again), which also keeps them unconditional:
+  // hipcc would otherwise wrap the update in an exec region (SALU round trip + branch per bin).
+  const uint64_t same = __builtin_amdgcn_uicmp(f.key, u.key[J], 32);  // 32: equal
+  asm volatile("v_pk_mad_u16 %1, %2, %3, %4 op_sel_hi:[1,0,1]\n\tv_cndmask_b32_e64 %0, %0, %1, %5"
+               : "+v"(st_v), "=v"(upd) : "v"(a_v), "v"(bin), "v"(rest), "s"(same));
+  if ((I & 3) == 0) quad_dec_topup(w);  // every 4th bin (4 bins consume at most 24 bits)
 }
 
 template <bool kSpecial, int L = 16>
@@ -1616,22 +1604,23 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
     w.hi = first >> 1;
     w.lo = first << 31;
   }
-  w.look = 16;
-  // the first 192 bytes go into the ring at once (blocks of 4 L bytes); the window itself started from bytes 0..3
+  // the first 192 bytes go into the ring at once (blocks of 4 L bytes); the window itself starts from bytes 0..7
   w.ring = ring_all + (wave * kSubs + row) * kRingStride;
   constexpr uint32_t kStageLanes = L > 16 ? 16u : (uint32_t)L;  // lanes that fetch a block (quad_dec_stage_load)
   for (uint32_t blk = 0; blk < 192u / (4u * kStageLanes); blk++) {
     w.filled = 4u * kStageLanes * blk;
-    w.rp = 0;  // "wanted"
+    w.npos = ~0u;  // "wanted"
     quad_dec_stage_load<L>(w, j);
     w.pf_mask = L > 16 ? neg_mask(j - kStageLanes) : ~0u;
     quad_dec_stage_store(w);
   }
   w.filled = 192;
-  w.rp = 4;
   w.pf_mask = 0;
-  w.q_hi = w.ring[1];
-  w.q_lo = w.ring[2];
+  w.q_hi = w.ring[63];  // dwords 1 and 2
+  w.q_lo = w.ring[62];
+  w.lo |= w.q_hi >> 1;  // 63 bits: the value and a full look-ahead from bin 0 on (quad_dec_topup)
+  w.look = 47;
+  w.npos = ~63u;
   w.range = 510;
   uint32_t bad = 0;
 
@@ -1733,14 +1722,14 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
     if (wave == 0) {
       V5_ADD(8, t0, t1);   // waiting for the record
       V5_ADD(9, t1, t2);   // prologue
-      V5_ADD(10, t2, t3);  // 16 chain steps incl. refills
+      V5_ADD(10, t2, t3);  // 16 chain steps incl. top-ups
       V5_ADD(11, t3, t4);  // epilogue
     }
   }
   if (prev_idx < n) out[prev_idx] = (uint8_t)prev_bin;
 
-  // bits shifted so far: everything moved into the window (8 * rp) minus value (16) minus look-ahead
-  const uint32_t shifts = 8u * w.rp - 16u - (uint32_t)w.look;
+  // bits shifted so far: everything moved into the window minus value (16) minus look-ahead
+  const uint32_t shifts = ~w.npos - 16u - (uint32_t)w.look;
   const uint32_t bytes_read = 2u + (shifts >> 3);  // the reference's counters (arith_codec.cpp:257-260)
   const int32_t bits_needed = (int32_t)(shifts & 7u) - 8;
   uint32_t flags = 0;
