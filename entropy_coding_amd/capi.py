@@ -71,6 +71,14 @@ EXPORTS_SEARCH_EMIT = [
 EXPORTS_PARSE_UNIT = [
     "cabac_hip_parse_unit_device", "cabac_hip_parse_unit_batch",
 ]
+# include/cabac_hip_parse_elements.h (the unit parse over a plan of syntax elements; tests/test_parse_elements_abi.py compares)
+EXPORTS_PARSE_ELEMENTS = [
+    "cabac_hip_parse_elements_device", "cabac_hip_parse_elements_batch",
+]
+RES_BAD_VALUE = 0x20                                             # CABAC_RES_BAD_VALUE
+TU_INFO_NOT_CODED = 0x40000                                      # CABAC_TU_INFO_NOT_CODED
+SE_CTX_BIN, SE_EP_BINS, SE_REM_ABS, SE_TRM, SE_UNARY_MAX, SE_UNARY_EP, SE_EXP_GOLOMB, SE_TRUNC_BIN, SE_ALIGN = range(9)   # CABAC_SE_*
+GUARD_NE, GUARD_EQ, GUARD_GE, GUARD_LT = range(4)                # CABAC_GUARD_*
 SEARCH_NO_CHAIN = 0xFFFFFFFF                                     # CABAC_SEARCH_NO_CHAIN
 SEARCH_LOG_OVERFLOW = 0x1                                        # CABAC_SEARCH_LOG_OVERFLOW and the capacity that was too small
 SEARCH_LOG_OVER_ENTRIES, SEARCH_LOG_OVER_RECORDS, SEARCH_LOG_OVER_BLOCKS, SEARCH_LOG_OVER_COEFFS = 0x10, 0x20, 0x40, 0x80
@@ -97,6 +105,46 @@ def splices_to_tu_at(splices):
     if len(splices) > 1 and (np.diff(splices["at"].astype(np.int64)) < 0).any():
         raise ValueError("the splice list is not sorted by `at`")
     return splices["tu"].astype(np.uint32), splices["at"].astype(np.uint32)
+
+
+def element(kind, ctx=0, ctx_n=None, n=0, rice=0, cutoff=5, max_log2=15, max_symbol=0, count=0):
+    """word0 of a syntax-element record (include/cabac_hip.h, "Syntax-element record"), the layout cabac_hip_binarize_device
+    reads: kind in bits 3..0, then per kind — CTX_BIN ctx; EP_BINS n; REM_ABS rice, cutoff, max_log2; UNARY_MAX ctx, ctx_n
+    (default ctx), max_symbol; UNARY_EP max_symbol; EXP_GOLOMB count; TRUNC_BIN max_symbol; TRM and ALIGN nothing.  Nothing is
+    range-checked beyond the field widths: a plan with a bad entry is the callee's to refuse."""
+    kind = int(kind)
+    if not 0 <= kind <= 15:
+        raise ValueError("kind must fit four bits")
+
+    def field(v, bits, shift):
+        v = int(v)
+        if not 0 <= v < (1 << bits):
+            raise ValueError("a parameter does not fit its field")
+        return v << shift
+    if kind == SE_CTX_BIN:
+        return kind | field(ctx, 9, 4)
+    if kind == SE_EP_BINS:
+        return kind | field(n, 6, 4)
+    if kind == SE_REM_ABS:
+        return kind | field(rice, 5, 4) | field(cutoff, 5, 9) | field(max_log2, 6, 14)
+    if kind == SE_UNARY_MAX:
+        return kind | field(ctx, 9, 4) | field(ctx if ctx_n is None else ctx_n, 9, 13) | field(max_symbol, 8, 22)
+    if kind == SE_UNARY_EP:
+        return kind | field(max_symbol, 6, 4)
+    if kind == SE_EXP_GOLOMB:
+        return kind | field(count, 5, 4)
+    if kind == SE_TRUNC_BIN:
+        return kind | field(max_symbol, 28, 4)
+    return kind
+
+
+def guard(back, cmp=GUARD_NE, imm=0):
+    """word1 of a plan element, or a block's guard word (include/cabac_hip_parse_elements.h, "GUARD WORD"): coded iff
+    value(i - back) cmp imm; back 0 = unguarded."""
+    back, cmp, imm = int(back), int(cmp), int(imm)
+    if not (0 <= back <= 255 and 0 <= cmp <= 3 and 0 <= imm <= 0xFFFF):
+        raise ValueError("back is 0..255, cmp 0..3, imm 0..65535")
+    return back | (cmp << 8) | (imm << 16)
 
 
 class SearchLogView(ctypes.Structure):
@@ -204,6 +252,9 @@ def load_library():
     L.cabac_hip_parse_unit_device.argtypes = [vp, ctypes.c_uint32] + [vp] * 7 + [ctypes.c_int] + [vp] * 3
     L.cabac_hip_parse_unit_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, ctypes.c_uint64, vp,
                                              ctypes.c_int, ctypes.c_uint64, vp, vp, vp]
+    L.cabac_hip_parse_elements_device.argtypes = [vp, ctypes.c_uint32] + [vp] * 8 + [ctypes.c_int] + [vp] * 3
+    L.cabac_hip_parse_elements_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, ctypes.c_uint64, vp,
+                                                 ctypes.c_int, ctypes.c_uint64, vp, vp, vp]
     L.cabac_hip_search_log_create.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                               ctypes.c_int, ctypes.POINTER(vp)]
     L.cabac_hip_search_log_destroy.argtypes = [vp]
@@ -359,7 +410,8 @@ class CabacHip:
         (the list is at cabac_hip_profile_read in include/cabac_hip.h; 12 in cabac_hip_estimate.h; 13 nal escape and 14 nal unescape in
         cabac_hip_nal.h; 15 residual estimate with contexts, 16 search select, 17 / 18 a round's estimate / commit in
         cabac_hip_search.h; 19 unit estimate, 20 / 21 / 22 a unit round's estimate / select / commit in cabac_hip_search_unit.h; 23 log append and
-        24 log place in cabac_hip_search_emit.h; 25 unit parse in cabac_hip_parse_unit.h)."""
+        24 log place in cabac_hip_search_emit.h; 25 unit parse in cabac_hip_parse_unit.h; 26 element parse in
+        cabac_hip_parse_elements.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -682,6 +734,47 @@ class CabacHip:
         self._check(rc, allow_substream=not check)
         out = (coeff[: int(n_coeff_total)], side_bins[: len(records)], res[: len(desc)])
         return out + (info[: len(tus)],) if with_info else out
+
+    # ---- spliced substreams read back element by element (include/cabac_hip_parse_elements.h) ------
+    def parse_elements_device(self, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff, d_values,
+                              d_results, d_tu_info=0, int16=False):
+        """cabac_hip_parse_elements_device: substream s = its plan d_plan[2 * rec_offset .. + 2 * n_records) of syntax elements
+        (element() words, guard() words) with the blocks coded in front of element d_tu_at[t], each block behind the guard
+        d_tu_guard[t] (0: none guarded): element values to d_values[rec_offset + i], blocks to d_coeff."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_parse_elements_device(
+            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), opt(d_tu), opt(d_tu_at), opt(d_tu_guard), opt(d_plan),
+            opt(d_coeff), 2 if int16 else 4, opt(d_values), opt(d_tu_info), vp(d_results)))
+
+    def parse_elements_batch(self, desc, data, tile_first, tus, tu_at, tu_guard, plan, n_coeff_total, check=True, int16=False,
+                             coeff=None, values=None, info=None):
+        """Host arrays through cabac_hip_parse_elements_batch (synchronous): (coeff, values, results, info).  plan: uint32
+        (n_elements, 2); `coeff` / `values` / `info` (optional): the caller's arrays, written in place; tu_at and tu_guard may be
+        None."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        data = np.ascontiguousarray(data, np.uint8)
+        tile_first = np.ascontiguousarray(tile_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
+        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
+        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
+        assert len(tile_first) == len(desc) + 1 and (tu_at is None or len(tu_at) == len(tus))
+        assert tu_guard is None or len(tu_guard) == len(tus)
+        if coeff is None:
+            coeff = np.zeros(max(int(n_coeff_total), 1), np.int16 if int16 else np.int32)
+        if values is None:
+            values = np.zeros(max(len(plan), 1), np.uint32)
+        if info is None:
+            info = np.zeros(max(len(tus), 1), np.uint32)
+        assert coeff.dtype == (np.int16 if int16 else np.int32) and values.dtype == np.uint32 and info.dtype == np.uint32
+        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
+        rc = self.L.cabac_hip_parse_elements_batch(
+            self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data,
+            tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
+            plan.ctypes.data, len(plan), coeff.ctypes.data, 2 if int16 else 4, int(n_coeff_total), values.ctypes.data,
+            info.ctypes.data, res.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return coeff[: int(n_coeff_total)], values[: len(plan)], res[: len(desc)], info[: len(tus)]
 
     def residual_batch(self, tus, coeff, check=True):
         """Host arrays in, (records, offsets, info) out (cabac_hip_residual_batch: both passes, synchronous)."""

@@ -19,6 +19,7 @@
 #include "cabac_hip.h"
 #include "cabac_hip_estimate.h"
 #include "cabac_hip_nal.h"
+#include "cabac_hip_parse_elements.h"
 #include "cabac_hip_parse_unit.h"
 #include "cabac_hip_search.h"
 #include "cabac_hip_search_emit.h"
@@ -49,8 +50,8 @@ struct cabac_hip_ctx {
   // [5]: scratch of the residual binariser, [6]: compacted payload, [7]: payload offsets; [8..]: the spliced-residual path
   // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
   // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included); [48..]: the winner log (kLog* below); [53..]: the
-  // unit parse (kUnit* below)
-  static constexpr int kSlots = 56;
+  // unit parse (kUnit* below); [56..]: the element parse (kElem* below)
+  static constexpr int kSlots = 59;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -1157,6 +1158,164 @@ int cabac_hip_parse_unit_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
   if (tu_info) HIP_TRY(c, down(tu_info, c->d_buf[6], size_t(n_tu) * sizeof(uint32_t)));
   if (n_tu) HIP_TRY(c, down(coeff, c->d_buf[1], n_coeff_total * size_t(coeff_bytes)));
   HIP_TRY(c, down(side_bins, c->d_buf[kUnitBins], size_t(n_records_total)));
+  HIP_TRY(c, down(results, c->d_buf[4], n_sub * sizeof(cabac_substream_result)));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int status = CABAC_HIP_OK;
+  for (uint32_t s = 0; s < n_sub; s++)
+    if (results[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
+  if (status) c->last_error = "substream flag set (see results[].flags)";
+  return status;
+}
+
+// ---- spliced substreams read back element by element (declared in cabac_hip_parse_elements.h; the element-walking instantiation) ----
+namespace {
+enum { kElemPlan = 56, kElemGuard = 57, kElemValues = 58 };
+
+// why a plan entry is bad (cabac_hip_parse_elements.h, "A BAD PLAN ENTRY"), or nullptr; i: its index in the substream's plan
+const char *bad_plan_entry(uint32_t w0, uint32_t gw, uint64_t i) {
+  const uint32_t kind = w0 & 15u, p = w0 >> 4;
+  if (kind > CABAC_SE_ALIGN) return "kind above 8";
+  if (gw & 0xfc00u) return "reserved guard bits set";
+  if ((gw & 0xffu) > i) return "guard reaches in front of the plan";
+  switch (kind) {
+  case CABAC_SE_CTX_BIN:
+    if ((p & 0x1ffu) >= CABAC_NUM_CONTEXTS) return "ctxId above 378";
+    break;
+  case CABAC_SE_UNARY_MAX:
+    if ((p & 0x1ffu) >= CABAC_NUM_CONTEXTS || ((p >> 9) & 0x1ffu) >= CABAC_NUM_CONTEXTS) return "ctxId above 378";
+    break;
+  case CABAC_SE_EP_BINS:
+    if ((p & 63u) > 32u) return "numBins above 32";
+    break;
+  case CABAC_SE_UNARY_EP:
+    if ((p & 63u) > 32u) return "maxSymbol above 32";
+    break;
+  case CABAC_SE_TRUNC_BIN:
+    if (p == 0u) return "maxSymbol 0";
+    break;
+  case CABAC_SE_REM_ABS: {
+    const uint32_t rice = p & 31u, cutoff = (p >> 5) & 31u, ml = (p >> 10) & 63u;
+    if (rice > 14u || ml < 15u || ml > 20u || cutoff > 32u - ml) return "REM_ABS parameters outside the defined region";
+    break;
+  }
+  default: break;
+  }
+  return nullptr;
+}
+}  // namespace
+
+int cabac_hip_parse_elements_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                    const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                    const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
+                                    uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results) {
+  // d_tu / d_coeff belong to the blocks, d_plan / d_values to the plans: either kind may be absent altogether
+  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  Bracket br = bracket_for(c, 26);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_element_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
+                                         coeff_bytes, d_values, d_tu_info, d_results));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_parse_elements_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                   uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                                   const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
+                                   int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
+                                   cabac_substream_result *results) {
+  if (!c || (n_sub && (!desc || !bytes || !tile_first || !results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  const uint32_t n_tu = tile_first[n_sub];
+  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_elements_total && (!plan || !values)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  char buf[200];
+  for (uint32_t s = 0; s < n_sub; s++) {
+    if (tile_first[s] > tile_first[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "tile_first must not decrease");
+    if (desc[s].byte_offset > bytes_total || desc[s].byte_capacity > bytes_total - desc[s].byte_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "bytes out of range");
+    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
+    const uint64_t n_el = desc[s].n_records;
+    if (desc[s].rec_offset > n_elements_total || n_el > n_elements_total - desc[s].rec_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "a plan leaves n_elements_total");
+    uint32_t at = 0;
+    for (uint32_t t = tile_first[s]; t < tile_first[s + 1]; t++) {
+      if (tu_at) {
+        if (tu_at[t] < at) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at decreases inside a substream");
+        if (tu_at[t] > n_el) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at exceeds the substream's plan length");
+        at = tu_at[t];
+      } else {
+        at = uint32_t(n_el);
+      }
+      if (tu_guard && ((tu_guard[t] & 0xfc00u) || (tu_guard[t] & 0xffu) > at)) {
+        snprintf(buf, sizeof buf, "bad block guard: substream %u, block %u of its blocks (guard 0x%x at element %u)", s,
+                 t - tile_first[s], tu_guard[t], at);
+        return fail(c, CABAC_HIP_ERR_INVALID, buf);
+      }
+    }
+    for (uint64_t i = 0; i < n_el; i++) {
+      const uint32_t *e = plan + 2 * (desc[s].rec_offset + i);
+      if (const char *why = bad_plan_entry(e[0], e[1], i)) {
+        snprintf(buf, sizeof buf, "bad plan entry: substream %u, element %llu of its plan (word0 0x%x, guard 0x%x): %s", s,
+                 (unsigned long long)i, e[0], e[1], why);
+        return fail(c, CABAC_HIP_ERR_INVALID, buf);
+      }
+    }
+  }
+  for (uint32_t t = 0; t < n_tu; t++) {
+    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, writes nothing
+    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
+    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
+  }
+  DeviceGuard g(c->device);
+  int rc;
+  // staging as cabac_hip_parse_unit_batch; the plan, the block guards and the values in slots of their own
+  const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), first_pad = (first_bytes + 15) / 16 * 16;
+  const size_t plan_bytes = size_t(n_elements_total) * 2 * sizeof(uint32_t), value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
+  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, 2, bytes_total + 4))) return rc;
+  if ((rc = ensure(c, 3, first_pad + size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
+  if ((rc = ensure(c, 1, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
+  if ((rc = ensure(c, 4, n_sub * sizeof(cabac_substream_result)))) return rc;
+  if ((rc = ensure(c, 6, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kUnitTuAt, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
+  if ((rc = ensure(c, kElemGuard, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
+  uint8_t *d_first = static_cast<uint8_t *>(c->d_buf[3]);
+  auto up = [&](void *dst, const void *src, size_t n) {
+    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+  };
+  auto down = [&](void *dst, const void *src, size_t n) {
+    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  };
+  HIP_TRY(c, up(c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc)));
+  HIP_TRY(c, up(c->d_buf[2], bytes, bytes_total));
+  HIP_TRY(c, up(d_first, tile_first, first_bytes));
+  HIP_TRY(c, up(d_first + first_pad, tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
+  HIP_TRY(c, up(c->d_buf[kElemPlan], plan, plan_bytes));
+  if (tu_at) HIP_TRY(c, up(c->d_buf[kUnitTuAt], tu_at, size_t(n_tu) * sizeof(uint32_t)));
+  if (tu_guard) HIP_TRY(c, up(c->d_buf[kElemGuard], tu_guard, size_t(n_tu) * sizeof(uint32_t)));
+  // what the walk does not write keeps the caller's values (int32 blocks, values, info words) or is zero (int16 blocks)
+  HIP_TRY(c, up(c->d_buf[kElemValues], values, value_bytes));
+  if (tu_info) HIP_TRY(c, up(c->d_buf[6], tu_info, size_t(n_tu) * sizeof(uint32_t)));
+  if (n_tu && coeff_bytes == 4) HIP_TRY(c, up(c->d_buf[1], coeff, n_coeff_total * sizeof(int32_t)));
+  if (n_tu && n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(c->d_buf[1], 0, n_coeff_total * sizeof(int16_t), c->stream));
+  rc = cabac_hip_parse_elements_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
+                                       (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad),
+                                       tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr,
+                                       tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr, (const uint32_t *)c->d_buf[kElemPlan],
+                                       c->d_buf[1], coeff_bytes, (uint32_t *)c->d_buf[kElemValues], (uint32_t *)c->d_buf[6],
+                                       (cabac_substream_result *)c->d_buf[4]);
+  if (rc) return rc;
+  if (tu_info) HIP_TRY(c, down(tu_info, c->d_buf[6], size_t(n_tu) * sizeof(uint32_t)));
+  if (n_tu) HIP_TRY(c, down(coeff, c->d_buf[1], n_coeff_total * size_t(coeff_bytes)));
+  HIP_TRY(c, down(values, c->d_buf[kElemValues], value_bytes));
   HIP_TRY(c, down(results, c->d_buf[4], n_sub * sizeof(cabac_substream_result)));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   int status = CABAC_HIP_OK;

@@ -149,6 +149,13 @@ hipError_t launch_unit_parse(hipStream_t st, uint32_t n_sub, const cabac_substre
                              const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint16_t *records,
                              void *coeff, int coeff_bytes /* 4 or 2 */, uint8_t *side_bins, uint32_t *tu_info,
                              cabac_substream_result *results);
+// its element-walking instantiation (cabac_hip_parse_elements.h): the run is a plan of syntax elements (2 words each: the
+// binariser's word0, a guard word), values[rec_offset + i] receives the value of element i; tu_guard (may be null): one guard word
+// per block
+hipError_t launch_element_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
+                                const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
+                                cabac_substream_result *results);
 
 // residual records spliced into host-recorded substreams (cabac_splice.hip); array sizes: pre n_splice + n_sub + 1,
 // sub_n / sub_cap / rec_base / byte_base n_sub, seen n_tu, err 1, totals 3 ({records, bytes, error})

@@ -37,6 +37,7 @@
 
 #include "cabac_device.h"
 #include "cabac_hip.h"
+#include "cabac_hip_parse_elements.h"
 #include "cabac_kernels.h"
 #include "cabac_scan.h"
 
@@ -292,6 +293,61 @@ __device__ __forceinline__ uint32_t pd_rem_abs(D &d, uint32_t rice, uint32_t max
     length += prefix == max_prefix ? max_log2 - rice : prefix - cutoff;
   }
   return offset + pd_bins_ep(d, length);
+}
+
+// ---- the element walk's code words (cabac_hip_parse_elements.h) -----------------------------------------------------------
+// A run of bypass ones: up to max_ones bins are read while they are 1; a 0 in front of the limit is consumed with them.  Returns
+// the ones (== max_ones: no 0 was read).  15 bins per look-ahead check, as the prefix of pd_rem_abs.
+template <class D>
+__device__ __forceinline__ uint32_t pd_ep_ones(D &d, uint32_t max_ones) {
+  uint32_t n = 0;
+  for (;;) {
+    const uint32_t want = min(15u, max_ones - n);
+    if (want == 0u) break;
+    pd_check(d);
+    const uint32_t b = pd_ep_peek(d, want);
+    const uint32_t ones = (uint32_t)__builtin_clz(~(b << (32u - want)));  // leading ones of the `want` bins (want < 32)
+    if (ones < want) {
+      pd_ep_take(d, b >> (want - ones - 1u), ones + 1u);  // the ones and the terminating zero
+      n += ones;
+      break;
+    }
+    pd_ep_take(d, b, want);
+    n += want;
+  }
+  return n;
+}
+
+// decodeRemAbsEP with the cutoff as a parameter (arith_codec.cpp:153-179); maxLog2 15..20, cutoff <= 32 - maxLog2, rice <= 14:
+// the suffix is at most max(maxLog2, 14 + 16) = 30 bins
+template <class D>
+__device__ __forceinline__ uint32_t pd_rem_abs_cut(D &d, uint32_t rice, uint32_t cutoff, uint32_t max_log2) {
+  const uint32_t max_prefix = 32u - max_log2;
+  const uint32_t prefix = pd_ep_ones(d, max_prefix);
+  uint32_t length = rice, offset;
+  if (prefix < cutoff) {
+    offset = prefix << rice;
+  } else {
+    offset = ((1u << (prefix - cutoff)) + cutoff - 1u) << rice;
+    length += prefix == max_prefix ? max_log2 - rice : prefix - cutoff;
+  }
+  return offset + pd_bins_ep(d, length);
+}
+
+// decodeBinTrm, arith_codec.cpp:181-197: decoding goes on whatever the bin is
+template <class D>
+__device__ __forceinline__ uint32_t pd_trm(D &d) {
+  const uint32_t range = rfl(d.range) - 2u;
+  const uint32_t bin = rfl(d.hi) >= (range << 22) ? 1u : 0u;
+  d.range = range;
+  if (!bin && range < 256u) {
+    const uint64_t v = (((uint64_t)d.hi << 32) | d.lo) << 1;
+    d.hi = (uint32_t)(v >> 32);
+    d.lo = (uint32_t)v;
+    d.look -= 1;
+    d.range = range << 1;
+  }
+  return bin;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -666,13 +722,22 @@ __device__ __forceinline__ void parse_ts(D &d, uint4 *ctx, int32_t *blk, const L
 // 379 contexts (slot = ctxId).  The records are fetched as the input bytes are: 64 at a time, one coalesced 2-byte load per
 // lane, the next 64 a step ahead, a record reaching the scalar side by v_readlane; the decoded bins are collected in the lanes
 // (lane i holds the bin of record i of the group) and stored 64 at a time, a partial group in front of every block and at a stop.
-template <int W, class C, bool kSide>
+//
+// kSide == 2 (cabac_hip_parse_elements.h): the run is a PLAN of syntax elements (word0 of the binariser's record, word1 a guard)
+// and every element is decoded to its value.  The plan is fetched as the records are (one coalesced 8-byte load per lane, the next
+// 64 elements a step ahead).  The values go to a per-wave ring of 256 words in LDS (`ring`, owned by the kernel so that the other
+// instantiations' LDS stays what it is): a guard reads value(i - back), back <= 255, from it, across group boundaries and blocks,
+// and the values are stored from it 64 at a time, a partial group in front of every block and at a stop.  Every lane writes the
+// (wave-uniform) value to the ring, so each lane reads back what it wrote itself.
+template <int W, class C, int kSide>
 __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
                                            const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ tile_first,
                                            const cabac_tu_desc *__restrict__ tus, C *__restrict__ coeff_all,
                                            uint32_t *__restrict__ tu_info, cabac_substream_result *__restrict__ results,
                                            const uint32_t *__restrict__ tu_at, const uint16_t *__restrict__ records,
-                                           uint8_t *__restrict__ side_bins) {
+                                           uint8_t *__restrict__ side_bins, const uint32_t *__restrict__ tu_guard = nullptr,
+                                           const uint32_t *__restrict__ plan = nullptr, uint32_t *__restrict__ values = nullptr,
+                                           uint32_t *ring = nullptr) {
   constexpr uint32_t kSlots = kSide ? kSideCtxSlots : kCtxSlots;
   __shared__ uint4 ctx_all[W * kSlots];
   __shared__ uint32_t side_park[kSide ? W : 1];  // the record cursor while a block is walked: out of the block walk's scalar registers
@@ -722,7 +787,7 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
   const bool scalar_wave = CABAC_PARSE_SCALAR_WAVES == 2 ||
                            (CABAC_PARSE_SCALAR_WAVES == 1 && (__builtin_amdgcn_s_getreg((4) | (0 << 6) | (3 << 11)) & 1u) != 0u);   // HW_ID.wave_id[3:0]
   auto walk = [&](auto kind) {
-  typedef PDecT<decltype(kind)::value, kSide> D;
+  typedef PDecT<decltype(kind)::value, kSide != 0> D;
   D d;
   d.lane = lane;
   d.cap = dsc.byte_capacity;
@@ -759,12 +824,124 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
     const uint32_t k = ((upto - 1u) & ~63u) + lane;
     if (k >= stored && k < upto) side_bins[dsc.rec_offset + k] = (uint8_t)bins_v;
   };
-  if (kSide && n_rec != 0u) {
+  if (kSide == 1 && n_rec != 0u) {
     rec_cur = load_records(0u);
     rec_nxt = load_records(1u);
   }
+  // element walk: el_cur / el_nxt = the plan words of the current group and of the 64 elements behind it
+  uint2 el_cur = make_uint2(0u, 0u), el_nxt = make_uint2(0u, 0u);
+  auto load_plan = [&](uint32_t group) {
+    const uint32_t k = 64u * group + lane;
+    return k < n_rec ? reinterpret_cast<const uint2 *>(plan)[dsc.rec_offset + k] : make_uint2(0xfu, 0u);
+  };
+  auto store_values = [&](uint32_t upto) {  // the values of elements [stored, upto) of the current group, out of the ring
+    const uint32_t k = ((upto - 1u) & ~63u) + lane;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (k >= stored && k < upto) values[dsc.rec_offset + k] = ring[k & 255u];
+  };
+  // value(i - back) cmp imm (cabac_hip_parse_elements.h, "Guard word"); back != 0 and back <= i
+  auto guard_holds = [&](uint32_t gw, uint32_t i) {
+    const uint32_t v = rfl(ring[(i - (gw & 0xffu)) & 255u]), imm = gw >> 16, cmp = (gw >> 8) & 3u;
+    return cmp == 0u ? v != imm : cmp == 1u ? v == imm : cmp == 2u ? v >= imm : v < imm;
+  };
+  if (kSide == 2 && n_rec != 0u) {
+    el_cur = load_plan(0u);
+    el_nxt = load_plan(1u);
+  }
   for (uint32_t t = tile_first[sub]; kSide || t < t_end; t++) {
-    if (kSide) {
+    if (kSide == 2) {
+      uint32_t upto = n_rec;
+      if (t < t_end && tu_at) upto = min(max(tu_at[t], rec_i), n_rec);
+      uint32_t stop = 0;
+      while (rec_i < upto) {
+        pd_check(d);  // 32 look-ahead bits for the element's first step; the longer code words check again as they go
+        const uint32_t w0 = rl(el_cur.x, rec_i & 63u), gw = rl(el_cur.y, rec_i & 63u);
+        const uint32_t kind = w0 & 15u, p = w0 >> 4, id0 = p & 0x1ffu, idn = (p >> 9) & 0x1ffu;
+        // a bad entry, whatever its guard would say: the substream stops in front of it
+        bool bad = kind > CABAC_SE_ALIGN || (gw & 0xfc00u) != 0u || (gw & 0xffu) > rec_i;
+        if (kind == CABAC_SE_CTX_BIN) bad |= id0 >= (uint32_t)CABAC_NUM_CONTEXTS;
+        else if (kind == CABAC_SE_UNARY_MAX) bad |= id0 >= (uint32_t)CABAC_NUM_CONTEXTS || idn >= (uint32_t)CABAC_NUM_CONTEXTS;
+        else if (kind == CABAC_SE_EP_BINS || kind == CABAC_SE_UNARY_EP) bad |= (p & 63u) > 32u;
+        else if (kind == CABAC_SE_TRUNC_BIN) bad |= p == 0u;
+        else if (kind == CABAC_SE_REM_ABS) {
+          const uint32_t ml = (p >> 10) & 63u;
+          bad |= (p & 31u) > 14u || ml < 15u || ml > 20u || ((p >> 5) & 31u) > 32u - ml;
+        }
+        if (bad) {
+          stop = CABAC_RES_BAD_RECORD;
+          break;
+        }
+        uint32_t v = 0;
+        if ((gw & 0xffu) == 0u || guard_holds(gw, rec_i)) {
+          if (kind == CABAC_SE_CTX_BIN) {
+            v = pd_bin(d, ctx, id0);
+          } else if (kind == CABAC_SE_EP_BINS) {
+            // one bin is decodeBinEP itself, the unit parse's CABAC_REC_EP: identity E1 then holds in every decoder state
+            v = (p & 63u) == 1u ? pd_ep(d) : pd_bins_ep(d, p & 63u);
+          } else if (kind == CABAC_SE_REM_ABS) {
+            v = pd_rem_abs_cut(d, p & 31u, (p >> 5) & 31u, (p >> 10) & 63u);
+          } else if (kind == CABAC_SE_TRM) {
+            v = pd_trm(d);
+          } else if (kind == CABAC_SE_UNARY_MAX) {  // cabac_reader.cpp:3349-3358: at most 255 context-coded bins, a check in front of each
+            const uint32_t mx = (p >> 18) & 0xffu;
+            while (v < mx) {
+              pd_check(d);
+              if (!pd_bin(d, ctx, v == 0u ? id0 : idn)) break;
+              v++;
+            }
+          } else if (kind == CABAC_SE_UNARY_EP) {   // :3360-3368
+            v = pd_ep_ones(d, p & 63u);
+          } else if (kind == CABAC_SE_EXP_GOLOMB) {  // :3370-3379, the prefix bounded: count + ones < 32
+            const uint32_t count = p & 31u, ones = pd_ep_ones(d, 32u - count);
+            if (ones == 32u - count) {
+              stop = CABAC_RES_BAD_VALUE;  // a code word no writer produces: the substream stops at this element
+              break;
+            }
+            v = (((1u << ones) - 1u) << count) + pd_bins_ep(d, count + ones);
+          } else if (kind == CABAC_SE_TRUNC_BIN) {   // cabac_reader.cpp:1162-1186
+            const uint32_t thresh = 31u - (uint32_t)__builtin_clz(p), val = 1u << thresh, b = p - val;
+            v = pd_bins_ep(d, thresh);
+            if (v >= val - b) {
+              pd_check(d);
+              v = (v << 1) + pd_ep(d) - (val - b);
+            }
+          } else {  // CABAC_SE_ALIGN
+            d.range = 256u;
+          }
+        }
+        ring[rec_i & 255u] = v;
+        rec_i++;
+        if ((rec_i & 63u) == 0u) {
+          store_values(rec_i);
+          stored = rec_i;
+          el_cur = el_nxt;
+          el_nxt = load_plan((rec_i >> 6) + 1u);
+        }
+      }
+      if (stored < rec_i) {  // a partial group: in front of every block and at a stop
+        store_values(rec_i);
+        stored = rec_i;
+      }
+      if (stop != 0u) {
+        flags_out |= stop;
+        break;
+      }
+      if (t >= t_end) break;
+      if (tu_guard) {  // the block's guard refers to element at(t) - back; a skipped block's descriptor is not examined
+        const uint32_t gw = tu_guard[t];
+        if ((gw & 0xfc00u) != 0u || (gw & 0xffu) > rec_i) {
+          flags_out |= CABAC_RES_BAD_RECORD;
+          break;
+        }
+        if ((gw & 0xffu) != 0u && !guard_holds(gw, rec_i)) {
+          if (tu_info && lane == 0u) tu_info[t] = CABAC_TU_INFO_NOT_CODED;
+          continue;
+        }
+      }
+      if (lane == 0u) side_park[wave] = rec_i;
+    } else if (kSide) {
       // at(t) = min(max(tu_at[t], at(t - 1)), n_rec); behind the last block the rest of the run
       uint32_t upto = n_rec;
       if (t < t_end && tu_at) upto = min(max(tu_at[t], rec_i), n_rec);
@@ -888,7 +1065,8 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
   // (not after a refused block or a refused start: the parse stopped before the end of the substream.  CABAC_RES_RANGE does
   // not stop anything.)
   // (the side walk has no implied terminate bin: it is a side record; CABAC_SUB_FINISH is the stop check alone)
-  const bool finish = (dsc.init_id & CABAC_SUB_FINISH) && !(flags_out & (CABAC_RES_BAD_RECORD | CABAC_RES_BAD_STOP));
+  const bool finish = (dsc.init_id & CABAC_SUB_FINISH) &&
+                      !(flags_out & (CABAC_RES_BAD_RECORD | CABAC_RES_BAD_STOP | (kSide == 2 ? CABAC_RES_BAD_VALUE : 0u)));
   if (finish && !kSide) {
     pd_check(d);
     const uint32_t range = rfl(d.range) - 2u, hi = rfl(d.hi);
@@ -932,7 +1110,7 @@ __global__ __launch_bounds__(64 * W) void residual_parse_kernel(uint32_t n_sub, 
                                                                   const cabac_tu_desc *__restrict__ tus, C *__restrict__ coeff_all,
                                                                   uint32_t *__restrict__ tu_info,
                                                                   cabac_substream_result *__restrict__ results) {
-  parse_walk<W, C, false>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, nullptr, nullptr, nullptr);
+  parse_walk<W, C, 0>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, nullptr, nullptr, nullptr);
 }
 
 template <int W, class C>
@@ -942,7 +1120,20 @@ __global__ __launch_bounds__(64 * W) void unit_parse_kernel(uint32_t n_sub, cons
                                                               const uint16_t *__restrict__ records, C *__restrict__ coeff_all,
                                                               uint8_t *__restrict__ side_bins, uint32_t *__restrict__ tu_info,
                                                               cabac_substream_result *__restrict__ results) {
-  parse_walk<W, C, true>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, tu_at, records, side_bins);
+  parse_walk<W, C, 1>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, tu_at, records, side_bins);
+}
+
+// the element walk (cabac_hip_parse_elements.h): the parser's geometry, the plan in place of the records
+template <int W, class C>
+__global__ __launch_bounds__(64 * W) void element_parse_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+                                                                 const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ tile_first,
+                                                                 const cabac_tu_desc *__restrict__ tus, const uint32_t *__restrict__ tu_at,
+                                                                 const uint32_t *__restrict__ tu_guard, const uint32_t *__restrict__ plan,
+                                                                 C *__restrict__ coeff_all, uint32_t *__restrict__ values,
+                                                                 uint32_t *__restrict__ tu_info, cabac_substream_result *__restrict__ results) {
+  __shared__ uint32_t ring_all[W * 256];  // the last 256 values of each wave's substream
+  parse_walk<W, C, 2>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, tu_at, nullptr, nullptr, tu_guard, plan, values,
+                      ring_all + 256u * (threadIdx.x >> 6));
 }
 
 #ifdef CABAC_PARSE_PROFILE
@@ -995,6 +1186,33 @@ hipError_t launch_unit_parse(hipStream_t st, uint32_t n_sub, const cabac_substre
     return launch_unit_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, records, static_cast<int16_t *>(coeff), side_bins, tu_info, results);
   if (coeff_bytes == 4)
     return launch_unit_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, records, static_cast<int32_t *>(coeff), side_bins, tu_info, results);
+  return hipErrorInvalidValue;
+}
+
+template <class C>
+static hipError_t launch_element_parse_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                          const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                                          const uint32_t *tu_guard, const uint32_t *plan, C *coeff, uint32_t *values, uint32_t *tu_info,
+                                          cabac_substream_result *results) {
+  // the parser's geometry and threshold
+  if (n_sub >= 1024u)
+    hipLaunchKernelGGL((element_parse_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at,
+                       tu_guard, plan, coeff, values, tu_info, results);
+  else
+    hipLaunchKernelGGL((element_parse_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard,
+                       plan, coeff, values, tu_info, results);
+  return hipGetLastError();
+}
+
+hipError_t launch_element_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
+                                const uint32_t *plan, void *coeff, int coeff_bytes, uint32_t *values, uint32_t *tu_info,
+                                cabac_substream_result *results) {
+  if (n_sub == 0) return hipSuccess;
+  if (coeff_bytes == 2)
+    return launch_element_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results);
+  if (coeff_bytes == 4)
+    return launch_element_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results);
   return hipErrorInvalidValue;
 }
 
