@@ -75,6 +75,12 @@ EXPORTS_PARSE_UNIT = [
 EXPORTS_PARSE_ELEMENTS = [
     "cabac_hip_parse_elements_device", "cabac_hip_parse_elements_batch",
 ]
+# include/cabac_hip_parse_plan.h (the element parse with computed entries; tests/test_parse_plan_abi.py compares)
+EXPORTS_PARSE_PLAN = [
+    "cabac_hip_parse_plan_device", "cabac_hip_parse_plan_batch",
+]
+PE_COND, PE_BLOCK_INFO = 9, 10                                   # CABAC_PE_COND, CABAC_PE_BLOCK_INFO
+JOIN_NONE, JOIN_AND, JOIN_OR = range(3)                          # CABAC_JOIN_*
 RES_BAD_VALUE = 0x20                                             # CABAC_RES_BAD_VALUE
 TU_INFO_NOT_CODED = 0x40000                                      # CABAC_TU_INFO_NOT_CODED
 SE_CTX_BIN, SE_EP_BINS, SE_REM_ABS, SE_TRM, SE_UNARY_MAX, SE_UNARY_EP, SE_EXP_GOLOMB, SE_TRUNC_BIN, SE_ALIGN = range(9)   # CABAC_SE_*
@@ -145,6 +151,24 @@ def guard(back, cmp=GUARD_NE, imm=0):
     if not (0 <= back <= 255 and 0 <= cmp <= 3 and 0 <= imm <= 0xFFFF):
         raise ValueError("back is 0..255, cmp 0..3, imm 0..65535")
     return back | (cmp << 8) | (imm << 16)
+
+
+def cond(test_back, cmp=GUARD_NE, imm=0, join=JOIN_NONE, back2=0):
+    """(word0, word1) of a CABAC_PE_COND entry (include/cabac_hip_parse_plan.h, "KIND 9"): value = value(i - test_back) cmp imm
+    (test_back 0: 1), joined by AND / OR with value(i - back2) != 0."""
+    join, back2 = int(join), int(back2)
+    if not (0 <= join <= 2 and 0 <= back2 <= 255):
+        raise ValueError("join is 0..2, back2 0..255")
+    return PE_COND | (back2 << 4) | (join << 12), guard(test_back, cmp, imm)
+
+
+def block_info(which=0, shift=0, width=16):
+    """word0 of a CABAC_PE_BLOCK_INFO entry (include/cabac_hip_parse_plan.h, "KIND 10"): bits shift .. shift + width - 1 of the
+    info word of the block `which` blocks in front of the last one walked."""
+    which, shift, width = int(which), int(shift), int(width)
+    if not (0 <= which <= 15 and 0 <= shift <= 31 and 1 <= width <= 32 and shift + width <= 32):
+        raise ValueError("which is 0..15, shift 0..31, width 1..32, shift + width at most 32")
+    return PE_BLOCK_INFO | (which << 4) | (shift << 8) | (width << 13)
 
 
 class SearchLogView(ctypes.Structure):
@@ -255,6 +279,9 @@ def load_library():
     L.cabac_hip_parse_elements_device.argtypes = [vp, ctypes.c_uint32] + [vp] * 8 + [ctypes.c_int] + [vp] * 3
     L.cabac_hip_parse_elements_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, ctypes.c_uint64, vp,
                                                  ctypes.c_int, ctypes.c_uint64, vp, vp, vp]
+    L.cabac_hip_parse_plan_device.argtypes = [vp, ctypes.c_uint32] + [vp] * 8 + [ctypes.c_int] + [vp] * 3
+    L.cabac_hip_parse_plan_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, ctypes.c_uint64, vp,
+                                             ctypes.c_int, ctypes.c_uint64, vp, vp, vp]
     L.cabac_hip_search_log_create.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                               ctypes.c_int, ctypes.POINTER(vp)]
     L.cabac_hip_search_log_destroy.argtypes = [vp]
@@ -411,7 +438,7 @@ class CabacHip:
         cabac_hip_nal.h; 15 residual estimate with contexts, 16 search select, 17 / 18 a round's estimate / commit in
         cabac_hip_search.h; 19 unit estimate, 20 / 21 / 22 a unit round's estimate / select / commit in cabac_hip_search_unit.h; 23 log append and
         24 log place in cabac_hip_search_emit.h; 25 unit parse in cabac_hip_parse_unit.h; 26 element parse in
-        cabac_hip_parse_elements.h)."""
+        cabac_hip_parse_elements.h; 27 plan parse in cabac_hip_parse_plan.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -769,6 +796,44 @@ class CabacHip:
         assert coeff.dtype == (np.int16 if int16 else np.int32) and values.dtype == np.uint32 and info.dtype == np.uint32
         res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
         rc = self.L.cabac_hip_parse_elements_batch(
+            self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data,
+            tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
+            plan.ctypes.data, len(plan), coeff.ctypes.data, 2 if int16 else 4, int(n_coeff_total), values.ctypes.data,
+            info.ctypes.data, res.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return coeff[: int(n_coeff_total)], values[: len(plan)], res[: len(desc)], info[: len(tus)]
+
+    # ---- a whole transform unit in one walk (include/cabac_hip_parse_plan.h) ------
+    def parse_plan_device(self, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff, d_values,
+                          d_results, d_tu_info=0, int16=False):
+        """cabac_hip_parse_plan_device: parse_elements_device on a plan that may hold cond() and block_info() entries."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_parse_plan_device(
+            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), opt(d_tu), opt(d_tu_at), opt(d_tu_guard), opt(d_plan),
+            opt(d_coeff), 2 if int16 else 4, opt(d_values), opt(d_tu_info), vp(d_results)))
+
+    def parse_plan_batch(self, desc, data, tile_first, tus, tu_at, tu_guard, plan, n_coeff_total, check=True, int16=False,
+                         coeff=None, values=None, info=None):
+        """Host arrays through cabac_hip_parse_plan_batch (synchronous): (coeff, values, results, info), as
+        parse_elements_batch."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        data = np.ascontiguousarray(data, np.uint8)
+        tile_first = np.ascontiguousarray(tile_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
+        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
+        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
+        assert len(tile_first) == len(desc) + 1 and (tu_at is None or len(tu_at) == len(tus))
+        assert tu_guard is None or len(tu_guard) == len(tus)
+        if coeff is None:
+            coeff = np.zeros(max(int(n_coeff_total), 1), np.int16 if int16 else np.int32)
+        if values is None:
+            values = np.zeros(max(len(plan), 1), np.uint32)
+        if info is None:
+            info = np.zeros(max(len(tus), 1), np.uint32)
+        assert coeff.dtype == (np.int16 if int16 else np.int32) and values.dtype == np.uint32 and info.dtype == np.uint32
+        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
+        rc = self.L.cabac_hip_parse_plan_batch(
             self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data,
             tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
             plan.ctypes.data, len(plan), coeff.ctypes.data, 2 if int16 else 4, int(n_coeff_total), values.ctypes.data,

@@ -20,6 +20,7 @@
 #include "cabac_hip_estimate.h"
 #include "cabac_hip_nal.h"
 #include "cabac_hip_parse_elements.h"
+#include "cabac_hip_parse_plan.h"
 #include "cabac_hip_parse_unit.h"
 #include "cabac_hip_search.h"
 #include "cabac_hip_search_emit.h"
@@ -1312,6 +1313,155 @@ int cabac_hip_parse_elements_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac
                                        tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr, (const uint32_t *)c->d_buf[kElemPlan],
                                        c->d_buf[1], coeff_bytes, (uint32_t *)c->d_buf[kElemValues], (uint32_t *)c->d_buf[6],
                                        (cabac_substream_result *)c->d_buf[4]);
+  if (rc) return rc;
+  if (tu_info) HIP_TRY(c, down(tu_info, c->d_buf[6], size_t(n_tu) * sizeof(uint32_t)));
+  if (n_tu) HIP_TRY(c, down(coeff, c->d_buf[1], n_coeff_total * size_t(coeff_bytes)));
+  HIP_TRY(c, down(values, c->d_buf[kElemValues], value_bytes));
+  HIP_TRY(c, down(results, c->d_buf[4], n_sub * sizeof(cabac_substream_result)));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int status = CABAC_HIP_OK;
+  for (uint32_t s = 0; s < n_sub; s++)
+    if (results[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
+  if (status) c->last_error = "substream flag set (see results[].flags)";
+  return status;
+}
+
+// ---- a whole transform unit in one walk (declared in cabac_hip_parse_plan.h; the plan-walking instantiation) ----
+namespace {
+// why an entry of the plan parse is bad, or nullptr; i: its index in the substream's plan, nb: nb(i), the blocks in front of it
+const char *bad_computed_entry(uint32_t w0, uint32_t w1, uint64_t i, uint32_t nb) {
+  const uint32_t kind = w0 & 15u, p = w0 >> 4;
+  if (kind < CABAC_PE_COND) return bad_plan_entry(w0, w1, i);
+  if (kind > CABAC_PE_BLOCK_INFO) return "kind above 10";
+  if (kind == CABAC_PE_COND) {
+    const uint32_t back2 = p & 0xffu, join = (p >> 8) & 3u;
+    if (w1 & 0xfc00u) return "reserved test bits set";
+    if ((w1 & 0xffu) > i) return "test reaches in front of the plan";
+    if (join == 3u) return "join 3";
+    if (join != 0u && back2 == 0u) return "a join with back2 0";
+    if (join != 0u && back2 > i) return "back2 reaches in front of the plan";
+    return nullptr;
+  }
+  const uint32_t which = p & 15u, shift = (p >> 4) & 31u, width = (p >> 9) & 63u;
+  if (w1 & 0xfc00u) return "reserved guard bits set";
+  if ((w1 & 0xffu) > i) return "guard reaches in front of the plan";
+  if (which >= nb) return "which reaches in front of the substream's blocks";
+  if (width == 0u) return "width 0";
+  if (shift + width > 32u) return "shift + width above 32";
+  return nullptr;
+}
+}  // namespace
+
+int cabac_hip_parse_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
+                                uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results) {
+  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  Bracket br = bracket_for(c, 27);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_plan_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
+                                      coeff_bytes, d_values, d_tu_info, d_results));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                               uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                               const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
+                               int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
+                               cabac_substream_result *results) {
+  if (!c || (n_sub && (!desc || !bytes || !tile_first || !results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  const uint32_t n_tu = tile_first[n_sub];
+  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_elements_total && (!plan || !values)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  char buf[200];
+  for (uint32_t s = 0; s < n_sub; s++) {
+    if (tile_first[s] > tile_first[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "tile_first must not decrease");
+    if (desc[s].byte_offset > bytes_total || desc[s].byte_capacity > bytes_total - desc[s].byte_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "bytes out of range");
+    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
+    const uint64_t n_el = desc[s].n_records;
+    if (desc[s].rec_offset > n_elements_total || n_el > n_elements_total - desc[s].rec_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "a plan leaves n_elements_total");
+    uint32_t at = 0;
+    for (uint32_t t = tile_first[s]; t < tile_first[s + 1]; t++) {
+      if (tu_at) {
+        if (tu_at[t] < at) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at decreases inside a substream");
+        if (tu_at[t] > n_el) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at exceeds the substream's plan length");
+        at = tu_at[t];
+      } else {
+        at = uint32_t(n_el);
+      }
+      if (tu_guard && ((tu_guard[t] & 0xfc00u) || (tu_guard[t] & 0xffu) > at)) {
+        snprintf(buf, sizeof buf, "bad block guard: substream %u, block %u of its blocks (guard 0x%x at element %u)", s,
+                 t - tile_first[s], tu_guard[t], at);
+        return fail(c, CABAC_HIP_ERR_INVALID, buf);
+      }
+    }
+    // nb(i): tu_at does not decrease here, so the blocks in front of element i are a prefix of the substream's blocks
+    uint32_t t = tile_first[s];
+    for (uint64_t i = 0; i < n_el; i++) {
+      while (tu_at && t < tile_first[s + 1] && tu_at[t] <= i) t++;
+      const uint32_t *e = plan + 2 * (desc[s].rec_offset + i);
+      if (const char *why = bad_computed_entry(e[0], e[1], i, t - tile_first[s])) {
+        snprintf(buf, sizeof buf, "bad plan entry: substream %u, element %llu of its plan (word0 0x%x, word1 0x%x): %s", s,
+                 (unsigned long long)i, e[0], e[1], why);
+        return fail(c, CABAC_HIP_ERR_INVALID, buf);
+      }
+    }
+  }
+  for (uint32_t t = 0; t < n_tu; t++) {
+    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, writes nothing
+    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
+    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
+  }
+  DeviceGuard g(c->device);
+  int rc;
+  // staged as cabac_hip_parse_elements_batch stages, in its slots
+  const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), first_pad = (first_bytes + 15) / 16 * 16;
+  const size_t plan_bytes = size_t(n_elements_total) * 2 * sizeof(uint32_t), value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
+  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, 2, bytes_total + 4))) return rc;
+  if ((rc = ensure(c, 3, first_pad + size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
+  if ((rc = ensure(c, 1, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
+  if ((rc = ensure(c, 4, n_sub * sizeof(cabac_substream_result)))) return rc;
+  if ((rc = ensure(c, 6, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kUnitTuAt, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
+  if ((rc = ensure(c, kElemGuard, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
+  uint8_t *d_first = static_cast<uint8_t *>(c->d_buf[3]);
+  auto up = [&](void *dst, const void *src, size_t n) {
+    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+  };
+  auto down = [&](void *dst, const void *src, size_t n) {
+    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  };
+  HIP_TRY(c, up(c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc)));
+  HIP_TRY(c, up(c->d_buf[2], bytes, bytes_total));
+  HIP_TRY(c, up(d_first, tile_first, first_bytes));
+  HIP_TRY(c, up(d_first + first_pad, tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
+  HIP_TRY(c, up(c->d_buf[kElemPlan], plan, plan_bytes));
+  if (tu_at) HIP_TRY(c, up(c->d_buf[kUnitTuAt], tu_at, size_t(n_tu) * sizeof(uint32_t)));
+  if (tu_guard) HIP_TRY(c, up(c->d_buf[kElemGuard], tu_guard, size_t(n_tu) * sizeof(uint32_t)));
+  // what the walk does not write keeps the caller's values (int32 blocks, values, info words) or is zero (int16 blocks)
+  HIP_TRY(c, up(c->d_buf[kElemValues], values, value_bytes));
+  if (tu_info) HIP_TRY(c, up(c->d_buf[6], tu_info, size_t(n_tu) * sizeof(uint32_t)));
+  if (n_tu && coeff_bytes == 4) HIP_TRY(c, up(c->d_buf[1], coeff, n_coeff_total * sizeof(int32_t)));
+  if (n_tu && n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(c->d_buf[1], 0, n_coeff_total * sizeof(int16_t), c->stream));
+  rc = cabac_hip_parse_plan_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
+                                   (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad),
+                                   tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr,
+                                   tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr, (const uint32_t *)c->d_buf[kElemPlan],
+                                   c->d_buf[1], coeff_bytes, (uint32_t *)c->d_buf[kElemValues], (uint32_t *)c->d_buf[6],
+                                   (cabac_substream_result *)c->d_buf[4]);
   if (rc) return rc;
   if (tu_info) HIP_TRY(c, down(tu_info, c->d_buf[6], size_t(n_tu) * sizeof(uint32_t)));
   if (n_tu) HIP_TRY(c, down(coeff, c->d_buf[1], n_coeff_total * size_t(coeff_bytes)));

@@ -156,6 +156,11 @@ hipError_t launch_element_parse(hipStream_t st, uint32_t n_sub, const cabac_subs
                                 const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
                                 const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
                                 cabac_substream_result *results);
+// the plan walk (cabac_hip_parse_plan.h): the element walk with the two computed entry kinds, on the same operands
+hipError_t launch_plan_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                             const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
+                             const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
+                             cabac_substream_result *results);
 
 // residual records spliced into host-recorded substreams (cabac_splice.hip); array sizes: pre n_splice + n_sub + 1,
 // sub_n / sub_cap / rec_base / byte_base n_sub, seen n_tu, err 1, totals 3 ({records, bytes, error})

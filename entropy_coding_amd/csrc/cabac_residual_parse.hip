@@ -38,6 +38,7 @@
 #include "cabac_device.h"
 #include "cabac_hip.h"
 #include "cabac_hip_parse_elements.h"
+#include "cabac_hip_parse_plan.h"
 #include "cabac_kernels.h"
 #include "cabac_scan.h"
 
@@ -729,6 +730,12 @@ __device__ __forceinline__ void parse_ts(D &d, uint4 *ctx, int32_t *blk, const L
 // instantiations' LDS stays what it is): a guard reads value(i - back), back <= 255, from it, across group boundaries and blocks,
 // and the values are stored from it 64 at a time, a partial group in front of every block and at a stop.  Every lane writes the
 // (wave-uniform) value to the ring, so each lane reads back what it wrote itself.
+//
+// kSide == 3 (cabac_hip_parse_plan.h): the element walk with two more entry kinds that read no bin.  CABAC_PE_COND is a test
+// on the ring, joined by AND / OR with another ring word; CABAC_PE_BLOCK_INFO is a field of the info word of one of the last 16
+// blocks walked.  Those words live in `inf` (LDS of the kernel, per wave: 16 info words, then the count of blocks walked,
+// skipped ones included), written where tu_info[t] is written, by every lane as the ring is, and read back the same way.  Both
+// kinds are wave-uniform scalar work in the element loop; everything else is the kSide == 2 walk, instruction for instruction.
 template <int W, class C, int kSide>
 __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
                                            const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ tile_first,
@@ -737,7 +744,7 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
                                            const uint32_t *__restrict__ tu_at, const uint16_t *__restrict__ records,
                                            uint8_t *__restrict__ side_bins, const uint32_t *__restrict__ tu_guard = nullptr,
                                            const uint32_t *__restrict__ plan = nullptr, uint32_t *__restrict__ values = nullptr,
-                                           uint32_t *ring = nullptr) {
+                                           uint32_t *ring = nullptr, uint32_t *inf = nullptr) {
   constexpr uint32_t kSlots = kSide ? kSideCtxSlots : kCtxSlots;
   __shared__ uint4 ctx_all[W * kSlots];
   __shared__ uint32_t side_park[kSide ? W : 1];  // the record cursor while a block is walked: out of the block walk's scalar registers
@@ -846,12 +853,19 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
     const uint32_t v = rfl(ring[(i - (gw & 0xffu)) & 255u]), imm = gw >> 16, cmp = (gw >> 8) & 3u;
     return cmp == 0u ? v != imm : cmp == 1u ? v == imm : cmp == 2u ? v >= imm : v < imm;
   };
-  if (kSide == 2 && n_rec != 0u) {
+  // the block that is walked next is block inf[16] of the substream; its info word goes to inf[that & 15]
+  auto note_info = [&](uint32_t info) {
+    const uint32_t k = rfl(inf[16]);
+    inf[k & 15u] = info;
+    inf[16] = k + 1u;
+  };
+  if (kSide == 3) inf[16] = 0u;
+  if (kSide >= 2 && n_rec != 0u) {
     el_cur = load_plan(0u);
     el_nxt = load_plan(1u);
   }
   for (uint32_t t = tile_first[sub]; kSide || t < t_end; t++) {
-    if (kSide == 2) {
+    if (kSide >= 2) {
       uint32_t upto = n_rec;
       if (t < t_end && tu_at) upto = min(max(tu_at[t], rec_i), n_rec);
       uint32_t stop = 0;
@@ -860,7 +874,7 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
         const uint32_t w0 = rl(el_cur.x, rec_i & 63u), gw = rl(el_cur.y, rec_i & 63u);
         const uint32_t kind = w0 & 15u, p = w0 >> 4, id0 = p & 0x1ffu, idn = (p >> 9) & 0x1ffu;
         // a bad entry, whatever its guard would say: the substream stops in front of it
-        bool bad = kind > CABAC_SE_ALIGN || (gw & 0xfc00u) != 0u || (gw & 0xffu) > rec_i;
+        bool bad = kind > (kSide == 3 ? CABAC_PE_BLOCK_INFO : CABAC_SE_ALIGN) || (gw & 0xfc00u) != 0u || (gw & 0xffu) > rec_i;
         if (kind == CABAC_SE_CTX_BIN) bad |= id0 >= (uint32_t)CABAC_NUM_CONTEXTS;
         else if (kind == CABAC_SE_UNARY_MAX) bad |= id0 >= (uint32_t)CABAC_NUM_CONTEXTS || idn >= (uint32_t)CABAC_NUM_CONTEXTS;
         else if (kind == CABAC_SE_EP_BINS || kind == CABAC_SE_UNARY_EP) bad |= (p & 63u) > 32u;
@@ -868,13 +882,26 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
         else if (kind == CABAC_SE_REM_ABS) {
           const uint32_t ml = (p >> 10) & 63u;
           bad |= (p & 31u) > 14u || ml < 15u || ml > 20u || ((p >> 5) & 31u) > 32u - ml;
+        } else if (kSide == 3 && kind == CABAC_PE_COND) {  // p: back2 in bits 7..0, join in 9..8; gw is the test
+          const uint32_t back2 = p & 0xffu, join = (p >> 8) & 3u;
+          bad |= join == 3u || (join != 0u && (back2 == 0u || back2 > rec_i));
+        } else if (kSide == 3 && kind == CABAC_PE_BLOCK_INFO) {  // p: which in bits 3..0, shift in 8..4, width in 14..9
+          const uint32_t width = (p >> 9) & 63u;
+          bad |= (p & 15u) >= rfl(inf[16]) || width == 0u || ((p >> 4) & 31u) + width > 32u;
         }
         if (bad) {
           stop = CABAC_RES_BAD_RECORD;
           break;
         }
         uint32_t v = 0;
-        if ((gw & 0xffu) == 0u || guard_holds(gw, rec_i)) {
+        if (kSide == 3 && kind == CABAC_PE_COND) {  // never skipped: word1 is a test, not a guard
+          v = (gw & 0xffu) == 0u || guard_holds(gw, rec_i);
+          const uint32_t join = (p >> 8) & 3u;
+          if (join != 0u) {
+            const uint32_t other = rfl(ring[(rec_i - (p & 0xffu)) & 255u]) != 0u;
+            v = join == 1u ? (v & other) : (v | other);
+          }
+        } else if ((gw & 0xffu) == 0u || guard_holds(gw, rec_i)) {
           if (kind == CABAC_SE_CTX_BIN) {
             v = pd_bin(d, ctx, id0);
           } else if (kind == CABAC_SE_EP_BINS) {
@@ -907,6 +934,9 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
               pd_check(d);
               v = (v << 1) + pd_ep(d) - (val - b);
             }
+          } else if (kSide == 3 && kind == CABAC_PE_BLOCK_INFO) {  // block nb(i) - 1 - which, nb(i) = inf[16]
+            const uint32_t width = (p >> 9) & 63u, word = rfl(inf[(rfl(inf[16]) - 1u - (p & 15u)) & 15u]);
+            v = (word >> ((p >> 4) & 31u)) & (width >= 32u ? 0xffffffffu : (1u << width) - 1u);
           } else {  // CABAC_SE_ALIGN
             d.range = 256u;
           }
@@ -937,6 +967,7 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
         }
         if ((gw & 0xffu) != 0u && !guard_holds(gw, rec_i)) {
           if (tu_info && lane == 0u) tu_info[t] = CABAC_TU_INFO_NOT_CODED;
+          if (kSide == 3) note_info(CABAC_TU_INFO_NOT_CODED);
           continue;
         }
       }
@@ -1020,6 +1051,7 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
     else if ((g.fl & CABAC_TU_SBT_ZERO_OUT) && g.chroma == 0u && g.lw <= 5u && g.lh <= 5u) info = parse_regular<decltype(d), true>(d, ctx, blk, tab, g, lane);
     else info = parse_regular<decltype(d), false>(d, ctx, blk, tab, g, lane);
     if (tu_info && lane == 0u) tu_info[t] = info;
+    if (kSide == 3) note_info(info);
     PP_TICK(b2);
     // the finished block goes out row by row (all lanes), the LDS copy is cleared for the next block
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1066,7 +1098,7 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
   // not stop anything.)
   // (the side walk has no implied terminate bin: it is a side record; CABAC_SUB_FINISH is the stop check alone)
   const bool finish = (dsc.init_id & CABAC_SUB_FINISH) &&
-                      !(flags_out & (CABAC_RES_BAD_RECORD | CABAC_RES_BAD_STOP | (kSide == 2 ? CABAC_RES_BAD_VALUE : 0u)));
+                      !(flags_out & (CABAC_RES_BAD_RECORD | CABAC_RES_BAD_STOP | (kSide >= 2 ? CABAC_RES_BAD_VALUE : 0u)));
   if (finish && !kSide) {
     pd_check(d);
     const uint32_t range = rfl(d.range) - 2u, hi = rfl(d.hi);
@@ -1134,6 +1166,20 @@ __global__ __launch_bounds__(64 * W) void element_parse_kernel(uint32_t n_sub, c
   __shared__ uint32_t ring_all[W * 256];  // the last 256 values of each wave's substream
   parse_walk<W, C, 2>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, tu_at, nullptr, nullptr, tu_guard, plan, values,
                       ring_all + 256u * (threadIdx.x >> 6));
+}
+
+// the plan walk (cabac_hip_parse_plan.h): the element walk's geometry and ring, and the info words of the last 16 blocks
+template <int W, class C>
+__global__ __launch_bounds__(64 * W) void plan_parse_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+                                                              const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ tile_first,
+                                                              const cabac_tu_desc *__restrict__ tus, const uint32_t *__restrict__ tu_at,
+                                                              const uint32_t *__restrict__ tu_guard, const uint32_t *__restrict__ plan,
+                                                              C *__restrict__ coeff_all, uint32_t *__restrict__ values,
+                                                              uint32_t *__restrict__ tu_info, cabac_substream_result *__restrict__ results) {
+  __shared__ uint32_t ring_all[W * 256];  // the last 256 values of each wave's substream
+  __shared__ uint32_t info_all[W * 17];   // per wave: the info words of the last 16 blocks walked, and how many were walked
+  parse_walk<W, C, 3>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, tu_at, nullptr, nullptr, tu_guard, plan, values,
+                      ring_all + 256u * (threadIdx.x >> 6), info_all + 17u * (threadIdx.x >> 6));
 }
 
 #ifdef CABAC_PARSE_PROFILE
@@ -1213,6 +1259,33 @@ hipError_t launch_element_parse(hipStream_t st, uint32_t n_sub, const cabac_subs
     return launch_element_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results);
   if (coeff_bytes == 4)
     return launch_element_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results);
+  return hipErrorInvalidValue;
+}
+
+template <class C>
+static hipError_t launch_plan_parse_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                       const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                                       const uint32_t *tu_guard, const uint32_t *plan, C *coeff, uint32_t *values, uint32_t *tu_info,
+                                       cabac_substream_result *results) {
+  // the parser's geometry and threshold
+  if (n_sub >= 1024u)
+    hipLaunchKernelGGL((plan_parse_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at,
+                       tu_guard, plan, coeff, values, tu_info, results);
+  else
+    hipLaunchKernelGGL((plan_parse_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard,
+                       plan, coeff, values, tu_info, results);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                             const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
+                             const uint32_t *plan, void *coeff, int coeff_bytes, uint32_t *values, uint32_t *tu_info,
+                             cabac_substream_result *results) {
+  if (n_sub == 0) return hipSuccess;
+  if (coeff_bytes == 2)
+    return launch_plan_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results);
+  if (coeff_bytes == 4)
+    return launch_plan_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results);
   return hipErrorInvalidValue;
 }
 
