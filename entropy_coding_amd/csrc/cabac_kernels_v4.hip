@@ -27,6 +27,7 @@
 // Layout: row r of wave w codes substream 4w + r.  Rows whose substreams are shorter idle at the end,
 // so batches should group substreams of similar length (cabac_hip.h: order is the caller's).
 #include <cstdlib>
+#include <type_traits>
 
 #include "cabac_device.h"
 #include "cabac_kernels.h"
@@ -1303,7 +1304,7 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
 
 struct QuadDec {   // row-uniform values
   uint32_t hi, lo;   // 64-bit window: value in [62:47] (see v2)
-  int32_t look;
+  uint32_t used;     // bits shifted out of the window since the last top-up (the look-ahead below the value is 47 - used)
   uint32_t range;
   uint32_t npos;     // bit cursor, complemented: ~pos, pos = the substream bits moved into the window so far (bits 5..10 of
                      // ~pos are 63 - the ring dword that holds bit pos: the ring runs backwards, see below)
@@ -1339,23 +1340,26 @@ struct QuadDecInfo {
 // 128 bytes are staged ahead of the cursor; 4 steps consume at most 48).
 //
 // Top-up, every fourth bin, without a question asked: the window is filled to all 63 bits below the sign bit
-// (look = 47).  Four bins consume at most 24 bits, so look is 23..47 here, the 47 - look missing bits lie wholly
-// in `lo`, and they are the top of the 32 stream bits at `pos` — cut out of (q_hi, q_lo), two ring dwords read
-// by the PREVIOUS top-up, which also reads the two dwords for the next one: no global memory, no compare, no
-// branch and no wait anywhere near the chain.  Both shift counts have an edge that the hardware takes modulo 32:
-// pos & 31 == 0 (the 64-bit shift by 0 leaves q_hi on top) and look == 47 (offset 32, but v_bfe_u32 with a width
-// of 0 returns 0 whatever its offset).  Reading ahead never changes a decision: a bit enters the comparison only
+// (a look-ahead of 47).  The chain keeps no look-ahead count: all a top-up needs is `used`, the sum of the four
+// shifts (tot) since the last one.  Four bins consume at most 24 bits, so used is 0..24 here, the missing `used`
+// bits lie wholly in `lo`, and they are the top of the 32 stream bits at `pos` — cut out of (q_hi, q_lo), two
+// ring dwords read by the PREVIOUS top-up, which also reads the two dwords for the next one: no global memory, no
+// compare, no branch and no wait anywhere near the chain.  The cut is v_bfe_u32(next32, offset 32 - used, width
+// used); both shift counts have an edge that the hardware takes modulo 32: pos & 31 == 0 (the 64-bit shift by 0
+// leaves q_hi on top) and used == 0 (the offset 32 is read as 0, but v_bfe_u32 with a width of 0 returns 0
+// whatever its offset; used <= 24 keeps the width inside the five bits the instruction reads, and the offset is
+// then 8..31).  Reading ahead never changes a decision: a bit enters the comparison only
 // when it reaches bit 54 of the window, and it is the same bit of the stream whenever it was appended (past the
 // end of the substream: a zero, as the staging feeds them).
 __device__ __forceinline__ void quad_dec_topup(QuadDec &w) {
   const uint64_t q = (((uint64_t)w.q_hi << 32) | w.q_lo) << (~w.npos & 31u);
   const uint32_t next32 = (uint32_t)(q >> 32);      // stream bits pos .. pos + 31
-  const uint32_t want = 47u - (uint32_t)w.look;     // 0..24
+  const uint32_t want = w.used;                     // 0..24
   uint32_t add;                                     // next32 >> (32 - want), 0 for want == 0
-  asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(add) : "v"(next32), "v"((uint32_t)w.look - 15u), "v"(want));
+  asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(add) : "v"(next32), "v"(32u - want), "v"(want));
   w.lo |= add;
   w.npos -= want;
-  w.look = 47;
+  w.used = 0;
   const uint32_t *p = w.ring + ((w.npos >> 5) & 63u);  // 63 - dword: the second of the pair (dword 64 = dword 0 sits at 0)
   w.q_lo = p[0];
   w.q_hi = p[1];
@@ -1478,7 +1482,7 @@ __device__ __forceinline__ void quad_dec_step(const QuadDecInfo &f, const QuadDe
     const uint64_t v = (((uint64_t)w.hi << 32) | w.lo) << tot;
     w.hi = (uint32_t)(v >> 32);
     w.lo = (uint32_t)v;
-    w.look -= (int32_t)tot;
+    w.used += tot;
   }
   bits[I >> 5] |= bin << (I & 31);
   if constexpr (L == 64) asm volatile("" : "+v"(bits[I >> 5]));  // now: left to itself hipcc keeps all 64 shifted bins and ORs them at the end
@@ -1619,7 +1623,7 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
   w.q_hi = w.ring[63];  // dwords 1 and 2
   w.q_lo = w.ring[62];
   w.lo |= w.q_hi >> 1;  // 63 bits: the value and a full look-ahead from bin 0 on (quad_dec_topup)
-  w.look = 47;
+  w.used = 0;
   w.npos = ~63u;
   w.range = 510;
   uint32_t bad = 0;
@@ -1633,20 +1637,19 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
   const uint32_t max_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_wave);
   const uint16_t *rec_safe = n != 0 ? rec : reinterpret_cast<const uint16_t *>(desc);
   const uint32_t last_rec = n != 0 ? n - 1u : 0u;
-  // Records are requested three steps ahead.  What a step needs besides the bins — the meaning of its record ids (rec_tab),
-  // the fields of the chain parked in LDS and read back per row (QuadDecRow), the choice of the step variant, the context
-  // states — is prepared in two stages off the top of the step: the table rows are requested at the START of the step
-  // before (they arrive during its chain), the rest at its END (the context store has just been written back).
-  uint32_t rec1 = rec_safe[min(j, last_rec)], rec2 = rec_safe[min(L + j, last_rec)], rec3 = rec_safe[min(2u * L + j, last_rec)];
+  // Records are requested four steps ahead (three in the rolled loop of L = 64).  What a step needs besides the bins — the
+  // meaning of its record ids (rec_tab), the fields of the chain parked in LDS and read back per row (QuadDecRow), the choice
+  // of the step variant, the context states — is prepared in two stages off the top of the step: the table rows are requested
+  // at the START of the step before (they arrive during its chain), the rest at its END (the context store has just been
+  // written back).
+  auto load_rec = [&](uint32_t at) { return (uint32_t)rec_safe[min(at + j, last_rec)]; };
+  // rq<k>: the record of the next step whose number is k mod 4 (L = 64: rq0..rq2 are the next three steps' and rotate)
+  uint32_t rq0 = load_rec(0), rq1 = load_rec(L), rq2 = load_rec(2u * L), rq3 = L == 64 ? 0u : load_rec(3u * L);
   uint32_t prev_bin = 0, prev_idx = ~0u;  // the bins of the previous step, not yet stored
   uint64_t prev_lanes = 0;                 // ... and the lanes that have one
   uint32_t nxt_id, nxt_actm;
   uint4 nxt_a, nxt_b;
-  auto request = [&](uint32_t base) {  // stage 1 for the step at `base`: its ids and their table rows
-    uint32_t r = rec1;               // loaded two steps ago
-    rec1 = rec2;
-    rec2 = rec3;
-    rec3 = rec_safe[min(base + 3u * L + j, last_rec)];
+  auto request = [&](uint32_t base, uint32_t r) {  // stage 1 for the step at `base`, whose record is r: its id and table row
     nxt_actm = neg_mask(base + j - n);                              // ~0: a record of this substream
     nxt_id = sel(nxt_actm, r & CABAC_REC_ID_MASK, 0x1f0u);         // past the end: an id that is nothing
     const uint4 *row4 = reinterpret_cast<const uint4 *>(rec_tab[nxt_id]);
@@ -1684,32 +1687,51 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
     asm volatile("" ::: "memory");
     u.fetch(&field_all[wave][0][0], row * L);
   };
-  request(0);
+  request(0, rq0);
+  if constexpr (L == 64) {
+    rq0 = rq1;
+    rq1 = rq2;
+    rq2 = load_rec(3u * L);
+  } else {
+    rq0 = load_rec(4u * L);
+  }
   prepare();
-  for (uint32_t base = 0; base < max_n; base += L) {
+  // One step.  P = 0..3: its place in a trip of four steps (L = 16 and L = 4, whose input staging has period four: the
+  // phases are then known where the step is written, the record register is the place's own and everything a step hands to
+  // the next is a plain value; only the trip's back-edge carries registers).  P = -1: the rolled loop of L = 64, which
+  // stages in every step.  rq: the register that holds the NEXT step's record; it is refilled for the step four on.
+  auto step = [&](uint32_t base, auto place, uint32_t &rq) __attribute__((always_inline)) {
+    constexpr int P = decltype(place)::value;
     V5_TICK(t0);
     V5_TICK(t1);
     // The bins of the previous step are stored only now, after the wait at the end of that step: loads and stores share
     // one in-order counter, so a store issued before a wait would add its whole latency to it (the same goes for the
     // input block requested a step ago: into the ring with it before anything new is issued)
     // (L = 64: a step consumes up to 48 bytes, so a 64-byte block is requested in EVERY step and stored in the next)
-    if (L == 64 ? base != 0u : (base & (3u * L)) == L) quad_dec_stage_store(w);     // steps 1, 5, 9, ...
+    if (P < 0 ? base != 0u : P == 1) quad_dec_stage_store(w);     // steps 1, 5, 9, ...
     {  // under the lane mask asked for at the end of the step before: an `if` here is a compare the scalar unit waits for
       uint64_t saved;
       asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\tglobal_store_byte %2, %3, off\n\ts_mov_b64 exec, %0"
                    : "=&s"(saved) : "s"(prev_lanes), "v"(out + min(prev_idx, last_rec)), "v"(prev_bin) : "memory");
     }
-    if (L == 64 || (base & (3u * L)) == 0u) quad_dec_stage_load<L>(w, j);    // steps 0, 4, 8, ...: request a block of input
+    if (P <= 0) quad_dec_stage_load<L>(w, j);    // steps 0, 4, 8, ...: request a block of input
     const uint32_t id = cur_id, ctxm = cur_ctxm;
     // asked long ago, needed now (the choice of the step variant): the branch finds the answer waiting
     uint64_t special = cur_special;
     asm volatile("" : "+s"(special));
     uint32_t st_v = cur_stored & ctxm;
     const uint32_t a_v = cur_av, r0_v = cur_r0v;
-    request(base + L);                                  // the ids and table rows of the next step
+    request(base + L, rq);                              // the id and table row of the next step
+    if constexpr (P < 0) {
+      rq0 = rq1;
+      rq1 = rq2;
+      rq2 = load_rec(base + 4u * L);
+    } else {
+      rq = load_rec(base + 5u * L);
+    }
     uint32_t bits[2] = {0u, 0u};  // row-uniform: bit I = the bin of record base + I
     V5_TICK(t2);
-    if (special == 0) quad_dec_steps<false, L>(f, u, &field_all[wave][0][0], r0_v, a_v, st_v, bits, w);
+    if (__builtin_expect(special == 0, 1)) quad_dec_steps<false, L>(f, u, &field_all[wave][0][0], r0_v, a_v, st_v, bits, w);
     else quad_dec_steps<true, L>(f, u, &field_all[wave][0][0], r0_v, a_v, st_v, bits, w);
     V5_TICK(t3);
     const uint32_t my_bin = ((L > 32 && j >= 32u ? bits[1] : bits[0]) >> (j & 31u)) & 1u;
@@ -1725,11 +1747,26 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
       V5_ADD(10, t2, t3);  // 16 chain steps incl. top-ups
       V5_ADD(11, t3, t4);  // epilogue
     }
+  };
+  if constexpr (L == 64) {
+    for (uint32_t base = 0; base < max_n; base += L) step(base, std::integral_constant<int, -1>{}, rq0);
+  } else {
+    // ceil(max_n / 4L) trips: the surplus steps of the last one are the no-op steps that the shorter rows of a wave run
+    // anyway — the id of "nothing", t = 0, tot = 0, no bin stored (prev_lanes), no record counted bad (nxt_actm); a top-up
+    // after them appends nothing (want = 0), and they sit at places 1..3, which request no input: shifts, bytes_read and
+    // the flags below do not depend on how many of them ran.
+    for (uint32_t base = 0; base < max_n; base += 4u * L) {
+      step(base, std::integral_constant<int, 0>{}, rq1);
+      step(base + L, std::integral_constant<int, 1>{}, rq2);
+      step(base + 2u * L, std::integral_constant<int, 2>{}, rq3);
+      step(base + 3u * L, std::integral_constant<int, 3>{}, rq0);
+    }
   }
   if (prev_idx < n) out[prev_idx] = (uint8_t)prev_bin;
 
-  // bits shifted so far: everything moved into the window minus value (16) minus look-ahead
-  const uint32_t shifts = ~w.npos - 16u - (uint32_t)w.look;
+  // bits shifted so far: everything moved into the window minus value (16) minus look-ahead (47 at the last top-up, less
+  // what the bins of the incomplete group since then have used)
+  const uint32_t shifts = ~w.npos - 63u + w.used;
   const uint32_t bytes_read = 2u + (shifts >> 3);  // the reference's counters (arith_codec.cpp:257-260)
   const int32_t bits_needed = (int32_t)(shifts & 7u) - 8;
   uint32_t flags = 0;
