@@ -79,6 +79,10 @@ EXPORTS_PARSE_ELEMENTS = [
 EXPORTS_PARSE_PLAN = [
     "cabac_hip_parse_plan_device", "cabac_hip_parse_plan_batch",
 ]
+# include/cabac_hip_write_plan.h (plan and values to coded substreams; tests/test_write_plan_abi.py compares)
+EXPORTS_WRITE_PLAN = [
+    "cabac_hip_write_plan_device", "cabac_hip_write_plan_batch",
+]
 PE_COND, PE_BLOCK_INFO = 9, 10                                   # CABAC_PE_COND, CABAC_PE_BLOCK_INFO
 JOIN_NONE, JOIN_AND, JOIN_OR = range(3)                          # CABAC_JOIN_*
 RES_BAD_VALUE = 0x20                                             # CABAC_RES_BAD_VALUE
@@ -282,6 +286,10 @@ def load_library():
     L.cabac_hip_parse_plan_device.argtypes = [vp, ctypes.c_uint32] + [vp] * 8 + [ctypes.c_int] + [vp] * 3
     L.cabac_hip_parse_plan_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, ctypes.c_uint64, vp,
                                              ctypes.c_int, ctypes.c_uint64, vp, vp, vp]
+    L.cabac_hip_write_plan_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_int, vp,
+                                              ctypes.c_uint64, vp, vp, vp, vp]
+    L.cabac_hip_write_plan_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, ctypes.c_int,
+                                             ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp, vp]
     L.cabac_hip_search_log_create.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                               ctypes.c_int, ctypes.POINTER(vp)]
     L.cabac_hip_search_log_destroy.argtypes = [vp]
@@ -438,7 +446,7 @@ class CabacHip:
         cabac_hip_nal.h; 15 residual estimate with contexts, 16 search select, 17 / 18 a round's estimate / commit in
         cabac_hip_search.h; 19 unit estimate, 20 / 21 / 22 a unit round's estimate / select / commit in cabac_hip_search_unit.h; 23 log append and
         24 log place in cabac_hip_search_emit.h; 25 unit parse in cabac_hip_parse_unit.h; 26 element parse in
-        cabac_hip_parse_elements.h; 27 plan parse in cabac_hip_parse_plan.h)."""
+        cabac_hip_parse_elements.h; 27 plan parse in cabac_hip_parse_plan.h; 28 plan write in cabac_hip_write_plan.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -840,6 +848,50 @@ class CabacHip:
             info.ctypes.data, res.ctypes.data)
         self._check(rc, allow_substream=not check)
         return coeff[: int(n_coeff_total)], values[: len(plan)], res[: len(desc)], info[: len(tus)]
+
+    # ---- plan and values to coded substreams (include/cabac_hip_write_plan.h) ------
+    def write_plan_device(self, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, d_payload,
+                          payload_capacity, d_payload_offsets, d_results, d_values_out=0, d_tu_info=0, int16=False):
+        """cabac_hip_write_plan_device: the plan of parse_plan_device, the values of its real elements and the blocks' coefficients
+        -> compacted coded substreams, the filled values (d_values_out, may be d_values_in) and the blocks' info words."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_write_plan_device(
+            self.h, n_sub, vp(d_desc), opt(d_plan), opt(d_values_in), vp(d_tile_first), n_tu, opt(d_tu), opt(d_tu_at), opt(d_tu_guard),
+            opt(d_coeff), 2 if int16 else 4, vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), opt(d_values_out),
+            opt(d_tu_info)))
+
+    def write_plan_batch(self, desc, plan, values, tile_first, tus, tu_at, tu_guard, coeff, payload, check=True, values_out=None,
+                         info=None):
+        """Host arrays through cabac_hip_write_plan_batch (synchronous): (payload bytes, offsets uint64[n + 1], results, filled
+        values, info words).  plan: uint32 (n_elements, 2); values: uint32 per element; coeff: int32 or int16; `payload`: the
+        caller's uint8 array, written in place; `values_out` / `info` (optional): the caller's arrays, written in place (values_out
+        may be `values`); tu_at and tu_guard may be None."""
+        narrow = isinstance(coeff, np.ndarray) and coeff.dtype == np.int16
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
+        values = np.ascontiguousarray(values, np.uint32)
+        tile_first = np.ascontiguousarray(tile_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
+        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
+        coeff = np.ascontiguousarray(coeff, np.int16 if narrow else np.int32)
+        n = len(desc)
+        assert len(tile_first) == n + 1 and len(values) >= len(plan) and (tu_at is None or len(tu_at) == len(tus))
+        assert tu_guard is None or len(tu_guard) == len(tus)
+        if values_out is None:
+            values_out = np.zeros(max(len(plan), 1), np.uint32)
+        if info is None:
+            info = np.zeros(max(len(tus), 1), np.uint32)
+        assert values_out.dtype == np.uint32 and len(values_out) >= len(plan) and info.dtype == np.uint32 and payload.dtype == np.uint8
+        offsets = np.zeros(n + 1, np.uint64)
+        res = np.zeros(max(n, 1), RESULT_DTYPE)
+        rc = self.L.cabac_hip_write_plan_batch(
+            self.h, n, desc.ctypes.data, plan.ctypes.data, values.ctypes.data, len(plan), tile_first.ctypes.data, tus.ctypes.data,
+            tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
+            coeff.ctypes.data, 2 if narrow else 4, len(coeff), payload.ctypes.data, payload.nbytes, offsets.ctypes.data,
+            res.ctypes.data, values_out.ctypes.data, info.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return payload[: int(offsets[n])], offsets, res[:n], values_out[: len(plan)], info[: len(tus)]
 
     def residual_batch(self, tus, coeff, check=True):
         """Host arrays in, (records, offsets, info) out (cabac_hip_residual_batch: both passes, synchronous)."""

@@ -25,6 +25,7 @@
 #include "cabac_hip_search.h"
 #include "cabac_hip_search_emit.h"
 #include "cabac_hip_search_unit.h"
+#include "cabac_hip_write_plan.h"
 #include "cabac_kernels.h"
 #include "cabac_nal_kernels.h"
 
@@ -51,8 +52,8 @@ struct cabac_hip_ctx {
   // [5]: scratch of the residual binariser, [6]: compacted payload, [7]: payload offsets; [8..]: the spliced-residual path
   // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
   // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included); [48..]: the winner log (kLog* below); [53..]: the
-  // unit parse (kUnit* below); [56..]: the element parse (kElem* below)
-  static constexpr int kSlots = 59;
+  // unit parse (kUnit* below); [56..]: the element parse (kElem* below); [59..]: the plan write (kPw* below)
+  static constexpr int kSlots = 61;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -1352,38 +1353,17 @@ const char *bad_computed_entry(uint32_t w0, uint32_t w1, uint64_t i, uint32_t nb
 }
 }  // namespace
 
-int cabac_hip_parse_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
-                                const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
-                                const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
-                                uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results) {
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 27);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_plan_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
-                                      coeff_bytes, d_values, d_tu_info, d_results));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
-}
-
-int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                               uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
-                               const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
-                               int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
-                               cabac_substream_result *results) {
-  if (!c || (n_sub && (!desc || !bytes || !tile_first || !results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
+namespace {
+// what the host-pointer forms of the plan parse and the plan write refuse about descriptors, plan, guards, tile_first, tu_at and
+// coefficient ranges; bytes_total: null where the descriptors' byte ranges are not input (the writer)
+int check_plan_host(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint64_t *bytes_total,
+                    const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
+                    const uint32_t *plan, uint64_t n_elements_total, uint64_t n_coeff_total) {
   const uint32_t n_tu = tile_first[n_sub];
-  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (n_elements_total && (!plan || !values)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   char buf[200];
   for (uint32_t s = 0; s < n_sub; s++) {
     if (tile_first[s] > tile_first[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "tile_first must not decrease");
-    if (desc[s].byte_offset > bytes_total || desc[s].byte_capacity > bytes_total - desc[s].byte_offset)
+    if (bytes_total && (desc[s].byte_offset > *bytes_total || desc[s].byte_capacity > *bytes_total - desc[s].byte_offset))
       return fail(c, CABAC_HIP_ERR_INVALID, "bytes out of range");
     if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
     const uint64_t n_el = desc[s].n_records;
@@ -1422,6 +1402,39 @@ int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
     if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
       return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
   }
+  return CABAC_HIP_OK;
+}
+}  // namespace
+
+int cabac_hip_parse_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
+                                uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results) {
+  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  Bracket br = bracket_for(c, 27);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_plan_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
+                                      coeff_bytes, d_values, d_tu_info, d_results));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                               uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                               const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
+                               int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
+                               cabac_substream_result *results) {
+  if (!c || (n_sub && (!desc || !bytes || !tile_first || !results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  const uint32_t n_tu = tile_first[n_sub];
+  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_elements_total && (!plan || !values)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (int bad = check_plan_host(c, n_sub, desc, &bytes_total, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, n_coeff_total)) return bad;
   DeviceGuard g(c->device);
   int rc;
   // staged as cabac_hip_parse_elements_batch stages, in its slots
@@ -1695,6 +1708,185 @@ int cabac_hip_encode_batch_residual16(cabac_hip_ctx *c, uint32_t n_sub, const ca
   return host_call_exit(c, encode_batch_residual_impl(c, n_sub, desc, records, n_records_total, splice_first, splices, n_tu, tus, coeff, 2,
                                                       n_coeff_total, payload, payload_capacity, payload_offsets, results, tu_info,
                                                       bin_counts));
+}
+
+// ---- plan + values -> bytes (cabac_plan_write.hip; declared in cabac_hip_write_plan.h) --------------------------------------
+namespace {
+// device slots of the plan write: its per-substream words, and the descriptor list of the records pass
+enum { kPwPlan = 59, kPwTu = 60 };
+}  // namespace
+
+int cabac_hip_write_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,
+                                const uint32_t *d_values_in, const uint32_t *d_tile_first, uint32_t n_tu, const cabac_tu_desc *d_tu,
+                                const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes,
+                                uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_payload_offsets,
+                                cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info) {
+  if (!c || !d_payload_offsets || (n_sub && (!d_desc || !d_tile_first || !d_payload || !d_results)) || (n_tu && (!d_tu || !d_coeff)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0 && n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "blocks without a substream");
+  DeviceGuard g(c->device);
+  int rc;
+  const size_t n_blk = n_tu ? n_tu : 1, n_s = n_sub ? n_sub : 1;
+  const size_t words = (3 * n_s + 2 + 1) & ~size_t(1);  // sub_n, sub_cap, sub_flag, err (+ pad)
+  if ((rc = ensure(c, kSpCnt, 2 * n_blk * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, 5, cabac::residual_scratch_bytes(n_tu)))) return rc;
+  if ((rc = ensure(c, kPwPlan, words * sizeof(uint32_t) + (2 * n_s + 3) * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kPwTu, n_blk * sizeof(cabac_tu_desc)))) return rc;
+  if ((rc = ensure(c, kSpDesc, n_s * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kSpTuOff, n_blk * sizeof(uint64_t)))) return rc;
+  if (!c->h_totals) HIP_TRY(c, hipHostMalloc(&c->h_totals, 64, hipHostMallocDefault));
+  uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kSpCnt]), *d_info = d_cnt + n_blk;
+  uint32_t *sub_n = static_cast<uint32_t *>(c->d_buf[kPwPlan]), *sub_cap = sub_n + n_s, *sub_flag = sub_cap + n_s, *err = sub_flag + n_s;
+  uint64_t *rec_base = reinterpret_cast<uint64_t *>(sub_n + words), *byte_base = rec_base + n_s, *totals = byte_base + n_s;
+  auto *desc2 = static_cast<cabac_substream_desc *>(c->d_buf[kSpDesc]);
+  auto *tus2 = static_cast<cabac_tu_desc *>(c->d_buf[kPwTu]);
+  auto *tu_off = static_cast<uint64_t *>(c->d_buf[kSpTuOff]);
+  const cabac::PlanWriteIn in{d_desc, d_plan, d_values_in, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_cnt, d_info};
+  c->timed = false;
+  {  // sizes and info words of ALL blocks: they do not depend on the guards, the guards depend on them
+    Timed t(c, 5);
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[5]));
+  }
+  {
+    Timed t(c, 28);
+    HIP_TRY(c, cabac::launch_plan_resolve(c->stream, n_sub, in, sub_n, sub_cap, sub_flag, err));
+    HIP_TRY(c, cabac::launch_splice_scan(c->stream, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals));
+  }
+  uint64_t *h_tot = static_cast<uint64_t *>(c->h_totals);
+  HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the one wait: sizes decide the buffers of the second half
+  if (h_tot[2]) return fail(c, CABAC_HIP_ERR_INVALID, "a substream outgrows 32 bits of records");
+  if ((rc = ensure(c, kSpRec, (h_tot[0] + 64) * sizeof(uint16_t)))) return rc;
+  if ((rc = ensure(c, kSpBytes, h_tot[1] + 64))) return rc;
+  auto *exp_rec = static_cast<uint16_t *>(c->d_buf[kSpRec]);
+  auto *slots = static_cast<uint8_t *>(c->d_buf[kSpBytes]);
+  {
+    Timed t(c, 28);
+    HIP_TRY(c, cabac::launch_plan_emit(c->stream, n_sub, in, sub_n, sub_cap, sub_flag, rec_base, byte_base, desc2, tus2, tu_off, exp_rec,
+                                       d_values_out, d_tu_info));
+  }
+  {  // block records of the coded blocks, straight into the expanded substreams: in tus2 a skipped block is one the binariser
+     // rejects, so it writes nothing whatever its coefficients hold (another list: the block order is made again)
+    Timed t(c, 5);
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, tus2, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[5]));
+  }
+  {
+    Timed t(c, 0);
+    HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, desc2, exp_rec, slots, d_results));
+  }
+  {
+    Timed t(c, 28);
+    HIP_TRY(c, cabac::launch_plan_stops(c->stream, n_sub, sub_flag, d_results));
+  }
+  {
+    Timed t(c, 6);
+    HIP_TRY(c, cabac::launch_assemble(c->stream, n_sub, desc2, d_results, slots, d_payload, payload_capacity, d_payload_offsets));
+  }
+  return CABAC_HIP_OK;
+}
+
+static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint32_t *plan,
+                                 const uint32_t *values_in, uint64_t n_elements_total, const uint32_t *tile_first,
+                                 const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard, const void *coeff,
+                                 int coeff_bytes, uint64_t n_coeff_total, uint8_t *payload, uint64_t payload_capacity,
+                                 uint64_t *payload_offsets, cabac_substream_result *results, uint32_t *values_out, uint32_t *tu_info) {
+  if (!c || !payload_offsets || (n_sub && (!desc || !tile_first || !results || !payload)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) {
+    payload_offsets[0] = 0;
+    return CABAC_HIP_OK;
+  }
+  const uint32_t n_tu = tile_first[n_sub];
+  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_elements_total && (!plan || !values_in)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (int bad = check_plan_host(c, n_sub, desc, nullptr, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, n_coeff_total)) return bad;
+  DeviceGuard g(c->device);
+  int rc;
+  if ((rc = pipe_init(c))) return rc;
+  const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), at_bytes = size_t(n_tu) * sizeof(uint32_t);
+  const size_t plan_bytes = size_t(n_elements_total) * 2 * sizeof(uint32_t), value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
+  if ((rc = ensure(c, kSpInDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kSpInFirst, first_bytes))) return rc;
+  if ((rc = ensure(c, kSpInTu, size_t(n_tu ? n_tu : 1) * sizeof(cabac_tu_desc)))) return rc;
+  if ((rc = ensure(c, kSpInCoeff, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
+  if ((rc = ensure(c, kSpOutRes, n_sub * sizeof(cabac_substream_result)))) return rc;
+  if ((rc = ensure(c, kSpOutInfo, size_t(n_tu ? n_tu : 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kUnitTuAt, at_bytes))) return rc;
+  if ((rc = ensure(c, kElemGuard, at_bytes))) return rc;
+  if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
+  if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
+  if ((rc = ensure(c, 6, payload_capacity ? payload_capacity : 16))) return rc;
+  if ((rc = ensure(c, 7, (size_t(n_sub) + 1) * sizeof(uint64_t)))) return rc;
+  const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result), off_bytes = (size_t(n_sub) + 1) * sizeof(uint64_t);
+  if ((rc = ensure_pinned(c, 0, res_bytes + off_bytes + 64))) return rc;
+  auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
+  auto *h_off = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(c->h_pin[0]) + res_bytes);
+  uint32_t *d_values = static_cast<uint32_t *>(c->d_buf[kElemValues]);
+
+  // what came before on the caller's stream is finished first; uploads run on the copy stream, the kernels on the ctx's
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((rc = h2d(c, c->d_buf[kSpInTu], tus, size_t(n_tu) * sizeof(cabac_tu_desc), c->s_in))) return rc;
+  if ((rc = h2d(c, c->d_buf[kSpInDesc], desc, n_sub * sizeof(cabac_substream_desc), c->s_in))) return rc;
+  if ((rc = h2d(c, c->d_buf[kSpInFirst], tile_first, first_bytes, c->s_in))) return rc;
+  if (tu_at && (rc = h2d(c, c->d_buf[kUnitTuAt], tu_at, at_bytes, c->s_in))) return rc;
+  if (tu_guard && (rc = h2d(c, c->d_buf[kElemGuard], tu_guard, at_bytes, c->s_in))) return rc;
+  if ((rc = h2d(c, c->d_buf[kElemPlan], plan, plan_bytes, c->s_in))) return rc;
+  if ((rc = h2d(c, d_values, values_in, value_bytes, c->s_in))) return rc;
+  if ((rc = h2d(c, c->d_buf[kSpInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), c->s_in))) return rc;
+  HIP_TRY(c, hipEventRecord(c->ev_in[0], c->s_in));
+  HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in[0], 0));
+  rc = cabac_hip_write_plan_device(c, n_sub, static_cast<const cabac_substream_desc *>(c->d_buf[kSpInDesc]),
+                                   static_cast<const uint32_t *>(c->d_buf[kElemPlan]), d_values,
+                                   static_cast<const uint32_t *>(c->d_buf[kSpInFirst]), n_tu,
+                                   static_cast<const cabac_tu_desc *>(c->d_buf[kSpInTu]),
+                                   tu_at ? static_cast<const uint32_t *>(c->d_buf[kUnitTuAt]) : nullptr,
+                                   tu_guard ? static_cast<const uint32_t *>(c->d_buf[kElemGuard]) : nullptr, c->d_buf[kSpInCoeff],
+                                   coeff_bytes, static_cast<uint8_t *>(c->d_buf[6]), payload_capacity, static_cast<uint64_t *>(c->d_buf[7]),
+                                   static_cast<cabac_substream_result *>(c->d_buf[kSpOutRes]), values_out ? d_values : nullptr,
+                                   tu_info ? static_cast<uint32_t *>(c->d_buf[kSpOutInfo]) : nullptr);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h_res, c->d_buf[kSpOutRes], res_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h_off, c->d_buf[7], off_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev_k[1], c->stream));
+  // the big things leave on the outgoing copy stream once the offsets are known
+  HIP_TRY(c, hipEventSynchronize(c->ev_k[1]));
+  const uint64_t n_pay = h_off[n_sub];
+  if (n_pay > payload_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "payload_capacity too small");
+  if ((rc = d2h(c, payload, c->d_buf[6], n_pay, c->s_out))) return rc;
+  // a stopped substream's values and info words are unspecified on the device: the caller's stay what they were
+  int status = CABAC_HIP_OK;
+  for (uint32_t s = 0; s < n_sub; s++) {
+    if (h_res[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
+    if (h_res[s].flags & (CABAC_RES_BAD_RECORD | CABAC_RES_BAD_VALUE)) continue;
+    if (values_out && desc[s].n_records &&
+        (rc = d2h(c, values_out + desc[s].rec_offset, d_values + desc[s].rec_offset, size_t(desc[s].n_records) * sizeof(uint32_t), c->s_out)))
+      return rc;
+    if (tu_info && tile_first[s + 1] > tile_first[s] &&
+        (rc = d2h(c, tu_info + tile_first[s], static_cast<uint32_t *>(c->d_buf[kSpOutInfo]) + tile_first[s],
+                  size_t(tile_first[s + 1] - tile_first[s]) * sizeof(uint32_t), c->s_out)))
+      return rc;
+  }
+  if ((rc = d2h_drain(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->s_out));
+  for (uint32_t s = 0; s < n_sub; s++) {
+    results[s] = h_res[s];
+    payload_offsets[s + 1] = h_off[s + 1];
+  }
+  payload_offsets[0] = 0;
+  if (status) c->last_error = "substream flag set (see results[].flags)";
+  return status;
+}
+
+int cabac_hip_write_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint32_t *plan,
+                               const uint32_t *values_in, uint64_t n_elements_total, const uint32_t *tile_first,
+                               const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard, const void *coeff,
+                               int coeff_bytes, uint64_t n_coeff_total, uint8_t *payload, uint64_t payload_capacity,
+                               uint64_t *payload_offsets, cabac_substream_result *results, uint32_t *values_out, uint32_t *tu_info) {
+  return host_call_exit(c, write_plan_batch_impl(c, n_sub, desc, plan, values_in, n_elements_total, tile_first, tus, tu_at, tu_guard,
+                                                 coeff, coeff_bytes, n_coeff_total, payload, payload_capacity, payload_offsets, results,
+                                                 values_out, tu_info));
 }
 
 // ---- pinned host memory for the caller's buffers ------------------------------------------------------------

@@ -177,6 +177,34 @@ hipError_t launch_tu_info_any(hipStream_t st, uint32_t n_tu, const uint32_t *inf
 hipError_t launch_bin_count(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
                             uint32_t *counts);
 
+// the scan of launch_splice_plan alone: rec_base / byte_base (n_sub each) from sub_n / sub_cap, totals = {records, bytes, *err != 0}
+hipError_t launch_splice_scan(hipStream_t st, uint32_t n_sub, const uint32_t *sub_n, const uint32_t *sub_cap, uint64_t *rec_base,
+                              uint64_t *byte_base, const uint32_t *err, uint64_t *totals);
+
+// the plan writer (cabac_plan_write.hip; cabac_hip_write_plan.h): the plan walk on the writer's side, once for the sizes and once
+// for the records.  What both walks read: the plan and the real values, the blocks with the sizes and info words of the residual
+// binariser's sizes pass.
+struct PlanWriteIn {
+  const cabac_substream_desc *desc;
+  const uint32_t *plan, *values, *tile_first;
+  const cabac_tu_desc *tus;
+  const uint32_t *tu_at, *tu_guard;         // may be null
+  const uint32_t *tu_n_records, *tu_info;   // of launch_residual's sizes pass over tus[]
+};
+// per substream the expanded length, the byte-slot size and the stop (0, CABAC_RES_BAD_RECORD or CABAC_RES_BAD_VALUE; a stopped
+// substream has length 0); *err is set when a substream outgrows 32 bits
+hipError_t launch_plan_resolve(hipStream_t st, uint32_t n_sub, const PlanWriteIn &in, uint32_t *sub_n, uint32_t *sub_cap,
+                               uint32_t *sub_flag, uint32_t *err);
+// the second walk: the expanded descriptors, the elements' bin records at their places, per block its destination and its
+// descriptor where it is coded (tus_out[t] is one the binariser rejects where it is skipped or its substream stopped), the filled
+// values (values_out may be null and may be in.values) and the info words (tu_info_out may be null)
+hipError_t launch_plan_emit(hipStream_t st, uint32_t n_sub, const PlanWriteIn &in, const uint32_t *sub_n, const uint32_t *sub_cap,
+                            const uint32_t *sub_flag, const uint64_t *rec_base, const uint64_t *byte_base,
+                            cabac_substream_desc *desc_out, cabac_tu_desc *tus_out, uint64_t *tu_offset, uint16_t *records,
+                            uint32_t *values_out, uint32_t *tu_info_out);
+// a stopped substream codes nothing: results[s] = {0, sub_flag[s]} where sub_flag[s] != 0
+hipError_t launch_plan_stops(hipStream_t st, uint32_t n_sub, const uint32_t *sub_flag, cabac_substream_result *results);
+
 // substream assembly (cabac_assemble.hip)
 hipError_t launch_assemble(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc,
                            const cabac_substream_result *results, const uint8_t *bytes, uint8_t *payload,

@@ -258,6 +258,12 @@ hipError_t launch_splice_plan(hipStream_t st, uint32_t n_sub, uint32_t n_tu, con
   return hipGetLastError();
 }
 
+hipError_t launch_splice_scan(hipStream_t st, uint32_t n_sub, const uint32_t *sub_n, const uint32_t *sub_cap, uint64_t *rec_base,
+                              uint64_t *byte_base, const uint32_t *err, uint64_t *totals) {
+  hipLaunchKernelGGL(splice_scan_kernel, dim3(1), dim3(1024), 0, st, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals);
+  return hipGetLastError();
+}
+
 hipError_t launch_splice_expand(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *host_records,
                                 const uint32_t *splice_first, const cabac_splice *splices, const uint32_t *pre,
                                 const uint32_t *sub_n, const uint32_t *sub_cap, const uint64_t *rec_base, const uint64_t *byte_base,
