@@ -20,8 +20,10 @@
 //          0xFFFF).  The emitted stream is the identical number: the top S+1 bits of low >> 8 with
 //          carries resolved (S = bits shifted), which is what finish() (:339-357) leaves.
 //  decode: a 64-bit look-ahead window per row, topped up from a bit cursor every fourth bin without a
-//          branch; after each bin every lane applies it to its own
-//          copy of the context state and the lanes of that row holding the same ctxId keep it.
+//          branch.  The context states: a step in which no row has a context more than twice (chosen a step ahead,
+//          quad_dec_steps_pairs) prepares what the chain needs of them lane-parallel in front of the chain and
+//          brings them up to date once behind it; in any other step every lane applies every bin to its own copy of
+//          the state and the lanes of that row holding the same ctxId keep it.
 //  estimate: BitEstimator_Std on the same records — quad_resolve plus a table lookup, no chain.
 //
 // Layout: row r of wave w codes substream 4w + r.  Rows whose substreams are shorter idle at the end,
@@ -1392,8 +1394,15 @@ constexpr uint32_t kRingStride = 66;  // 64 ring dwords + the mirror of dword 0 
 // depends on the previous one (tools/ubench_ilp.hip), so nothing is gained by shortening dependency
 // chains and everything by dropping instructions.
 // Per-lane state: st_v, the packed context word of the lane's own record (0 for a non-context record).
-// kSpecial: the 16 records contain a terminate or an align record (rare) — the common variant leaves their
-// handling out.
+// Three variants of a step, chosen a step ahead (prepare() in the kernel):
+//   pairs (kPairs, L = 16 only): no row has a context more than twice.  The chain does no context update at all: lane I
+//     hands bin I the derived word of its state (QuadDecPair), and the states are brought up to date once behind the
+//     chain, lane-parallel (quad_dec_steps_pairs).
+//   generic: any repetition.  After each bin every lane applies it to its own copy of the state, and the lanes of the
+//     row that hold the bin's ctxId keep the result — six instructions per bin of which all but the matching lanes'
+//     are thrown away.
+//   kSpecial: the generic one for steps whose 16 records contain a terminate or an align record (rare) — the other
+//     two leave their handling out.
 // The row-uniform fields of the 16 records of a step, one register per bin: the lanes compute them (lane I for bin I),
 // park them in LDS and every lane reads its row's sixteen back with four 16-byte reads per field — an LDS read of one
 // address by all lanes of a row IS the broadcast, and it replaces one v_mov_b32_dpp per bin and field (the consumers are
@@ -1423,10 +1432,64 @@ struct QuadDecRow {   // L = 64: the fields of sixteen bins at a time (quad_dec_
   }
 };
 
-template <int I, bool kSpecial, int L = 16>
+// What the pairs variant keeps per lane instead of a state that is updated bin by bin.  A context occurs at most twice
+// in the row's step: the lane of a first (or only) occurrence hands the chain the derived word of the stored state; the
+// lane of a second occurrence that of the state after ONE earlier bin — one of two candidates, both known before the
+// chain starts, picked as soon as that earlier bin is in `bits` (row-uniform).
+// Derived word: k | MPS << 31 — the 24-bit multiply-add of the LPS width reads k unmasked, and the MPS meets the sign of
+// value - scaledRange in bit 31 with one exclusive or.
+#ifndef CABAC_PAIR_PICK
+#define CABAC_PAIR_PICK 4     // experiments only: 1, 2 — other cadences; 0 — the choice is made, the variant never taken
+#endif
+constexpr int kPairPick = CABAC_PAIR_PICK;  // the pick runs behind bins kPairPick - 1, 2 kPairPick - 1, ...: the two occurrences of a
+                                            // context then must not share an aligned group of kPairPick bins (1: no such condition)
+constexpr int kPairEvery = kPairPick > 0 ? kPairPick : 1;
+struct QuadDecPair {
+  uint32_t d;       // the derived word this lane hands to the chain (settled before the lane's bin is reached)
+  uint32_t d0, d1;  // ... after the earlier occurrence decoded 0 / 1 (a first occurrence: twice that of the stored state)
+  uint32_t p1;      // position of the context's first occurrence in the step
+};
+__device__ __forceinline__ uint32_t quad_dec_derived(uint32_t st) {  // state() / getLPS, contexts.cpp:939-950
+  const uint32_t sum = (st & 0xffffu) + (st >> 16);
+  const uint32_t sx = (uint32_t)((int32_t)(sum << 16) >> 31);
+  return (((sum >> 10) ^ sx) & 31u) | (sx & 0x80000000u);
+}
+
+template <int I, bool kSpecial, int L = 16, bool kPairs = false>
 __device__ __forceinline__ void quad_dec_step(const QuadDecInfo &f, const QuadDecRow<L> &u, uint32_t r0_v, uint32_t a_v, uint32_t &st_v,
-                                              uint32_t (&bits)[2], QuadDec &w) {
+                                              uint32_t (&bits)[2], QuadDec &w, QuadDecPair *pr = nullptr) {
   constexpr int J = I % QuadDecRow<L>::kN;  // where bin I's fields sit in u
+  if constexpr (kPairs) {
+    static_assert(L == 16 && !kSpecial, "the pairs variant is the quad decoder's, without special records");
+    const uint32_t dw = group_bcast<L, I>(pr->d);
+    const uint32_t t = (__umul24(w.range >> 5, dw) + u.c2[J]) >> 1;  // (the multiplication reads bits 23..0: k)
+    const uint32_t rm = w.range - t;
+    uint32_t e, ngem;  // as below
+    asm("v_mad_i32_i24 %0, %2, %3, %4\n\tv_ashrrev_i32 %1, 31, %0" : "=v"(e), "=v"(ngem) : "v"(rm), "v"(u.srmul[J]), "v"(w.hi));
+    const uint32_t x = sel(u.ctxm[J] & ~ngem, t, rm);
+    const uint32_t nsh = (uint32_t)__builtin_clz(x) - 23u;
+    w.hi = sel(ngem, w.hi, e);
+    w.range = x << nsh;
+    const uint32_t tot = nsh + u.ep[J];
+    const uint64_t v = (((uint64_t)w.hi << 32) | w.lo) << tot;
+    w.hi = (uint32_t)(v >> 32);
+    w.lo = (uint32_t)v;
+    w.used += tot;
+    // The bin as 0 / 1 is needed by no update here, so it is never formed: bit 31 of e ^ dw is (LPS taken) ^ MPS = NOT the bin,
+    // and one v_alignbit_b32 shifts it into bits[0] from below — the bins run the other way, inverted, and after bin I the
+    // bin of position p sits at bit I - p; behind bin 15 they are turned into the usual order (bit I = bin I).
+    bits[0] = __builtin_amdgcn_alignbit(bits[0], e ^ dw, 31);
+    if constexpr (I % kPairEvery == kPairEvery - 1 && I != 15) {
+      // every lane, a second occurrence or not: NOT bin p1 as a mask (some other bit where p1 is yet to come — those lanes
+      // pick again before their bin is reached)
+      uint32_t pm;
+      asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(pm) : "v"(bits[0]), "v"((uint32_t)I - pr->p1));
+      pr->d = sel(pm, pr->d0, pr->d1);
+    }
+    if constexpr (I == 15) bits[0] = ~__builtin_bitreverse32(bits[0]) >> 16;
+    if ((I & 3) == 0) quad_dec_topup(w);
+    return;
+  }
   // the state of this bin's context, from the lane that holds the record; state() / getLPS, contexts.cpp:939-950
   uint32_t sum;  // the two estimators added: the low half carries no rate bits here (see the kernel)
   if constexpr (L == 64) {
@@ -1486,8 +1549,8 @@ __device__ __forceinline__ void quad_dec_step(const QuadDecInfo &f, const QuadDe
   }
   bits[I >> 5] |= bin << (I & 31);
   if constexpr (L == 64) asm volatile("" : "+v"(bits[I >> 5]));  // now: left to itself hipcc keeps all 64 shifted bins and ORs them at the end
-  // every lane applies the bin to its own copy of the state; the lanes of this row that hold the
-  // same ctxId keep it (update(), contexts.cpp:903-913).
+  // (generic and special steps) every lane applies the bin to its own copy of the state; the lanes of this row that hold
+  // the same ctxId keep it (update(), contexts.cpp:903-913).
   // Both 15-bit estimators at once with packed 16-bit math: the halves never borrow or carry into each
   // other, and the rate bits below bit 5 ride along untouched.
   typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -1530,6 +1593,43 @@ __device__ __forceinline__ void quad_dec_steps(const QuadDecInfo &f, QuadDecRow<
 #undef QSTEP
 }
 
+// The pairs variant of a 16-bin step (L = 16).  same: the lanes of this lane's row that hold its context (bit k: lane k of
+// the row; itself included; 0 for a lane without a context) — at most two, and no two inside an aligned group of kPairPick
+// bins, which is what prepare() chose the variant by.  In front of the chain every lane forms the two states its context
+// can have after one bin and the derived words; behind it every lane of a context computes the same final state — the
+// stored one updated by the first occurrence's bin, then by the second's if there is one — with the packed 16-bit update
+// of the generic step, so that the store that follows stays the unconditional one it is.
+__device__ __forceinline__ void quad_dec_steps_pairs(const QuadDecInfo &f, const QuadDecRow<16> &u, uint32_t r0_v, uint32_t a_v, uint32_t same,
+                                                     uint32_t j, uint32_t &st_v, uint32_t (&bits)[2], QuadDec &w) {
+  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+  const u16x2 r2 = __builtin_bit_cast(u16x2, r0_v), a2 = __builtin_bit_cast(u16x2, a_v);
+  const u16x2 mask2 = __builtin_bit_cast(u16x2, (kMask1 << 16) | kMask0);
+  auto decayed = [&](uint32_t s) {  // update(), contexts.cpp:903-913, by a bin 0; a bin 1 adds a2 to it
+    const u16x2 s2 = __builtin_bit_cast(u16x2, s);
+    return (u16x2)(s2 - ((s2 >> r2) & mask2));
+  };
+  const u16x2 rest = decayed(st_v);
+  const uint32_t u0 = __builtin_bit_cast(uint32_t, rest), u1 = __builtin_bit_cast(uint32_t, (u16x2)(rest + a2));
+  const uint32_t secondm = neg_mask(0u - (same & ((1u << j) - 1u)));  // ~0: an earlier lane of the row holds this context
+  QuadDecPair pr;
+  pr.p1 = (uint32_t)__builtin_ctz(same | 0x10000u);
+  pr.d0 = quad_dec_derived(sel(secondm, u0, st_v));
+  pr.d1 = quad_dec_derived(sel(secondm, u1, st_v));
+  pr.d = pr.d0;
+#define QSTEP(I) quad_dec_step<I, false, 16, true>(f, u, r0_v, a_v, st_v, bits, w, &pr)
+  QSTEP(0); QSTEP(1); QSTEP(2); QSTEP(3); QSTEP(4); QSTEP(5); QSTEP(6); QSTEP(7);
+  QSTEP(8); QSTEP(9); QSTEP(10); QSTEP(11); QSTEP(12); QSTEP(13); QSTEP(14); QSTEP(15);
+#undef QSTEP
+  uint32_t m1;
+  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m1) : "v"(bits[0]), "v"(pr.p1));
+  const uint32_t s1 = sel(m1, u1, u0);
+  const uint32_t later = same & (same - 1u);                          // the second occurrence, if there is one
+  uint32_t m2;
+  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m2) : "v"(bits[0]), "v"((uint32_t)__builtin_ctz(later | 0x10000u)));
+  const uint32_t s2 = __builtin_bit_cast(uint32_t, (u16x2)(decayed(s1) + __builtin_bit_cast(u16x2, a_v & m2)));
+  st_v = sel(neg_mask(0u - later), s2, s1);
+}
+
 // W independent waves per workgroup: with W = 4 a workgroup's waves are dealt to the CU's four SIMDs, which
 // pins "one chain wave per SIMD" instead of leaving it to where the dispatcher happens to put
 // single-wave workgroups (measured: the same decode kernel ran 2.06 ms or 3.3 ms depending on the geometry
@@ -1556,6 +1656,10 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
   __shared__ __attribute__((aligned(16))) uint32_t rec_tab[512][8];
   __shared__ uint32_t ring_all[W * kSubs * kRingStride];
   __shared__ uint32_t field_all[W][5][64];  // the record fields of a step on their way from lane I to the row (QuadDecRow)
+  // L = 16: which lanes of a row hold which context, 16 bits per row and context, two rows per word (the bitmap of the v7
+  // encoder's context waves, quad_resolve; only contexts take part, so 384 words per pair of rows; all zero between uses)
+  constexpr uint32_t kPairWords = L == 16 ? 768u : 1u;
+  __shared__ uint32_t pair_all[W][kPairWords];
   const uint32_t wave = threadIdx.x >> 6;
   uint32_t *ctx = ctx_all + wave * (kSubs * kQuadCtxStride);
   const uint32_t lane = threadIdx.x & 63u, row = lane / L, j = lane % L;
@@ -1593,6 +1697,9 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
     rec_tab[id][5] = a_v;
     rec_tab[id][6] = ~trm_m;
     rec_tab[id][7] = aln_m;
+  }
+  if constexpr (L == 16) {
+    for (uint32_t k = threadIdx.x; k < W * kPairWords; k += 64u * W) (&pair_all[0][0])[k] = 0u;
   }
   __syncthreads();
 
@@ -1647,6 +1754,14 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
   uint32_t rq0 = load_rec(0), rq1 = load_rec(L), rq2 = load_rec(2u * L), rq3 = L == 64 ? 0u : load_rec(3u * L);
   uint32_t prev_bin = 0, prev_idx = ~0u;  // the bins of the previous step, not yet stored
   uint64_t prev_lanes = 0;                 // ... and the lanes that have one
+  // L = 16, the choice of the pairs variant: this lane's place in the bitmap, its own bit among the row's sixteen and the
+  // other lanes of its aligned group of kPairPick (a context twice in there is too close for the pick's cadence)
+  uint32_t *const pair_words = &pair_all[wave][(row >> 1) * 384u];
+  const uint32_t pair_shift = (row & 1u) << 4, pair_own = 1u << (j & 15u);
+  const uint32_t pair_near = ((((1u << kPairEvery) - 1u) << (j & 15u & ~(uint32_t)(kPairEvery - 1))) & ~pair_own) & 0xffffu;
+  uint32_t cur_same = 0;
+  uint64_t cur_generic = 0;  // lanes that rule the pairs variant out for the step
+  uint32_t nxt_got = 0;       // the bitmap word of this lane's context, read a step ahead
   uint32_t nxt_id, nxt_actm;
   uint4 nxt_a, nxt_b;
   auto request = [&](uint32_t base, uint32_t r) {  // stage 1 for the step at `base`, whose record is r: its id and table row
@@ -1655,6 +1770,18 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
     const uint4 *row4 = reinterpret_cast<const uint4 *>(rec_tab[nxt_id]);
     nxt_a = row4[0];
     nxt_b = row4[1];
+    if constexpr (L == 16) {
+      // the lanes of the row with this lane's context: every context lane ORs its bit into the word of (row, id), reads the
+      // word back and clears it (one wave: LDS executes its instructions in order).  Lanes without a context — bypass,
+      // terminate, align, "nothing" past the row's end — go to spare words, and prepare() leaves them no lane at all.
+      // Asked here, a whole chain before prepare() reads the answer: at the end of the step it was a round trip waited for.
+      uint32_t *word = pair_words + sel(neg_mask(nxt_id - (uint32_t)kNumCtx), nxt_id, (uint32_t)kNumCtx + (j & 3u));
+      atomicOr(word, pair_own << pair_shift);
+      asm volatile("" ::: "memory");
+      nxt_got = *word;
+      asm volatile("" ::: "memory");
+      *word = 0u;
+    }
   };
   uint32_t cur_id, cur_stored, cur_ctxm, cur_r0v, cur_av;
   uint64_t cur_special;
@@ -1674,6 +1801,12 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
     f.ntrm = nxt_b.z;
     f.alm = nxt_b.w;
     cur_special = __ballot((~f.ntrm | f.alm) != 0);
+    if constexpr (L == 16) {
+      cur_same = (nxt_got >> pair_shift) & 0xffffu & ctxm;   // the row's lanes with this lane's context (request())
+      // pairs variant iff no lane has a special record, two other lanes with its context, or one too near
+      const uint32_t others = cur_same & ~pair_own;
+      cur_generic = __ballot(((~f.ntrm | f.alm) | (others & (others - 1u)) | (others & pair_near)) != 0);
+    }
     bad |= nxt_actm & ~ctxm & neg_mask(id - CABAC_REC_ALIGN);
     f.key = sel(ctxm, id, 0x200u + j);
     // one wave writes and reads: LDS executes a wave's instructions in order, only the compiler has to keep it
@@ -1719,6 +1852,9 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
     // asked long ago, needed now (the choice of the step variant): the branch finds the answer waiting
     uint64_t special = cur_special;
     asm volatile("" : "+s"(special));
+    uint64_t generic = cur_generic;
+    const uint32_t same = cur_same;
+    if constexpr (L == 16) asm volatile("" : "+s"(generic));
     uint32_t st_v = cur_stored & ctxm;
     const uint32_t a_v = cur_av, r0_v = cur_r0v;
     request(base + L, rq);                              // the id and table row of the next step
@@ -1731,8 +1867,15 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
     }
     uint32_t bits[2] = {0u, 0u};  // row-uniform: bit I = the bin of record base + I
     V5_TICK(t2);
-    if (__builtin_expect(special == 0, 1)) quad_dec_steps<false, L>(f, u, &field_all[wave][0][0], r0_v, a_v, st_v, bits, w);
-    else quad_dec_steps<true, L>(f, u, &field_all[wave][0][0], r0_v, a_v, st_v, bits, w);
+    if constexpr (L == 16) {
+      // one branch on the expected path: pairs or not; from the other side on as before
+      if (kPairPick > 0 && __builtin_expect(generic == 0, 1)) quad_dec_steps_pairs(f, u, r0_v, a_v, same, j, st_v, bits, w);
+      else if (__builtin_expect(special == 0, 1)) quad_dec_steps<false, L>(f, u, &field_all[wave][0][0], r0_v, a_v, st_v, bits, w);
+      else quad_dec_steps<true, L>(f, u, &field_all[wave][0][0], r0_v, a_v, st_v, bits, w);
+    } else {
+      if (__builtin_expect(special == 0, 1)) quad_dec_steps<false, L>(f, u, &field_all[wave][0][0], r0_v, a_v, st_v, bits, w);
+      else quad_dec_steps<true, L>(f, u, &field_all[wave][0][0], r0_v, a_v, st_v, bits, w);
+    }
     V5_TICK(t3);
     const uint32_t my_bin = ((L > 32 && j >= 32u ? bits[1] : bits[0]) >> (j & 31u)) & 1u;
     rctx[sel(ctxm, id, (uint32_t)kNumCtx)] = st_v;  // a lane without a context writes the pad word
