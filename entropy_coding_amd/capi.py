@@ -83,6 +83,10 @@ EXPORTS_PARSE_PLAN = [
 EXPORTS_WRITE_PLAN = [
     "cabac_hip_write_plan_device", "cabac_hip_write_plan_batch",
 ]
+# include/cabac_hip_search_plan.h (search rounds over plans; tests/test_search_plan_abi.py compares)
+EXPORTS_SEARCH_PLAN = [
+    "cabac_hip_resolve_plan_device", "cabac_hip_search_plan_round_device", "cabac_hip_search_plan_round_batch",
+]
 PE_COND, PE_BLOCK_INFO = 9, 10                                   # CABAC_PE_COND, CABAC_PE_BLOCK_INFO
 JOIN_NONE, JOIN_AND, JOIN_OR = range(3)                          # CABAC_JOIN_*
 RES_BAD_VALUE = 0x20                                             # CABAC_RES_BAD_VALUE
@@ -290,6 +294,13 @@ def load_library():
                                               ctypes.c_uint64, vp, vp, vp, vp]
     L.cabac_hip_write_plan_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, ctypes.c_int,
                                              ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp, vp]
+    L.cabac_hip_resolve_plan_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_int, vp, vp,
+                                                ctypes.c_uint64, vp, vp, vp, vp, vp, vp]
+    L.cabac_hip_search_plan_round_device.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, ctypes.c_int] + \
+        [vp] * 10 + [ctypes.c_uint64] + [vp] * 8 + [ctypes.c_uint64] + [vp] * 4
+    L.cabac_hip_search_plan_round_batch.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, ctypes.c_uint64,
+                                                    vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp,
+                                                    ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_search_log_create.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                               ctypes.c_int, ctypes.POINTER(vp)]
     L.cabac_hip_search_log_destroy.argtypes = [vp]
@@ -446,7 +457,8 @@ class CabacHip:
         cabac_hip_nal.h; 15 residual estimate with contexts, 16 search select, 17 / 18 a round's estimate / commit in
         cabac_hip_search.h; 19 unit estimate, 20 / 21 / 22 a unit round's estimate / select / commit in cabac_hip_search_unit.h; 23 log append and
         24 log place in cabac_hip_search_emit.h; 25 unit parse in cabac_hip_parse_unit.h; 26 element parse in
-        cabac_hip_parse_elements.h; 27 plan parse in cabac_hip_parse_plan.h; 28 plan write in cabac_hip_write_plan.h)."""
+        cabac_hip_parse_elements.h; 27 plan parse in cabac_hip_parse_plan.h; 28 plan write in cabac_hip_write_plan.h; 29 plan resolve in
+        cabac_hip_search_plan.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -690,6 +702,77 @@ class CabacHip:
             info.ctypes.data if with_blocks else None)
         self._check(rc, allow_substream=not check)
         out = (bits[:n_cand], pick[:n_group], cost[:n_group])
+        if with_blocks:
+            out += (tu_bits[: len(tus)], info[: len(tus)])
+        return out
+
+    # ---- search rounds over plans (include/cabac_hip_search_plan.h) ------
+    def resolve_plan_device(self, n_cand, d_cand_first, d_ent_first, d_plan, d_values_in, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff,
+                            d_rec_first, d_records, record_capacity, d_tu_at_out, d_tu_out, d_flags, d_values_out=0, d_tu_info=0,
+                            d_total=0, int16=False):
+        """cabac_hip_resolve_plan_device: candidate c = the plan entries d_plan[2 * d_ent_first[c] ..) (d_ent_first uint64) with the
+        values d_values_in and its blocks -> the candidate format of estimate_unit_device / search_unit_round_device /
+        SearchLog.append_device: d_rec_first, d_records (record_capacity records), d_tu_at_out, d_tu_out; d_flags[c] = 0,
+        RES_BAD_RECORD, RES_BAD_VALUE or RES_OVERFLOW (the call did not fit: d_total says what it needs)."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_resolve_plan_device(
+            self.h, n_cand, vp(d_cand_first), vp(d_ent_first), opt(d_plan), opt(d_values_in), n_tu, opt(d_tu), opt(d_tu_at),
+            opt(d_tu_guard), opt(d_coeff), 2 if int16 else 4, vp(d_rec_first), opt(d_records), record_capacity, opt(d_tu_at_out),
+            opt(d_tu_out), opt(d_values_out), opt(d_tu_info), vp(d_flags), opt(d_total)))
+
+    def search_plan_round_device(self, n_group, d_group_first, n_cand, d_cand_first, n_tu, d_tu, d_coeff, d_state, d_rate, d_set,
+                                 d_ent_first, d_plan, d_values_in, d_tu_at, d_tu_guard, d_group_out_set, d_dist, lambda_q16, d_frac_bits,
+                                 d_pick, d_cost, d_rec_first, d_records, record_capacity, d_tu_at_out, d_tu_out, d_tu_frac_bits=0,
+                                 d_tu_info=0, d_flags=0, d_values_out=0, d_total=0, int16=False):
+        """cabac_hip_search_plan_round_device: search_unit_round_device over candidates given as plans (see resolve_plan_device);
+        the resolved form is left in d_rec_first / d_records / d_tu_at_out / d_tu_out for SearchLog.append_device."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_search_plan_round_device(
+            self.h, n_group, vp(d_group_first), n_cand, vp(d_cand_first), n_tu, opt(d_tu), opt(d_coeff), 2 if int16 else 4, vp(d_state),
+            vp(d_rate), vp(d_set), vp(d_ent_first), opt(d_plan), opt(d_values_in), opt(d_tu_at), opt(d_tu_guard), opt(d_group_out_set),
+            opt(d_dist), lambda_q16, vp(d_frac_bits), vp(d_pick), vp(d_cost), opt(d_tu_frac_bits), opt(d_tu_info), opt(d_flags),
+            vp(d_rec_first), opt(d_records), record_capacity, opt(d_tu_at_out), opt(d_tu_out), opt(d_values_out), opt(d_total)))
+
+    def search_plan_round_batch(self, group_first, cand_first, tus, coeff, state, rate, sets, plan, values, ent_first, tu_at, tu_guard,
+                                group_out_set, dist, lambda_q16, int16=False, with_blocks=False, check=True):
+        """Host arrays through cabac_hip_search_plan_round_batch (synchronous): search_unit_round_batch with the plans `plan`
+        (uint32 (n_entries, 2)), `values` (uint32 per entry), `ent_first` (uint64[n_cand + 1]), `tu_at` (in plan entries) and
+        `tu_guard` (uint32 per block, or None) in place of the side records.  state / rate are updated IN PLACE.  Returns
+        (frac_bits, pick, cost, flags, filled values), with with_blocks also (tu_frac_bits, tu_info)."""
+        group_first = np.ascontiguousarray(group_first, np.uint32)
+        cand_first = np.ascontiguousarray(cand_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        coeff = np.ascontiguousarray(coeff, np.int16 if int16 else np.int32)
+        sets = np.ascontiguousarray(sets, np.uint32)
+        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
+        values = np.ascontiguousarray(values, np.uint32)
+        ent_first = np.ascontiguousarray(ent_first, np.uint64)
+        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
+        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
+        assert state.dtype == np.uint32 and rate.dtype == np.uint8 and state.flags.c_contiguous and rate.flags.c_contiguous
+        assert state.size == rate.size and state.size % NUM_CTX == 0
+        n_group, n_cand = len(group_first) - 1, len(cand_first) - 1
+        assert n_group >= 0 and n_cand >= 0 and len(sets) == n_cand and len(ent_first) == n_cand + 1 and len(values) >= len(plan)
+        assert (tu_at is None or len(tu_at) == len(tus)) and (tu_guard is None or len(tu_guard) == len(tus))
+        out_set = None if group_out_set is None else np.ascontiguousarray(group_out_set, np.uint32)
+        dist = None if dist is None else np.ascontiguousarray(dist, np.uint64)
+        assert (out_set is None or len(out_set) == n_group) and (dist is None or len(dist) == n_cand)
+        bits = np.zeros(max(n_cand, 1), np.uint64)
+        pick = np.zeros(max(n_group, 1), np.uint32)
+        cost = np.zeros(max(n_group, 1), np.uint64)
+        flags = np.zeros(max(n_cand, 1), np.uint32)
+        filled = np.zeros(max(len(plan), 1), np.uint32)
+        tu_bits = np.zeros(max(len(tus), 1), np.uint64)
+        info = np.zeros(max(len(tus), 1), np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        rc = self.L.cabac_hip_search_plan_round_batch(
+            self.h, n_group, group_first.ctypes.data, n_cand, cand_first.ctypes.data, tus.ctypes.data, coeff.ctypes.data,
+            2 if int16 else 4, len(coeff), state.ctypes.data, rate.ctypes.data, state.size // NUM_CTX, sets.ctypes.data,
+            plan.ctypes.data, values.ctypes.data, len(plan), ent_first.ctypes.data, ptr(tu_at), ptr(tu_guard), ptr(out_set), ptr(dist),
+            lambda_q16, bits.ctypes.data, pick.ctypes.data, cost.ctypes.data, tu_bits.ctypes.data if with_blocks else None,
+            info.ctypes.data if with_blocks else None, flags.ctypes.data, filled.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        out = (bits[:n_cand], pick[:n_group], cost[:n_group], flags[:n_cand], filled[: len(plan)])
         if with_blocks:
             out += (tu_bits[: len(tus)], info[: len(tus)])
         return out

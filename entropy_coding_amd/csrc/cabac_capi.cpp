@@ -24,6 +24,7 @@
 #include "cabac_hip_parse_unit.h"
 #include "cabac_hip_search.h"
 #include "cabac_hip_search_emit.h"
+#include "cabac_hip_search_plan.h"
 #include "cabac_hip_search_unit.h"
 #include "cabac_hip_write_plan.h"
 #include "cabac_kernels.h"
@@ -52,8 +53,9 @@ struct cabac_hip_ctx {
   // [5]: scratch of the residual binariser, [6]: compacted payload, [7]: payload offsets; [8..]: the spliced-residual path
   // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
   // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included); [48..]: the winner log (kLog* below); [53..]: the
-  // unit parse (kUnit* below); [56..]: the element parse (kElem* below); [59..]: the plan write (kPw* below)
-  static constexpr int kSlots = 61;
+  // unit parse (kUnit* below); [56..]: the element parse (kElem* below); [59..]: the plan write (kPw* below); [61..]: the plan
+  // resolve of the search rounds (kPs* below)
+  static constexpr int kSlots = 64;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -1355,10 +1357,11 @@ const char *bad_computed_entry(uint32_t w0, uint32_t w1, uint64_t i, uint32_t nb
 
 namespace {
 // what the host-pointer forms of the plan parse and the plan write refuse about descriptors, plan, guards, tile_first, tu_at and
-// coefficient ranges; bytes_total: null where the descriptors' byte ranges are not input (the writer)
+// coefficient ranges; bytes_total: null where the descriptors' byte ranges are not input (the writer); unit: what the messages call
+// a descriptor's owner (the plan search describes its candidates this way)
 int check_plan_host(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint64_t *bytes_total,
                     const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
-                    const uint32_t *plan, uint64_t n_elements_total, uint64_t n_coeff_total) {
+                    const uint32_t *plan, uint64_t n_elements_total, uint64_t n_coeff_total, const char *unit = "substream") {
   const uint32_t n_tu = tile_first[n_sub];
   char buf[200];
   for (uint32_t s = 0; s < n_sub; s++) {
@@ -1379,7 +1382,7 @@ int check_plan_host(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc
         at = uint32_t(n_el);
       }
       if (tu_guard && ((tu_guard[t] & 0xfc00u) || (tu_guard[t] & 0xffu) > at)) {
-        snprintf(buf, sizeof buf, "bad block guard: substream %u, block %u of its blocks (guard 0x%x at element %u)", s,
+        snprintf(buf, sizeof buf, "bad block guard: %s %u, block %u of its blocks (guard 0x%x at element %u)", unit, s,
                  t - tile_first[s], tu_guard[t], at);
         return fail(c, CABAC_HIP_ERR_INVALID, buf);
       }
@@ -1390,7 +1393,7 @@ int check_plan_host(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc
       while (tu_at && t < tile_first[s + 1] && tu_at[t] <= i) t++;
       const uint32_t *e = plan + 2 * (desc[s].rec_offset + i);
       if (const char *why = bad_computed_entry(e[0], e[1], i, t - tile_first[s])) {
-        snprintf(buf, sizeof buf, "bad plan entry: substream %u, element %llu of its plan (word0 0x%x, word1 0x%x): %s", s,
+        snprintf(buf, sizeof buf, "bad plan entry: %s %u, element %llu of its plan (word0 0x%x, word1 0x%x): %s", unit, s,
                  (unsigned long long)i, e[0], e[1], why);
         return fail(c, CABAC_HIP_ERR_INVALID, buf);
       }
@@ -2181,6 +2184,21 @@ struct HostSide {
   const uint32_t *tu_at;
 };
 
+// the plans of the host-pointer form of cabac_hip_search_plan.h (null: one of the other two rounds)
+struct HostPlan {
+  const uint32_t *plan, *values_in;
+  uint64_t n_entries_total;
+  const uint64_t *ent_first;
+  const uint32_t *tu_at, *tu_guard;
+  uint32_t *flags, *values_out;
+};
+int check_search_plan_host(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus, const HostPlan &hp,
+                           uint64_t n_coeff_total, uint64_t *record_bound);
+int search_plan_stage_and_run(cabac_hip_ctx *c, uint32_t n_group, uint32_t n_cand, uint32_t n_tu, int coeff_bytes, const HostPlan &hp,
+                              uint64_t record_bound, bool has_out_set, bool has_dist, uint64_t lambda_q16, uint64_t *d_bits,
+                              uint64_t *d_tu_bits, uint32_t *d_info);
+int search_plan_fetch(cabac_hip_ctx *c, uint32_t n_cand, const HostPlan &hp, int *status);
+
 int estimate_residual_ctx_device_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
                                       const void *d_coeff, int coeff_bytes, const uint32_t *d_state, const uint8_t *d_rate,
                                       const uint32_t *d_set, uint64_t *d_frac_bits, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info,
@@ -2273,7 +2291,8 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
                                    const uint32_t *cand_first, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
                                    uint64_t n_coeff_total, uint32_t *state, uint8_t *rate, uint32_t n_sets, const uint32_t *set,
                                    const uint32_t *group_out_set, const uint64_t *dist, uint64_t lambda_q16, uint64_t *frac_bits,
-                                   uint32_t *pick, uint64_t *cost, uint64_t *tu_frac_bits, uint32_t *tu_info, const HostSide *side) {
+                                   uint32_t *pick, uint64_t *cost, uint64_t *tu_frac_bits, uint32_t *tu_info, const HostSide *side,
+                                   const HostPlan *hp = nullptr) {
   if (!c || !group_first || !cand_first || (n_cand && (!state || !rate || !set || !frac_bits)) || (n_group && (!pick || !cost)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
@@ -2339,6 +2358,9 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
       }
     }
   }
+  uint64_t record_bound = 0;
+  if (hp)  // what cabac_hip_search_plan.h refuses on top
+    if (int bad = check_search_plan_host(c, n_cand, cand_first, tus, *hp, n_coeff_total, &record_bound)) return bad;
   if (n_cand == 0 && n_group == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
   int rc;
@@ -2382,7 +2404,10 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
     HIP_TRY(c, hipMemsetAsync(d_tu_bits, 0, size_t(n_tu) * sizeof(uint64_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(d_info, 0, size_t(n_tu) * sizeof(uint32_t), c->stream));
   }
-  if (side)
+  if (hp)
+    rc = search_plan_stage_and_run(c, n_group, n_cand, n_tu, coeff_bytes, *hp, record_bound, group_out_set != nullptr, dist != nullptr,
+                                   lambda_q16, d_bits, d_tu_bits, d_info);
+  else if (side)
     rc = cabac_hip_search_unit_round_device(
         c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand, (const uint32_t *)c->d_buf[kEstInFirst],
         (const cabac_tu_desc *)c->d_buf[kEstInTu], c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState],
@@ -2421,6 +2446,12 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   int status = CABAC_HIP_OK;
+  if (hp) {  // the plan's info words: a block without records stops its candidate only where it is coded (see flags[])
+    for (uint32_t t = 0; t < n_tu && tu_info; t++) tu_info[t] = info[t];
+    if ((rc = search_plan_fetch(c, n_cand, *hp, &status))) return rc;
+    if (status) c->last_error = "a candidate has a flag set (see flags[])";
+    return status;
+  }
   for (uint32_t t = 0; t < n_tu; t++) {
     if (tu_info) tu_info[t] = info[t];
     if (info[t] & (CABAC_TU_INFO_EMPTY | CABAC_TU_INFO_BAD_DESC)) status = CABAC_HIP_ERR_SUBSTREAM;
@@ -2508,6 +2539,236 @@ int cabac_hip_search_unit_round_batch(cabac_hip_ctx *c, uint32_t n_group, const 
   const HostSide side{records, n_records_total, rec_first, tu_at};
   return search_round_batch_impl(c, n_group, group_first, n_cand, cand_first, tus, coeff, coeff_bytes, n_coeff_total, state, rate,
                                  n_sets, set, group_out_set, dist, lambda_q16, frac_bits, pick, cost, tu_frac_bits, tu_info, &side);
+}
+
+// ---- search rounds over plans (declared in cabac_hip_search_plan.h; kernels in cabac_plan_search.hip) ---------------------------
+namespace {
+// device slots: the counts and (where the caller gives none) the flags of the resolve; the staging of the host-pointer form (the
+// rest of it goes through the slots of the other rounds, of the plan write and of the element parse)
+enum { kPsCnt = 61, kPsEnt = 62, kPsFlags = 63 };
+
+// the most bins a value in its domain makes of an entry that is not bad (cabac_hip_search_plan.h, "THE MOST BINS")
+uint32_t plan_entry_max_bins(uint32_t w0) {
+  const uint32_t kind = w0 & 15u, p = w0 >> 4;
+  switch (kind) {
+  case CABAC_SE_CTX_BIN:
+  case CABAC_SE_TRM:
+  case CABAC_SE_ALIGN: return 1;
+  case CABAC_SE_EP_BINS:
+  case CABAC_SE_UNARY_EP: return p & 63u;
+  case CABAC_SE_UNARY_MAX: return (p >> 18) & 0xffu;
+  case CABAC_SE_TRUNC_BIN: {
+    uint32_t l = 0;
+    while ((p >> l) > 1u) l++;
+    return l + 1;
+  }
+  case CABAC_SE_EXP_GOLOMB: return 63u - (p & 31u);
+  case CABAC_SE_REM_ABS: {
+    const uint32_t rice = p & 31u, cutoff = (p >> 5) & 31u, longest = 32u - cutoff - ((p >> 10) & 63u);
+    return std::max(32u, cutoff + rice + (longest ? 2u * longest - 1u : 0u));
+  }
+  default: return 0;  // computed entries
+  }
+}
+
+// sizes pass, count walk, scan, emit walk: the resolved form of every candidate.  d_flags: never null here
+int resolve_plan_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const uint64_t *d_ent_first, const uint32_t *d_plan,
+                      const uint32_t *d_values_in, uint32_t n_tu, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                      const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes, uint64_t *d_rec_first, uint16_t *d_records,
+                      uint64_t record_capacity, uint32_t *d_tu_at_out, cabac_tu_desc *d_tu_out, uint32_t *d_values_out,
+                      uint32_t *d_tu_info, uint32_t *d_flags, uint64_t *d_total) {
+  int rc;
+  const size_t n_blk = n_tu ? n_tu : 1;
+  if ((rc = ensure(c, kSpCnt, 2 * n_blk * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, 5, cabac::residual_scratch_bytes(n_tu)))) return rc;
+  uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kSpCnt]), *d_info = d_cnt + n_blk;
+  uint32_t *cnt = static_cast<uint32_t *>(c->d_buf[kPsCnt]);
+  const cabac::PlanResolveIn in{n_cand, d_cand_first, d_ent_first, d_plan, d_values_in, n_tu, d_tu, d_tu_at, d_tu_guard, d_info};
+  const cabac::PlanResolveOut out{d_rec_first, d_records, d_tu_at_out, d_tu_out, d_values_out, d_tu_info};
+  {  // info words of ALL blocks: they do not depend on the guards, the guards depend on them
+    Timed t(c, 5);
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[5]));
+  }
+  {
+    Timed t(c, 29);
+    HIP_TRY(c, cabac::launch_plan_resolve_count(c->stream, in, cnt, d_flags));
+    HIP_TRY(c, cabac::launch_plan_resolve_scan(c->stream, n_cand, cnt, d_flags, record_capacity, d_rec_first, d_total));
+    HIP_TRY(c, cabac::launch_plan_resolve_emit(c->stream, in, cnt, d_flags, out));
+  }
+  return CABAC_HIP_OK;
+}
+
+// the pointers a resolve needs, for both device forms
+bool resolve_plan_null(uint32_t n_cand, const uint32_t *d_cand_first, const uint64_t *d_ent_first, uint32_t n_tu, const cabac_tu_desc *d_tu,
+                       const void *d_coeff, uint64_t *d_rec_first, uint16_t *d_records, uint64_t record_capacity, uint32_t *d_tu_at_out,
+                       cabac_tu_desc *d_tu_out) {
+  return !d_rec_first || (n_cand && (!d_cand_first || !d_ent_first)) || (n_tu && (!d_tu || !d_coeff || !d_tu_at_out || !d_tu_out)) ||
+         (record_capacity && !d_records) || (n_tu && d_tu_out == d_tu);
+}
+}  // namespace
+
+int cabac_hip_resolve_plan_device(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const uint64_t *d_ent_first,
+                                  const uint32_t *d_plan, const uint32_t *d_values_in, uint32_t n_tu, const cabac_tu_desc *d_tu,
+                                  const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes,
+                                  uint64_t *d_rec_first, uint16_t *d_records, uint64_t record_capacity, uint32_t *d_tu_at_out,
+                                  cabac_tu_desc *d_tu_out, uint32_t *d_values_out, uint32_t *d_tu_info, uint32_t *d_flags,
+                                  uint64_t *d_total) {
+  if (!c || (n_cand && !d_flags) ||
+      resolve_plan_null(n_cand, d_cand_first, d_ent_first, n_tu, d_tu, d_coeff, d_rec_first, d_records, record_capacity, d_tu_at_out, d_tu_out))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_cand == 0 && n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "blocks without a candidate");
+  DeviceGuard g(c->device);
+  if (int rc = ensure(c, kPsCnt, size_t(n_cand ? n_cand : 1) * sizeof(uint32_t))) return rc;
+  c->timed = false;
+  return resolve_plan_impl(c, n_cand, d_cand_first, d_ent_first, d_plan, d_values_in, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, coeff_bytes,
+                           d_rec_first, d_records, record_capacity, d_tu_at_out, d_tu_out, d_values_out, d_tu_info, d_flags, d_total);
+}
+
+int cabac_hip_search_plan_round_device(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *d_group_first, uint32_t n_cand,
+                                       const uint32_t *d_cand_first, uint32_t n_tu, const cabac_tu_desc *d_tu, const void *d_coeff,
+                                       int coeff_bytes, uint32_t *d_state, uint8_t *d_rate, const uint32_t *d_set,
+                                       const uint64_t *d_ent_first, const uint32_t *d_plan, const uint32_t *d_values_in,
+                                       const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const uint32_t *d_group_out_set,
+                                       const uint64_t *d_dist, uint64_t lambda_q16, uint64_t *d_frac_bits, uint32_t *d_pick,
+                                       uint64_t *d_cost, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info, uint32_t *d_flags,
+                                       uint64_t *d_rec_first, uint16_t *d_records, uint64_t record_capacity, uint32_t *d_tu_at_out,
+                                       cabac_tu_desc *d_tu_out, uint32_t *d_values_out, uint64_t *d_total) {
+  if (!c || (n_cand && (!d_state || !d_rate || !d_set || !d_frac_bits)) || (n_group && (!d_group_first || !d_pick || !d_cost)) ||
+      resolve_plan_null(n_cand, d_cand_first, d_ent_first, n_tu, d_tu, d_coeff, d_rec_first, d_records, record_capacity, d_tu_at_out, d_tu_out))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_cand == 0 && n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "blocks without a candidate");
+  if (n_cand == 0 && n_group == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  int rc;
+  if ((rc = ensure(c, kEstScratch, cabac::residual_estimate_scratch_bytes(std::max(n_cand, n_group))))) return rc;
+  if ((rc = ensure(c, kPsCnt, 2 * size_t(n_cand ? n_cand : 1) * sizeof(uint32_t)))) return rc;
+  uint32_t *flags = d_flags ? d_flags : static_cast<uint32_t *>(c->d_buf[kPsCnt]) + (n_cand ? n_cand : 1);
+  c->timed = false;  // several brackets: read them with cabac_hip_profile_read
+  if ((rc = resolve_plan_impl(c, n_cand, d_cand_first, d_ent_first, d_plan, d_values_in, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff,
+                              coeff_bytes, d_rec_first, d_records, record_capacity, d_tu_at_out, d_tu_out, d_values_out, d_tu_info, flags,
+                              d_total)))
+    return rc;
+  {  // estimate: every candidate's resolved form from its start set; the info words and the flags stay the resolve's
+    Timed t(c, 20);
+    HIP_TRY(c, cabac::launch_unit_estimate(c->stream, n_cand, nullptr, n_cand, d_cand_first, d_tu_out, d_coeff, coeff_bytes, d_state, d_rate,
+                                           d_set, d_rec_first, d_records, d_tu_at_out, nullptr, nullptr, nullptr, d_frac_bits,
+                                           d_tu_frac_bits, nullptr, nullptr, c->d_buf[kEstScratch]));
+  }
+  {  // select, in front of it the cost of the flagged candidates
+    Timed t(c, 21);
+    HIP_TRY(c, cabac::launch_plan_flag_cost(c->stream, n_cand, flags, d_frac_bits));
+    if (n_group)
+      HIP_TRY(c, cabac::launch_search_select(c->stream, n_group, n_cand, d_group_first, d_frac_bits, d_dist, lambda_q16, d_pick, d_cost));
+  }
+  {  // commit: the picked candidates walked once more in their resolved form (d_pick is the index list)
+    Timed t(c, 22);
+    if (n_group && d_group_out_set && n_cand)
+      HIP_TRY(c, cabac::launch_unit_estimate(c->stream, n_group, d_pick, n_cand, d_cand_first, d_tu_out, d_coeff, coeff_bytes, d_state,
+                                             d_rate, d_set, d_rec_first, d_records, d_tu_at_out, d_group_out_set, d_state, d_rate, nullptr,
+                                             nullptr, nullptr, nullptr, c->d_buf[kEstScratch]));
+  }
+  return CABAC_HIP_OK;
+}
+
+namespace {
+int check_search_plan_host(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus, const HostPlan &hp,
+                           uint64_t n_coeff_total, uint64_t *record_bound) {
+  if (!hp.ent_first || (hp.n_entries_total && (!hp.plan || !hp.values_in))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  for (uint32_t k = 0; k < n_cand; k++)
+    if (hp.ent_first[k] > hp.ent_first[k + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "ent_first is not non-decreasing");
+  if (hp.ent_first[n_cand] > hp.n_entries_total) return fail(c, CABAC_HIP_ERR_INVALID, "ent_first ends past n_entries_total");
+  // the plans as the plan write's check sees them: one descriptor per candidate
+  std::vector<cabac_substream_desc> desc(n_cand);
+  for (uint32_t k = 0; k < n_cand; k++) {
+    const uint64_t n_ent = hp.ent_first[k + 1] - hp.ent_first[k];
+    if (n_ent > 0xffffffffull) return fail(c, CABAC_HIP_ERR_INVALID, "ent_first: a plan longer than 2^32 - 1 entries");
+    uint32_t at = 0;
+    for (uint32_t t = cand_first[k]; hp.tu_at && t < cand_first[k + 1]; t++) {
+      if (hp.tu_at[t] < at) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at decreases inside a candidate");
+      if (hp.tu_at[t] > n_ent) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at exceeds the candidate's plan length");
+      at = hp.tu_at[t];
+    }
+    desc[k] = cabac_substream_desc{};
+    desc[k].rec_offset = hp.ent_first[k];
+    desc[k].n_records = uint32_t(n_ent);
+  }
+  if (int bad = check_plan_host(c, n_cand, desc.data(), nullptr, cand_first, tus, hp.tu_at, hp.tu_guard, hp.plan, hp.n_entries_total,
+                                n_coeff_total, "candidate"))
+    return bad;
+  uint64_t bound = 0;
+  for (uint64_t i = hp.ent_first[0]; i < hp.ent_first[n_cand]; i++) bound += plan_entry_max_bins(hp.plan[2 * i]);
+  *record_bound = bound;
+  return CABAC_HIP_OK;
+}
+
+// the plan inputs staged behind what search_round_batch_impl has staged, the resolved form in the library's own buffers (the
+// record buffer sized from the bound), and the round
+int search_plan_stage_and_run(cabac_hip_ctx *c, uint32_t n_group, uint32_t n_cand, uint32_t n_tu, int coeff_bytes, const HostPlan &hp,
+                              uint64_t record_bound, bool has_out_set, bool has_dist, uint64_t lambda_q16, uint64_t *d_bits,
+                              uint64_t *d_tu_bits, uint32_t *d_info) {
+  int rc;
+  const size_t at_bytes = size_t(n_tu) * sizeof(uint32_t), ent_bytes = (size_t(n_cand) + 1) * sizeof(uint64_t);
+  const size_t plan_bytes = size_t(hp.n_entries_total) * 2 * sizeof(uint32_t), value_bytes = size_t(hp.n_entries_total) * sizeof(uint32_t);
+  if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
+  if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
+  if ((rc = ensure(c, kUnitTuAt, at_bytes))) return rc;
+  if ((rc = ensure(c, kElemGuard, at_bytes))) return rc;
+  if ((rc = ensure(c, kPsEnt, ent_bytes))) return rc;
+  if ((rc = ensure(c, kPsFlags, size_t(n_cand ? n_cand : 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kSearchInRecords, size_t(record_bound) * sizeof(uint16_t)))) return rc;
+  if ((rc = ensure(c, kSearchInRecFirst, ent_bytes))) return rc;
+  if ((rc = ensure(c, kSearchInTuAt, at_bytes))) return rc;
+  if ((rc = ensure(c, kPwTu, size_t(n_tu ? n_tu : 1) * sizeof(cabac_tu_desc)))) return rc;
+  auto up = [&](int slot, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(c->d_buf[slot], src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+  };
+  HIP_TRY(c, up(kElemPlan, hp.plan, plan_bytes));
+  HIP_TRY(c, up(kElemValues, hp.values_in, value_bytes));
+  HIP_TRY(c, up(kPsEnt, hp.ent_first, ent_bytes));
+  if (hp.tu_at) HIP_TRY(c, up(kUnitTuAt, hp.tu_at, at_bytes));
+  if (hp.tu_guard) HIP_TRY(c, up(kElemGuard, hp.tu_guard, at_bytes));
+  return cabac_hip_search_plan_round_device(
+      c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand, (const uint32_t *)c->d_buf[kEstInFirst], n_tu,
+      (const cabac_tu_desc *)c->d_buf[kEstInTu], c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState],
+      (uint8_t *)c->d_buf[kEstInRate], (const uint32_t *)c->d_buf[kEstInSet], (const uint64_t *)c->d_buf[kPsEnt],
+      (const uint32_t *)c->d_buf[kElemPlan], (const uint32_t *)c->d_buf[kElemValues],
+      hp.tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr, hp.tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr,
+      has_out_set ? (const uint32_t *)c->d_buf[kSearchInOutSet] : nullptr, has_dist ? (const uint64_t *)c->d_buf[kSearchInDist] : nullptr,
+      lambda_q16, d_bits, (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info,
+      (uint32_t *)c->d_buf[kPsFlags], (uint64_t *)c->d_buf[kSearchInRecFirst], (uint16_t *)c->d_buf[kSearchInRecords], record_bound,
+      (uint32_t *)c->d_buf[kSearchInTuAt], (cabac_tu_desc *)c->d_buf[kPwTu], hp.values_out ? (uint32_t *)c->d_buf[kElemValues] : nullptr,
+      nullptr);
+}
+
+// the flags and the filled values back; *status: CABAC_HIP_ERR_SUBSTREAM when a candidate has a flag
+int search_plan_fetch(cabac_hip_ctx *c, uint32_t n_cand, const HostPlan &hp, int *status) {
+  std::vector<uint32_t> fl(n_cand);
+  if (n_cand) HIP_TRY(c, hipMemcpyAsync(fl.data(), c->d_buf[kPsFlags], size_t(n_cand) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (hp.values_out && hp.n_entries_total)
+    HIP_TRY(c, hipMemcpyAsync(hp.values_out, c->d_buf[kElemValues], size_t(hp.n_entries_total) * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                              c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (uint32_t k = 0; k < n_cand; k++) {
+    if (hp.flags) hp.flags[k] = fl[k];
+    if (fl[k]) *status = CABAC_HIP_ERR_SUBSTREAM;
+  }
+  return CABAC_HIP_OK;
+}
+}  // namespace
+
+int cabac_hip_search_plan_round_batch(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *group_first, uint32_t n_cand,
+                                      const uint32_t *cand_first, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
+                                      uint64_t n_coeff_total, uint32_t *state, uint8_t *rate, uint32_t n_sets, const uint32_t *set,
+                                      const uint32_t *plan, const uint32_t *values_in, uint64_t n_entries_total,
+                                      const uint64_t *ent_first, const uint32_t *tu_at, const uint32_t *tu_guard,
+                                      const uint32_t *group_out_set, const uint64_t *dist, uint64_t lambda_q16, uint64_t *frac_bits,
+                                      uint32_t *pick, uint64_t *cost, uint64_t *tu_frac_bits, uint32_t *tu_info, uint32_t *flags,
+                                      uint32_t *values_out) {
+  const HostPlan hp{plan, values_in, n_entries_total, ent_first, tu_at, tu_guard, flags, values_out};
+  return search_round_batch_impl(c, n_group, group_first, n_cand, cand_first, tus, coeff, coeff_bytes, n_coeff_total, state, rate,
+                                 n_sets, set, group_out_set, dist, lambda_q16, frac_bits, pick, cost, tu_frac_bits, tu_info, nullptr, &hp);
 }
 
 // ---- the winner log (declared in cabac_hip_search_emit.h; kernels in cabac_search_emit.hip) -------------------------------------

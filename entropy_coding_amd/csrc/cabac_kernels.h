@@ -205,6 +205,38 @@ hipError_t launch_plan_emit(hipStream_t st, uint32_t n_sub, const PlanWriteIn &i
 // a stopped substream codes nothing: results[s] = {0, sub_flag[s]} where sub_flag[s] != 0
 hipError_t launch_plan_stops(hipStream_t st, uint32_t n_sub, const uint32_t *sub_flag, cabac_substream_result *results);
 
+// the plan resolve of the search rounds (cabac_plan_search.hip; cabac_hip_search_plan.h): the same walk, one candidate per unit,
+// into the unit-candidate form.  What both walks read: candidate c owns the entries [ent_first[c], ent_first[c+1]) of plan /
+// values and the blocks [cand_first[c], cand_first[c+1]) of the n_tu blocks; tu_info: of launch_residual's sizes pass over tus[].
+struct PlanResolveIn {
+  uint32_t n_cand;
+  const uint32_t *cand_first;
+  const uint64_t *ent_first;
+  const uint32_t *plan, *values;
+  uint32_t n_tu;
+  const cabac_tu_desc *tus;
+  const uint32_t *tu_at, *tu_guard;  // may be null
+  const uint32_t *tu_info;
+};
+struct PlanResolveOut {  // what the second walk writes (values_out, tu_info_out may be null; values_out may be the values read)
+  const uint64_t *rec_first;
+  uint16_t *records;
+  uint32_t *tu_at_out;
+  cabac_tu_desc *tus_out;
+  uint32_t *values_out, *tu_info_out;
+};
+// per candidate the side records it needs (cnt, 0 for a stopped one) and its stop (flags: 0, CABAC_RES_BAD_RECORD,
+// CABAC_RES_BAD_VALUE)
+hipError_t launch_plan_resolve_count(hipStream_t st, const PlanResolveIn &in, uint32_t *cnt, uint32_t *flags);
+// rec_first (n_cand + 1) from cnt, *total (may be null) = the need; a need above `capacity`: rec_first all 0 and
+// CABAC_RES_OVERFLOW in the flags of every candidate that has none
+hipError_t launch_plan_resolve_scan(hipStream_t st, uint32_t n_cand, const uint32_t *cnt, uint32_t *flags, uint64_t capacity,
+                                    uint64_t *rec_first, uint64_t *total);
+// the second walk; a candidate with a flag gets the empty form (no record, every block rejected at position 0)
+hipError_t launch_plan_resolve_emit(hipStream_t st, const PlanResolveIn &in, uint32_t *cnt, uint32_t *flags, const PlanResolveOut &out);
+// frac_bits[c] = UINT64_MAX where flags[c] != 0
+hipError_t launch_plan_flag_cost(hipStream_t st, uint32_t n_cand, const uint32_t *flags, uint64_t *frac_bits);
+
 // substream assembly (cabac_assemble.hip)
 hipError_t launch_assemble(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc,
                            const cabac_substream_result *results, const uint8_t *bytes, uint8_t *payload,

@@ -1,6 +1,6 @@
-// The plan walk on the writer's side (cabac_hip_write_plan.h): a plan of syntax elements, guards, computed entries and guarded
-// blocks (cabac_hip_parse_plan.h) plus the values of the real elements and the blocks' coefficients -> the expanded substream of
-// bin records the encode kernel codes.  What tests/parse_plan_model.py::fill / expand do on the CPU.
+// The plan write (cabac_hip_write_plan.h): a plan of syntax elements, guards, computed entries and guarded blocks
+// (cabac_hip_parse_plan.h) plus the values of the real elements and the blocks' coefficients -> the expanded substream of bin
+// records the encode kernel codes.  What tests/parse_plan_model.py::fill / expand do on the CPU.
 //
 //   residual sizes pass (cabac_residual.hip)  ->  n_records and info word per block, whatever its guard will say
 //   plan_resolve_kernel   per substream: the walk for its sizes — filled values (in LDS only), coded / skipped per block, bin
@@ -11,16 +11,8 @@
 //   residual records pass over a descriptor list in which skipped blocks are ones the binariser rejects (they write nothing)
 //   encode kernel, plan_stops_kernel (a stopped substream codes nothing), assembly
 //
-// The walk.  One wave per substream.  The only serial thing in a plan is liveness along reference chains (a guard on a COND on a
-// guarded element ...), so the wave does not step through the entries: it takes a STAGE of up to 64 consecutive entries with no
-// block position inside, one entry per lane, and lets every lane resolve its entry as soon as the entries it refers to are
-// resolved — those in front of the stage are (their values lie in the ring), those inside it are named by a ballot.  The number
-// of rounds is the depth of the reference chain inside the stage (2 - 4 in the worked transform unit), at most the stage's
-// width: the lowest unresolved lane refers to lower lanes only and is always ready.  Between two stages the blocks at that
-// position are taken 64 at a time; their guards refer to entries in front of them, so one round does.  LDS per wave: the ring of
-// the last 256 values, the last 16 info words (the count of blocks walked is wave-uniform and lives in a register), and the
-// tile of the output-position loop.  Every loop is bounded by n_records, the number of blocks and 64; no workgroup waits for
-// another; no atomics on the data path (one atomicOr reports a substream that outgrows 32 bits).
+// The walk itself is cabac_plan_walk.h's, one wave per substream; this file says where a substream's plan lies and where its
+// results go (one atomicOr reports a substream that outgrows 32 bits).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -28,84 +20,11 @@
 #include "cabac_hip_parse_elements.h"
 #include "cabac_hip_parse_plan.h"
 #include "cabac_kernels.h"
-#include "cabac_se_code.h"
+#include "cabac_plan_walk.h"
 
 namespace cabac {
 
 namespace {
-
-constexpr uint32_t kPwWaves = 4;  // substreams per workgroup
-
-struct PwLds {
-  uint32_t ring[256];  // value(i) at ring[i & 255]
-  uint32_t inf[16];    // info word of block k of the substream at inf[k & 15]
-  uint32_t scan[65];   // output-position loop: exclusive bin offsets of the stage's elements
-  uint32_t w0s[64], vals[64];
-};
-
-// orders the LDS accesses of the lanes of one wave
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane, uint32_t *total) {
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(incl, d);
-    if ((int)lane >= d) incl += up;
-  }
-  *total = __shfl(incl, 63);
-  return incl - v;
-}
-
-__device__ __forceinline__ bool test_holds(uint32_t gw, uint32_t v) {
-  const uint32_t imm = gw >> 16, cmp = (gw >> 8) & 3u;
-  return cmp == 0u ? v != imm : cmp == 1u ? v == imm : cmp == 2u ? v >= imm : v < imm;
-}
-
-// the list of cabac_hip_parse_plan.h; i: the entry's index in its plan, nb: nb(i)
-__device__ __forceinline__ bool bad_entry(uint32_t w0, uint32_t gw, uint32_t i, uint32_t nb) {
-  const uint32_t kind = w0 & 15u, p = w0 >> 4, id0 = p & 0x1ffu, idn = (p >> 9) & 0x1ffu;
-  bool bad = kind > CABAC_PE_BLOCK_INFO || (gw & 0xfc00u) != 0u || (gw & 0xffu) > i;
-  if (kind == CABAC_SE_CTX_BIN) bad |= id0 >= (uint32_t)CABAC_NUM_CONTEXTS;
-  else if (kind == CABAC_SE_UNARY_MAX) bad |= id0 >= (uint32_t)CABAC_NUM_CONTEXTS || idn >= (uint32_t)CABAC_NUM_CONTEXTS;
-  else if (kind == CABAC_SE_EP_BINS || kind == CABAC_SE_UNARY_EP) bad |= (p & 63u) > 32u;
-  else if (kind == CABAC_SE_TRUNC_BIN) bad |= p == 0u;
-  else if (kind == CABAC_SE_REM_ABS) {
-    const uint32_t ml = (p >> 10) & 63u;
-    bad |= (p & 31u) > 14u || ml < 15u || ml > 20u || ((p >> 5) & 31u) > 32u - ml;
-  } else if (kind == CABAC_PE_COND) {
-    const uint32_t back2 = p & 0xffu, join = (p >> 8) & 3u;
-    bad |= join == 3u || (join != 0u && (back2 == 0u || back2 > i));
-  } else if (kind == CABAC_PE_BLOCK_INFO) {
-    const uint32_t width = (p >> 9) & 63u;
-    bad |= (p & 15u) >= nb || width == 0u || ((p >> 4) & 31u) + width > 32u;
-  }
-  return bad;
-}
-
-// the values an element's code carries (cabac_hip_write_plan.h, "BAD VALUE"); the entry is a real one and not bad
-__device__ __forceinline__ bool in_domain(uint32_t w0, uint32_t v) {
-  const uint32_t kind = w0 & 15u, p = w0 >> 4;
-  switch (kind) {
-  case CABAC_SE_CTX_BIN:
-  case CABAC_SE_TRM: return v <= 1u;
-  case CABAC_SE_EP_BINS: return (p & 63u) >= 32u || v < (1u << (p & 63u));
-  case CABAC_SE_UNARY_MAX: return v <= ((p >> 18) & 0xffu);
-  case CABAC_SE_UNARY_EP: return v <= (p & 63u);
-  case CABAC_SE_TRUNC_BIN: return v < p;
-  case CABAC_SE_EXP_GOLOMB: return v < 0u - (1u << (p & 31u));  // count + prefix ones < 32
-  case CABAC_SE_REM_ABS: {  // up to the longest prefix and a suffix of ones
-    const uint32_t rice = p & 31u, cutoff = (p >> 5) & 31u, ml = (p >> 10) & 63u;
-    const uint64_t top = ((((uint64_t)1 << (32u - ml - cutoff)) + cutoff - 1u) << rice) + ((uint64_t)1 << ml) - 1u;
-    return (uint64_t)v <= top;
-  }
-  default: return true;  // ALIGN carries no value
-  }
-}
 
 __device__ __forceinline__ uint64_t pw_slot_bytes(uint64_t n_records) { return ((7u * n_records + 7u) / 8u + 8u + 15u) / 16u * 16u; }
 
@@ -119,183 +38,56 @@ struct PwOut {  // what the second walk writes
   uint32_t *values_out, *tu_info_out;
 };
 
-template <bool kEmit>
-__device__ __forceinline__ void plan_walk(uint32_t n_sub, const PlanWriteIn &in, uint32_t *sub_n, uint32_t *sub_cap, uint32_t *sub_flag,
-                                          uint32_t *err, const PwOut &out) {
-  __shared__ PwLds lds_all[kPwWaves];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const uint32_t sub = blockIdx.x * kPwWaves + wave;
-  if (sub >= n_sub) return;
-  PwLds &lds = lds_all[wave];
-  const cabac_substream_desc dsc = in.desc[sub];
-  const uint32_t n = dsc.n_records, t0 = in.tile_first[sub], t1 = in.tile_first[sub + 1];
-  const uint2 *plan = reinterpret_cast<const uint2 *>(in.plan) + dsc.rec_offset;
-  const uint32_t *vin = in.values + dsc.rec_offset;
-  uint64_t base = 0;
-  cabac_tu_desc rejected{};  // what the records pass gets for a block that writes nothing
-  rejected.log2_width = rejected.log2_height = 7;
-  if (kEmit) {
+// the plan write as cabac_plan_walk.h sees it: a unit is a substream, its run is the expanded substream (blocks included)
+struct PwIo {
+  static constexpr bool kBlocksInRun = true;
+  uint32_t n_units;
+  const cabac_substream_desc *desc;
+  const uint32_t *plan, *values, *tile_first;
+  const cabac_tu_desc *tus;
+  const uint32_t *tu_at, *tu_guard, *tu_n_records, *tu_info;
+  uint32_t *sub_n, *sub_cap, *sub_flag, *err;  // first walk
+  PwOut out;                                   // second walk
+  uint16_t *records;
+
+  __device__ __forceinline__ PlanWalkUnit unit(uint32_t sub) const {
+    const cabac_substream_desc dsc = desc[sub];
+    PlanWalkUnit u;
+    u.plan = reinterpret_cast<const uint2 *>(plan) + dsc.rec_offset;
+    u.vin = values + dsc.rec_offset;
+    u.vout = out.values_out ? out.values_out + dsc.rec_offset : nullptr;
+    u.n = dsc.n_records;
+    u.t0 = tile_first[sub];
+    u.t1 = tile_first[sub + 1];
+    return u;
+  }
+  __device__ __forceinline__ bool emit_begin(uint32_t sub, const PlanWalkUnit &u, uint32_t lane, uint64_t &base) const {
     base = out.rec_base[sub];
     if (lane == 0u) {
-      cabac_substream_desc o = dsc;
+      cabac_substream_desc o = desc[sub];
       o.rec_offset = base;
       o.byte_offset = out.byte_base[sub];
       o.n_records = out.sub_n[sub];
       o.byte_capacity = out.sub_cap[sub];
       out.desc_out[sub] = o;
     }
-    if (out.sub_flag[sub] != 0u) {  // a stopped substream: none of its blocks is coded, nothing else of it is written
-      for (uint32_t t = t0 + lane; t < t1; t += 64u) {
-        out.tus_out[t] = rejected;
-        out.tu_offset[t] = base;
-      }
-      return;
+    if (out.sub_flag[sub] == 0u) return true;
+    cabac_tu_desc rejected{};  // a stopped substream: none of its blocks is coded, nothing else of it is written
+    rejected.log2_width = rejected.log2_height = 7;
+    for (uint32_t t = u.t0 + lane; t < u.t1; t += 64u) {
+      out.tus_out[t] = rejected;
+      out.tu_offset[t] = base;
     }
+    return false;
   }
-
-  uint32_t i = 0, t = t0, nb = 0;  // the next element, the next block, the blocks walked (all wave-uniform)
-  uint64_t off = 0;                // records of the substream so far
-  bool bad_rec = false, bad_val = false;
-  while (i < n || t < t1) {
-    // Everything either kind of trip reads from memory is asked for here, at once and unconditionally: the walk is bound by
-    // latency (one wave per substream, a few hundred trips in a row), so a trip must cost one round to memory, not one per
-    // decision.  The half that the trip does not use stays in flight behind it.
-    const uint32_t idx = i + lane, tt = t + lane;
-    uint32_t w0 = 0xfu, gw = 0, value_in = 0;
-    if (idx < n) {
-      const uint2 w = plan[idx];
-      w0 = w.x;
-      gw = w.y;
-      value_in = vin[idx];
-    }
-    uint32_t raw_at = n, gw_b = 0, raw_info = 0, cnt_b = 0, fl_b = 0;
-    if (tt < t1) {
-      if (in.tu_at) raw_at = in.tu_at[tt];
-      if (in.tu_guard) gw_b = in.tu_guard[tt];
-      raw_info = in.tu_info[tt];
-      cnt_b = in.tu_n_records[tt];
-      fl_b = in.tus[tt].flags;
-    }
-    const uint32_t at_next = t < t1 ? min(max((uint32_t)__shfl((int)raw_at, 0), i), n) : n;
-    if (t < t1 && at_next == i) {
-      // ---- the blocks at position i, up to 64 of them: their guards refer to elements in front of i ----
-      const bool here = tt < t1 && (i == n || raw_at <= i);
-      const uint64_t not_here = ~__ballot(here);
-      const uint32_t m = not_here ? (uint32_t)__builtin_ctzll(not_here) : 64u;  // the run of blocks whose at(t) is i
-      const bool mine = lane < m;
-      uint32_t info = CABAC_TU_INFO_NOT_CODED, sz = 0;
-      bool coded = false, b_rec = false, b_val = false;
-      if (mine) {
-        const uint32_t back = gw_b & 0xffu;
-        b_rec = !kEmit && ((gw_b & 0xfc00u) != 0u || back > i);  // (the second walk sees no stopped substream)
-        coded = back == 0u || test_holds(gw_b, lds.ring[(i - back) & 255u]);
-        if (coded) {
-          b_val = !kEmit && (raw_info & (CABAC_TU_INFO_EMPTY | CABAC_TU_INFO_BAD_DESC)) != 0u;
-          // the binariser reports a position for a transform-skip block too; the reader reports CABAC_TU_INFO_TS alone
-          info = b_val ? raw_info : (fl_b & CABAC_TU_TRANSFORM_SKIP) ? CABAC_TU_INFO_TS : raw_info;
-          sz = b_val ? 0u : cnt_b;
-        }
-      }
-      bad_rec |= __ballot(b_rec) != 0ull;
-      bad_val |= __ballot(b_val) != 0ull;
-      uint32_t total;
-      const uint32_t excl = wave_excl_scan(sz, lane, &total);
-      wave_sync();  // the ring and the info words read so far, before the info words change
-      if (mine && lane + 16u >= m) lds.inf[(nb + lane) & 15u] = info;  // the last 16 of the run
-      wave_sync();
-      if (kEmit && mine) {
-        out.tus_out[tt] = coded ? in.tus[tt] : rejected;
-        out.tu_offset[tt] = base + off + excl;
-        if (out.tu_info_out) out.tu_info_out[tt] = info;
-      }
-      nb += m;
-      t += m;
-      off += total;
-      continue;
-    }
-    // ---- a stage of elements [i, e): no block position inside ----
-    const uint32_t e = min(i + 64u, at_next);
-    const bool valid = idx < e;
-    if (!valid) {
-      w0 = 0xfu;
-      gw = 0;
-    }
-    uint32_t v = 0;
-    const uint32_t kind = w0 & 15u;
-    const bool bad = !kEmit && valid && bad_entry(w0, gw, idx, nb);  // (the second walk sees no stopped substream)
-    bad_rec |= __ballot(bad) != 0ull;
-    const bool real = valid && kind <= CABAC_SE_ALIGN;
-    // what the entry refers to: r1 the guard's (the test's) element, r2 a COND's second one; 0: none
-    const uint32_t r1 = valid ? (gw & 0xffu) : 0u;
-    const uint32_t r2 = (valid && kind == CABAC_PE_COND && ((w0 >> 12) & 3u) != 0u) ? ((w0 >> 4) & 0xffu) : 0u;
-    // values in front of the stage are read now: their ring slots may be overwritten by this stage (a reference 255 back lies
-    // in the slot of the next element)
-    uint32_t v1 = 0, v2 = 0;
-    if (r1 > lane) v1 = lds.ring[(idx - r1) & 255u];
-    if (r2 > lane) v2 = lds.ring[(idx - r2) & 255u];
-    wave_sync();
-    uint64_t done = ~__ballot(valid);
-    bool resolved = !valid, active = false;
-    for (uint32_t round = 0; round < 64u && done != ~0ull; round++) {
-      const bool dep1 = r1 == 0u || r1 > lane || ((done >> (lane - r1)) & 1ull) != 0ull;
-      const bool dep2 = r2 == 0u || r2 > lane || ((done >> (lane - r2)) & 1ull) != 0ull;
-      const bool ready = !resolved && dep1 && dep2;
-      if (ready) {
-        if (r1 != 0u && r1 <= lane) v1 = lds.ring[(idx - r1) & 255u];
-        if (r2 != 0u && r2 <= lane) v2 = lds.ring[(idx - r2) & 255u];
-        const bool holds = r1 == 0u || test_holds(gw, v1);
-        if (kind == CABAC_PE_COND) {
-          const uint32_t join = (w0 >> 12) & 3u, other = v2 != 0u ? 1u : 0u;
-          v = holds ? 1u : 0u;
-          if (join == 1u) v &= other;
-          else if (join == 2u) v |= other;
-        } else if (kind == CABAC_PE_BLOCK_INFO) {
-          if (holds && !bad) {
-            const uint32_t p = w0 >> 4, width = (p >> 9) & 63u, word = lds.inf[(nb - 1u - (p & 15u)) & 15u];
-            v = (word >> ((p >> 4) & 31u)) & (width >= 32u ? 0xffffffffu : (1u << width) - 1u);
-          }
-        } else if (real && holds) {
-          active = true;
-          v = value_in;
-        }
-        lds.ring[idx & 255u] = v;
-        resolved = true;
-      }
-      done |= __ballot(ready);
-      wave_sync();
-    }
-    // the active elements' bins; a value its code does not carry stops the substream
-    const bool outside = !kEmit && active && !bad && !in_domain(w0, v);
-    bad_val |= __ballot(outside) != 0ull;
-    active = active && !bad && !outside;
-    const uint32_t cnt = active ? se_decode(w0, v).n : 0u;
-    uint32_t total;
-    const uint32_t excl = wave_excl_scan(cnt, lane, &total);
-    if (kEmit) {
-      if (out.values_out && valid) out.values_out[dsc.rec_offset + idx] = v;
-      // by output position: bin o of the stage belongs to the last element whose offset is <= o
-      lds.scan[lane] = excl;
-      lds.w0s[lane] = active ? w0 : 0xfu;
-      lds.vals[lane] = v;
-      if (lane == 0u) lds.scan[64] = total;
-      wave_sync();
-      uint16_t *dst = out.records + base + off;
-      for (uint32_t o = lane; o < total; o += 64u) {
-        uint32_t lo = 0, hi = 64;  // invariant: scan[lo] <= o < scan[hi]
-        while (hi - lo > 1u) {
-          const uint32_t mid = (lo + hi) >> 1;
-          if (lds.scan[mid] <= o) lo = mid;
-          else hi = mid;
-        }
-        const SeCode s = se_decode(lds.w0s[lo], lds.vals[lo]);
-        dst[o] = se_bin(s, o - lds.scan[lo]);
-      }
-      wave_sync();
-    }
-    off += total;
-    i = e;
+  __device__ __forceinline__ void emit_block(uint32_t t, bool coded, uint64_t base, uint64_t off, uint32_t excl, uint32_t info) const {
+    cabac_tu_desc rejected{};  // what the records pass gets for a block that writes nothing
+    rejected.log2_width = rejected.log2_height = 7;
+    out.tus_out[t] = coded ? tus[t] : rejected;
+    out.tu_offset[t] = base + off + excl;
+    if (out.tu_info_out) out.tu_info_out[t] = info;
   }
-  if (!kEmit && lane == 0u) {
+  __device__ __forceinline__ void count_end(uint32_t sub, bool bad_rec, bool bad_val, uint64_t off) const {
     const uint32_t flag = bad_rec ? CABAC_RES_BAD_RECORD : bad_val ? CABAC_RES_BAD_VALUE : 0u;
     const uint64_t expanded = flag ? 0u : off;
     if (expanded > 0xfffffff0ull || pw_slot_bytes(expanded) > 0xfffffff0ull) atomicOr(err, 1u);
@@ -303,6 +95,12 @@ __device__ __forceinline__ void plan_walk(uint32_t n_sub, const PlanWriteIn &in,
     sub_n[sub] = (uint32_t)expanded;
     sub_cap[sub] = (uint32_t)pw_slot_bytes(expanded);
   }
+};
+
+__device__ __forceinline__ PwIo pw_io(uint32_t n_sub, const PlanWriteIn &in, uint32_t *sub_n, uint32_t *sub_cap, uint32_t *sub_flag,
+                                      uint32_t *err, const PwOut &out) {
+  return PwIo{n_sub, in.desc, in.plan, in.values, in.tile_first, in.tus, in.tu_at, in.tu_guard, in.tu_n_records, in.tu_info,
+              sub_n, sub_cap, sub_flag, err, out, out.records};
 }
 
 }  // namespace
@@ -310,11 +108,11 @@ __device__ __forceinline__ void plan_walk(uint32_t n_sub, const PlanWriteIn &in,
 __global__ __launch_bounds__(64 * kPwWaves) void plan_resolve_kernel(uint32_t n_sub, PlanWriteIn in, uint32_t *__restrict__ sub_n,
                                                                       uint32_t *__restrict__ sub_cap, uint32_t *__restrict__ sub_flag,
                                                                       uint32_t *__restrict__ err) {
-  plan_walk<false>(n_sub, in, sub_n, sub_cap, sub_flag, err, PwOut{});
+  plan_walk<false>(pw_io(n_sub, in, sub_n, sub_cap, sub_flag, err, PwOut{}));
 }
 
 __global__ __launch_bounds__(64 * kPwWaves) void plan_emit_kernel(uint32_t n_sub, PlanWriteIn in, PwOut out) {
-  plan_walk<true>(n_sub, in, nullptr, nullptr, nullptr, nullptr, out);
+  plan_walk<true>(pw_io(n_sub, in, nullptr, nullptr, nullptr, nullptr, out));
 }
 
 __global__ __launch_bounds__(256) void plan_stops_kernel(uint32_t n_sub, const uint32_t *__restrict__ sub_flag,

@@ -1,6 +1,6 @@
 // The device binariser's code of one syntax element (cabac_hip.h, "Syntax-element record"): {n_bins, two bypass code words or a
 // context-coded unary run}, and bin `idx` of it as a bin record.  Shared by the binariser (cabac_binarize.hip) and the plan
-// writer (cabac_plan_write.hip), which binarises the active elements of a plan the same way.
+// walk (cabac_plan_walk.h: the plan write and the plan resolve), which binarises the active elements of a plan the same way.
 #ifndef CABAC_SE_CODE_H
 #define CABAC_SE_CODE_H
 #include <hip/hip_runtime.h>
