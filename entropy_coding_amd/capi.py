@@ -87,6 +87,13 @@ EXPORTS_WRITE_PLAN = [
 EXPORTS_SEARCH_PLAN = [
     "cabac_hip_resolve_plan_device", "cabac_hip_search_plan_round_device", "cabac_hip_search_plan_round_batch",
 ]
+# include/cabac_hip_ctx_sets.h (the codec from and into context sets, WPP on top; tests/test_ctx_sets_abi.py compares)
+EXPORTS_CTX_SETS = [
+    "cabac_hip_encode_sets_device", "cabac_hip_decode_sets_device", "cabac_hip_ctx_advance_device", "cabac_hip_encode_wpp_device",
+    "cabac_hip_decode_wpp_device", "cabac_hip_encode_wpp_batch", "cabac_hip_decode_wpp_batch",
+]
+CTX_NO_SET = 0xFFFFFFFF                                          # CABAC_CTX_NO_SET
+RES_BAD_SET = 0x40                                               # CABAC_RES_BAD_SET
 PE_COND, PE_BLOCK_INFO = 9, 10                                   # CABAC_PE_COND, CABAC_PE_BLOCK_INFO
 JOIN_NONE, JOIN_AND, JOIN_OR = range(3)                          # CABAC_JOIN_*
 RES_BAD_VALUE = 0x20                                             # CABAC_RES_BAD_VALUE
@@ -237,6 +244,19 @@ def load_library():
     L.cabac_hip_decode_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp]
     L.cabac_hip_ctx_init_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
     L.cabac_hip_binarize_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp]
+    sets7 = [ctypes.c_uint32] + [vp] * 6   # n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate
+    # (CABAC_HIP_LIBRARY may name a build from before cabac_hip_ctx_sets.h — tools/bench_ctx_sets.py --legs plain --label parent —:
+    # everything else is bound all the same)
+    if hasattr(L, "cabac_hip_encode_sets_device"):
+        L.cabac_hip_encode_sets_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp] + sets7
+        L.cabac_hip_decode_sets_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp] + sets7
+        L.cabac_hip_ctx_advance_device.argtypes = [vp, ctypes.c_uint32, vp, vp] + sets7 + [vp]
+        L.cabac_hip_encode_wpp_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp]
+        L.cabac_hip_decode_wpp_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp]
+        L.cabac_hip_encode_wpp_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32,
+                                                 vp, vp, vp]
+        L.cabac_hip_decode_wpp_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp,
+                                                 ctypes.c_uint32, vp, vp, vp]
     L.cabac_hip_residual_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_residual_parse_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_residual_parse_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, vp, vp]
@@ -458,7 +478,8 @@ class CabacHip:
         cabac_hip_search.h; 19 unit estimate, 20 / 21 / 22 a unit round's estimate / select / commit in cabac_hip_search_unit.h; 23 log append and
         24 log place in cabac_hip_search_emit.h; 25 unit parse in cabac_hip_parse_unit.h; 26 element parse in
         cabac_hip_parse_elements.h; 27 plan parse in cabac_hip_parse_plan.h; 28 plan write in cabac_hip_write_plan.h; 29 plan resolve in
-        cabac_hip_search_plan.h)."""
+        cabac_hip_search_plan.h; 30 encode with sets, 31 decode with sets, 32 context advance and 33 a WPP prefix pass in
+        cabac_hip_ctx_sets.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -524,6 +545,72 @@ class CabacHip:
     def decode_device(self, n_sub, d_desc, d_records, d_bytes, d_bins, d_results):
         self._check(self.L.cabac_hip_decode_device(self.h, n_sub, vp(d_desc), vp(d_records), vp(d_bytes), vp(d_bins),
                                                    vp(d_results)))
+
+    # ---- include/cabac_hip_ctx_sets.h: context sets in and out, WPP ------------------------------
+    @staticmethod
+    def _sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate):
+        return [int(n_sets)] + [vp(p) if p else None for p in (d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate)]
+
+    def encode_sets_device(self, n_sub, d_desc, d_records, d_bytes, d_results, n_sets=0, d_state=0, d_rate=0, d_start_set=0,
+                           d_out_set=0, d_out_state=0, d_out_rate=0):
+        """encode_device with substream s started from set d_start_set[s] (CTX_NO_SET: Ctx::init) and its final contexts written
+        as set d_out_set[s]; 0 for a pointer = NULL."""
+        self._check(self.L.cabac_hip_encode_sets_device(self.h, n_sub, vp(d_desc), vp(d_records), vp(d_bytes), vp(d_results),
+                                                        *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state,
+                                                                     d_out_rate)))
+
+    def decode_sets_device(self, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, n_sets=0, d_state=0, d_rate=0, d_start_set=0,
+                           d_out_set=0, d_out_state=0, d_out_rate=0):
+        self._check(self.L.cabac_hip_decode_sets_device(self.h, n_sub, vp(d_desc), vp(d_records), vp(d_bytes), vp(d_bins),
+                                                        vp(d_results), *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set,
+                                                                                    d_out_state, d_out_rate)))
+
+    def ctx_advance_device(self, n_sub, d_desc, d_records, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate,
+                           d_flags=0):
+        """update() for every context-coded record of the runs: sets in, sets out, nothing coded."""
+        self._check(self.L.cabac_hip_ctx_advance_device(self.h, n_sub, vp(d_desc), vp(d_records),
+                                                        *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state,
+                                                                     d_out_rate), vp(d_flags) if d_flags else None))
+
+    def encode_wpp_device(self, n_sub, d_desc, d_records, d_bytes, d_results, level_first, d_sync_from, d_sync_at):
+        """level_first: HOST, n_level + 1 entries."""
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        self._check(self.L.cabac_hip_encode_wpp_device(self.h, n_sub, vp(d_desc), vp(d_records), vp(d_bytes), vp(d_results),
+                                                       len(lf) - 1, lf.ctypes.data, vp(d_sync_from), vp(d_sync_at)))
+
+    def decode_wpp_device(self, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, level_first, d_sync_from, d_sync_at):
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        self._check(self.L.cabac_hip_decode_wpp_device(self.h, n_sub, vp(d_desc), vp(d_records), vp(d_bytes), vp(d_bins),
+                                                       vp(d_results), len(lf) - 1, lf.ctypes.data, vp(d_sync_from), vp(d_sync_at)))
+
+    def encode_wpp_batch(self, desc, records, bytes_total, level_first, sync_from, sync_at, check=True):
+        """Host arrays through cabac_hip_encode_wpp_batch: (bytes uint8[bytes_total], results)."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        records = np.ascontiguousarray(records, np.uint16)
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        sf, sa = np.ascontiguousarray(sync_from, np.uint32), np.ascontiguousarray(sync_at, np.uint32)
+        out = np.zeros(max(int(bytes_total), 1), np.uint8)
+        res = np.zeros(len(desc), RESULT_DTYPE)
+        rc = self.L.cabac_hip_encode_wpp_batch(self.h, len(desc), desc.ctypes.data, records.ctypes.data, len(records), out.ctypes.data,
+                                               int(bytes_total), res.ctypes.data, len(lf) - 1, lf.ctypes.data, sf.ctypes.data,
+                                               sa.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return out, res
+
+    def decode_wpp_batch(self, desc, records, data, level_first, sync_from, sync_at, check=True):
+        """Host arrays through cabac_hip_decode_wpp_batch: (bins uint8[len(records)], results)."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        records = np.ascontiguousarray(records, np.uint16)
+        data = np.ascontiguousarray(data, np.uint8)
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        sf, sa = np.ascontiguousarray(sync_from, np.uint32), np.ascontiguousarray(sync_at, np.uint32)
+        bins = np.zeros(max(len(records), 1), np.uint8)
+        res = np.zeros(len(desc), RESULT_DTYPE)
+        rc = self.L.cabac_hip_decode_wpp_batch(self.h, len(desc), desc.ctypes.data, records.ctypes.data, len(records), data.ctypes.data,
+                                               len(data), bins.ctypes.data, res.ctypes.data, len(lf) - 1, lf.ctypes.data,
+                                               sf.ctypes.data, sa.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return bins[: len(records)], res
 
     def estimate_device(self, n_sub, d_desc, d_records, d_frac_bits, d_flags=0):
         """BitEstimator_Std over a batch of bin strings: d_frac_bits[s] (uint64) = cost in 1/32768 bit."""

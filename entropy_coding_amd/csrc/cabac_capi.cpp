@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "cabac_hip.h"
+#include "cabac_hip_ctx_sets.h"
 #include "cabac_hip_estimate.h"
 #include "cabac_hip_nal.h"
 #include "cabac_hip_parse_elements.h"
@@ -54,8 +55,8 @@ struct cabac_hip_ctx {
   // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
   // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included); [48..]: the winner log (kLog* below); [53..]: the
   // unit parse (kUnit* below); [56..]: the element parse (kElem* below); [59..]: the plan write (kPw* below); [61..]: the plan
-  // resolve of the search rounds (kPs* below)
-  static constexpr int kSlots = 64;
+  // resolve of the search rounds (kPs* below); [64..]: the WPP calls (kWpp* below)
+  static constexpr int kSlots = 72;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -2913,6 +2914,229 @@ int cabac_hip_search_log_encode_device(cabac_search_log *log, const cabac_substr
   }
   return encode_residual_device_impl(c, a.n_chain, desc2, rec, first, splices, n_tu, n_tu, a.tu, a.coeff, log->coeff_bytes, d_payload,
                                      payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts);
+}
+
+// ---- context sets and WPP (cabac_hip_ctx_sets.h) -------------------------------------------------------------------
+// device slots: the slots of a WPP call (one set per substream), its prefix descriptors, its checked links and slot indices,
+// the results of its prefix passes, and the links of the host-pointer forms
+enum { kWppState = 64, kWppRate = 65, kWppDesc = 66, kWppIndex = 67, kWppRes = 68, kWppFrom = 69, kWppAt = 70 };
+
+static bool sets_args_ok(uint32_t n_sub, uint32_t n_sets, const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
+                         const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate) {
+  if (n_sub == 0) return true;
+  if (d_start_set && n_sets && (!d_state || !d_rate)) return false;
+  if (d_out_set && n_sets && (!d_out_state || !d_out_rate)) return false;
+  return true;
+}
+
+int cabac_hip_encode_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                 uint8_t *d_bytes, cabac_substream_result *d_results, uint32_t n_sets, const uint32_t *d_state,
+                                 const uint8_t *d_rate, const uint32_t *d_start_set, const uint32_t *d_out_set, uint32_t *d_out_state,
+                                 uint8_t *d_out_rate) {
+  if (!c || (n_sub && (!d_desc || !d_records || !d_bytes || !d_results)) ||
+      !sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  DeviceGuard g(c->device);
+  const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
+  Bracket br = bracket_for(c, 30);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, d_desc, d_records, d_bytes, d_results, 0, &sets));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_decode_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                 const uint8_t *d_bytes, uint8_t *d_bins, cabac_substream_result *d_results, uint32_t n_sets,
+                                 const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
+                                 const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate) {
+  if (!c || (n_sub && (!d_desc || !d_records || !d_bytes || !d_bins || !d_results)) ||
+      !sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  DeviceGuard g(c->device);
+  const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
+  Bracket br = bracket_for(c, 31);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_decode(c->stream, c->dec_variant, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, 0, c->d_select, &sets));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_ctx_advance_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                 uint32_t n_sets, const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
+                                 const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate, uint32_t *d_flags) {
+  if (!c || (n_sub && (!d_desc || !d_records)) ||
+      !sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  DeviceGuard g(c->device);
+  const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
+  Bracket br = bracket_for(c, 32);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_ctx_advance(c->stream, n_sub, d_desc, d_records, sets, d_flags));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+// level_first as the WPP calls need it: n_level + 1 entries, non-decreasing, from 0 to n_sub
+static int check_levels(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, const uint32_t *level_first) {
+  if (n_sub == 0) return CABAC_HIP_OK;
+  if (n_level == 0 || !level_first || level_first[0] != 0u || level_first[n_level] != n_sub)
+    return fail(c, CABAC_HIP_ERR_INVALID, "level_first must run from 0 to n_sub");
+  for (uint32_t l = 0; l < n_level; l++)
+    if (level_first[l] > level_first[l + 1]) {
+      char buf[96];
+      snprintf(buf, sizeof buf, "level_first decreases at level %u", l + 1);
+      return fail(c, CABAC_HIP_ERR_INVALID, buf);
+    }
+  return CABAC_HIP_OK;
+}
+
+// The schedule of a WPP call on the ctx stream: per level the level kernel (prefix descriptors, checked links, slot indices), for
+// every level but the last its prefix pass into the slots, then the pass over all substreams from their slots.  encode: d_bins
+// null, the prefix pass is the context advance; decode: the sets decoder (its bins land in d_bins and are written again, the
+// same, by the last pass; its results go to a scratch).
+static int wpp_device_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                           uint8_t *d_bytes, uint8_t *d_bins, cabac_substream_result *d_results, uint32_t n_level,
+                           const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
+  if (!c || (n_sub && (!d_desc || !d_records || !d_bytes || !d_results || (decode && !d_bins) || !d_sync_from || !d_sync_at)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  int rc = check_levels(c, n_sub, n_level, level_first);
+  if (rc) return rc;
+  DeviceGuard g(c->device);
+  const size_t set_words = size_t(n_sub) * CABAC_NUM_CONTEXTS;
+  if ((rc = ensure(c, kWppState, set_words * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kWppRate, set_words))) return rc;
+  if ((rc = ensure(c, kWppDesc, size_t(n_sub) * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kWppIndex, 2 * size_t(n_sub) * sizeof(uint32_t)))) return rc;
+  if (decode && (rc = ensure(c, kWppRes, size_t(n_sub) * sizeof(cabac_substream_result)))) return rc;
+  auto *slot_state = static_cast<uint32_t *>(c->d_buf[kWppState]);
+  auto *slot_rate = static_cast<uint8_t *>(c->d_buf[kWppRate]);
+  auto *pre_desc = static_cast<cabac_substream_desc *>(c->d_buf[kWppDesc]);
+  auto *start = static_cast<uint32_t *>(c->d_buf[kWppIndex]);
+  auto *slot = start + n_sub;
+  auto *pre_res = static_cast<cabac_substream_result *>(c->d_buf[kWppRes]);
+  for (uint32_t l = 0; l < n_level; l++) {
+    const uint32_t first = level_first[l], n = level_first[l + 1] - first;
+    if (n == 0) continue;
+    HIP_TRY(c, cabac::launch_wpp_level(c->stream, first, n, d_desc, d_sync_from, d_sync_at, pre_desc, start, slot));
+    if (l + 1 == n_level) break;
+    const cabac::CtxSets sets{n_sub, slot_state, slot_rate, start + first, slot + first, slot_state, slot_rate};
+    Timed t(c, 33);
+    if (decode)
+      HIP_TRY(c, cabac::launch_decode(c->stream, c->dec_variant, n, pre_desc + first, d_records, d_bytes, d_bins, pre_res + first, 0,
+                                      c->d_select, &sets));
+    else
+      HIP_TRY(c, cabac::launch_ctx_advance(c->stream, n, pre_desc + first, d_records, sets, nullptr));
+  }
+  const cabac::CtxSets sets{n_sub, slot_state, slot_rate, start, nullptr, nullptr, nullptr};
+  Bracket br = bracket_for(c, decode ? 31 : 30);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  if (decode)
+    HIP_TRY(c, cabac::launch_decode(c->stream, c->dec_variant, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, 0, c->d_select, &sets));
+  else
+    HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, d_desc, d_records, d_bytes, d_results, 0, &sets));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_encode_wpp_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                uint8_t *d_bytes, cabac_substream_result *d_results, uint32_t n_level, const uint32_t *level_first,
+                                const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
+  return wpp_device_impl(c, false, n_sub, d_desc, d_records, d_bytes, nullptr, d_results, n_level, level_first, d_sync_from, d_sync_at);
+}
+
+int cabac_hip_decode_wpp_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                const uint8_t *d_bytes, uint8_t *d_bins, cabac_substream_result *d_results, uint32_t n_level,
+                                const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
+  return wpp_device_impl(c, true, n_sub, d_desc, d_records, const_cast<uint8_t *>(d_bytes), d_bins, d_results, n_level, level_first,
+                         d_sync_from, d_sync_at);
+}
+
+// host-pointer forms: one chunk (chunks would cut links), everything on the ctx stream
+static int wpp_batch_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                          uint64_t n_records_total, uint8_t *bytes, uint64_t bytes_total, uint8_t *bins, cabac_substream_result *results,
+                          uint32_t n_level, const uint32_t *level_first, const uint32_t *sync_from, const uint32_t *sync_at) {
+  if (!c || (n_sub && (!desc || !results || !bytes || (n_records_total && !records) || (decode && n_records_total && !bins) ||
+                       !sync_from || !sync_at)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  int rc = check_desc_host(c, n_sub, desc, n_records_total, bytes_total);
+  if (rc) return rc;
+  if ((rc = check_levels(c, n_sub, n_level, level_first))) return rc;
+  for (uint32_t l = 0; l < n_level; l++)
+    for (uint32_t s = level_first[l]; s < level_first[l + 1]; s++) {
+      const uint32_t from = sync_from[s];
+      if (from == CABAC_CTX_NO_SET || from < level_first[l]) continue;
+      char buf[128];
+      if (from >= n_sub) snprintf(buf, sizeof buf, "substream %u links to %u, beyond the batch", s, from);
+      else snprintf(buf, sizeof buf, "substream %u (level %u) links to %u in the same or a later level", s, l, from);
+      return fail(c, CABAC_HIP_ERR_INVALID, buf);
+    }
+  DeviceGuard g(c->device);
+  if ((rc = pipe_init(c))) return rc;
+  const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result);
+  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, 1, n_records_total * 2))) return rc;
+  if ((rc = ensure(c, 2, bytes_total + 4))) return rc;
+  if ((rc = ensure(c, 3, res_bytes))) return rc;
+  if (decode && (rc = ensure(c, 4, n_records_total + 8))) return rc;
+  if ((rc = ensure(c, kWppFrom, size_t(n_sub) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kWppAt, size_t(n_sub) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure_pinned(c, 0, res_bytes))) return rc;
+  auto *d_desc = static_cast<cabac_substream_desc *>(c->d_buf[0]);
+  auto *d_rec = static_cast<uint16_t *>(c->d_buf[1]);
+  auto *d_slots = static_cast<uint8_t *>(c->d_buf[2]);
+  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[3]);
+  auto *d_bins = static_cast<uint8_t *>(c->d_buf[4]);
+  auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
+  hipStream_t st = c->stream;
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if ((rc = h2d(c, d_desc, desc, n_sub * sizeof(cabac_substream_desc), st))) return rc;
+  if ((rc = h2d(c, d_rec, records, n_records_total * 2, st))) return rc;
+  if ((rc = h2d(c, c->d_buf[kWppFrom], sync_from, size_t(n_sub) * sizeof(uint32_t), st))) return rc;
+  if ((rc = h2d(c, c->d_buf[kWppAt], sync_at, size_t(n_sub) * sizeof(uint32_t), st))) return rc;
+  if (decode) {
+    if ((rc = h2d(c, d_slots, bytes, bytes_total, st))) return rc;
+  } else {
+    HIP_TRY(c, hipMemsetAsync(d_slots, 0, bytes_total, st));  // the whole range goes back: what no substream writes stays zero
+  }
+  if ((rc = wpp_device_impl(c, decode, n_sub, d_desc, d_rec, d_slots, decode ? d_bins : nullptr, d_res, n_level, level_first,
+                            static_cast<const uint32_t *>(c->d_buf[kWppFrom]), static_cast<const uint32_t *>(c->d_buf[kWppAt]))))
+    return rc;
+  HIP_TRY(c, hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, st));
+  if (decode) {
+    if ((rc = d2h(c, bins, d_bins, n_records_total, st))) return rc;
+  } else {
+    if ((rc = d2h(c, bytes, d_slots, bytes_total, st))) return rc;
+  }
+  if ((rc = d2h_drain(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(st));
+  int status = CABAC_HIP_OK;
+  for (uint32_t s = 0; s < n_sub; s++) {
+    results[s] = h_res[s];
+    if (h_res[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
+  }
+  if (status) c->last_error = "substream flag set (see results[].flags)";
+  return status;
+}
+
+int cabac_hip_encode_wpp_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                               uint64_t n_records_total, uint8_t *bytes, uint64_t bytes_total, cabac_substream_result *results,
+                               uint32_t n_level, const uint32_t *level_first, const uint32_t *sync_from, const uint32_t *sync_at) {
+  return host_call_exit(c, wpp_batch_impl(c, false, n_sub, desc, records, n_records_total, bytes, bytes_total, nullptr, results, n_level,
+                                          level_first, sync_from, sync_at));
+}
+
+int cabac_hip_decode_wpp_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                               uint64_t n_records_total, const uint8_t *bytes, uint64_t bytes_total, uint8_t *bins,
+                               cabac_substream_result *results, uint32_t n_level, const uint32_t *level_first,
+                               const uint32_t *sync_from, const uint32_t *sync_at) {
+  return host_call_exit(c, wpp_batch_impl(c, true, n_sub, desc, records, n_records_total, const_cast<uint8_t *>(bytes), bytes_total, bins,
+                                          results, n_level, level_first, sync_from, sync_at));
 }
 
 int cabac_hip_host_alloc(size_t bytes, void **out) {

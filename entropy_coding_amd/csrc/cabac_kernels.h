@@ -11,34 +11,59 @@ struct cabac_search_log_entry;
 
 namespace cabac {
 
+// Context sets of the codec calls (cabac_hip_ctx_sets.h): substream s starts from set start_set[s] of state / rate and writes the
+// contexts it leaves as set out_set[s] of out_state / out_rate (0xffffffff: Ctx::init / nothing; start_set / out_set null: all
+// of them so).  An index >= n_sets codes nothing.  The out arrays may be the start arrays.
+struct CtxSets {
+  uint32_t n_sets;
+  const uint32_t *state;
+  const uint8_t *rate;
+  const uint32_t *start_set;
+  const uint32_t *out_set;
+  uint32_t *out_state;
+  uint8_t *out_rate;
+};
+
 hipError_t launch_ctx_init(hipStream_t st, uint32_t n_sub, const int32_t *qp, const uint32_t *init_id, uint32_t *state,
                            uint8_t *rate);
 // in_flight: the number of substreams on the device at the same time when this launch is one chunk of a batch whose
 // chunks run concurrently on several streams (0 = this launch is alone); the workgroup geometry follows the whole batch
 hipError_t launch_encode(hipStream_t st, int variant, uint32_t n_sub, const cabac_substream_desc *desc,
-                         const uint16_t *records, uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight = 0);
+                         const uint16_t *records, uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight = 0,
+                         const CtxSets *sets = nullptr);
 hipError_t launch_decode(hipStream_t st, int variant, uint32_t n_sub, const cabac_substream_desc *desc,
                          const uint16_t *records, const uint8_t *bytes, uint8_t *bins,
-                         cabac_substream_result *results, uint32_t in_flight = 0, uint32_t *select = nullptr);
+                         cabac_substream_result *results, uint32_t in_flight = 0, uint32_t *select = nullptr,
+                         const CtxSets *sets = nullptr);
 
 // v4 "quad" kernels (cabac_kernels_v4.hip): four substreams per wave
 hipError_t launch_encode_v4(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                            uint8_t *bytes, cabac_substream_result *results);
+                            uint8_t *bytes, cabac_substream_result *results, const CtxSets *sets = nullptr);
 hipError_t launch_encode_v6(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                            uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight = 0);
+                            uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight = 0, const CtxSets *sets = nullptr);
 hipError_t launch_encode_v7(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                            uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight = 0);
+                            uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight = 0, const CtxSets *sets = nullptr);
 // lanes_per_sub: 16 = the quad decoder (four substreams per wave), 4 = sixteen substreams per wave, 0 = by the batch: from
 // 9 216 substreams in flight the choice is made on the device (select: one device word of the caller's, not shared with
 // another launch in flight; null = the quad decoder)
 hipError_t launch_decode_v4(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
                             const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight = 0,
-                            int lanes_per_sub = 16, uint32_t *select = nullptr);
+                            int lanes_per_sub = 16, uint32_t *select = nullptr, const CtxSets *sets = nullptr);
 
 // bit estimator (cabac_kernels_v4.hip)
 hipError_t launch_estimate(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
                            uint64_t *frac_bits, uint32_t *flags, const uint32_t *start_state = nullptr,
                            const uint8_t *start_rate = nullptr, const uint32_t *start_set = nullptr);
+
+// context advance (cabac_kernels_v4.hip; cabac_hip_ctx_sets.h): update() for every context-coded record of the runs, sets in, sets
+// out; nothing is coded.  flags (may be null): CABAC_RES_BAD_RECORD, CABAC_RES_BAD_SET or 0 per substream
+hipError_t launch_ctx_advance(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                              const CtxSets &sets, uint32_t *flags);
+// one level of a WPP call, substreams [first, first + n): desc_out[s] = desc[s] with n_records = min(sync_at[s], n_records) and
+// the flag bits of init_id cleared; slot_out[s] = s; start_out[s] = sync_from[s] if it is 0xffffffff or below `first`, else an
+// index that every sets call answers with CABAC_RES_BAD_SET
+hipError_t launch_wpp_level(hipStream_t st, uint32_t first, uint32_t n, const cabac_substream_desc *desc, const uint32_t *sync_from,
+                            const uint32_t *sync_at, cabac_substream_desc *desc_out, uint32_t *start_out, uint32_t *slot_out);
 
 // device binariser (cabac_binarize.hip)
 hipError_t launch_binarize(hipStream_t st, uint32_t n_sub, const uint64_t *se_offset, const uint32_t *se,

@@ -49,15 +49,16 @@ hipError_t launch_ctx_init(hipStream_t st, uint32_t n_sub, const int32_t *qp, co
 
 // variant: 0 = auto, 4 = one-wave quad encoder (the round-1 baseline of this family), 6, 7; anything else is refused
 hipError_t launch_encode(hipStream_t st, int variant, uint32_t n_sub, const cabac_substream_desc *desc,
-                         const uint16_t *records, uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight) {
+                         const uint16_t *records, uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight,
+                         const CtxSets *sets) {
   if (n_sub == 0) return hipSuccess;
   const int kind = variant & 0xff;
   // auto (measured, DESIGN.md section 3, tools/enc_scaling.py): from 3 072 substreams the lane-serial encoder (v7: C4 0.64, C5 10.3 ms,
   // 16 384 substreams 1.90 ms against v6's 0.82 / 12.8 / 2.81); below, one unit per workgroup, the four-wave quad encoder (v6:
   // C2 0.61, C3 12.8 ms, 1 024 substreams 0.43, 2 048: 0.57 ms against v7's 0.78 / 16.5 / 0.65 / 0.64)
-  if (kind == 7 || (kind == 0 && max(n_sub, in_flight) >= 3072u)) return launch_encode_v7(st, n_sub, desc, records, bytes, results, in_flight);
-  if (kind == 6 || kind == 0) return launch_encode_v6(st, n_sub, desc, records, bytes, results, in_flight);
-  if (kind == 4) return launch_encode_v4(st, n_sub, desc, records, bytes, results);
+  if (kind == 7 || (kind == 0 && max(n_sub, in_flight) >= 3072u)) return launch_encode_v7(st, n_sub, desc, records, bytes, results, in_flight, sets);
+  if (kind == 6 || kind == 0) return launch_encode_v6(st, n_sub, desc, records, bytes, results, in_flight, sets);
+  if (kind == 4) return launch_encode_v4(st, n_sub, desc, records, bytes, results, sets);
   return hipErrorInvalidValue;
 }
 
@@ -65,16 +66,16 @@ hipError_t launch_encode(hipStream_t st, int variant, uint32_t n_sub, const caba
 // wave (few substreams); anything else is refused
 hipError_t launch_decode(hipStream_t st, int variant, uint32_t n_sub, const cabac_substream_desc *desc,
                          const uint16_t *records, const uint8_t *bytes, uint8_t *bins,
-                         cabac_substream_result *results, uint32_t in_flight, uint32_t *select) {
+                         cabac_substream_result *results, uint32_t in_flight, uint32_t *select, const CtxSets *sets) {
   if (n_sub == 0) return hipSuccess;
   const int kind = variant & 0xff;
   // auto: up to 1 024 substreams in flight one substream per wave (C2: 10, C3: 256); then the quad decoder (four substreams per
   // wave), the shortest chain per bin up to two quad waves per SIMD (C4: 4 096); from 9 216 about equally long substreams in flight sixteen per wave
   // decode 12 288 substreams in 2.23 ms against 3.14, 16 384 in 2.24 against 4.05
-  if (kind == 0) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 0, select);
-  if (kind == 4) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 16);
-  if (kind == 8) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 4);
-  if (kind == 1) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 64);
+  if (kind == 0) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 0, select, sets);
+  if (kind == 4) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 16, nullptr, sets);
+  if (kind == 8) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 4, nullptr, sets);
+  if (kind == 1) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 64, nullptr, sets);
   return hipErrorInvalidValue;
 }
 

@@ -435,19 +435,86 @@ __device__ __forceinline__ void quad_ctx_init(uint32_t *rctx, int qp_in, uint32_
     rctx[k] = ctx2_init(qp, c_init_tables[iid * kNumCtx + k], c_init_tables[3 * kNumCtx + k]);
 }
 
+// ---- context sets (cabac_hip_ctx_sets.h) ------------------------------------------------------------------------
+// The codec kernels take the sets as a trailing parameter PACK: empty for the instantiations the plain entry points
+// launch — the signature, the kernel arguments and the code are then the ones from before the sets — and one CtxSets for
+// the sets calls.  Everything about sets is in the overloads below; the empty ones say "no set, never bad".
+constexpr uint32_t kNoSet = 0xffffffffu;
+struct QuadSetUse {
+  uint32_t start, out;  // kNoSet: Ctx::init / nothing written
+  bool bad;             // an index >= n_sets: the substream codes nothing (CABAC_RES_BAD_SET)
+};
+__device__ __forceinline__ QuadSetUse quad_set_use(uint32_t, bool) { return QuadSetUse{kNoSet, kNoSet, false}; }
+__device__ __forceinline__ QuadSetUse quad_set_use(uint32_t sub, bool in_batch, const CtxSets &cs) {
+  QuadSetUse u;
+  u.start = (in_batch && cs.start_set != nullptr) ? cs.start_set[sub] : kNoSet;
+  u.out = (in_batch && cs.out_set != nullptr) ? cs.out_set[sub] : kNoSet;
+  u.bad = (u.start != kNoSet && u.start >= cs.n_sets) || (u.out != kNoSet && u.out >= cs.n_sets);  // once per substream
+  return u;
+}
+// the row's context store from its start set, lanes j, j + L, ...: the loop of estimate_kernel.  kRates: with the window
+// sizes in the low five bits (the encoders' packed word); the decoder keeps those bits zero
+template <bool kRates>
+__device__ __forceinline__ void quad_ctx_load(uint32_t *rctx, int qp_in, uint32_t iid, uint32_t j, uint32_t L, const QuadSetUse &u,
+                                              const CtxSets &cs) {
+  if (u.start == kNoSet || u.bad) {
+    const int qp = qp_in < 0 ? 0 : (qp_in > 63 ? 63 : qp_in);
+    for (uint32_t k = j; k < (uint32_t)kNumCtx; k += L) {
+      const uint32_t packed = ctx2_init(qp, c_init_tables[iid * kNumCtx + k], c_init_tables[3 * kNumCtx + k]);
+      rctx[k] = kRates ? packed : packed & ~31u;
+    }
+  } else {
+    const uint64_t at = (uint64_t)u.start * (uint64_t)kNumCtx;
+    for (uint32_t k = j; k < (uint32_t)kNumCtx; k += L) {
+      const uint32_t st = cs.state[at + k];
+      uint32_t w = (st & kMask0) | (st & 0xffff0000u);
+      if (kRates) {
+        const uint32_t rt = cs.rate[at + k];
+        w |= (((rt >> 4) - 2u) & 3u) | ((((rt & 15u) - 5u) & 7u) << 2);
+      }
+      rctx[k] = w;
+    }
+  }
+}
+// the contexts the row has now as its out set: all 379 states, and as rates the window sizes of the context (the fourth row of
+// the init table; every set this library writes holds them).  The caller has made the row's stores visible to its lanes.
+__device__ __forceinline__ void quad_ctx_export(const uint32_t *, uint32_t, uint32_t, const QuadSetUse &) {}
+__device__ __forceinline__ void quad_ctx_export(const uint32_t *rctx, uint32_t j, uint32_t L, const QuadSetUse &u, const CtxSets &cs) {
+  if (u.out == kNoSet || u.bad) return;
+  const uint64_t at = (uint64_t)u.out * (uint64_t)kNumCtx;
+  for (uint32_t k = j; k < (uint32_t)kNumCtx; k += L) {
+    const uint32_t r = ctx_init_rates(c_init_tables[3 * kNumCtx + k]);
+    cs.out_state[at + k] = rctx[k] & ~31u;
+    cs.out_rate[at + k] = (uint8_t)(16u * (r & 0xffu) + (r >> 8));  // m_rate
+  }
+}
+// a substream with a bad set index: results[sub] = {0, CABAC_RES_BAD_SET}
+__device__ __forceinline__ void quad_bad_set_result(cabac_substream_result *results, uint32_t sub, bool first_lane, const QuadSetUse &u) {
+  if (u.bad && first_lane) {
+    cabac_substream_result res;
+    res.n_bits = 0u;
+    res.flags = 0x40u;  // CABAC_RES_BAD_SET
+    results[sub] = res;
+  }
+}
+
 // encode, one wave per 4 substreams: phase (a) and the chain alternate in the same wave
+template <class... Sets>
 __global__ __launch_bounds__(64) void encode_kernel_v4(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
                                                        const uint16_t *__restrict__ records, uint8_t *__restrict__ bytes,
-                                                       cabac_substream_result *__restrict__ results) {
+                                                       cabac_substream_result *__restrict__ results, Sets... sets) {
+  constexpr bool kSets = sizeof...(Sets) != 0;
   __shared__ uint32_t ctx[kQuadSubs * kQuadCtxStride];
   const uint32_t lane = threadIdx.x, row = lane >> 4, j = lane & 15u;
   const uint32_t sub = blockIdx.x * kQuadSubs + row;
-  const bool live = sub < n_sub;  // rows beyond the batch idle with n = 0
+  const QuadSetUse su = quad_set_use(sub, sub < n_sub, sets...);
+  const bool live = sub < n_sub && !su.bad;  // rows beyond the batch idle with n = 0
   const cabac_substream_desc d = desc[live ? sub : 0];
   const uint32_t n = live ? d.n_records : 0u;
   const uint16_t *rec = records + d.rec_offset;
   uint32_t *rctx = ctx + row * kQuadCtxStride;
-  quad_ctx_init(rctx, d.qp, d.init_id & 3u, j);
+  if constexpr (kSets) quad_ctx_load<true>(rctx, d.qp, d.init_id & 3u, j, 16u, su, sets...);
+  else quad_ctx_init(rctx, d.qp, d.init_id & 3u, j);
   __syncthreads();
 
   QuadEnc e;
@@ -486,6 +553,11 @@ __global__ __launch_bounds__(64) void encode_kernel_v4(uint32_t n_sub, const cab
     res.n_bits = n_bits;
     res.flags = (e.pos > e.cap ? CABAC_RES_OVERFLOW : 0u) | (row_bad ? CABAC_RES_BAD_RECORD : 0u);
     results[sub] = res;
+  }
+  if constexpr (kSets) {
+    __syncthreads();  // the store of the last step's phase (a) (surplus steps of shorter rows write the pad word only)
+    quad_ctx_export(rctx, j, 16u, su, sets...);
+    quad_bad_set_result(results, sub, j == 0, su);
   }
 }
 
@@ -767,11 +839,12 @@ __device__ __forceinline__ uint32_t quad_low_join(uint32_t v0, uint32_t v1, uint
 // code value and the emission in ONE output wave, that wave became the longest (its tree and its LDS round trips in a row:
 // 1.02 ms against v5's 0.98); apart, each fits beside the chain wave.  One workgroup barrier per 16-bin step; step k is
 // coded by the chain wave in iteration k, turned into units in iteration k + 1 and written out in iteration k + 2.
-template <int U, int kSync>
+template <int U, int kSync, class... Sets>
 __global__ __launch_bounds__(256 * U) void encode_kernel_v6(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
                                                             const uint16_t *__restrict__ records,
                                                             uint8_t *__restrict__ bytes,
-                                                            cabac_substream_result *__restrict__ results) {
+                                                            cabac_substream_result *__restrict__ results, Sets... sets) {
+  constexpr bool kSets = sizeof...(Sets) != 0;
   // kSync 16-bin steps per workgroup barrier.  Measured (tools/ubench_v5.hip, per-role probes): every role waits ~130 ns
   // at each barrier on top of its own work, whoever arrives last.  With one unit per CU (small batches) two steps per
   // barrier are 8 % faster (C2 0.81 -> 0.75 ms, C3 17.2 -> 15.9 ms); with four units per CU the SIMDs are the limit and
@@ -798,7 +871,8 @@ __global__ __launch_bounds__(256 * U) void encode_kernel_v6(uint32_t n_sub, cons
   constexpr bool kLdsMatch = true;
   for (uint32_t k = threadIdx.x; k < U * kMatchWords; k += 256u * U) (&match_all[0][0])[k] = 0u;
   const uint32_t sub = (blockIdx.x * U + unit) * kQuadSubs + row;
-  const bool live = sub < n_sub;
+  const QuadSetUse su = quad_set_use(sub, sub < n_sub, sets...);
+  const bool live = sub < n_sub && !su.bad;
   const cabac_substream_desc d = desc[live ? sub : 0];
   const uint32_t n = live ? d.n_records : 0u;
   uint32_t (*mail)[4][64] = mail_all[unit];
@@ -816,7 +890,8 @@ __global__ __launch_bounds__(256 * U) void encode_kernel_v6(uint32_t n_sub, cons
     __builtin_amdgcn_s_setprio(CABAC_V6_PRIO_CTX);
     const uint16_t *rec = records + d.rec_offset;
     uint32_t *rctx = ctx_all + (unit * kQuadSubs + row) * kQuadCtxStride;
-    quad_ctx_init(rctx, d.qp, d.init_id & 3u, j);
+    if constexpr (kSets) quad_ctx_load<true>(rctx, d.qp, d.init_id & 3u, j, 16u, su, sets...);
+    else quad_ctx_init(rctx, d.qp, d.init_id & 3u, j);
     uint32_t bad = 0;
     const uint16_t *rec_safe = n != 0 ? rec : reinterpret_cast<const uint16_t *>(desc);
     const uint32_t last_rec = n != 0 ? n - 1u : 0u;
@@ -860,6 +935,16 @@ __global__ __launch_bounds__(256 * U) void encode_kernel_v6(uint32_t n_sub, cons
       uint32_t rows = 0;
       for (uint32_t k = 0; k < 4; k++) rows |= ((bad_mask >> (16u * k)) & 0xffffull) ? (1u << k) : 0u;
       bad_rows[unit] = rows;
+    }
+    if constexpr (kSets) {
+      // This wave alone owns the unit's context stores, and it has run phase (a) of every step of every row (the steps it runs
+      // ahead of the chain are past the longest substream: no active record, the pad word): the final states are here, written
+      // by this wave's own lanes — LDS executes one wave's instructions in order, so no workgroup barrier is needed, only the
+      // compiler kept from moving the reads
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      asm volatile("" ::: "memory");
+      quad_ctx_export(rctx, j, 16u, su, sets...);
     }
     __syncthreads();
     __syncthreads();
@@ -1008,6 +1093,7 @@ __global__ __launch_bounds__(256 * U) void encode_kernel_v6(uint32_t n_sub, cons
       res.flags = (e.pos > e.cap ? CABAC_RES_OVERFLOW : 0u) | (((bad_rows[unit] >> row) & 1u) ? CABAC_RES_BAD_RECORD : 0u);
       results[sub] = res;
     }
+    if constexpr (kSets) quad_bad_set_result(results, sub, j == 0, su);
   }
 }
 
@@ -1040,11 +1126,12 @@ __device__ __forceinline__ uint32_t lane_rng_step(uint32_t k, uint32_t c2, uint3
   return rm | (nb << 9);
 }
 
-template <int U>
+template <int U, class... Sets>
 __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
                                                                       const uint16_t *__restrict__ records,
                                                                       uint8_t *__restrict__ bytes,
-                                                                      cabac_substream_result *__restrict__ results) {
+                                                                      cabac_substream_result *__restrict__ results, Sets... sets) {
+  constexpr bool kSets = sizeof...(Sets) != 0;
   constexpr uint32_t S = U * kQuadSubs;
   __shared__ uint32_t ctx_all[S * kQuadCtxStride];
   __shared__ __attribute__((aligned(16))) uint32_t fld[4][kV7Fields][S * kV7Pad];  // context waves -> chain / low wave
@@ -1099,9 +1186,11 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
     local = min(lane, S - 1u);
   }
   const uint32_t sub = blockIdx.x * S + local;
-  const bool live = sub < n_sub && in_range;
-  const cabac_substream_desc d = desc[sub < n_sub ? sub : 0];
-  const uint32_t n = sub < n_sub ? d.n_records : 0u;
+  const QuadSetUse su = quad_set_use(sub, sub < n_sub, sets...);
+  const bool in_batch = sub < n_sub && !su.bad;
+  const bool live = in_batch && in_range;
+  const cabac_substream_desc d = desc[in_batch ? sub : 0];
+  const uint32_t n = in_batch ? d.n_records : 0u;
 
   if (threadIdx.x == 0) wg_max_n = 0;
   __syncthreads();
@@ -1116,7 +1205,8 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
   if (is_ctx) {
     const uint16_t *rec = records + d.rec_offset;
     uint32_t *rctx = ctx_all + local * kQuadCtxStride;
-    quad_ctx_init(rctx, d.qp, d.init_id & 3u, j);
+    if constexpr (kSets) quad_ctx_load<true>(rctx, d.qp, d.init_id & 3u, j, 16u, su, sets...);
+    else quad_ctx_init(rctx, d.qp, d.init_id & 3u, j);
     uint32_t bad = 0;
     const uint16_t *rec_safe = n != 0 ? rec : reinterpret_cast<const uint16_t *>(desc);
     const uint32_t last_rec = n != 0 ? n - 1u : 0u;
@@ -1154,6 +1244,12 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
       uint32_t rows = 0;
       for (uint32_t q = 0; q < 4; q++) rows |= ((bad_mask >> (16u * q)) & 0xffffull) ? (1u << q) : 0u;
       bad_rows[unit] = rows;
+    }
+    if constexpr (kSets) {  // as in v6: each context wave owns its unit's four stores and has run every step of them
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      asm volatile("" ::: "memory");
+      quad_ctx_export(rctx, j, 16u, su, sets...);
     }
     __syncthreads();
     __syncthreads();
@@ -1297,6 +1393,7 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
       res.flags = (e.pos > e.cap ? CABAC_RES_OVERFLOW : 0u) | (((bad_rows[unit] >> row) & 1u) ? CABAC_RES_BAD_RECORD : 0u);
       results[sub] = res;
     }
+    if constexpr (kSets) quad_bad_set_result(results, sub, in_range && j == 0, su);
     __syncthreads();
   }
 }
@@ -1640,12 +1737,13 @@ __device__ __forceinline__ void quad_dec_steps_pairs(const QuadDecInfo &f, const
 // instruction: the geometry for batches that offer more than one quad wave per SIMD (launch_decode_v4).
 // select (may be null): the launch runs only if *select == want — the dispatch launches both geometries behind
 // decode_select_kernel, which looks at the batch on the device (the descriptors of a *_device call are not on the host).
-template <int W, int L = 16>
+template <int W, int L = 16, class... Sets>
 __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
                                                            const uint16_t *__restrict__ records,
                                                            const uint8_t *__restrict__ bytes, uint8_t *__restrict__ bins,
                                                            cabac_substream_result *__restrict__ results,
-                                                           const uint32_t *__restrict__ select, uint32_t want) {
+                                                           const uint32_t *__restrict__ select, uint32_t want, Sets... sets) {
+  constexpr bool kSets = sizeof...(Sets) != 0;
   if (select != nullptr && *select != want) return;
   // decode keeps the two window sizes of a context (they never change) apart from its state word, whose low
   // five bits are then zero: state() is one SDWA add of the two halves, without masking
@@ -1664,13 +1762,16 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
   uint32_t *ctx = ctx_all + wave * (kSubs * kQuadCtxStride);
   const uint32_t lane = threadIdx.x & 63u, row = lane / L, j = lane % L;
   const uint32_t sub = (blockIdx.x * W + wave) * kSubs + row;
-  const bool live = sub < n_sub;
+  const QuadSetUse su = quad_set_use(sub, sub < n_sub, sets...);
+  const bool live = sub < n_sub && !su.bad;
   const cabac_substream_desc d = desc[live ? sub : 0];
   const uint32_t n = live ? d.n_records : 0u;
   const uint16_t *rec = records + d.rec_offset;
   uint8_t *out = bins + d.rec_offset;
   uint32_t *rctx = ctx + row * kQuadCtxStride;
-  {
+  if constexpr (kSets) {
+    quad_ctx_load<false>(rctx, d.qp, d.init_id & 3u, j, (uint32_t)L, su, sets...);
+  } else {
     const int qp = d.qp < 0 ? 0 : (d.qp > 63 ? 63 : d.qp);
     const uint32_t iid = d.init_id & 3u;
     for (uint32_t k = j; k < (uint32_t)kNumCtx; k += L) {
@@ -1930,6 +2031,17 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
     res.flags = flags;
     results[sub] = res;
   }
+  if constexpr (kSets) {
+    // Every step ends with the store of its final states (all lanes of a context hold the same word, after a pairs step too:
+    // quad_dec_steps_pairs brings st_v up to date behind its chain), and the surplus steps of the last trip and of shorter rows
+    // carry the id of "nothing": they write the pad word.  The row's lanes belong to one wave, whose LDS instructions execute in
+    // order: only the compiler has to be kept from moving the reads.
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+    quad_ctx_export(rctx, j, (uint32_t)L, su, sets...);
+    quad_bad_set_result(results, sub, j == 0, su);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2041,24 +2153,115 @@ hipError_t launch_estimate(hipStream_t st, uint32_t n_sub, const cabac_substream
 }
 
 // ---------------------------------------------------------------------------------------------
+// context advance (cabac_hip_ctx_sets.h): the estimator's walk with the cost dropped and the export added — quad_resolve brings
+// the row's store up to date for the sixteen records of a step, same-context repeats included; bypass, terminate and align
+// records touch no context, any other id is a bad record.  Sets in, sets out; nothing is coded.
+template <int W>
+__global__ __launch_bounds__(64 * W) void ctx_advance_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+                                                             const uint16_t *__restrict__ records, CtxSets cs,
+                                                             uint32_t *__restrict__ flags) {
+  __shared__ uint32_t ctx_all[W * kQuadSubs * kQuadCtxStride];
+  __shared__ uint32_t match_all[W][kMatchWords];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, row = lane >> 4, j = lane & 15u;
+  for (uint32_t k = threadIdx.x; k < W * kMatchWords; k += 64u * W) (&match_all[0][0])[k] = 0u;
+  const uint32_t sub = (blockIdx.x * W + wave) * kQuadSubs + row;
+  const QuadSetUse su = quad_set_use(sub, sub < n_sub, cs);
+  const bool live = sub < n_sub && !su.bad;
+  const cabac_substream_desc d = desc[live ? sub : 0];
+  const uint32_t n = live ? d.n_records : 0u;
+  const uint16_t *rec = records + d.rec_offset;
+  uint32_t *rctx = ctx_all + (wave * kQuadSubs + row) * kQuadCtxStride;
+  quad_ctx_load<true>(rctx, d.qp, d.init_id & 3u, j, 16u, su, cs);
+  __syncthreads();
+
+  uint32_t n_wave = n;
+  n_wave = max(n_wave, (uint32_t)__shfl_xor((int)n_wave, 16));
+  n_wave = max(n_wave, (uint32_t)__shfl_xor((int)n_wave, 32));
+  const uint32_t max_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_wave);
+  const uint16_t *rec_safe = n != 0 ? rec : reinterpret_cast<const uint16_t *>(desc);
+  const uint32_t last_rec = n != 0 ? n - 1u : 0u;
+  uint32_t next_rec = rec_safe[min(j, last_rec)];
+  uint32_t bad = 0;
+  for (uint32_t base = 0; base < max_n; base += 16) {
+    const uint32_t r = next_rec;
+    next_rec = rec_safe[min(base + 16u + j, last_rec)];
+    (void)quad_resolve<CABAC_REC_ALIGN, true>(r, base + j < n, lane, row, rctx, bad, match_all[wave]);
+  }
+  const uint64_t bad_mask = __ballot(bad != 0);
+  asm volatile("" ::: "memory");  // the row's stores are its own wave's: in order in LDS
+  __builtin_amdgcn_wave_barrier();
+  asm volatile("" ::: "memory");
+  quad_ctx_export(rctx, j, 16u, su, cs);
+  if (sub < n_sub && j == 0 && flags != nullptr)
+    flags[sub] = su.bad ? 0x40u : (((bad_mask >> (row * 16u)) & 0xffffull) ? CABAC_RES_BAD_RECORD : 0u);
+}
+
+hipError_t launch_ctx_advance(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                              const CtxSets &sets, uint32_t *flags) {
+  if (n_sub == 0) return hipSuccess;
+  const uint32_t waves = (n_sub + kQuadSubs - 1) / kQuadSubs;
+  if (waves >= 1024u) hipLaunchKernelGGL(ctx_advance_kernel<4>, dim3((waves + 3) / 4), dim3(256), 0, st, n_sub, desc, records, sets, flags);
+  else hipLaunchKernelGGL(ctx_advance_kernel<1>, dim3(waves), dim3(64), 0, st, n_sub, desc, records, sets, flags);
+  return hipGetLastError();
+}
+
+// One level of a WPP call (cabac_hip_ctx_sets.h), substreams [first, first + n): the descriptors of its prefix pass (the first
+// min(sync_at, n_records) records, flag bits cleared), its slot indices (slot = substream) and its links checked against the
+// level — a link that does not point below `first` becomes an index no call accepts (CABAC_RES_BAD_SET)
+__global__ __launch_bounds__(256) void wpp_level_kernel(uint32_t first, uint32_t n, const cabac_substream_desc *__restrict__ desc,
+                                                        const uint32_t *__restrict__ sync_from, const uint32_t *__restrict__ sync_at,
+                                                        cabac_substream_desc *__restrict__ desc_out, uint32_t *__restrict__ start_out,
+                                                        uint32_t *__restrict__ slot_out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t s = first + i;
+  cabac_substream_desc d = desc[s];
+  d.n_records = min(sync_at[s], d.n_records);
+  d.init_id &= 3u;
+  desc_out[s] = d;
+  const uint32_t from = sync_from[s];
+  start_out[s] = (from == kNoSet || from < first) ? from : 0xfffffffeu;
+  slot_out[s] = s;
+}
+
+hipError_t launch_wpp_level(hipStream_t st, uint32_t first, uint32_t n, const cabac_substream_desc *desc, const uint32_t *sync_from,
+                            const uint32_t *sync_at, cabac_substream_desc *desc_out, uint32_t *start_out, uint32_t *slot_out) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(wpp_level_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, first, n, desc, sync_from, sync_at, desc_out,
+                     start_out, slot_out);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 hipError_t launch_encode_v4(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                            uint8_t *bytes, cabac_substream_result *results) {
-  hipLaunchKernelGGL(encode_kernel_v4, dim3((n_sub + kQuadSubs - 1) / kQuadSubs), dim3(64), 0, st, n_sub, desc, records,
-                     bytes, results);
+                            uint8_t *bytes, cabac_substream_result *results, const CtxSets *sets) {
+  const dim3 grid((n_sub + kQuadSubs - 1) / kQuadSubs);
+  if (sets != nullptr) hipLaunchKernelGGL(encode_kernel_v4<CtxSets>, grid, dim3(64), 0, st, n_sub, desc, records, bytes, results, *sets);
+  else hipLaunchKernelGGL(encode_kernel_v4<>, grid, dim3(64), 0, st, n_sub, desc, records, bytes, results);
   return hipGetLastError();
 }
 
 hipError_t launch_encode_v6(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                            uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight) {
+                            uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight, const CtxSets *sets) {
   const uint32_t units = (n_sub + kQuadSubs - 1) / kQuadSubs;
   const uint32_t units_on_chip = (max(n_sub, in_flight) + kQuadSubs - 1) / kQuadSubs;
+  if (sets != nullptr) {  // the same geometries, from / into context sets
+    if (units_on_chip >= 1024u) hipLaunchKernelGGL((encode_kernel_v6<4, 1, CtxSets>), dim3((units + 3) / 4), dim3(1024), 0, st, n_sub, desc, records, bytes, results, *sets);
+    else hipLaunchKernelGGL((encode_kernel_v6<1, 2, CtxSets>), dim3(units), dim3(256), 0, st, n_sub, desc, records, bytes, results, *sets);
+    return hipGetLastError();
+  }
   if (units_on_chip >= 1024u) hipLaunchKernelGGL((encode_kernel_v6<4, 1>), dim3((units + 3) / 4), dim3(1024), 0, st, n_sub, desc, records, bytes, results);
   else hipLaunchKernelGGL((encode_kernel_v6<1, 2>), dim3(units), dim3(256), 0, st, n_sub, desc, records, bytes, results);
   return hipGetLastError();
 }
 
 hipError_t launch_encode_v7(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                            uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight) {
+                            uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight, const CtxSets *sets) {
+  if (sets != nullptr) {
+    if (max(n_sub, in_flight) >= 1024u) hipLaunchKernelGGL((encode_kernel_v7<4, CtxSets>), dim3((n_sub + 15) / 16), dim3(512), 0, st, n_sub, desc, records, bytes, results, *sets);
+    else hipLaunchKernelGGL((encode_kernel_v7<1, CtxSets>), dim3((n_sub + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes, results, *sets);
+    return hipGetLastError();
+  }
   // sixteen substreams per workgroup once there are enough of them to give every CU one; four below that
   if (max(n_sub, in_flight) >= 1024u) hipLaunchKernelGGL(encode_kernel_v7<4>, dim3((n_sub + 15) / 16), dim3(512), 0, st, n_sub, desc, records, bytes, results);
   else hipLaunchKernelGGL(encode_kernel_v7<1>, dim3((n_sub + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes, results);
@@ -2130,13 +2333,18 @@ __global__ __launch_bounds__(1024) void decode_select_solo_kernel(uint32_t n_sub
   if (threadIdx.x == 0) *select = (longest != 0u && past <= max_long) ? 2u : 0u;
 }
 
+static hipError_t launch_decode_v4_sets(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                        const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight,
+                                        int lanes_per_sub, uint32_t *select, const CtxSets &sets);
+
 constexpr uint32_t kSoloUpTo = 1024;
 constexpr uint32_t kSoloAskUpTo = 3072;  // ... and up to here the batch is looked at on the device (below the headline's 4 096)  // substreams in flight up to which each gets a wave (and a SIMD) of its own
 constexpr uint32_t kHexFrom = 9216;  // measured (tools/batch_scaling.py): 8 192 equal substreams 2.12 ms quad / 2.23 ms hex, 12 288: 3.14 / 2.23
 
 hipError_t launch_decode_v4(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
                             const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight, int lanes_per_sub,
-                            uint32_t *select) {
+                            uint32_t *select, const CtxSets *sets) {
+  if (sets != nullptr) return launch_decode_v4_sets(st, n_sub, desc, records, bytes, bins, results, in_flight, lanes_per_sub, select, *sets);
   if (lanes_per_sub == 0) {  // auto
     // up to one substream per SIMD: a wave each, 64 bins a step (16 ... 1 024 C4-type substreams 1.13-1.16 ms against 1.30)
     if (max(n_sub, in_flight) <= kSoloUpTo) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 64);
@@ -2173,6 +2381,42 @@ hipError_t launch_decode_v4(hipStream_t st, uint32_t n_sub, const cabac_substrea
   } else {
     hipLaunchKernelGGL(decode_kernel_v4<1>, dim3(waves), dim3(64), 0, st, n_sub, desc, records, bytes, bins, results,
                        (const uint32_t *)nullptr, 0u);
+  }
+  return hipGetLastError();
+}
+
+// the dispatch above, geometry for geometry, with the instantiations that start from and write context sets
+static hipError_t launch_decode_v4_sets(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                        const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight,
+                                        int lanes_per_sub, uint32_t *select, const CtxSets &sets) {
+  const uint32_t *const no_select = nullptr;
+  if (lanes_per_sub == 0) {  // auto
+    if (max(n_sub, in_flight) <= kSoloUpTo) return launch_decode_v4_sets(st, n_sub, desc, records, bytes, bins, results, in_flight, 64, select, sets);
+    if (select != nullptr && max(n_sub, in_flight) <= kSoloAskUpTo && in_flight <= n_sub) {
+      hipLaunchKernelGGL(decode_select_solo_kernel, dim3(1), dim3(1024), 0, st, n_sub, desc, kSoloUpTo, select);
+      hipLaunchKernelGGL((decode_kernel_v4<4, 64, CtxSets>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 2u, sets);
+      hipLaunchKernelGGL((decode_kernel_v4<4, 16, CtxSets>), dim3((n_sub + 15u) / 16u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 0u, sets);
+      return hipGetLastError();
+    }
+    if (max(n_sub, in_flight) < kHexFrom || select == nullptr) return launch_decode_v4_sets(st, n_sub, desc, records, bytes, bins, results, in_flight, 16, select, sets);
+    const uint32_t thr = (uint32_t)((uint64_t)kHexFrom * n_sub / max(n_sub, in_flight));
+    hipLaunchKernelGGL(decode_select_kernel, dim3(1), dim3(1024), 0, st, n_sub, desc, thr, select);
+    hipLaunchKernelGGL((decode_kernel_v4<4, 4, CtxSets>), dim3((n_sub + 63u) / 64u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 1u, sets);
+    hipLaunchKernelGGL((decode_kernel_v4<4, 16, CtxSets>), dim3((n_sub + 15u) / 16u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 0u, sets);
+    return hipGetLastError();
+  }
+  const uint32_t waves = (n_sub + kQuadSubs - 1) / kQuadSubs;
+  if (lanes_per_sub == 64) {
+    if (max(n_sub, in_flight) >= 1024u)
+      hipLaunchKernelGGL((decode_kernel_v4<4, 64, CtxSets>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, no_select, 0u, sets);
+    else
+      hipLaunchKernelGGL((decode_kernel_v4<1, 64, CtxSets>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, records, bytes, bins, results, no_select, 0u, sets);
+  } else if (lanes_per_sub == 4) {
+    hipLaunchKernelGGL((decode_kernel_v4<4, 4, CtxSets>), dim3((n_sub + 63u) / 64u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, no_select, 0u, sets);
+  } else if ((max(n_sub, in_flight) + kQuadSubs - 1) / kQuadSubs >= 1024u) {
+    hipLaunchKernelGGL((decode_kernel_v4<4, 16, CtxSets>), dim3((waves + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, no_select, 0u, sets);
+  } else {
+    hipLaunchKernelGGL((decode_kernel_v4<1, 16, CtxSets>), dim3(waves), dim3(64), 0, st, n_sub, desc, records, bytes, bins, results, no_select, 0u, sets);
   }
   return hipGetLastError();
 }
