@@ -92,6 +92,12 @@ EXPORTS_CTX_SETS = [
     "cabac_hip_encode_sets_device", "cabac_hip_decode_sets_device", "cabac_hip_ctx_advance_device", "cabac_hip_encode_wpp_device",
     "cabac_hip_decode_wpp_device", "cabac_hip_encode_wpp_batch", "cabac_hip_decode_wpp_batch",
 ]
+# include/cabac_hip_plan_rows.h (the plan parse and the plan write from and into sets, and in WPP rows; tests/test_plan_rows_abi.py
+# compares)
+EXPORTS_PLAN_ROWS = [
+    "cabac_hip_plan_parse_sets_device", "cabac_hip_plan_parse_rows_device", "cabac_hip_plan_parse_rows_batch",
+    "cabac_hip_plan_write_sets_device", "cabac_hip_plan_write_rows_device", "cabac_hip_plan_write_rows_batch",
+]
 CTX_NO_SET = 0xFFFFFFFF                                          # CABAC_CTX_NO_SET
 RES_BAD_SET = 0x40                                               # CABAC_RES_BAD_SET
 PE_COND, PE_BLOCK_INFO = 9, 10                                   # CABAC_PE_COND, CABAC_PE_BLOCK_INFO
@@ -314,6 +320,15 @@ def load_library():
                                               ctypes.c_uint64, vp, vp, vp, vp]
     L.cabac_hip_write_plan_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp, ctypes.c_int,
                                              ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp, vp]
+    # (CABAC_HIP_LIBRARY may name a build from before cabac_hip_plan_rows.h — tools/bench_plan_rows.py --label parent)
+    if hasattr(L, "cabac_hip_plan_parse_sets_device"):
+        rows4 = [ctypes.c_uint32, vp, vp, vp]   # n_level, level_first, sync_from, sync_at
+        L.cabac_hip_plan_parse_sets_device.argtypes = L.cabac_hip_parse_plan_device.argtypes + sets7 + [vp]
+        L.cabac_hip_plan_parse_rows_device.argtypes = L.cabac_hip_parse_plan_device.argtypes + rows4
+        L.cabac_hip_plan_parse_rows_batch.argtypes = L.cabac_hip_parse_plan_batch.argtypes + rows4
+        L.cabac_hip_plan_write_sets_device.argtypes = L.cabac_hip_write_plan_device.argtypes + sets7
+        L.cabac_hip_plan_write_rows_device.argtypes = L.cabac_hip_write_plan_device.argtypes + rows4
+        L.cabac_hip_plan_write_rows_batch.argtypes = L.cabac_hip_write_plan_batch.argtypes + rows4
     L.cabac_hip_resolve_plan_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_int, vp, vp,
                                                 ctypes.c_uint64, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_search_plan_round_device.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, ctypes.c_int] + \
@@ -479,7 +494,8 @@ class CabacHip:
         24 log place in cabac_hip_search_emit.h; 25 unit parse in cabac_hip_parse_unit.h; 26 element parse in
         cabac_hip_parse_elements.h; 27 plan parse in cabac_hip_parse_plan.h; 28 plan write in cabac_hip_write_plan.h; 29 plan resolve in
         cabac_hip_search_plan.h; 30 encode with sets, 31 decode with sets, 32 context advance and 33 a WPP prefix pass in
-        cabac_hip_ctx_sets.h)."""
+        cabac_hip_ctx_sets.h; 34 plan parse with sets, 35 a level of a rows parse and 36 the encode launch of a plan write with sets
+        in cabac_hip_plan_rows.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -1060,6 +1076,111 @@ class CabacHip:
             tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
             coeff.ctypes.data, 2 if narrow else 4, len(coeff), payload.ctypes.data, payload.nbytes, offsets.ctypes.data,
             res.ctypes.data, values_out.ctypes.data, info.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return payload[: int(offsets[n])], offsets, res[:n], values_out[: len(plan)], info[: len(tus)]
+
+    # ---- plans from and into context sets, and in WPP rows (include/cabac_hip_plan_rows.h) ------
+    def plan_parse_sets_device(self, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff, d_values,
+                               d_results, d_tu_info=0, int16=False, n_sets=0, d_state=0, d_rate=0, d_start_set=0, d_out_set=0,
+                               d_out_state=0, d_out_rate=0, d_out_at=0):
+        """parse_plan_device with substream s started from set d_start_set[s] (CTX_NO_SET: Ctx::init) and the contexts it holds
+        when it arrives at plan entry d_out_at[s] (0: the end) written as set d_out_set[s]; 0 for a pointer = NULL."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_plan_parse_sets_device(
+            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), opt(d_tu), opt(d_tu_at), opt(d_tu_guard), opt(d_plan),
+            opt(d_coeff), 2 if int16 else 4, opt(d_values), opt(d_tu_info), vp(d_results),
+            *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate), opt(d_out_at)))
+
+    def plan_parse_rows_device(self, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff, d_values,
+                               d_results, level_first, d_sync_from, d_sync_at, d_tu_info=0, int16=False):
+        """parse_plan_device over WPP rows in level order; level_first: HOST, n_level + 1 entries; d_sync_at in plan entries."""
+        opt = lambda p: vp(p) if p else None
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        self._check(self.L.cabac_hip_plan_parse_rows_device(
+            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), opt(d_tu), opt(d_tu_at), opt(d_tu_guard), opt(d_plan),
+            opt(d_coeff), 2 if int16 else 4, opt(d_values), opt(d_tu_info), vp(d_results), len(lf) - 1, lf.ctypes.data,
+            vp(d_sync_from), vp(d_sync_at)))
+
+    def plan_parse_rows_batch(self, desc, data, tile_first, tus, tu_at, tu_guard, plan, n_coeff_total, level_first, sync_from, sync_at,
+                              check=True, int16=False, coeff=None, values=None, info=None):
+        """Host arrays through cabac_hip_plan_parse_rows_batch (synchronous): (coeff, values, results, info), as parse_plan_batch."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        data = np.ascontiguousarray(data, np.uint8)
+        tile_first = np.ascontiguousarray(tile_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
+        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
+        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        sf, sa = np.ascontiguousarray(sync_from, np.uint32), np.ascontiguousarray(sync_at, np.uint32)
+        assert len(tile_first) == len(desc) + 1 and (tu_at is None or len(tu_at) == len(tus))
+        assert (tu_guard is None or len(tu_guard) == len(tus)) and len(sf) == len(desc) and len(sa) == len(desc)
+        if coeff is None:
+            coeff = np.zeros(max(int(n_coeff_total), 1), np.int16 if int16 else np.int32)
+        if values is None:
+            values = np.zeros(max(len(plan), 1), np.uint32)
+        if info is None:
+            info = np.zeros(max(len(tus), 1), np.uint32)
+        assert coeff.dtype == (np.int16 if int16 else np.int32) and values.dtype == np.uint32 and info.dtype == np.uint32
+        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
+        rc = self.L.cabac_hip_plan_parse_rows_batch(
+            self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data,
+            tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
+            plan.ctypes.data, len(plan), coeff.ctypes.data, 2 if int16 else 4, int(n_coeff_total), values.ctypes.data,
+            info.ctypes.data, res.ctypes.data, len(lf) - 1, lf.ctypes.data, sf.ctypes.data, sa.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return coeff[: int(n_coeff_total)], values[: len(plan)], res[: len(desc)], info[: len(tus)]
+
+    def plan_write_sets_device(self, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff,
+                               d_payload, payload_capacity, d_payload_offsets, d_results, d_values_out=0, d_tu_info=0, int16=False,
+                               n_sets=0, d_state=0, d_rate=0, d_start_set=0, d_out_set=0, d_out_state=0, d_out_rate=0):
+        """write_plan_device with substream s coded from set d_start_set[s] and its final contexts written as set d_out_set[s]."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_plan_write_sets_device(
+            self.h, n_sub, vp(d_desc), opt(d_plan), opt(d_values_in), vp(d_tile_first), n_tu, opt(d_tu), opt(d_tu_at), opt(d_tu_guard),
+            opt(d_coeff), 2 if int16 else 4, vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), opt(d_values_out),
+            opt(d_tu_info), *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate)))
+
+    def plan_write_rows_device(self, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff,
+                               d_payload, payload_capacity, d_payload_offsets, d_results, level_first, d_sync_from, d_sync_at,
+                               d_values_out=0, d_tu_info=0, int16=False):
+        """write_plan_device over WPP rows in level order; level_first: HOST, n_level + 1 entries; d_sync_at in plan entries."""
+        opt = lambda p: vp(p) if p else None
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        self._check(self.L.cabac_hip_plan_write_rows_device(
+            self.h, n_sub, vp(d_desc), opt(d_plan), opt(d_values_in), vp(d_tile_first), n_tu, opt(d_tu), opt(d_tu_at), opt(d_tu_guard),
+            opt(d_coeff), 2 if int16 else 4, vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), opt(d_values_out),
+            opt(d_tu_info), len(lf) - 1, lf.ctypes.data, vp(d_sync_from), vp(d_sync_at)))
+
+    def plan_write_rows_batch(self, desc, plan, values, tile_first, tus, tu_at, tu_guard, coeff, payload, level_first, sync_from,
+                              sync_at, check=True, values_out=None, info=None):
+        """Host arrays through cabac_hip_plan_write_rows_batch (synchronous): as write_plan_batch."""
+        narrow = isinstance(coeff, np.ndarray) and coeff.dtype == np.int16
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
+        values = np.ascontiguousarray(values, np.uint32)
+        tile_first = np.ascontiguousarray(tile_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
+        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
+        coeff = np.ascontiguousarray(coeff, np.int16 if narrow else np.int32)
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        sf, sa = np.ascontiguousarray(sync_from, np.uint32), np.ascontiguousarray(sync_at, np.uint32)
+        n = len(desc)
+        assert len(tile_first) == n + 1 and len(values) >= len(plan) and (tu_at is None or len(tu_at) == len(tus))
+        assert (tu_guard is None or len(tu_guard) == len(tus)) and len(sf) == n and len(sa) == n
+        if values_out is None:
+            values_out = np.zeros(max(len(plan), 1), np.uint32)
+        if info is None:
+            info = np.zeros(max(len(tus), 1), np.uint32)
+        assert values_out.dtype == np.uint32 and len(values_out) >= len(plan) and info.dtype == np.uint32 and payload.dtype == np.uint8
+        offsets = np.zeros(n + 1, np.uint64)
+        res = np.zeros(max(n, 1), RESULT_DTYPE)
+        rc = self.L.cabac_hip_plan_write_rows_batch(
+            self.h, n, desc.ctypes.data, plan.ctypes.data, values.ctypes.data, len(plan), tile_first.ctypes.data, tus.ctypes.data,
+            tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
+            coeff.ctypes.data, 2 if narrow else 4, len(coeff), payload.ctypes.data, payload.nbytes, offsets.ctypes.data,
+            res.ctypes.data, values_out.ctypes.data, info.ctypes.data, len(lf) - 1, lf.ctypes.data, sf.ctypes.data, sa.ctypes.data)
         self._check(rc, allow_substream=not check)
         return payload[: int(offsets[n])], offsets, res[:n], values_out[: len(plan)], info[: len(tus)]
 

@@ -23,6 +23,7 @@
 #include "cabac_hip_parse_elements.h"
 #include "cabac_hip_parse_plan.h"
 #include "cabac_hip_parse_unit.h"
+#include "cabac_hip_plan_rows.h"
 #include "cabac_hip_search.h"
 #include "cabac_hip_search_emit.h"
 #include "cabac_hip_search_plan.h"
@@ -55,7 +56,7 @@ struct cabac_hip_ctx {
   // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
   // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included); [48..]: the winner log (kLog* below); [53..]: the
   // unit parse (kUnit* below); [56..]: the element parse (kElem* below); [59..]: the plan write (kPw* below); [61..]: the plan
-  // resolve of the search rounds (kPs* below); [64..]: the WPP calls (kWpp* below)
+  // resolve of the search rounds (kPs* below); [64..]: the WPP calls (kWpp* below); [71]: the plan rows (kRowsWords below)
   static constexpr int kSlots = 72;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
@@ -1427,20 +1428,46 @@ int cabac_hip_parse_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_su
   return CABAC_HIP_OK;
 }
 
-int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                               uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
-                               const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
-                               int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
-                               cabac_substream_result *results) {
-  if (!c || (n_sub && (!desc || !bytes || !tile_first || !results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+namespace {
+// the rows of a call of cabac_hip_plan_rows.h: levels (HOST memory) and links (device memory; host memory in the batch forms)
+struct PlanRows {
+  uint32_t n_level;
+  const uint32_t *level_first, *d_sync_from, *d_sync_at;
+};
+// device slot of the plan rows: per substream the record index of its hand-over entry, then the out sets of the substreams that
+// did not stop (the rows write); the slots of the rows parse and the links of the batch forms are the WPP calls' (kWpp* below)
+enum { kRowsWords = 71, kRowsState = 64, kRowsRate = 65, kRowsFrom = 69, kRowsAt = 70 };
+}  // namespace
+
+static int check_levels(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, const uint32_t *level_first);
+static int check_links_host(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, const uint32_t *level_first, const uint32_t *sync_from);
+static int parse_rows_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                  const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                  const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes, uint32_t *d_values,
+                                  uint32_t *d_tu_info, cabac_substream_result *d_results, const PlanRows &rows);
+
+// rows (may be null): the levels and the links, all in HOST memory here; the rows parse then takes the plan parse's place
+static int parse_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                 uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                                 const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
+                                 int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
+                                 cabac_substream_result *results, const PlanRows *rows) {
+  if (!c || (n_sub && (!desc || !bytes || !tile_first || !results)) || (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (n_sub == 0) return CABAC_HIP_OK;
   const uint32_t n_tu = tile_first[n_sub];
   if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (n_elements_total && (!plan || !values)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (int bad = check_plan_host(c, n_sub, desc, &bytes_total, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, n_coeff_total)) return bad;
+  if (rows) {
+    if (int bad = check_levels(c, n_sub, rows->n_level, rows->level_first)) return bad;
+    if (int bad = check_links_host(c, n_sub, rows->n_level, rows->level_first, rows->d_sync_from)) return bad;
+  }
   DeviceGuard g(c->device);
   int rc;
+  const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
+  if (rows && ((rc = ensure(c, kRowsFrom, link_bytes)) || (rc = ensure(c, kRowsAt, link_bytes)))) return rc;
   // staged as cabac_hip_parse_elements_batch stages, in its slots
   const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), first_pad = (first_bytes + 15) / 16 * 16;
   const size_t plan_bytes = size_t(n_elements_total) * 2 * sizeof(uint32_t), value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
@@ -1473,12 +1500,24 @@ int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
   if (tu_info) HIP_TRY(c, up(c->d_buf[6], tu_info, size_t(n_tu) * sizeof(uint32_t)));
   if (n_tu && coeff_bytes == 4) HIP_TRY(c, up(c->d_buf[1], coeff, n_coeff_total * sizeof(int32_t)));
   if (n_tu && n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(c->d_buf[1], 0, n_coeff_total * sizeof(int16_t), c->stream));
-  rc = cabac_hip_parse_plan_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
-                                   (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad),
-                                   tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr,
-                                   tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr, (const uint32_t *)c->d_buf[kElemPlan],
-                                   c->d_buf[1], coeff_bytes, (uint32_t *)c->d_buf[kElemValues], (uint32_t *)c->d_buf[6],
-                                   (cabac_substream_result *)c->d_buf[4]);
+  if (rows) {
+    HIP_TRY(c, up(c->d_buf[kRowsFrom], rows->d_sync_from, link_bytes));
+    HIP_TRY(c, up(c->d_buf[kRowsAt], rows->d_sync_at, link_bytes));
+    const PlanRows d_rows{rows->n_level, rows->level_first, (const uint32_t *)c->d_buf[kRowsFrom], (const uint32_t *)c->d_buf[kRowsAt]};
+    rc = parse_rows_device_impl(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
+                                (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad),
+                                tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr,
+                                tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr, (const uint32_t *)c->d_buf[kElemPlan],
+                                c->d_buf[1], coeff_bytes, (uint32_t *)c->d_buf[kElemValues], (uint32_t *)c->d_buf[6],
+                                (cabac_substream_result *)c->d_buf[4], d_rows);
+  } else {
+    rc = cabac_hip_parse_plan_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
+                                     (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad),
+                                     tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr,
+                                     tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr, (const uint32_t *)c->d_buf[kElemPlan],
+                                     c->d_buf[1], coeff_bytes, (uint32_t *)c->d_buf[kElemValues], (uint32_t *)c->d_buf[6],
+                                     (cabac_substream_result *)c->d_buf[4]);
+  }
   if (rc) return rc;
   if (tu_info) HIP_TRY(c, down(tu_info, c->d_buf[6], size_t(n_tu) * sizeof(uint32_t)));
   if (n_tu) HIP_TRY(c, down(coeff, c->d_buf[1], n_coeff_total * size_t(coeff_bytes)));
@@ -1490,6 +1529,15 @@ int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
     if (results[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
   if (status) c->last_error = "substream flag set (see results[].flags)";
   return status;
+}
+
+int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                               uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                               const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
+                               int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
+                               cabac_substream_result *results) {
+  return parse_plan_batch_impl(c, n_sub, desc, bytes, bytes_total, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, coeff,
+                               coeff_bytes, n_coeff_total, values, tu_info, results, nullptr);
 }
 
 // ---- coefficients -> bytes (cabac_splice.hip) -------------------------------------------------------------------
@@ -1720,17 +1768,34 @@ namespace {
 enum { kPwPlan = 59, kPwTu = 60 };
 }  // namespace
 
-int cabac_hip_write_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,
-                                const uint32_t *d_values_in, const uint32_t *d_tile_first, uint32_t n_tu, const cabac_tu_desc *d_tu,
-                                const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes,
-                                uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_payload_offsets,
-                                cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info) {
+static int wpp_device_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                           uint8_t *d_bytes, uint8_t *d_bins, cabac_substream_result *d_results, uint32_t n_level,
+                           const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at);
+
+// sets (may be null): the encode launch starts from and writes context sets; rows (may be null): the emit walk notes each
+// substream's hand-over record and the WPP encode schedule takes the encode launch's place.  Not both.
+static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,
+                                  const uint32_t *d_values_in, const uint32_t *d_tile_first, uint32_t n_tu, const cabac_tu_desc *d_tu,
+                                  const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes,
+                                  uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_payload_offsets,
+                                  cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info,
+                                  const cabac::CtxSets *sets, const PlanRows *rows) {
   if (!c || !d_payload_offsets || (n_sub && (!d_desc || !d_tile_first || !d_payload || !d_results)) || (n_tu && (!d_tu || !d_coeff)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (n_sub == 0 && n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "blocks without a substream");
+  if (rows && n_sub) {
+    if (!rows->d_sync_from || !rows->d_sync_at) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+    if (int bad = check_levels(c, n_sub, rows->n_level, rows->level_first)) return bad;
+  }
   DeviceGuard g(c->device);
   int rc;
+  if ((sets || rows) && (rc = ensure(c, kRowsWords, 2 * size_t(n_sub ? n_sub : 1) * sizeof(uint32_t)))) return rc;
+  uint32_t *sync_rec = nullptr, *out_live = nullptr;  // the hand-over records of a rows call; the out sets of the rows that did not stop
+  if (sets || rows) {
+    sync_rec = static_cast<uint32_t *>(c->d_buf[kRowsWords]);
+    out_live = sync_rec + (n_sub ? n_sub : 1);
+  }
   const size_t n_blk = n_tu ? n_tu : 1, n_s = n_sub ? n_sub : 1;
   const size_t words = (3 * n_s + 2 + 1) & ~size_t(1);  // sub_n, sub_cap, sub_flag, err (+ pad)
   if ((rc = ensure(c, kSpCnt, 2 * n_blk * sizeof(uint32_t)))) return rc;
@@ -1768,14 +1833,25 @@ int cabac_hip_write_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_su
   {
     Timed t(c, 28);
     HIP_TRY(c, cabac::launch_plan_emit(c->stream, n_sub, in, sub_n, sub_cap, sub_flag, rec_base, byte_base, desc2, tus2, tu_off, exp_rec,
-                                       d_values_out, d_tu_info));
+                                       d_values_out, d_tu_info, rows ? rows->d_sync_at : nullptr, rows ? sync_rec : nullptr));
+    if (sets && sets->out_set) HIP_TRY(c, cabac::launch_plan_out_sets(c->stream, n_sub, sub_flag, sets->out_set, out_live));
   }
   {  // block records of the coded blocks, straight into the expanded substreams: in tus2 a skipped block is one the binariser
      // rejects, so it writes nothing whatever its coefficients hold (another list: the block order is made again)
     Timed t(c, 5);
     HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, tus2, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[5]));
   }
-  {
+  if (rows) {  // the context-advance prefix passes per level, then one encode launch from the slots
+    if (n_sub && (rc = wpp_device_impl(c, false, n_sub, desc2, exp_rec, slots, nullptr, d_results, rows->n_level, rows->level_first,
+                                       rows->d_sync_from, sync_rec)))
+      return rc;
+    c->timed = false;
+  } else if (sets) {
+    cabac::CtxSets live = *sets;  // a stopped substream has an empty run: it would write a copy of its start set
+    if (live.out_set) live.out_set = out_live;
+    Timed t(c, 36);
+    HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, desc2, exp_rec, slots, d_results, 0, &live));
+  } else {
     Timed t(c, 0);
     HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, desc2, exp_rec, slots, d_results));
   }
@@ -1790,12 +1866,24 @@ int cabac_hip_write_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_su
   return CABAC_HIP_OK;
 }
 
+int cabac_hip_write_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,
+                                const uint32_t *d_values_in, const uint32_t *d_tile_first, uint32_t n_tu, const cabac_tu_desc *d_tu,
+                                const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes,
+                                uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_payload_offsets,
+                                cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info) {
+  return write_plan_device_impl(c, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, coeff_bytes,
+                                d_payload, payload_capacity, d_payload_offsets, d_results, d_values_out, d_tu_info, nullptr, nullptr);
+}
+
+// rows (may be null): the levels and the links, all in HOST memory here
 static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint32_t *plan,
                                  const uint32_t *values_in, uint64_t n_elements_total, const uint32_t *tile_first,
                                  const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard, const void *coeff,
                                  int coeff_bytes, uint64_t n_coeff_total, uint8_t *payload, uint64_t payload_capacity,
-                                 uint64_t *payload_offsets, cabac_substream_result *results, uint32_t *values_out, uint32_t *tu_info) {
-  if (!c || !payload_offsets || (n_sub && (!desc || !tile_first || !results || !payload)))
+                                 uint64_t *payload_offsets, cabac_substream_result *results, uint32_t *values_out, uint32_t *tu_info,
+                                 const PlanRows *rows = nullptr) {
+  if (!c || !payload_offsets || (n_sub && (!desc || !tile_first || !results || !payload)) ||
+      (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (n_sub == 0) {
@@ -1806,10 +1894,16 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (n_elements_total && (!plan || !values_in)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (int bad = check_plan_host(c, n_sub, desc, nullptr, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, n_coeff_total)) return bad;
+  if (rows) {
+    if (int bad = check_levels(c, n_sub, rows->n_level, rows->level_first)) return bad;
+    if (int bad = check_links_host(c, n_sub, rows->n_level, rows->level_first, rows->d_sync_from)) return bad;
+  }
   DeviceGuard g(c->device);
   int rc;
   if ((rc = pipe_init(c))) return rc;
   const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), at_bytes = size_t(n_tu) * sizeof(uint32_t);
+  const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
+  if (rows && ((rc = ensure(c, kRowsFrom, link_bytes)) || (rc = ensure(c, kRowsAt, link_bytes)))) return rc;
   const size_t plan_bytes = size_t(n_elements_total) * 2 * sizeof(uint32_t), value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
   if ((rc = ensure(c, kSpInDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
   if ((rc = ensure(c, kSpInFirst, first_bytes))) return rc;
@@ -1839,9 +1933,16 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   if ((rc = h2d(c, c->d_buf[kElemPlan], plan, plan_bytes, c->s_in))) return rc;
   if ((rc = h2d(c, d_values, values_in, value_bytes, c->s_in))) return rc;
   if ((rc = h2d(c, c->d_buf[kSpInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), c->s_in))) return rc;
+  PlanRows d_rows{};
+  if (rows) {
+    if ((rc = h2d(c, c->d_buf[kRowsFrom], rows->d_sync_from, link_bytes, c->s_in))) return rc;
+    if ((rc = h2d(c, c->d_buf[kRowsAt], rows->d_sync_at, link_bytes, c->s_in))) return rc;
+    d_rows = PlanRows{rows->n_level, rows->level_first, static_cast<const uint32_t *>(c->d_buf[kRowsFrom]),
+                      static_cast<const uint32_t *>(c->d_buf[kRowsAt])};
+  }
   HIP_TRY(c, hipEventRecord(c->ev_in[0], c->s_in));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in[0], 0));
-  rc = cabac_hip_write_plan_device(c, n_sub, static_cast<const cabac_substream_desc *>(c->d_buf[kSpInDesc]),
+  rc = write_plan_device_impl(c, n_sub, static_cast<const cabac_substream_desc *>(c->d_buf[kSpInDesc]),
                                    static_cast<const uint32_t *>(c->d_buf[kElemPlan]), d_values,
                                    static_cast<const uint32_t *>(c->d_buf[kSpInFirst]), n_tu,
                                    static_cast<const cabac_tu_desc *>(c->d_buf[kSpInTu]),
@@ -1849,7 +1950,7 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
                                    tu_guard ? static_cast<const uint32_t *>(c->d_buf[kElemGuard]) : nullptr, c->d_buf[kSpInCoeff],
                                    coeff_bytes, static_cast<uint8_t *>(c->d_buf[6]), payload_capacity, static_cast<uint64_t *>(c->d_buf[7]),
                                    static_cast<cabac_substream_result *>(c->d_buf[kSpOutRes]), values_out ? d_values : nullptr,
-                                   tu_info ? static_cast<uint32_t *>(c->d_buf[kSpOutInfo]) : nullptr);
+                                   tu_info ? static_cast<uint32_t *>(c->d_buf[kSpOutInfo]) : nullptr, nullptr, rows ? &d_rows : nullptr);
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(h_res, c->d_buf[kSpOutRes], res_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(h_off, c->d_buf[7], off_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2920,6 +3021,8 @@ int cabac_hip_search_log_encode_device(cabac_search_log *log, const cabac_substr
 // device slots: the slots of a WPP call (one set per substream), its prefix descriptors, its checked links and slot indices,
 // the results of its prefix passes, and the links of the host-pointer forms
 enum { kWppState = 64, kWppRate = 65, kWppDesc = 66, kWppIndex = 67, kWppRes = 68, kWppFrom = 69, kWppAt = 70 };
+static_assert(kRowsState == kWppState && kRowsRate == kWppRate && kRowsFrom == kWppFrom && kRowsAt == kWppAt,
+              "the plan rows share the WPP calls' slots and link staging");
 
 static bool sets_args_ok(uint32_t n_sub, uint32_t n_sets, const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
                          const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate) {
@@ -2988,6 +3091,20 @@ static int check_levels(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, cons
     if (level_first[l] > level_first[l + 1]) {
       char buf[96];
       snprintf(buf, sizeof buf, "level_first decreases at level %u", l + 1);
+      return fail(c, CABAC_HIP_ERR_INVALID, buf);
+    }
+  return CABAC_HIP_OK;
+}
+
+// the links of a host-pointer form (level_first checked): every link points into an earlier level
+static int check_links_host(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, const uint32_t *level_first, const uint32_t *sync_from) {
+  for (uint32_t l = 0; l < n_level; l++)
+    for (uint32_t s = level_first[l]; s < level_first[l + 1]; s++) {
+      const uint32_t from = sync_from[s];
+      if (from == CABAC_CTX_NO_SET || from < level_first[l]) continue;
+      char buf[128];
+      if (from >= n_sub) snprintf(buf, sizeof buf, "substream %u links to %u, beyond the batch", s, from);
+      else snprintf(buf, sizeof buf, "substream %u (level %u) links to %u in the same or a later level", s, l, from);
       return fail(c, CABAC_HIP_ERR_INVALID, buf);
     }
   return CABAC_HIP_OK;
@@ -3067,15 +3184,7 @@ static int wpp_batch_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const c
   int rc = check_desc_host(c, n_sub, desc, n_records_total, bytes_total);
   if (rc) return rc;
   if ((rc = check_levels(c, n_sub, n_level, level_first))) return rc;
-  for (uint32_t l = 0; l < n_level; l++)
-    for (uint32_t s = level_first[l]; s < level_first[l + 1]; s++) {
-      const uint32_t from = sync_from[s];
-      if (from == CABAC_CTX_NO_SET || from < level_first[l]) continue;
-      char buf[128];
-      if (from >= n_sub) snprintf(buf, sizeof buf, "substream %u links to %u, beyond the batch", s, from);
-      else snprintf(buf, sizeof buf, "substream %u (level %u) links to %u in the same or a later level", s, l, from);
-      return fail(c, CABAC_HIP_ERR_INVALID, buf);
-    }
+  if ((rc = check_links_host(c, n_sub, n_level, level_first, sync_from))) return rc;
   DeviceGuard g(c->device);
   if ((rc = pipe_init(c))) return rc;
   const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result);
@@ -3137,6 +3246,121 @@ int cabac_hip_decode_wpp_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
                                const uint32_t *sync_from, const uint32_t *sync_at) {
   return host_call_exit(c, wpp_batch_impl(c, true, n_sub, desc, records, n_records_total, const_cast<uint8_t *>(bytes), bytes_total, bins,
                                           results, n_level, level_first, sync_from, sync_at));
+}
+
+// ---- plan rows (cabac_hip_plan_rows.h): the plan parse and the plan write from and into context sets, and in WPP rows ----------
+int cabac_hip_plan_parse_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                     const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                     const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
+                                     uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results, uint32_t n_sets,
+                                     const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
+                                     const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate, const uint32_t *d_out_at) {
+  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results)) ||
+      !sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
+  Bracket br = bracket_for(c, 34);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  HIP_TRY(c, cabac::launch_plan_parse_sets(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
+                                           coeff_bytes, d_values, d_tu_info, d_results, sets, d_out_at, n_sets, 0xFFFFFFFFu));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+// The schedule of a rows parse on the ctx stream: for every non-empty level ONE launch of the sets kernel over that level's
+// substreams.  A substream starts from the slot of its link (checked on the device against the level: it must lie below the
+// level's first substream) and writes its own slot at its hand-over entry; the last level writes none.
+static int parse_rows_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                  const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                  const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes, uint32_t *d_values,
+                                  uint32_t *d_tu_info, cabac_substream_result *d_results, const PlanRows &rows) {
+  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results || !rows.d_sync_from || !rows.d_sync_at)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  int rc = check_levels(c, n_sub, rows.n_level, rows.level_first);
+  if (rc) return rc;
+  DeviceGuard g(c->device);
+  const size_t set_words = size_t(n_sub) * CABAC_NUM_CONTEXTS;
+  if ((rc = ensure(c, kRowsState, set_words * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kRowsRate, set_words))) return rc;
+  auto *slot_state = static_cast<uint32_t *>(c->d_buf[kRowsState]);
+  auto *slot_rate = static_cast<uint8_t *>(c->d_buf[kRowsRate]);
+  uint32_t last = rows.n_level;  // the last non-empty level
+  while (last > 0 && rows.level_first[last - 1] == rows.level_first[last]) last--;
+  c->timed = false;
+  for (uint32_t l = 0; l < last; l++) {
+    const uint32_t first = rows.level_first[l], n = rows.level_first[l + 1] - first;
+    if (n == 0) continue;
+    const bool hands_over = l + 1 < last;
+    const cabac::CtxSets sets{n_sub, slot_state, slot_rate, rows.d_sync_from + first, nullptr, slot_state, slot_rate};
+    Timed t(c, 35);
+    HIP_TRY(c, cabac::launch_plan_parse_sets(c->stream, n, d_desc + first, d_bytes, d_tile_first + first, d_tu, d_tu_at, d_tu_guard, d_plan,
+                                             d_coeff, coeff_bytes, d_values, d_tu_info, d_results + first, sets, rows.d_sync_at + first,
+                                             first, hands_over ? first : 0xFFFFFFFFu));
+  }
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_plan_parse_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                     const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                     const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
+                                     uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results, uint32_t n_level,
+                                     const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
+  return parse_rows_device_impl(c, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff, coeff_bytes, d_values,
+                                d_tu_info, d_results, PlanRows{n_level, level_first, d_sync_from, d_sync_at});
+}
+
+int cabac_hip_plan_parse_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                    uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                                    const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
+                                    int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
+                                    cabac_substream_result *results, uint32_t n_level, const uint32_t *level_first,
+                                    const uint32_t *sync_from, const uint32_t *sync_at) {
+  const PlanRows rows{n_level, level_first, sync_from, sync_at};
+  return parse_plan_batch_impl(c, n_sub, desc, bytes, bytes_total, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, coeff,
+                               coeff_bytes, n_coeff_total, values, tu_info, results, &rows);
+}
+
+int cabac_hip_plan_write_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,
+                                     const uint32_t *d_values_in, const uint32_t *d_tile_first, uint32_t n_tu, const cabac_tu_desc *d_tu,
+                                     const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes,
+                                     uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_payload_offsets,
+                                     cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info, uint32_t n_sets,
+                                     const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
+                                     const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate) {
+  if (!sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
+  return write_plan_device_impl(c, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, coeff_bytes,
+                                d_payload, payload_capacity, d_payload_offsets, d_results, d_values_out, d_tu_info, &sets, nullptr);
+}
+
+int cabac_hip_plan_write_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,
+                                     const uint32_t *d_values_in, const uint32_t *d_tile_first, uint32_t n_tu, const cabac_tu_desc *d_tu,
+                                     const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes,
+                                     uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_payload_offsets,
+                                     cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info, uint32_t n_level,
+                                     const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
+  const PlanRows rows{n_level, level_first, d_sync_from, d_sync_at};
+  return write_plan_device_impl(c, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, coeff_bytes,
+                                d_payload, payload_capacity, d_payload_offsets, d_results, d_values_out, d_tu_info, nullptr, &rows);
+}
+
+int cabac_hip_plan_write_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint32_t *plan,
+                                    const uint32_t *values_in, uint64_t n_elements_total, const uint32_t *tile_first,
+                                    const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard, const void *coeff,
+                                    int coeff_bytes, uint64_t n_coeff_total, uint8_t *payload, uint64_t payload_capacity,
+                                    uint64_t *payload_offsets, cabac_substream_result *results, uint32_t *values_out, uint32_t *tu_info,
+                                    uint32_t n_level, const uint32_t *level_first, const uint32_t *sync_from, const uint32_t *sync_at) {
+  const PlanRows rows{n_level, level_first, sync_from, sync_at};
+  return host_call_exit(c, write_plan_batch_impl(c, n_sub, desc, plan, values_in, n_elements_total, tile_first, tus, tu_at, tu_guard,
+                                                 coeff, coeff_bytes, n_coeff_total, payload, payload_capacity, payload_offsets, results,
+                                                 values_out, tu_info, &rows));
 }
 
 int cabac_hip_host_alloc(size_t bytes, void **out) {

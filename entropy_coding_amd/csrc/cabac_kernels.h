@@ -186,6 +186,14 @@ hipError_t launch_plan_parse(hipStream_t st, uint32_t n_sub, const cabac_substre
                              const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
                              const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
                              cabac_substream_result *results);
+// the plan walk from and into context sets (cabac_hip_plan_rows.h): substream s hands its contexts over when the walk arrives at
+// entry out_at[s] (out_at null: behind the substream).  A start index at or above start_bound is a bad one.  slot_base
+// 0xffffffff: the out sets are sets.out_set's; otherwise substream s writes set slot_base + s and sets.out_set is not read
+hipError_t launch_plan_parse_sets(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                  const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
+                                  const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
+                                  cabac_substream_result *results, const CtxSets &sets, const uint32_t *out_at, uint32_t start_bound,
+                                  uint32_t slot_base);
 
 // residual records spliced into host-recorded substreams (cabac_splice.hip); array sizes: pre n_splice + n_sub + 1,
 // sub_n / sub_cap / rec_base / byte_base n_sub, seen n_tu, err 1, totals 3 ({records, bytes, error})
@@ -226,7 +234,12 @@ hipError_t launch_plan_resolve(hipStream_t st, uint32_t n_sub, const PlanWriteIn
 hipError_t launch_plan_emit(hipStream_t st, uint32_t n_sub, const PlanWriteIn &in, const uint32_t *sub_n, const uint32_t *sub_cap,
                             const uint32_t *sub_flag, const uint64_t *rec_base, const uint64_t *byte_base,
                             cabac_substream_desc *desc_out, cabac_tu_desc *tus_out, uint64_t *tu_offset, uint16_t *records,
-                            uint32_t *values_out, uint32_t *tu_info_out);
+                            uint32_t *values_out, uint32_t *tu_info_out, const uint32_t *sync_entry = nullptr,
+                            uint32_t *sync_rec = nullptr);
+// sync_entry (the rows form; null: the plain walk): per substream the hand-over entry of its plan; sync_rec[s] then receives the
+// records of its expanded run in front of that entry
+// out_set_live[s] = out_set[s], or 0xffffffff for a stopped substream
+hipError_t launch_plan_out_sets(hipStream_t st, uint32_t n_sub, const uint32_t *sub_flag, const uint32_t *out_set, uint32_t *out_set_live);
 // a stopped substream codes nothing: results[s] = {0, sub_flag[s]} where sub_flag[s] != 0
 hipError_t launch_plan_stops(hipStream_t st, uint32_t n_sub, const uint32_t *sub_flag, cabac_substream_result *results);
 

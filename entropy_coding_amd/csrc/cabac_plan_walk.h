@@ -27,6 +27,12 @@
 //   emit_block(t, coded, base, off, excl, info) second walk, the lane of block t: `off` records of the unit in front of the run of
 //                                               blocks at this position, `excl` those of the coded blocks of the run in front of it
 //   records                                     second walk: the elements' bins go to records[base + their place in the run]
+// plan_walk<true, true> (the rows form of the plan write, cabac_hip_plan_rows.h) asks two things more of the Io:
+//   sync_at(k)                                  the unit's hand-over entry
+//   emit_sync(k, off)                           second walk, one lane: `off` records of the unit lie in front of that entry — the
+//                                               elements' bins and the records of the coded blocks at positions up to it (behind
+//                                               the run for an entry at or behind the end of the plan; 0 for a unit not walked)
+// With kSync false, the default, nothing of this is instantiated.
 #ifndef CABAC_PLAN_WALK_H
 #define CABAC_PLAN_WALK_H
 #include <hip/hip_runtime.h>
@@ -121,8 +127,9 @@ struct PlanWalkUnit {
   uint32_t n, t0, t1;   // entries; its blocks [t0, t1)
 };
 
-template <bool kEmit, class Io>
+template <bool kEmit, bool kSync = false, class Io>
 __device__ __forceinline__ void plan_walk(const Io &io) {
+  static_assert(kEmit || !kSync, "the hand-over index belongs to the second walk");
   __shared__ PwLds lds_all[kPwWaves];
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t unit = blockIdx.x * kPwWaves + wave;
@@ -131,7 +138,14 @@ __device__ __forceinline__ void plan_walk(const Io &io) {
   const PlanWalkUnit u = io.unit(unit);
   const uint32_t n = u.n, t0 = u.t0, t1 = u.t1;
   uint64_t base = 0;
-  if (kEmit && !io.emit_begin(unit, u, lane, base)) return;
+  if (kEmit && !io.emit_begin(unit, u, lane, base)) {
+    if constexpr (kSync) {
+      if (lane == 0u) io.emit_sync(unit, 0u);
+    }
+    return;
+  }
+  [[maybe_unused]] uint32_t sync_at = 0;
+  if constexpr (kSync) sync_at = min(io.sync_at(unit), n);
 
   uint32_t i = 0, t = t0, nb = 0;  // the next element, the next block, the blocks walked (all wave-uniform)
   uint64_t off = 0;                // records of the unit so far
@@ -247,6 +261,9 @@ __device__ __forceinline__ void plan_walk(const Io &io) {
     const uint32_t cnt = active ? se_decode(w0, v).n : 0u;
     uint32_t total;
     const uint32_t excl = wave_excl_scan(cnt, lane, &total);
+    if constexpr (kSync) {  // the hand-over entry lies in this stage: the blocks at its position have been taken in front of it
+      if (idx == sync_at && valid) io.emit_sync(unit, off + excl);
+    }
     if (kEmit) {
       if (u.vout && valid) u.vout[idx] = v;
       // by output position: bin o of the stage belongs to the last element whose offset is <= o
@@ -272,6 +289,9 @@ __device__ __forceinline__ void plan_walk(const Io &io) {
     i = e;
   }
   if (!kEmit && lane == 0u) io.count_end(unit, bad_rec, bad_val, off);
+  if constexpr (kSync) {
+    if (sync_at >= n && lane == 0u) io.emit_sync(unit, off);
+  }
 }
 
 }  // namespace

@@ -10,6 +10,8 @@
 //                         each coded block's destination, the filled values, the info words
 //   residual records pass over a descriptor list in which skipped blocks are ones the binariser rejects (they write nothing)
 //   encode kernel, plan_stops_kernel (a stopped substream codes nothing), assembly
+// The rows form (cabac_hip_plan_rows.h) runs plan_emit_rows_kernel in place of plan_emit_kernel: the same walk, which also notes
+// where in its expanded run each substream's hand-over entry lies; the WPP encode schedule takes that as its sync_at.
 //
 // The walk itself is cabac_plan_walk.h's, one wave per substream; this file says where a substream's plan lies and where its
 // results go (one atomicOr reports a substream that outgrows 32 bits).
@@ -97,6 +99,14 @@ struct PwIo {
   }
 };
 
+// the rows form (cabac_hip_plan_rows.h): the same unit, and the record index of its hand-over entry
+struct PwRowsIo : PwIo {
+  const uint32_t *sync_entry;  // per substream: the hand-over entry of its plan
+  uint32_t *sync_rec;          // per substream: the records of its expanded run in front of that entry
+  __device__ __forceinline__ uint32_t sync_at(uint32_t sub) const { return sync_entry[sub]; }
+  __device__ __forceinline__ void emit_sync(uint32_t sub, uint64_t off) const { sync_rec[sub] = (uint32_t)off; }
+};
+
 __device__ __forceinline__ PwIo pw_io(uint32_t n_sub, const PlanWriteIn &in, uint32_t *sub_n, uint32_t *sub_cap, uint32_t *sub_flag,
                                       uint32_t *err, const PwOut &out) {
   return PwIo{n_sub, in.desc, in.plan, in.values, in.tile_first, in.tus, in.tu_at, in.tu_guard, in.tu_n_records, in.tu_info,
@@ -113,6 +123,19 @@ __global__ __launch_bounds__(64 * kPwWaves) void plan_resolve_kernel(uint32_t n_
 
 __global__ __launch_bounds__(64 * kPwWaves) void plan_emit_kernel(uint32_t n_sub, PlanWriteIn in, PwOut out) {
   plan_walk<true>(pw_io(n_sub, in, nullptr, nullptr, nullptr, nullptr, out));
+}
+
+__global__ __launch_bounds__(64 * kPwWaves) void plan_emit_rows_kernel(uint32_t n_sub, PlanWriteIn in, PwOut out,
+                                                                        const uint32_t *__restrict__ sync_entry,
+                                                                        uint32_t *__restrict__ sync_rec) {
+  plan_walk<true, true>(PwRowsIo{pw_io(n_sub, in, nullptr, nullptr, nullptr, nullptr, out), sync_entry, sync_rec});
+}
+
+// the out sets of a plan write from sets: a stopped substream writes none
+__global__ __launch_bounds__(256) void plan_out_sets_kernel(uint32_t n_sub, const uint32_t *__restrict__ sub_flag,
+                                                            const uint32_t *__restrict__ out_set, uint32_t *__restrict__ out_set_live) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s < n_sub) out_set_live[s] = sub_flag[s] != 0u ? 0xffffffffu : out_set[s];
 }
 
 __global__ __launch_bounds__(256) void plan_stops_kernel(uint32_t n_sub, const uint32_t *__restrict__ sub_flag,
@@ -141,9 +164,16 @@ hipError_t launch_plan_resolve(hipStream_t st, uint32_t n_sub, const PlanWriteIn
 hipError_t launch_plan_emit(hipStream_t st, uint32_t n_sub, const PlanWriteIn &in, const uint32_t *sub_n, const uint32_t *sub_cap,
                             const uint32_t *sub_flag, const uint64_t *rec_base, const uint64_t *byte_base,
                             cabac_substream_desc *desc_out, cabac_tu_desc *tus_out, uint64_t *tu_offset, uint16_t *records,
-                            uint32_t *values_out, uint32_t *tu_info_out) {
+                            uint32_t *values_out, uint32_t *tu_info_out, const uint32_t *sync_entry, uint32_t *sync_rec) {
   const PwOut out{sub_n, sub_cap, sub_flag, rec_base, byte_base, desc_out, tus_out, tu_offset, records, values_out, tu_info_out};
-  if (n_sub) hipLaunchKernelGGL(plan_emit_kernel, dim3((n_sub + kPwWaves - 1u) / kPwWaves), dim3(64 * kPwWaves), 0, st, n_sub, in, out);
+  const dim3 grid((n_sub + kPwWaves - 1u) / kPwWaves), block(64 * kPwWaves);
+  if (n_sub && sync_entry) hipLaunchKernelGGL(plan_emit_rows_kernel, grid, block, 0, st, n_sub, in, out, sync_entry, sync_rec);
+  else if (n_sub) hipLaunchKernelGGL(plan_emit_kernel, grid, block, 0, st, n_sub, in, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_out_sets(hipStream_t st, uint32_t n_sub, const uint32_t *sub_flag, const uint32_t *out_set, uint32_t *out_set_live) {
+  if (n_sub) hipLaunchKernelGGL(plan_out_sets_kernel, dim3((n_sub + 255u) / 256u), dim3(256), 0, st, n_sub, sub_flag, out_set, out_set_live);
   return hipGetLastError();
 }
 

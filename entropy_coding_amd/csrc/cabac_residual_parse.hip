@@ -736,7 +736,54 @@ __device__ __forceinline__ void parse_ts(D &d, uint4 *ctx, int32_t *blk, const L
 // blocks walked.  Those words live in `inf` (LDS of the kernel, per wave: 16 info words, then the count of blocks walked,
 // skipped ones included), written where tu_info[t] is written, by every lane as the ring is, and read back the same way.  Both
 // kinds are wave-uniform scalar work in the element loop; everything else is the kSide == 2 walk, instruction for instruction.
-template <int W, class C, int kSide>
+//
+// Context sets (cabac_hip_plan_rows.h): the plan walk takes them the way the codec kernels do, as a trailing parameter PACK — empty
+// for every instantiation the plain entry points launch, whose signature, arguments and code are then the ones from before the
+// sets, and one ParseSets for the sets and rows calls.  Everything about sets is in the overloads below and behind
+// `if constexpr (kSets)` in the walk: the LOAD (the init loop reads the start set instead), the EXPORT (all 64 lanes store the
+// slots when the walk arrives at entry out_at, or behind the last block), and the bad index, checked once per substream.
+struct ParseSets {
+  CtxSets cs;
+  const uint32_t *out_at;  // per substream the entry at which its contexts are handed over (null: behind the substream)
+  uint32_t start_bound;    // a start index at or above it (other than "no set") is a bad one: n_sets, or the level's first row
+  uint32_t slot_base;      // 0xffffffff: out sets as cs.out_set says; otherwise substream s writes set slot_base + s (rows)
+};
+struct ParseSetUse {
+  const uint32_t *start;  // the start set's states (null: Ctx::init)
+  uint32_t *out_state;    // where the out set goes (null: nowhere)
+  uint8_t *out_rate;
+  uint32_t out_at;
+  bool bad;
+};
+__device__ __forceinline__ ParseSetUse parse_set_use(uint32_t, bool) { return ParseSetUse{nullptr, nullptr, nullptr, 0xffffffffu, false}; }
+__device__ __forceinline__ ParseSetUse parse_set_use(uint32_t sub, bool live, const ParseSets &ps) {
+  constexpr uint32_t kNone = 0xffffffffu;
+  const CtxSets &cs = ps.cs;
+  const uint32_t start = (live && cs.start_set != nullptr) ? cs.start_set[sub] : kNone;
+  const uint32_t out = !live ? kNone : ps.slot_base != kNone ? ps.slot_base + sub : cs.out_set != nullptr ? cs.out_set[sub] : kNone;
+  ParseSetUse u;
+  u.bad = (start != kNone && start >= ps.start_bound) || (out != kNone && out >= cs.n_sets);  // once per substream
+  u.start = (start != kNone && !u.bad) ? cs.state + (uint64_t)start * (uint64_t)kNumCtx : nullptr;
+  u.out_state = (out != kNone && !u.bad) ? cs.out_state + (uint64_t)out * (uint64_t)kNumCtx : nullptr;
+  u.out_rate = (out != kNone && !u.bad) ? cs.out_rate + (uint64_t)out * (uint64_t)kNumCtx : nullptr;
+  u.out_at = (live && ps.out_at != nullptr) ? ps.out_at[sub] : kNone;
+  return u;
+}
+// the contexts the wave holds now as its out set: all 379 states, and as rates the window sizes the slots carry (m_rate, what
+// cabac_hip_ctx_init_device writes).  Slot = ctxId here.
+__device__ __forceinline__ void parse_ctx_export(const uint4 *ctx, uint32_t lane, const ParseSetUse &u) {
+  if (u.out_state == nullptr) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (uint32_t k = lane; k < (uint32_t)kNumCtx; k += 64u) {
+    const uint4 e = ctx[k];
+    u.out_state[k] = e.x;
+    u.out_rate[k] = (uint8_t)(16u * (e.y & 0xffffu) + (e.y >> 16));
+  }
+}
+
+template <int W, class C, int kSide, class... Sets>
 __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
                                            const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ tile_first,
                                            const cabac_tu_desc *__restrict__ tus, C *__restrict__ coeff_all,
@@ -744,7 +791,9 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
                                            const uint32_t *__restrict__ tu_at, const uint16_t *__restrict__ records,
                                            uint8_t *__restrict__ side_bins, const uint32_t *__restrict__ tu_guard = nullptr,
                                            const uint32_t *__restrict__ plan = nullptr, uint32_t *__restrict__ values = nullptr,
-                                           uint32_t *ring = nullptr, uint32_t *inf = nullptr) {
+                                           uint32_t *ring = nullptr, uint32_t *inf = nullptr, Sets... sets) {
+  constexpr bool kSets = sizeof...(Sets) != 0;
+  static_assert(!kSets || kSide == 3, "only the plan walk takes sets");
   constexpr uint32_t kSlots = kSide ? kSideCtxSlots : kCtxSlots;
   __shared__ uint4 ctx_all[W * kSlots];
   __shared__ uint32_t side_park[kSide ? W : 1];  // the record cursor while a block is walked: out of the block walk's scalar registers
@@ -772,12 +821,19 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
   uint4 *ctx = ctx_all + wave * kSlots;
   int32_t *blk = blk_all + wave * kBlkWords;
   const cabac_substream_desc dsc = desc[live ? sub : 0];
+  [[maybe_unused]] const ParseSetUse su = parse_set_use(sub, live, sets...);
   {
     const int qp = dsc.qp < 0 ? 0 : (dsc.qp > 63 ? 63 : dsc.qp);
     const uint32_t iid = dsc.init_id & 3u;
     for (uint32_t k = lane; k < (kSide ? (uint32_t)CABAC_NUM_CONTEXTS : 230u); k += 64u) {
       const uint32_t id = kSide ? k : id_of_slot(k);
-      const uint32_t packed = ctx2_init(qp, c_init_tables[iid * kNumCtx + id], c_init_tables[3 * kNumCtx + id]);
+      uint32_t packed = ctx2_init(qp, c_init_tables[iid * kNumCtx + id], c_init_tables[3 * kNumCtx + id]);
+      if constexpr (kSets) {  // the state halves of the start set; the window sizes stay the init table's (they depend on the id alone)
+        if (su.start != nullptr) {
+          const uint32_t st = su.start[k];
+          packed = (st & kMask0) | (st & (kMask1 << 16)) | (packed & 31u);
+        }
+      }
       const uint32_t r0 = (packed & 3u) + 2u, r1 = ((packed >> 2) & 7u) + 5u;
       ctx[k] = make_uint4(packed & ~31u, r0 | (r1 << 16), ((0x7fffu >> r0) & kMask0) | (((0x7fffu >> r1) & kMask1) << 16), 0u);
     }
@@ -785,6 +841,17 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
   }
   __syncthreads();
   if (!live) return;
+  if constexpr (kSets) {
+    if (su.bad) {  // a start or out index beyond the sets: nothing is parsed, nothing is written but the result
+      if (lane == 0u) {
+        cabac_substream_result r;
+        r.n_bits = 0u;
+        r.flags = 0x40u;  // CABAC_RES_BAD_SET
+        results[sub] = r;
+      }
+      return;
+    }
+  }
 
   // every other wave SLOT of a SIMD keeps its decoder on the scalar pipe (pd_bin): whatever the placement, the waves that
   // share a SIMD split about evenly
@@ -822,6 +889,7 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
   // side walk: i = the next record of the run, n_rec its length; rec_cur / rec_nxt = records 64 * (i >> 6) + lane and the 64
   // behind them; bins_v = the bins of the current group, stored from record `stored` on
   const uint32_t n_rec = (kSide && !bad_start) ? dsc.n_records : 0u;
+  [[maybe_unused]] bool hand_over = kSets;  // the out set is still to be written
   uint32_t rec_i = 0, stored = 0, rec_cur = 0, rec_nxt = 0, bins_v = 0;
   auto load_records = [&](uint32_t group) {
     const uint32_t k = 64u * group + lane;
@@ -870,6 +938,12 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
       if (t < t_end && tu_at) upto = min(max(tu_at[t], rec_i), n_rec);
       uint32_t stop = 0;
       while (rec_i < upto) {
+        if constexpr (kSets) {
+          if (rec_i == su.out_at) {  // wave-uniform: the walk arrives at the hand-over entry, every block in front of it walked
+            parse_ctx_export(ctx, lane, su);
+            hand_over = false;
+          }
+        }
         pd_check(d);  // 32 look-ahead bits for the element's first step; the longer code words check again as they go
         const uint32_t w0 = rl(el_cur.x, rec_i & 63u), gw = rl(el_cur.y, rec_i & 63u);
         const uint32_t kind = w0 & 15u, p = w0 >> 4, id0 = p & 0x1ffu, idn = (p >> 9) & 0x1ffu;
@@ -1076,6 +1150,9 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
 #endif
     if (kSide) stored = rec_i = rfl(side_park[wave]);  // (the barriers of the write-out order the lanes' accesses)
   }
+  if constexpr (kSets) {
+    if (hand_over) parse_ctx_export(ctx, lane, su);  // out_at at or behind the end of the plan, or a stop in front of it
+  }
   PP_TICK(k1);
   PP_ADD(8, k0, k1);
 #ifdef CABAC_PARSE_PROFILE
@@ -1182,6 +1259,21 @@ __global__ __launch_bounds__(64 * W) void plan_parse_kernel(uint32_t n_sub, cons
                       ring_all + 256u * (threadIdx.x >> 6), info_all + 17u * (threadIdx.x >> 6));
 }
 
+// the plan walk from and into context sets (cabac_hip_plan_rows.h): the same geometry and LDS, one ParseSets more
+template <int W, class C>
+__global__ __launch_bounds__(64 * W) void plan_parse_sets_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+                                                                   const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ tile_first,
+                                                                   const cabac_tu_desc *__restrict__ tus, const uint32_t *__restrict__ tu_at,
+                                                                   const uint32_t *__restrict__ tu_guard, const uint32_t *__restrict__ plan,
+                                                                   C *__restrict__ coeff_all, uint32_t *__restrict__ values,
+                                                                   uint32_t *__restrict__ tu_info, cabac_substream_result *__restrict__ results,
+                                                                   ParseSets ps) {
+  __shared__ uint32_t ring_all[W * 256];
+  __shared__ uint32_t info_all[W * 17];
+  parse_walk<W, C, 3>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, tu_at, nullptr, nullptr, tu_guard, plan, values,
+                      ring_all + 256u * (threadIdx.x >> 6), info_all + 17u * (threadIdx.x >> 6), ps);
+}
+
 #ifdef CABAC_PARSE_PROFILE
 hipError_t debug_read_parse_waves(unsigned long long *out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_parse_wave), sizeof(unsigned long long) * 3 * 8192);
@@ -1286,6 +1378,35 @@ hipError_t launch_plan_parse(hipStream_t st, uint32_t n_sub, const cabac_substre
     return launch_plan_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results);
   if (coeff_bytes == 4)
     return launch_plan_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results);
+  return hipErrorInvalidValue;
+}
+
+template <class C>
+static hipError_t launch_plan_parse_sets_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                            const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                                            const uint32_t *tu_guard, const uint32_t *plan, C *coeff, uint32_t *values, uint32_t *tu_info,
+                                            cabac_substream_result *results, const ParseSets &ps) {
+  // the parser's geometry and threshold
+  if (n_sub >= 1024u)
+    hipLaunchKernelGGL((plan_parse_sets_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus,
+                       tu_at, tu_guard, plan, coeff, values, tu_info, results, ps);
+  else
+    hipLaunchKernelGGL((plan_parse_sets_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at,
+                       tu_guard, plan, coeff, values, tu_info, results, ps);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_parse_sets(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                  const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
+                                  const uint32_t *plan, void *coeff, int coeff_bytes, uint32_t *values, uint32_t *tu_info,
+                                  cabac_substream_result *results, const CtxSets &sets, const uint32_t *out_at, uint32_t start_bound,
+                                  uint32_t slot_base) {
+  if (n_sub == 0) return hipSuccess;
+  const ParseSets ps{sets, out_at, start_bound, slot_base};
+  if (coeff_bytes == 2)
+    return launch_plan_parse_sets_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results, ps);
+  if (coeff_bytes == 4)
+    return launch_plan_parse_sets_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results, ps);
   return hipErrorInvalidValue;
 }
 
