@@ -98,6 +98,12 @@ EXPORTS_PLAN_ROWS = [
     "cabac_hip_plan_parse_sets_device", "cabac_hip_plan_parse_rows_device", "cabac_hip_plan_parse_rows_batch",
     "cabac_hip_plan_write_sets_device", "cabac_hip_plan_write_rows_device", "cabac_hip_plan_write_rows_batch",
 ]
+# include/cabac_hip_splice_rows.h (the splice pipeline and the winner log's emit from and into sets, and in WPP rows;
+# tests/test_splice_rows_abi.py compares)
+EXPORTS_SPLICE_ROWS = [
+    "cabac_hip_encode_residual_sets_device", "cabac_hip_encode_residual_rows_device", "cabac_hip_encode_residual_rows_batch",
+    "cabac_hip_search_log_mark_device", "cabac_hip_search_log_encode_sets_device", "cabac_hip_search_log_encode_rows_device",
+]
 CTX_NO_SET = 0xFFFFFFFF                                          # CABAC_CTX_NO_SET
 RES_BAD_SET = 0x40                                               # CABAC_RES_BAD_SET
 PE_COND, PE_BLOCK_INFO = 9, 10                                   # CABAC_PE_COND, CABAC_PE_BLOCK_INFO
@@ -343,6 +349,19 @@ def load_library():
     L.cabac_hip_search_log_append_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_int, vp, vp, vp]
     L.cabac_hip_search_log_view.argtypes = [vp, ctypes.POINTER(SearchLogView)]
     L.cabac_hip_search_log_encode_device.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp]
+    # (CABAC_HIP_LIBRARY may name a build from before cabac_hip_splice_rows.h)
+    if hasattr(L, "cabac_hip_encode_residual_sets_device"):
+        rows5 = [ctypes.c_uint32, vp, vp, vp, vp]   # n_level, level_first, sync_from, sync_at, sync_splice
+        plain = L.cabac_hip_encode_residual_device.argtypes
+        plain = plain[:10] + [ctypes.c_int] + plain[10:]                     # const void *d_coeff, int coeff_bytes
+        plain_b = L.cabac_hip_encode_batch_residual.argtypes
+        plain_b = plain_b[:10] + [ctypes.c_int] + plain_b[10:]
+        L.cabac_hip_encode_residual_sets_device.argtypes = plain + sets7
+        L.cabac_hip_encode_residual_rows_device.argtypes = plain + rows5
+        L.cabac_hip_encode_residual_rows_batch.argtypes = plain_b + rows5
+        L.cabac_hip_search_log_mark_device.argtypes = [vp, ctypes.c_uint32, vp]
+        L.cabac_hip_search_log_encode_sets_device.argtypes = L.cabac_hip_search_log_encode_device.argtypes + sets7
+        L.cabac_hip_search_log_encode_rows_device.argtypes = L.cabac_hip_search_log_encode_device.argtypes + [ctypes.c_uint32, vp, vp]
     L.cabac_hip_nal_escape_bound.restype = ctypes.c_size_t
     L.cabac_hip_nal_escape_bound.argtypes = [ctypes.c_uint64]
     L.cabac_hip_nal_escape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
@@ -495,7 +514,8 @@ class CabacHip:
         cabac_hip_parse_elements.h; 27 plan parse in cabac_hip_parse_plan.h; 28 plan write in cabac_hip_write_plan.h; 29 plan resolve in
         cabac_hip_search_plan.h; 30 encode with sets, 31 decode with sets, 32 context advance and 33 a WPP prefix pass in
         cabac_hip_ctx_sets.h; 34 plan parse with sets, 35 a level of a rows parse and 36 the encode launch of a plan write with sets
-        in cabac_hip_plan_rows.h)."""
+        in cabac_hip_plan_rows.h; 37 hand-over index, 38 log mark and 39 the encode launch of a spliced call with sets in
+        cabac_hip_splice_rows.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -1237,6 +1257,62 @@ class CabacHip:
             out.append(counts[:n])
         return tuple(out)
 
+    # ---- the splice pipeline from and into context sets, and in WPP rows (include/cabac_hip_splice_rows.h) ------
+    def encode_residual_sets_device(self, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff,
+                                    d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info=0, d_bin_counts=0, int16=False,
+                                    n_sets=0, d_state=0, d_rate=0, d_start_set=0, d_out_set=0, d_out_state=0, d_out_rate=0):
+        """encode_residual_device with substream s coded from set d_start_set[s] and the contexts after the last record of its
+        expanded string written as set d_out_set[s]."""
+        opt = lambda p: vp(p) if p else None
+        self._check(self.L.cabac_hip_encode_residual_sets_device(
+            self.h, n_sub, opt(d_desc), opt(d_records), opt(d_splice_first), opt(d_splices), n_splice, n_tu, opt(d_tu), opt(d_coeff),
+            2 if int16 else 4, opt(d_payload), payload_capacity, vp(d_payload_offsets), opt(d_results), opt(d_tu_info),
+            opt(d_bin_counts), *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate)))
+
+    def encode_residual_rows_device(self, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff,
+                                    d_payload, payload_capacity, d_payload_offsets, d_results, level_first, d_sync_from, d_sync_at,
+                                    d_sync_splice=0, d_tu_info=0, d_bin_counts=0, int16=False):
+        """encode_residual_device over WPP rows in level order; level_first: HOST, n_level + 1 entries; (d_sync_at, d_sync_splice):
+        the hand-over pair of every substream (d_sync_splice 0: every block at the position goes in front)."""
+        opt = lambda p: vp(p) if p else None
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        self._check(self.L.cabac_hip_encode_residual_rows_device(
+            self.h, n_sub, opt(d_desc), opt(d_records), opt(d_splice_first), opt(d_splices), n_splice, n_tu, opt(d_tu), opt(d_coeff),
+            2 if int16 else 4, opt(d_payload), payload_capacity, vp(d_payload_offsets), opt(d_results), opt(d_tu_info),
+            opt(d_bin_counts), len(lf) - 1, lf.ctypes.data, opt(d_sync_from), opt(d_sync_at), opt(d_sync_splice)))
+
+    def encode_residual_rows_batch(self, desc, records, splice_first, splices, tus, coeff, payload, level_first, sync_from, sync_at,
+                                   sync_splice=None, check=True, offsets=None, results=None, info=None, counts=None):
+        """Host arrays through cabac_hip_encode_residual_rows_batch (synchronous): (offsets uint64[n + 1], results, tu_info, counts).
+        offsets / results / info / counts: the caller's arrays (else fresh ones).  A sync_from, sync_at or sync_splice shorter than
+        the batch is refused here as the library refuses a bad link: CabacHipError(-2), nothing run, no output touched."""
+        narrow = isinstance(coeff, np.ndarray) and coeff.dtype == np.int16
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        records = np.ascontiguousarray(records, np.uint16)
+        splice_first = np.ascontiguousarray(splice_first, np.uint32)
+        splices = np.ascontiguousarray(splices, SPLICE_DTYPE)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        coeff = np.ascontiguousarray(coeff, np.int16 if narrow else np.int32)
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        sf, sa = np.ascontiguousarray(sync_from, np.uint32), np.ascontiguousarray(sync_at, np.uint32)
+        ss = None if sync_splice is None else np.ascontiguousarray(sync_splice, np.uint32)
+        n = len(desc)
+        for name, a in (("sync_from", sf), ("sync_at", sa), ("sync_splice", ss)):
+            if a is not None and len(a) < n:
+                raise CabacHipError(-2, "%s is shorter than the batch: substream %d has none" % (name, len(a)))
+        assert len(splice_first) == n + 1 and payload.dtype == np.uint8
+        offsets = np.zeros(n + 1, np.uint64) if offsets is None else offsets
+        res = np.zeros(max(n, 1), RESULT_DTYPE) if results is None else results
+        info = np.zeros(max(len(tus), 1), np.uint32) if info is None else info
+        counts = np.zeros((max(n, 1), BIN_COUNT_WORDS), np.uint32) if counts is None else counts
+        rc = self.L.cabac_hip_encode_residual_rows_batch(
+            self.h, n, desc.ctypes.data, records.ctypes.data, len(records), splice_first.ctypes.data, splices.ctypes.data, len(tus),
+            tus.ctypes.data, coeff.ctypes.data, 2 if narrow else 4, len(coeff), payload.ctypes.data, payload.nbytes,
+            offsets.ctypes.data, res.ctypes.data, info.ctypes.data, counts.ctypes.data, len(lf) - 1, lf.ctypes.data, sf.ctypes.data,
+            sa.ctypes.data, ss.ctypes.data if ss is not None else None)
+        self._check(rc, allow_substream=not check)
+        return offsets, res[:n], info[: len(tus)], counts[:n]
+
     def assemble_device(self, n_sub, d_desc, d_results, d_bytes, d_payload, payload_capacity, d_offsets):
         self._check(self.L.cabac_hip_assemble_device(self.h, n_sub, vp(d_desc), vp(d_results), vp(d_bytes), vp(d_payload),
                                                      payload_capacity, vp(d_offsets)))
@@ -1401,3 +1477,28 @@ class SearchLog:
         self.hip._check(self.L.cabac_hip_search_log_encode_device(
             self.h, vp(d_desc), vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results),
             vp(d_tu_info) if d_tu_info else None, vp(d_bin_counts) if d_bin_counts else None))
+
+    # ---- marks, and the emit from sets and in rows (include/cabac_hip_splice_rows.h) ------
+    def search_log_mark_device(self, n, d_chain):
+        """cabac_hip_search_log_mark_device (asynchronous): the present cursors of the n listed chains become their hand-over
+        points; a later mark replaces an earlier one, reset() clears them all."""
+        self.hip._check(self.L.cabac_hip_search_log_mark_device(self.h, n, vp(d_chain) if d_chain else None))
+
+    def search_log_encode_sets_device(self, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info=0,
+                                      d_bin_counts=0, n_sets=0, d_state=0, d_rate=0, d_start_set=0, d_out_set=0, d_out_state=0,
+                                      d_out_rate=0):
+        """encode_device with chain k coded from set d_start_set[k] and its final contexts written as set d_out_set[k]."""
+        opt = lambda p: vp(p) if p else None
+        self.hip._check(self.L.cabac_hip_search_log_encode_sets_device(
+            self.h, vp(d_desc), vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), opt(d_tu_info), opt(d_bin_counts),
+            *CabacHip._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate)))
+
+    def search_log_encode_rows_device(self, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, level_first, d_sync_from,
+                                      d_tu_info=0, d_bin_counts=0):
+        """encode_device over WPP rows: the chains in level order (level_first: HOST, n_level + 1 entries), chain k coded from the
+        contexts chain d_sync_from[k] holds at its mark."""
+        opt = lambda p: vp(p) if p else None
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        self.hip._check(self.L.cabac_hip_search_log_encode_rows_device(
+            self.h, vp(d_desc), vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), opt(d_tu_info), opt(d_bin_counts),
+            len(lf) - 1, lf.ctypes.data, opt(d_sync_from)))

@@ -28,6 +28,7 @@
 #include "cabac_hip_search_emit.h"
 #include "cabac_hip_search_plan.h"
 #include "cabac_hip_search_unit.h"
+#include "cabac_hip_splice_rows.h"
 #include "cabac_hip_write_plan.h"
 #include "cabac_kernels.h"
 #include "cabac_nal_kernels.h"
@@ -56,8 +57,9 @@ struct cabac_hip_ctx {
   // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
   // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included); [48..]: the winner log (kLog* below); [53..]: the
   // unit parse (kUnit* below); [56..]: the element parse (kElem* below); [59..]: the plan write (kPw* below); [61..]: the plan
-  // resolve of the search rounds (kPs* below); [64..]: the WPP calls (kWpp* below); [71]: the plan rows (kRowsWords below)
-  static constexpr int kSlots = 72;
+  // resolve of the search rounds (kPs* below); [64..]: the WPP calls (kWpp* below); [71]: the plan rows and the spliced rows
+  // (kRowsWords below); [72]: the spliced rows' host-pointer form (kSpInSync below)
+  static constexpr int kSlots = 73;
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -1546,7 +1548,9 @@ namespace {
 enum { kSpCnt = 8, kSpPlan = 9, kSpDesc = 10, kSpTuOff = 11, kSpRec = 12, kSpBytes = 13, kSpFlag = 14,
        // ... and the staging of its host-pointer form
        kSpInDesc = 15, kSpInRec = 16, kSpInFirst = 17, kSpInSplice = 18, kSpInTu = 19, kSpInCoeff = 20, kSpOutRes = 21,
-       kSpOutInfo = 22, kSpOutCnt = 23 };
+       kSpOutInfo = 22, kSpOutCnt = 23,
+       // ... and the hand-over splice counts of its rows form (cabac_hip_splice_rows.h)
+       kSpInSync = 72 };
 
 struct Timed {  // profile-ring bracket around a group of launches (nothing when the ring is off or full)
   cabac_hip_ctx *c;
@@ -1563,17 +1567,40 @@ struct Timed {  // profile-ring bracket around a group of launches (nothing when
 };
 }  // namespace
 
+namespace {
+// the rows of a call of cabac_hip_splice_rows.h: levels (HOST memory), links and hand-over pairs (device memory; d_sync_splice may be
+// null: every block at the hand-over position goes in front)
+struct SpliceRows {
+  uint32_t n_level;
+  const uint32_t *level_first, *d_sync_from, *d_sync_at, *d_sync_splice;
+};
+}  // namespace
+
+static int wpp_device_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                           uint8_t *d_bytes, uint8_t *d_bins, cabac_substream_result *d_results, uint32_t n_level,
+                           const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at);
+
+// sets (may be null): the encode launch starts from and writes context sets; rows (may be null): every substream's hand-over pair
+// becomes an index into its expanded string and the WPP encode schedule takes the encode launch's place.  Not both.  The plain
+// calls pass neither.
 static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
                                        const uint32_t *d_splice_first, const cabac_splice *d_splices, uint32_t n_splice, uint32_t n_tu,
                                        const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes, uint8_t *d_payload,
                                        uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
-                                       uint32_t *d_tu_info, uint32_t *d_bin_counts) {
+                                       uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets = nullptr,
+                                       const SpliceRows *rows = nullptr) {
   if (!c || !d_payload_offsets || (n_sub && (!d_desc || !d_records || !d_splice_first || !d_payload || !d_results)) ||
       (n_splice && !d_splices) || (n_tu && (!d_tu || !d_coeff)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (n_splice != n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "every block must be spliced exactly once (n_splice != n_tu)");
+  if (rows && n_sub) {
+    if (!rows->d_sync_from || !rows->d_sync_at) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+    if (int bad = check_levels(c, n_sub, rows->n_level, rows->level_first)) return bad;
+  }
   DeviceGuard g(c->device);
   int rc;
+  if (rows && (rc = ensure(c, kRowsWords, size_t(n_sub ? n_sub : 1) * sizeof(uint32_t)))) return rc;
   const size_t n_pre = size_t(n_splice) + n_sub + 1;
   const size_t plan32 = n_pre + 2 * size_t(n_sub) + size_t(n_tu ? n_tu : 1) + 2;  // pre, sub_n, sub_cap, seen, err (+ pad)
   const size_t plan32_pad = (plan32 + 1) & ~size_t(1);
@@ -1618,7 +1645,21 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
     HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[5],
                                       /*order_ready=*/true));  // the block order of the sizes pass above: same tus[], same scratch
   }
-  {
+  if (rows) {  // the hand-over indices, the context-advance prefix passes per level, then one encode launch from the slots
+    uint32_t *sync_rec = static_cast<uint32_t *>(c->d_buf[kRowsWords]);
+    {
+      Timed t(c, 37);
+      HIP_TRY(c, cabac::launch_splice_sync_index(c->stream, n_sub, d_desc, d_splice_first, d_splices, pre, rows->d_sync_at,
+                                                 rows->d_sync_splice, sync_rec));
+    }
+    if (n_sub && (rc = wpp_device_impl(c, false, n_sub, desc2, exp_rec, slots, nullptr, d_results, rows->n_level, rows->level_first,
+                                       rows->d_sync_from, sync_rec)))
+      return rc;
+    c->timed = false;
+  } else if (sets) {
+    Timed t(c, 39);
+    HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, desc2, exp_rec, slots, d_results, 0, sets));
+  } else {
     Timed t(c, 0);
     HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, desc2, exp_rec, slots, d_results));
   }
@@ -1656,10 +1697,28 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
                                       uint64_t n_records_total, const uint32_t *splice_first, const cabac_splice *splices, uint32_t n_tu,
                                       const cabac_tu_desc *tus, const void *coeff, int coeff_bytes, uint64_t n_coeff_total, uint8_t *payload,
                                       uint64_t payload_capacity, uint64_t *payload_offsets, cabac_substream_result *results,
-                                      uint32_t *tu_info, uint32_t *bin_counts) {
-  if (!c || !payload_offsets || (n_sub && (!desc || !splice_first || !results || !payload)) || (n_tu && (!tus || !coeff || !splices)))
+                                      uint32_t *tu_info, uint32_t *bin_counts, const SpliceRows *rows = nullptr) {
+  if (!c || !payload_offsets || (n_sub && (!desc || !splice_first || !results || !payload)) || (n_tu && (!tus || !coeff || !splices)) ||
+      (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  payload_offsets[0] = 0;
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (rows && n_sub) {  // refused before anything is touched, payload_offsets[0] included
+    if (int bad = check_levels(c, n_sub, rows->n_level, rows->level_first)) return bad;
+    if (int bad = check_links_host(c, n_sub, rows->n_level, rows->level_first, rows->d_sync_from)) return bad;
+    for (uint32_t s = 0; s < n_sub; s++) {
+      const char *what = nullptr;
+      if (desc[s].rec_offset > n_records_total || desc[s].n_records > n_records_total - desc[s].rec_offset) what = "records out of range";
+      else if ((desc[s].init_id & 3u) > 2u) what = "init_id must be 0..2";
+      else if (splice_first[s] > splice_first[s + 1]) what = "splice_first must not decrease";
+      if (what) {
+        char buf[96];
+        snprintf(buf, sizeof buf, "substream %u: %s", s, what);
+        return fail(c, CABAC_HIP_ERR_INVALID, buf);
+      }
+    }
+    if (splice_first[0] != 0 || splice_first[n_sub] != n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "every block must be spliced exactly once");
+  }
+  if (!rows || n_sub == 0) payload_offsets[0] = 0;  // (the rows form writes no output before it has run)
   if (n_sub == 0) return n_tu ? fail(c, CABAC_HIP_ERR_INVALID, "blocks without a substream") : CABAC_HIP_OK;
   for (uint32_t s = 0; s < n_sub; s++) {
     if (desc[s].rec_offset > n_records_total || desc[s].n_records > n_records_total - desc[s].rec_offset)
@@ -1685,6 +1744,9 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if ((rc = ensure(c, 6, payload_capacity ? payload_capacity : 16))) return rc;
   if ((rc = ensure(c, 7, (size_t(n_sub) + 1) * sizeof(uint64_t)))) return rc;
   if ((rc = ensure(c, kSpFlag, 64))) return rc;
+  const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
+  if (rows && ((rc = ensure(c, kRowsFrom, link_bytes)) || (rc = ensure(c, kRowsAt, link_bytes)) || (rc = ensure(c, kSpInSync, link_bytes))))
+    return rc;
   const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result), off_bytes = (size_t(n_sub) + 1) * sizeof(uint64_t);
   if ((rc = ensure_pinned(c, 0, res_bytes + off_bytes + 64))) return rc;
   auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
@@ -1706,6 +1768,15 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if ((rc = h2d(c, c->d_buf[kSpInSplice], splices, size_t(n_splice) * sizeof(cabac_splice), c->s_in))) return rc;
   if ((rc = h2d(c, c->d_buf[kSpInRec], records, n_records_total * sizeof(uint16_t), c->s_in))) return rc;
   if ((rc = h2d(c, c->d_buf[kSpInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), c->s_in))) return rc;
+  SpliceRows d_rows{};
+  if (rows) {
+    if ((rc = h2d(c, c->d_buf[kRowsFrom], rows->d_sync_from, link_bytes, c->s_in))) return rc;
+    if ((rc = h2d(c, c->d_buf[kRowsAt], rows->d_sync_at, link_bytes, c->s_in))) return rc;
+    if (rows->d_sync_splice && (rc = h2d(c, c->d_buf[kSpInSync], rows->d_sync_splice, link_bytes, c->s_in))) return rc;
+    d_rows = SpliceRows{rows->n_level, rows->level_first, static_cast<const uint32_t *>(c->d_buf[kRowsFrom]),
+                        static_cast<const uint32_t *>(c->d_buf[kRowsAt]),
+                        rows->d_sync_splice ? static_cast<const uint32_t *>(c->d_buf[kSpInSync]) : nullptr};
+  }
   HIP_TRY(c, hipEventRecord(c->ev_in[1], c->s_in));
   HIP_TRY(c, hipEventSynchronize(c->ev_k[0]));
   if (*h_flag) return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
@@ -1716,7 +1787,8 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
                                         static_cast<const cabac_tu_desc *>(c->d_buf[kSpInTu]), c->d_buf[kSpInCoeff], coeff_bytes,
                                         static_cast<uint8_t *>(c->d_buf[6]), payload_capacity, static_cast<uint64_t *>(c->d_buf[7]),
                                         static_cast<cabac_substream_result *>(c->d_buf[kSpOutRes]), static_cast<uint32_t *>(c->d_buf[kSpOutInfo]),
-                                        bin_counts ? static_cast<uint32_t *>(c->d_buf[kSpOutCnt]) : nullptr);
+                                        bin_counts ? static_cast<uint32_t *>(c->d_buf[kSpOutCnt]) : nullptr, nullptr,
+                                        rows ? &d_rows : nullptr);
   if (rc) return rc;
   HIP_TRY(c, cabac::launch_tu_info_any(c->stream, n_tu, static_cast<const uint32_t *>(c->d_buf[kSpOutInfo]), d_flag + 1));
   HIP_TRY(c, hipMemcpyAsync(h_res, c->d_buf[kSpOutRes], res_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1733,6 +1805,7 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if ((rc = d2h_drain(c))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->s_out));
   int status = *h_flag ? CABAC_HIP_ERR_SUBSTREAM : CABAC_HIP_OK;
+  payload_offsets[0] = 0;
   for (uint32_t s = 0; s < n_sub; s++) {
     results[s] = h_res[s];
     payload_offsets[s + 1] = h_off[s + 1];
@@ -2878,7 +2951,8 @@ namespace {
 enum { kLogScratch = 48, kLogDesc = 49, kLogFirst = 50, kLogRec = 51, kLogSplice = 52 };
 
 void log_free(cabac_search_log *log) {
-  void *p[] = {log->a.counters, log->a.entries, log->a.records, log->a.tu, log->a.tu_at, log->a.coeff, log->a.chain_rec, log->a.chain_tu};
+  void *p[] = {log->a.counters, log->a.entries, log->a.records, log->a.tu, log->a.tu_at, log->a.coeff, log->a.chain_rec, log->a.chain_tu,
+               log->a.mark_rec, log->a.mark_tu};
   for (void *q : p)
     if (q) (void)hipFree(q);
   delete log;
@@ -2907,7 +2981,8 @@ int cabac_hip_search_log_create(cabac_hip_ctx *c, uint32_t n_chain, uint32_t ent
   if (!alloc(&a.counters, sizeof(cabac_search_log_counters)) || !alloc(&a.entries, size_t(entry_capacity) * sizeof(cabac_search_log_entry)) ||
       !alloc(&a.records, record_capacity * sizeof(uint16_t)) || !alloc(&a.tu, size_t(tu_capacity) * sizeof(cabac_tu_desc)) ||
       !alloc(&a.tu_at, size_t(tu_capacity) * sizeof(uint32_t)) || !alloc(&a.coeff, coeff_capacity * size_t(coeff_bytes)) ||
-      !alloc(&a.chain_rec, size_t(n_chain) * sizeof(uint32_t)) || !alloc(&a.chain_tu, size_t(n_chain) * sizeof(uint32_t))) {
+      !alloc(&a.chain_rec, size_t(n_chain) * sizeof(uint32_t)) || !alloc(&a.chain_tu, size_t(n_chain) * sizeof(uint32_t)) ||
+      !alloc(&a.mark_rec, size_t(n_chain) * sizeof(uint32_t)) || !alloc(&a.mark_tu, size_t(n_chain) * sizeof(uint32_t))) {
     (void)hipGetLastError();
     log_free(log);
     return fail(c, CABAC_HIP_ERR_NOMEM, "hipMalloc failed");
@@ -2975,9 +3050,11 @@ int cabac_hip_search_log_view(const cabac_search_log *log, cabac_search_log_view
   return CABAC_HIP_OK;
 }
 
-int cabac_hip_search_log_encode_device(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
-                                       uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
-                                       uint32_t *d_tu_info, uint32_t *d_bin_counts) {
+// sets / rows (may be null, not both): handed on to the spliced encode; a rows call takes the chains' marks as the hand-over pairs
+// (its d_sync_at and d_sync_splice are not read)
+static int search_log_encode_impl(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
+                                  uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
+                                  uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets, const SpliceRows *rows) {
   if (!log) return CABAC_HIP_ERR_INVALID;
   cabac_hip_ctx *c = log->ctx;
   if (!d_desc || !d_payload || !d_payload_offsets || !d_results) return fail(c, CABAC_HIP_ERR_INVALID, "null");
@@ -3013,8 +3090,18 @@ int cabac_hip_search_log_encode_device(cabac_search_log *log, const cabac_substr
     Timed t(c, 24);
     HIP_TRY(c, cabac::launch_search_log_place(c->stream, a, d_desc, n_entry, cnt.n_record, n_tu, desc2, first, rec, splices));
   }
+  SpliceRows marked{};
+  if (rows) marked = SpliceRows{rows->n_level, rows->level_first, rows->d_sync_from, a.mark_rec, a.mark_tu};
   return encode_residual_device_impl(c, a.n_chain, desc2, rec, first, splices, n_tu, n_tu, a.tu, a.coeff, log->coeff_bytes, d_payload,
-                                     payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts);
+                                     payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, sets,
+                                     rows ? &marked : nullptr);
+}
+
+int cabac_hip_search_log_encode_device(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
+                                       uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
+                                       uint32_t *d_tu_info, uint32_t *d_bin_counts) {
+  return search_log_encode_impl(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr,
+                                nullptr);
 }
 
 // ---- context sets and WPP (cabac_hip_ctx_sets.h) -------------------------------------------------------------------
@@ -3361,6 +3448,82 @@ int cabac_hip_plan_write_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const caba
   return host_call_exit(c, write_plan_batch_impl(c, n_sub, desc, plan, values_in, n_elements_total, tile_first, tus, tu_at, tu_guard,
                                                  coeff, coeff_bytes, n_coeff_total, payload, payload_capacity, payload_offsets, results,
                                                  values_out, tu_info, &rows));
+}
+
+// ---- spliced rows (cabac_hip_splice_rows.h): the splice pipeline and the winner log's emit from and into sets, and in WPP rows ----
+int cabac_hip_encode_residual_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                          const uint32_t *d_splice_first, const cabac_splice *d_splices, uint32_t n_splice, uint32_t n_tu,
+                                          const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes, uint8_t *d_payload,
+                                          uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
+                                          uint32_t *d_tu_info, uint32_t *d_bin_counts, uint32_t n_sets, const uint32_t *d_state,
+                                          const uint8_t *d_rate, const uint32_t *d_start_set, const uint32_t *d_out_set,
+                                          uint32_t *d_out_state, uint8_t *d_out_rate) {
+  if (!sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
+  return encode_residual_device_impl(c, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes,
+                                     d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, &sets, nullptr);
+}
+
+int cabac_hip_encode_residual_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                          const uint32_t *d_splice_first, const cabac_splice *d_splices, uint32_t n_splice, uint32_t n_tu,
+                                          const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes, uint8_t *d_payload,
+                                          uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
+                                          uint32_t *d_tu_info, uint32_t *d_bin_counts, uint32_t n_level, const uint32_t *level_first,
+                                          const uint32_t *d_sync_from, const uint32_t *d_sync_at, const uint32_t *d_sync_splice) {
+  const SpliceRows rows{n_level, level_first, d_sync_from, d_sync_at, d_sync_splice};
+  return encode_residual_device_impl(c, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes,
+                                     d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr, &rows);
+}
+
+int cabac_hip_encode_residual_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                         uint64_t n_records_total, const uint32_t *splice_first, const cabac_splice *splices, uint32_t n_tu,
+                                         const cabac_tu_desc *tus, const void *coeff, int coeff_bytes, uint64_t n_coeff_total,
+                                         uint8_t *payload, uint64_t payload_capacity, uint64_t *payload_offsets,
+                                         cabac_substream_result *results, uint32_t *tu_info, uint32_t *bin_counts, uint32_t n_level,
+                                         const uint32_t *level_first, const uint32_t *sync_from, const uint32_t *sync_at,
+                                         const uint32_t *sync_splice) {
+  const SpliceRows rows{n_level, level_first, sync_from, sync_at, sync_splice};
+  return host_call_exit(c, encode_batch_residual_impl(c, n_sub, desc, records, n_records_total, splice_first, splices, n_tu, tus, coeff,
+                                                      coeff_bytes, n_coeff_total, payload, payload_capacity, payload_offsets, results,
+                                                      tu_info, bin_counts, &rows));
+}
+
+int cabac_hip_search_log_mark_device(cabac_search_log *log, uint32_t n, const uint32_t *d_chain) {
+  if (!log) return CABAC_HIP_ERR_INVALID;
+  cabac_hip_ctx *c = log->ctx;
+  if (n && !d_chain) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  c->timed = false;
+  Timed t(c, 38);
+  HIP_TRY(c, cabac::launch_search_log_mark(c->stream, log->a, n, d_chain));
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_search_log_encode_sets_device(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
+                                            uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
+                                            uint32_t *d_tu_info, uint32_t *d_bin_counts, uint32_t n_sets, const uint32_t *d_state,
+                                            const uint8_t *d_rate, const uint32_t *d_start_set, const uint32_t *d_out_set,
+                                            uint32_t *d_out_state, uint8_t *d_out_rate) {
+  if (!log) return CABAC_HIP_ERR_INVALID;
+  if (!sets_args_ok(log->a.n_chain, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(log->ctx, CABAC_HIP_ERR_INVALID, "null");
+  const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
+  return search_log_encode_impl(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, &sets,
+                                nullptr);
+}
+
+int cabac_hip_search_log_encode_rows_device(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
+                                            uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
+                                            uint32_t *d_tu_info, uint32_t *d_bin_counts, uint32_t n_level, const uint32_t *level_first,
+                                            const uint32_t *d_sync_from) {
+  if (!log) return CABAC_HIP_ERR_INVALID;
+  if (!d_sync_from) return fail(log->ctx, CABAC_HIP_ERR_INVALID, "null");
+  if (int bad = check_levels(log->ctx, log->a.n_chain, n_level, level_first)) return bad;  // before the first wait
+  const SpliceRows rows{n_level, level_first, d_sync_from, nullptr, nullptr};
+  return search_log_encode_impl(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr,
+                                &rows);
 }
 
 int cabac_hip_host_alloc(size_t bytes, void **out) {

@@ -121,6 +121,7 @@ struct SearchLogArrays {
   uint32_t *tu_at;
   void *coeff;
   uint32_t *chain_rec, *chain_tu;  // per chain: the records / blocks of its entries so far
+  uint32_t *mark_rec, *mark_tu;    // per chain: its hand-over point (cabac_hip_splice_rows.h), 0xffffffff = the end of the chain
   uint64_t record_cap, coeff_cap;
   uint32_t n_chain, entry_cap, tu_cap;
 };
@@ -151,6 +152,8 @@ inline SearchLogScratch search_log_scratch(void *p, uint32_t n_group) {
 }
 size_t search_log_scratch_bytes(uint32_t n_group);
 hipError_t launch_search_log_reset(hipStream_t st, const SearchLogArrays &log);
+// the hand-over points of the n listed chains (cabac_hip_splice_rows.h): mark_rec / mark_tu = the chains' cursors as they stand
+hipError_t launch_search_log_mark(hipStream_t st, const SearchLogArrays &log, uint32_t n, const uint32_t *chain);
 // the three launches of an append: sizes, scan (capacity, entries, cursors), copy; scratch: search_log_scratch_bytes(n_group)
 hipError_t launch_search_log_append(hipStream_t st, const SearchLogArrays &log, uint32_t n_group, const uint32_t *pick,
                                     const uint32_t *group_chain, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus,
@@ -205,6 +208,12 @@ hipError_t launch_splice_expand(hipStream_t st, uint32_t n_sub, const cabac_subs
                                 const uint32_t *splice_first, const cabac_splice *splices, const uint32_t *pre,
                                 const uint32_t *sub_n, const uint32_t *sub_cap, const uint64_t *rec_base, const uint64_t *byte_base,
                                 cabac_substream_desc *desc_out, uint64_t *tu_offset, uint16_t *records);
+// the hand-over points of spliced substreams (cabac_hip_splice_rows.h) as indices into their expanded strings: sync_rec[s] =
+// k + pre[m] with k = min(sync_at[s], n_records) host records and m = sync_splice[s] splices in front, clipped to
+// [#{at < k}, #{at <= k}] (sync_splice null: the upper end).  After launch_splice_plan accepted the list.
+hipError_t launch_splice_sync_index(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint32_t *splice_first,
+                                    const cabac_splice *splices, const uint32_t *pre, const uint32_t *sync_at,
+                                    const uint32_t *sync_splice, uint32_t *sync_rec);
 hipError_t launch_tu_range_check(hipStream_t st, uint32_t n_tu, const cabac_tu_desc *tus, uint64_t n_coeff_total, uint32_t *err);
 hipError_t launch_tu_info_any(hipStream_t st, uint32_t n_tu, const uint32_t *info, uint32_t *flag);
 hipError_t launch_bin_count(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,

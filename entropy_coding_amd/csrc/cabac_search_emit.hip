@@ -17,6 +17,7 @@
 //                      hundred 4 x 4 winners share one or two.  Memory bound: every logged byte is read once and written once.
 // PLACE, at encode time: log_place_scan_kernel (exclusive sums over the chains' record and block counts: descriptors and
 // splice_first) and log_place_move_kernel (a row per entry: its records to their place in the chain's string, its splices).
+// MARK (cabac_hip_splice_rows.h): log_mark_kernel copies the listed chains' cursors into their hand-over words.
 // No MFMA anywhere: there is no arithmetic to speak of.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -383,13 +384,33 @@ __global__ __launch_bounds__(256) void log_place_move_kernel(uint32_t n_entry, S
   }
 }
 
+// ---- mark (cabac_hip_splice_rows.h) --------------------------------------------------------------------------------------------
+// the hand-over point of every listed chain: its cursors as they stand in stream order (a dropped append left them unchanged)
+__global__ __launch_bounds__(256) void log_mark_kernel(uint32_t n, const uint32_t *__restrict__ chain, SearchLogArrays log) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t ch = chain[i];
+  if (ch >= log.n_chain) return;  // 0xffffffff too
+  log.mark_rec[ch] = log.chain_rec[ch];
+  log.mark_tu[ch] = log.chain_tu[ch];
+}
+
 // ---- launches ---------------------------------------------------------------------------------------------------------------
 hipError_t launch_search_log_reset(hipStream_t st, const SearchLogArrays &log) {
   hipError_t e = hipMemsetAsync(log.counters, 0, sizeof(cabac_search_log_counters), st);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(log.chain_rec, 0, sizeof(uint32_t) * log.n_chain, st);
   if (e != hipSuccess) return e;
-  return hipMemsetAsync(log.chain_tu, 0, sizeof(uint32_t) * log.n_chain, st);
+  e = hipMemsetAsync(log.chain_tu, 0, sizeof(uint32_t) * log.n_chain, st);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(log.mark_rec, 0xff, sizeof(uint32_t) * log.n_chain, st);  // every mark: the end of the chain
+  if (e != hipSuccess) return e;
+  return hipMemsetAsync(log.mark_tu, 0xff, sizeof(uint32_t) * log.n_chain, st);
+}
+
+hipError_t launch_search_log_mark(hipStream_t st, const SearchLogArrays &log, uint32_t n, const uint32_t *chain) {
+  if (n) hipLaunchKernelGGL(log_mark_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, n, chain, log);
+  return hipGetLastError();
 }
 
 hipError_t launch_search_log_append(hipStream_t st, const SearchLogArrays &log, uint32_t n_group, const uint32_t *pick,

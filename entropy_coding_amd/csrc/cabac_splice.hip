@@ -9,6 +9,7 @@
 //   splice_plan_kernel    per substream: running sum of its blocks' sizes at every splice, expanded length, byte-slot size
 //   splice_scan_kernel    across substreams: where each expanded substream starts (records, bytes); totals; list check
 //   splice_expand_kernel  per substream: its final descriptor, every block's destination, the host records moved apart
+//   splice_sync_index_kernel  (rows form, cabac_hip_splice_rows.h) per substream: its hand-over point as an index into its expanded string
 //   residual records pass (cabac_residual.hip) writes each block's records at its destination
 //   encode kernel (cabac_kernels_v4.hip) on the expanded substreams; bin_count_kernel for the BinCounter totals
 // No atomics on the data path (one atomicAdd per splice checks that every block is spliced exactly once).
@@ -189,6 +190,36 @@ __global__ __launch_bounds__(256) void splice_expand_kernel(uint32_t n_sub, cons
   }
 }
 
+// the hand-over point of every substream (cabac_hip_splice_rows.h) as an index into its expanded string: k host records and m of
+// its splices in front, m clipped to [#{at < k}, #{at <= k}] — two bisections of the sorted splices — and the records of those m
+// blocks from the running sums of splice_plan_kernel.  One thread per substream; nothing is shared.
+__global__ __launch_bounds__(256) void splice_sync_index_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+                                                                const uint32_t *__restrict__ splice_first,
+                                                                const cabac_splice *__restrict__ splices, const uint32_t *__restrict__ pre,
+                                                                const uint32_t *__restrict__ sync_at, const uint32_t *__restrict__ sync_splice,
+                                                                uint32_t *__restrict__ sync_rec) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= n_sub) return;
+  const uint32_t j0 = splice_first[s], ns = splice_first[s + 1] - j0;
+  const uint32_t k = min(sync_at[s], desc[s].n_records);
+  const cabac_splice *sp = splices + j0;
+  uint32_t lo = 0, hi = ns;  // #{at < k}
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (sp[mid].at < k) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint32_t below = lo;
+  hi = ns;  // #{at <= k}, from there on
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (sp[mid].at <= k) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint32_t m = sync_splice ? min(max(sync_splice[s], below), lo) : lo;
+  sync_rec[s] = k + pre[j0 + s + m];
+}
+
 // BinCounter totals of the expanded substreams (arith_codec.cpp:281-316): per substream 379 context-bin counts, then the
 // bypass and the terminate bins
 __global__ __launch_bounds__(256) void bin_count_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
@@ -271,6 +302,15 @@ hipError_t launch_splice_expand(hipStream_t st, uint32_t n_sub, const cabac_subs
   if (n_sub)
     hipLaunchKernelGGL(splice_expand_kernel, dim3(n_sub), dim3(256), 0, st, n_sub, desc, host_records, splice_first, splices, pre,
                        sub_n, sub_cap, rec_base, byte_base, desc_out, tu_offset, records);
+  return hipGetLastError();
+}
+
+hipError_t launch_splice_sync_index(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint32_t *splice_first,
+                                    const cabac_splice *splices, const uint32_t *pre, const uint32_t *sync_at,
+                                    const uint32_t *sync_splice, uint32_t *sync_rec) {
+  if (n_sub)
+    hipLaunchKernelGGL(splice_sync_index_kernel, dim3((n_sub + 255u) / 256u), dim3(256), 0, st, n_sub, desc, splice_first, splices, pre,
+                       sync_at, sync_splice, sync_rec);
   return hipGetLastError();
 }
 
