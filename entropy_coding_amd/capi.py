@@ -130,6 +130,16 @@ _lib = None
 vp = ctypes.c_void_p
 
 
+def _opt(p):
+    """A device address as an optional pointer argument: 0 is NULL."""
+    return vp(p) if p else None
+
+
+def _ptr(a):
+    """The address of an optional host array: None is NULL."""
+    return a.ctypes.data if a is not None else None
+
+
 def splices_to_tu_at(splices):
     """One substream's sorted cabac_splice list (SPLICE_DTYPE: at, tu) -> (block order, tu_at): the indices into tus[] in coded
     order and the position of each in the substream's side run — with the records and descriptors handed to
@@ -774,21 +784,19 @@ class CabacHip:
         uint64) with its blocks spliced in front of index d_tu_at[t] of that run (d_tu_at = 0: behind the run), costed in one walk;
         d_flags[c] = RES_BAD_RECORD for a side record that is none; d_out_set = 0 writes no set, else as
         estimate_residual_ctx_device with all 379 entries taken from the walk."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_estimate_unit_device(
             self.h, n_cand, vp(d_cand_first), vp(d_tu), vp(d_coeff), 2 if int16 else 4, vp(d_state), vp(d_rate), vp(d_set),
-            vp(d_rec_first), opt(d_records), opt(d_tu_at), vp(d_frac_bits), opt(d_tu_frac_bits), opt(d_tu_info), opt(d_flags),
-            opt(d_out_set), opt(d_out_state), opt(d_out_rate)))
+            vp(d_rec_first), _opt(d_records), _opt(d_tu_at), vp(d_frac_bits), _opt(d_tu_frac_bits), _opt(d_tu_info), _opt(d_flags),
+            _opt(d_out_set), _opt(d_out_state), _opt(d_out_rate)))
 
     def search_unit_round_device(self, n_group, d_group_first, n_cand, d_cand_first, d_tu, d_coeff, d_state, d_rate, d_set,
                                  d_rec_first, d_records, d_tu_at, d_group_out_set, d_dist, lambda_q16, d_frac_bits, d_pick, d_cost,
                                  d_tu_frac_bits=0, d_tu_info=0, d_flags=0, int16=False):
         """cabac_hip_search_unit_round_device: search_round_device over candidates with side records (see estimate_unit_device)."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_search_unit_round_device(
             self.h, n_group, vp(d_group_first), n_cand, vp(d_cand_first), vp(d_tu), vp(d_coeff), 2 if int16 else 4, vp(d_state),
-            vp(d_rate), vp(d_set), vp(d_rec_first), opt(d_records), opt(d_tu_at), opt(d_group_out_set), opt(d_dist), lambda_q16,
-            vp(d_frac_bits), vp(d_pick), vp(d_cost), opt(d_tu_frac_bits), opt(d_tu_info), opt(d_flags)))
+            vp(d_rate), vp(d_set), vp(d_rec_first), _opt(d_records), _opt(d_tu_at), _opt(d_group_out_set), _opt(d_dist), lambda_q16,
+            vp(d_frac_bits), vp(d_pick), vp(d_cost), _opt(d_tu_frac_bits), _opt(d_tu_info), _opt(d_flags)))
 
     def search_unit_round_batch(self, group_first, cand_first, tus, coeff, state, rate, sets, records, rec_first, tu_at, group_out_set,
                                 dist, lambda_q16, int16=False, with_blocks=False, check=True):
@@ -837,11 +845,10 @@ class CabacHip:
         values d_values_in and its blocks -> the candidate format of estimate_unit_device / search_unit_round_device /
         SearchLog.append_device: d_rec_first, d_records (record_capacity records), d_tu_at_out, d_tu_out; d_flags[c] = 0,
         RES_BAD_RECORD, RES_BAD_VALUE or RES_OVERFLOW (the call did not fit: d_total says what it needs)."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_resolve_plan_device(
-            self.h, n_cand, vp(d_cand_first), vp(d_ent_first), opt(d_plan), opt(d_values_in), n_tu, opt(d_tu), opt(d_tu_at),
-            opt(d_tu_guard), opt(d_coeff), 2 if int16 else 4, vp(d_rec_first), opt(d_records), record_capacity, opt(d_tu_at_out),
-            opt(d_tu_out), opt(d_values_out), opt(d_tu_info), vp(d_flags), opt(d_total)))
+            self.h, n_cand, vp(d_cand_first), vp(d_ent_first), _opt(d_plan), _opt(d_values_in), n_tu, _opt(d_tu), _opt(d_tu_at),
+            _opt(d_tu_guard), _opt(d_coeff), 2 if int16 else 4, vp(d_rec_first), _opt(d_records), record_capacity, _opt(d_tu_at_out),
+            _opt(d_tu_out), _opt(d_values_out), _opt(d_tu_info), vp(d_flags), _opt(d_total)))
 
     def search_plan_round_device(self, n_group, d_group_first, n_cand, d_cand_first, n_tu, d_tu, d_coeff, d_state, d_rate, d_set,
                                  d_ent_first, d_plan, d_values_in, d_tu_at, d_tu_guard, d_group_out_set, d_dist, lambda_q16, d_frac_bits,
@@ -849,12 +856,11 @@ class CabacHip:
                                  d_tu_info=0, d_flags=0, d_values_out=0, d_total=0, int16=False):
         """cabac_hip_search_plan_round_device: search_unit_round_device over candidates given as plans (see resolve_plan_device);
         the resolved form is left in d_rec_first / d_records / d_tu_at_out / d_tu_out for SearchLog.append_device."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_search_plan_round_device(
-            self.h, n_group, vp(d_group_first), n_cand, vp(d_cand_first), n_tu, opt(d_tu), opt(d_coeff), 2 if int16 else 4, vp(d_state),
-            vp(d_rate), vp(d_set), vp(d_ent_first), opt(d_plan), opt(d_values_in), opt(d_tu_at), opt(d_tu_guard), opt(d_group_out_set),
-            opt(d_dist), lambda_q16, vp(d_frac_bits), vp(d_pick), vp(d_cost), opt(d_tu_frac_bits), opt(d_tu_info), opt(d_flags),
-            vp(d_rec_first), opt(d_records), record_capacity, opt(d_tu_at_out), opt(d_tu_out), opt(d_values_out), opt(d_total)))
+            self.h, n_group, vp(d_group_first), n_cand, vp(d_cand_first), n_tu, _opt(d_tu), _opt(d_coeff), 2 if int16 else 4, vp(d_state),
+            vp(d_rate), vp(d_set), vp(d_ent_first), _opt(d_plan), _opt(d_values_in), _opt(d_tu_at), _opt(d_tu_guard), _opt(d_group_out_set),
+            _opt(d_dist), lambda_q16, vp(d_frac_bits), vp(d_pick), vp(d_cost), _opt(d_tu_frac_bits), _opt(d_tu_info), _opt(d_flags),
+            vp(d_rec_first), _opt(d_records), record_capacity, _opt(d_tu_at_out), _opt(d_tu_out), _opt(d_values_out), _opt(d_total)))
 
     def search_plan_round_batch(self, group_first, cand_first, tus, coeff, state, rate, sets, plan, values, ent_first, tu_at, tu_guard,
                                 group_out_set, dist, lambda_q16, int16=False, with_blocks=False, check=True):
@@ -920,16 +926,87 @@ class CabacHip:
         self._check((self.L.cabac_hip_residual_parse16_device if int16 else self.L.cabac_hip_residual_parse_device)(self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), vp(d_tu),
                                                            vp(d_coeff), vp(d_tu_info) if d_tu_info else None, vp(d_results)))
 
-    def residual_parse_batch(self, desc, data, tile_first, tus, n_coeff_total, check=True, with_info=False, int16=False, coeff=None):
-        """Host arrays in, (coeff, results[, info]) out (cabac_hip_residual_parse_batch, synchronous; int16:
-        cabac_hip_residual_parse_batch16, the blocks as int16)."""
+    # ---- what the host-pointer forms of the parser family share ------
+    @staticmethod
+    def _parse_inputs(desc, data, tile_first, tus, n_coeff_total, int16, coeff):
+        """The arrays every parser batch form takes, normalised; `coeff` (the caller's, else zeros); fresh results."""
         desc = np.ascontiguousarray(desc, DESC_DTYPE)
         data = np.ascontiguousarray(data, np.uint8)
         tile_first = np.ascontiguousarray(tile_first, np.uint32)
         tus = np.ascontiguousarray(tus, TU_DTYPE)
         if coeff is None:
             coeff = np.zeros(max(int(n_coeff_total), 1), np.int16 if int16 else np.int32)
-        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
+        return desc, data, tile_first, tus, coeff, np.zeros(max(len(desc), 1), RESULT_DTYPE)
+
+    @staticmethod
+    def _per_block(a, tus):
+        """tu_at or tu_guard: None, or uint32 with one entry per block."""
+        if a is not None:
+            a = np.ascontiguousarray(a, np.uint32)
+            assert len(a) == len(tus)
+        return a
+
+    @staticmethod
+    def _rows(level_first, sync_from, sync_at, n):
+        """The trailing arguments of a rows batch form as arrays (kept alive by the caller): level_first, and one link and one
+        hand-over position per substream."""
+        lf = np.ascontiguousarray(level_first, np.uint32)
+        sf, sa = np.ascontiguousarray(sync_from, np.uint32), np.ascontiguousarray(sync_at, np.uint32)
+        assert len(sf) == n and len(sa) == n
+        return lf, sf, sa
+
+    def _parse_plan_batch(self, fn, desc, data, tile_first, tus, tu_at, tu_guard, plan, n_coeff_total, check, int16, coeff, values,
+                          info, rows=None):
+        """parse_elements_batch, parse_plan_batch and plan_parse_rows_batch through the library function `fn`; rows: None, or
+        (level_first, sync_from, sync_at) for the rows form."""
+        desc, data, tile_first, tus, coeff, res = self._parse_inputs(desc, data, tile_first, tus, n_coeff_total, int16, coeff)
+        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
+        assert len(tile_first) == len(desc) + 1
+        tu_at, tu_guard = self._per_block(tu_at, tus), self._per_block(tu_guard, tus)
+        lf, sf, sa = self._rows(*rows, len(desc)) if rows else (None,) * 3
+        if values is None:
+            values = np.zeros(max(len(plan), 1), np.uint32)
+        if info is None:
+            info = np.zeros(max(len(tus), 1), np.uint32)
+        assert coeff.dtype == (np.int16 if int16 else np.int32) and values.dtype == np.uint32 and info.dtype == np.uint32
+        rc = fn(self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data, _ptr(tu_at),
+                _ptr(tu_guard), plan.ctypes.data, len(plan), coeff.ctypes.data, 2 if int16 else 4, int(n_coeff_total), values.ctypes.data,
+                info.ctypes.data, res.ctypes.data, *((len(lf) - 1, lf.ctypes.data, sf.ctypes.data, sa.ctypes.data) if rows else ()))
+        self._check(rc, allow_substream=not check)
+        return coeff[: int(n_coeff_total)], values[: len(plan)], res[: len(desc)], info[: len(tus)]
+
+    def _write_plan_batch(self, fn, desc, plan, values, tile_first, tus, tu_at, tu_guard, coeff, payload, check, values_out, info,
+                          rows=None):
+        """write_plan_batch and plan_write_rows_batch through the library function `fn`; rows as in _parse_plan_batch."""
+        narrow = isinstance(coeff, np.ndarray) and coeff.dtype == np.int16
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
+        values = np.ascontiguousarray(values, np.uint32)
+        tile_first = np.ascontiguousarray(tile_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        coeff = np.ascontiguousarray(coeff, np.int16 if narrow else np.int32)
+        n = len(desc)
+        assert len(tile_first) == n + 1 and len(values) >= len(plan)
+        tu_at, tu_guard = self._per_block(tu_at, tus), self._per_block(tu_guard, tus)
+        lf, sf, sa = self._rows(*rows, n) if rows else (None,) * 3
+        if values_out is None:
+            values_out = np.zeros(max(len(plan), 1), np.uint32)
+        if info is None:
+            info = np.zeros(max(len(tus), 1), np.uint32)
+        assert values_out.dtype == np.uint32 and len(values_out) >= len(plan) and info.dtype == np.uint32 and payload.dtype == np.uint8
+        offsets = np.zeros(n + 1, np.uint64)
+        res = np.zeros(max(n, 1), RESULT_DTYPE)
+        rc = fn(self.h, n, desc.ctypes.data, plan.ctypes.data, values.ctypes.data, len(plan), tile_first.ctypes.data, tus.ctypes.data,
+                _ptr(tu_at), _ptr(tu_guard), coeff.ctypes.data, 2 if narrow else 4, len(coeff), payload.ctypes.data, payload.nbytes,
+                offsets.ctypes.data, res.ctypes.data, values_out.ctypes.data, info.ctypes.data,
+                *((len(lf) - 1, lf.ctypes.data, sf.ctypes.data, sa.ctypes.data) if rows else ()))
+        self._check(rc, allow_substream=not check)
+        return payload[: int(offsets[n])], offsets, res[:n], values_out[: len(plan)], info[: len(tus)]
+
+    def residual_parse_batch(self, desc, data, tile_first, tus, n_coeff_total, check=True, with_info=False, int16=False, coeff=None):
+        """Host arrays in, (coeff, results[, info]) out (cabac_hip_residual_parse_batch, synchronous; int16:
+        cabac_hip_residual_parse_batch16, the blocks as int16)."""
+        desc, data, tile_first, tus, coeff, res = self._parse_inputs(desc, data, tile_first, tus, n_coeff_total, int16, coeff)
         info = np.zeros(max(len(tus), 1), np.uint32)
         rc = (self.L.cabac_hip_residual_parse_batch16 if int16 else self.L.cabac_hip_residual_parse_batch)(self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data),
                                                    tile_first.ctypes.data, tus.ctypes.data, coeff.ctypes.data, int(n_coeff_total),
@@ -945,33 +1022,26 @@ class CabacHip:
         """cabac_hip_parse_unit_device: substream s = its side run d_records[rec_offset .. + n_records) with the blocks
         d_tu[d_tile_first[s] .. d_tile_first[s + 1]) coded in front of index d_tu_at[t] of that run (d_tu_at = 0: behind it), read
         back in one walk on one context store: blocks to d_coeff, side bins to d_side_bins[rec_offset + i]."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_parse_unit_device(
-            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), opt(d_tu), opt(d_tu_at), opt(d_records), opt(d_coeff),
-            2 if int16 else 4, opt(d_side_bins), opt(d_tu_info), vp(d_results)))
+            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), _opt(d_tu), _opt(d_tu_at), _opt(d_records), _opt(d_coeff),
+            2 if int16 else 4, _opt(d_side_bins), _opt(d_tu_info), vp(d_results)))
 
     def parse_unit_batch(self, desc, data, tile_first, tus, tu_at, records, n_coeff_total, check=True, int16=False, coeff=None,
                          side_bins=None, with_info=False):
         """Host arrays through cabac_hip_parse_unit_batch (synchronous): (coeff, side_bins, results[, info]).  `coeff` /
         `side_bins` (optional): the caller's arrays, written in place; tu_at may be None."""
-        desc = np.ascontiguousarray(desc, DESC_DTYPE)
-        data = np.ascontiguousarray(data, np.uint8)
-        tile_first = np.ascontiguousarray(tile_first, np.uint32)
-        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        desc, data, tile_first, tus, coeff, res = self._parse_inputs(desc, data, tile_first, tus, n_coeff_total, int16, coeff)
         records = np.ascontiguousarray(records, np.uint16)
-        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
-        assert len(tile_first) == len(desc) + 1 and (tu_at is None or len(tu_at) == len(tus))
-        if coeff is None:
-            coeff = np.zeros(max(int(n_coeff_total), 1), np.int16 if int16 else np.int32)
+        assert len(tile_first) == len(desc) + 1
+        tu_at = self._per_block(tu_at, tus)
         if side_bins is None:
             side_bins = np.zeros(max(len(records), 1), np.uint8)
         assert coeff.dtype == (np.int16 if int16 else np.int32) and side_bins.dtype == np.uint8
-        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
         info = np.zeros(max(len(tus), 1), np.uint32)
         rc = self.L.cabac_hip_parse_unit_batch(
-            self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data,
-            tu_at.ctypes.data if tu_at is not None else None, records.ctypes.data, len(records), coeff.ctypes.data,
-            2 if int16 else 4, int(n_coeff_total), side_bins.ctypes.data, info.ctypes.data, res.ctypes.data)
+            self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data, _ptr(tu_at),
+            records.ctypes.data, len(records), coeff.ctypes.data, 2 if int16 else 4, int(n_coeff_total), side_bins.ctypes.data,
+            info.ctypes.data, res.ctypes.data)
         self._check(rc, allow_substream=not check)
         out = (coeff[: int(n_coeff_total)], side_bins[: len(records)], res[: len(desc)])
         return out + (info[: len(tus)],) if with_info else out
@@ -982,89 +1052,42 @@ class CabacHip:
         """cabac_hip_parse_elements_device: substream s = its plan d_plan[2 * rec_offset .. + 2 * n_records) of syntax elements
         (element() words, guard() words) with the blocks coded in front of element d_tu_at[t], each block behind the guard
         d_tu_guard[t] (0: none guarded): element values to d_values[rec_offset + i], blocks to d_coeff."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_parse_elements_device(
-            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), opt(d_tu), opt(d_tu_at), opt(d_tu_guard), opt(d_plan),
-            opt(d_coeff), 2 if int16 else 4, opt(d_values), opt(d_tu_info), vp(d_results)))
+            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), _opt(d_tu), _opt(d_tu_at), _opt(d_tu_guard), _opt(d_plan),
+            _opt(d_coeff), 2 if int16 else 4, _opt(d_values), _opt(d_tu_info), vp(d_results)))
 
     def parse_elements_batch(self, desc, data, tile_first, tus, tu_at, tu_guard, plan, n_coeff_total, check=True, int16=False,
                              coeff=None, values=None, info=None):
         """Host arrays through cabac_hip_parse_elements_batch (synchronous): (coeff, values, results, info).  plan: uint32
         (n_elements, 2); `coeff` / `values` / `info` (optional): the caller's arrays, written in place; tu_at and tu_guard may be
         None."""
-        desc = np.ascontiguousarray(desc, DESC_DTYPE)
-        data = np.ascontiguousarray(data, np.uint8)
-        tile_first = np.ascontiguousarray(tile_first, np.uint32)
-        tus = np.ascontiguousarray(tus, TU_DTYPE)
-        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
-        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
-        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
-        assert len(tile_first) == len(desc) + 1 and (tu_at is None or len(tu_at) == len(tus))
-        assert tu_guard is None or len(tu_guard) == len(tus)
-        if coeff is None:
-            coeff = np.zeros(max(int(n_coeff_total), 1), np.int16 if int16 else np.int32)
-        if values is None:
-            values = np.zeros(max(len(plan), 1), np.uint32)
-        if info is None:
-            info = np.zeros(max(len(tus), 1), np.uint32)
-        assert coeff.dtype == (np.int16 if int16 else np.int32) and values.dtype == np.uint32 and info.dtype == np.uint32
-        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
-        rc = self.L.cabac_hip_parse_elements_batch(
-            self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data,
-            tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
-            plan.ctypes.data, len(plan), coeff.ctypes.data, 2 if int16 else 4, int(n_coeff_total), values.ctypes.data,
-            info.ctypes.data, res.ctypes.data)
-        self._check(rc, allow_substream=not check)
-        return coeff[: int(n_coeff_total)], values[: len(plan)], res[: len(desc)], info[: len(tus)]
+        return self._parse_plan_batch(self.L.cabac_hip_parse_elements_batch, desc, data, tile_first, tus, tu_at, tu_guard, plan,
+                                      n_coeff_total, check, int16, coeff, values, info)
 
     # ---- a whole transform unit in one walk (include/cabac_hip_parse_plan.h) ------
     def parse_plan_device(self, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff, d_values,
                           d_results, d_tu_info=0, int16=False):
         """cabac_hip_parse_plan_device: parse_elements_device on a plan that may hold cond() and block_info() entries."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_parse_plan_device(
-            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), opt(d_tu), opt(d_tu_at), opt(d_tu_guard), opt(d_plan),
-            opt(d_coeff), 2 if int16 else 4, opt(d_values), opt(d_tu_info), vp(d_results)))
+            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), _opt(d_tu), _opt(d_tu_at), _opt(d_tu_guard), _opt(d_plan),
+            _opt(d_coeff), 2 if int16 else 4, _opt(d_values), _opt(d_tu_info), vp(d_results)))
 
     def parse_plan_batch(self, desc, data, tile_first, tus, tu_at, tu_guard, plan, n_coeff_total, check=True, int16=False,
                          coeff=None, values=None, info=None):
         """Host arrays through cabac_hip_parse_plan_batch (synchronous): (coeff, values, results, info), as
         parse_elements_batch."""
-        desc = np.ascontiguousarray(desc, DESC_DTYPE)
-        data = np.ascontiguousarray(data, np.uint8)
-        tile_first = np.ascontiguousarray(tile_first, np.uint32)
-        tus = np.ascontiguousarray(tus, TU_DTYPE)
-        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
-        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
-        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
-        assert len(tile_first) == len(desc) + 1 and (tu_at is None or len(tu_at) == len(tus))
-        assert tu_guard is None or len(tu_guard) == len(tus)
-        if coeff is None:
-            coeff = np.zeros(max(int(n_coeff_total), 1), np.int16 if int16 else np.int32)
-        if values is None:
-            values = np.zeros(max(len(plan), 1), np.uint32)
-        if info is None:
-            info = np.zeros(max(len(tus), 1), np.uint32)
-        assert coeff.dtype == (np.int16 if int16 else np.int32) and values.dtype == np.uint32 and info.dtype == np.uint32
-        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
-        rc = self.L.cabac_hip_parse_plan_batch(
-            self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data,
-            tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
-            plan.ctypes.data, len(plan), coeff.ctypes.data, 2 if int16 else 4, int(n_coeff_total), values.ctypes.data,
-            info.ctypes.data, res.ctypes.data)
-        self._check(rc, allow_substream=not check)
-        return coeff[: int(n_coeff_total)], values[: len(plan)], res[: len(desc)], info[: len(tus)]
+        return self._parse_plan_batch(self.L.cabac_hip_parse_plan_batch, desc, data, tile_first, tus, tu_at, tu_guard, plan,
+                                      n_coeff_total, check, int16, coeff, values, info)
 
     # ---- plan and values to coded substreams (include/cabac_hip_write_plan.h) ------
     def write_plan_device(self, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, d_payload,
                           payload_capacity, d_payload_offsets, d_results, d_values_out=0, d_tu_info=0, int16=False):
         """cabac_hip_write_plan_device: the plan of parse_plan_device, the values of its real elements and the blocks' coefficients
         -> compacted coded substreams, the filled values (d_values_out, may be d_values_in) and the blocks' info words."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_write_plan_device(
-            self.h, n_sub, vp(d_desc), opt(d_plan), opt(d_values_in), vp(d_tile_first), n_tu, opt(d_tu), opt(d_tu_at), opt(d_tu_guard),
-            opt(d_coeff), 2 if int16 else 4, vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), opt(d_values_out),
-            opt(d_tu_info)))
+            self.h, n_sub, vp(d_desc), _opt(d_plan), _opt(d_values_in), vp(d_tile_first), n_tu, _opt(d_tu), _opt(d_tu_at), _opt(d_tu_guard),
+            _opt(d_coeff), 2 if int16 else 4, vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), _opt(d_values_out),
+            _opt(d_tu_info)))
 
     def write_plan_batch(self, desc, plan, values, tile_first, tus, tu_at, tu_guard, coeff, payload, check=True, values_out=None,
                          info=None):
@@ -1072,32 +1095,8 @@ class CabacHip:
         values, info words).  plan: uint32 (n_elements, 2); values: uint32 per element; coeff: int32 or int16; `payload`: the
         caller's uint8 array, written in place; `values_out` / `info` (optional): the caller's arrays, written in place (values_out
         may be `values`); tu_at and tu_guard may be None."""
-        narrow = isinstance(coeff, np.ndarray) and coeff.dtype == np.int16
-        desc = np.ascontiguousarray(desc, DESC_DTYPE)
-        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
-        values = np.ascontiguousarray(values, np.uint32)
-        tile_first = np.ascontiguousarray(tile_first, np.uint32)
-        tus = np.ascontiguousarray(tus, TU_DTYPE)
-        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
-        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
-        coeff = np.ascontiguousarray(coeff, np.int16 if narrow else np.int32)
-        n = len(desc)
-        assert len(tile_first) == n + 1 and len(values) >= len(plan) and (tu_at is None or len(tu_at) == len(tus))
-        assert tu_guard is None or len(tu_guard) == len(tus)
-        if values_out is None:
-            values_out = np.zeros(max(len(plan), 1), np.uint32)
-        if info is None:
-            info = np.zeros(max(len(tus), 1), np.uint32)
-        assert values_out.dtype == np.uint32 and len(values_out) >= len(plan) and info.dtype == np.uint32 and payload.dtype == np.uint8
-        offsets = np.zeros(n + 1, np.uint64)
-        res = np.zeros(max(n, 1), RESULT_DTYPE)
-        rc = self.L.cabac_hip_write_plan_batch(
-            self.h, n, desc.ctypes.data, plan.ctypes.data, values.ctypes.data, len(plan), tile_first.ctypes.data, tus.ctypes.data,
-            tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
-            coeff.ctypes.data, 2 if narrow else 4, len(coeff), payload.ctypes.data, payload.nbytes, offsets.ctypes.data,
-            res.ctypes.data, values_out.ctypes.data, info.ctypes.data)
-        self._check(rc, allow_substream=not check)
-        return payload[: int(offsets[n])], offsets, res[:n], values_out[: len(plan)], info[: len(tus)]
+        return self._write_plan_batch(self.L.cabac_hip_write_plan_batch, desc, plan, values, tile_first, tus, tu_at, tu_guard, coeff,
+                                      payload, check, values_out, info)
 
     # ---- plans from and into context sets, and in WPP rows (include/cabac_hip_plan_rows.h) ------
     def plan_parse_sets_device(self, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff, d_values,
@@ -1105,104 +1104,50 @@ class CabacHip:
                                d_out_state=0, d_out_rate=0, d_out_at=0):
         """parse_plan_device with substream s started from set d_start_set[s] (CTX_NO_SET: Ctx::init) and the contexts it holds
         when it arrives at plan entry d_out_at[s] (0: the end) written as set d_out_set[s]; 0 for a pointer = NULL."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_plan_parse_sets_device(
-            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), opt(d_tu), opt(d_tu_at), opt(d_tu_guard), opt(d_plan),
-            opt(d_coeff), 2 if int16 else 4, opt(d_values), opt(d_tu_info), vp(d_results),
-            *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate), opt(d_out_at)))
+            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), _opt(d_tu), _opt(d_tu_at), _opt(d_tu_guard), _opt(d_plan),
+            _opt(d_coeff), 2 if int16 else 4, _opt(d_values), _opt(d_tu_info), vp(d_results),
+            *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate), _opt(d_out_at)))
 
     def plan_parse_rows_device(self, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff, d_values,
                                d_results, level_first, d_sync_from, d_sync_at, d_tu_info=0, int16=False):
         """parse_plan_device over WPP rows in level order; level_first: HOST, n_level + 1 entries; d_sync_at in plan entries."""
-        opt = lambda p: vp(p) if p else None
         lf = np.ascontiguousarray(level_first, np.uint32)
         self._check(self.L.cabac_hip_plan_parse_rows_device(
-            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), opt(d_tu), opt(d_tu_at), opt(d_tu_guard), opt(d_plan),
-            opt(d_coeff), 2 if int16 else 4, opt(d_values), opt(d_tu_info), vp(d_results), len(lf) - 1, lf.ctypes.data,
+            self.h, n_sub, vp(d_desc), vp(d_bytes), vp(d_tile_first), _opt(d_tu), _opt(d_tu_at), _opt(d_tu_guard), _opt(d_plan),
+            _opt(d_coeff), 2 if int16 else 4, _opt(d_values), _opt(d_tu_info), vp(d_results), len(lf) - 1, lf.ctypes.data,
             vp(d_sync_from), vp(d_sync_at)))
 
     def plan_parse_rows_batch(self, desc, data, tile_first, tus, tu_at, tu_guard, plan, n_coeff_total, level_first, sync_from, sync_at,
                               check=True, int16=False, coeff=None, values=None, info=None):
         """Host arrays through cabac_hip_plan_parse_rows_batch (synchronous): (coeff, values, results, info), as parse_plan_batch."""
-        desc = np.ascontiguousarray(desc, DESC_DTYPE)
-        data = np.ascontiguousarray(data, np.uint8)
-        tile_first = np.ascontiguousarray(tile_first, np.uint32)
-        tus = np.ascontiguousarray(tus, TU_DTYPE)
-        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
-        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
-        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
-        lf = np.ascontiguousarray(level_first, np.uint32)
-        sf, sa = np.ascontiguousarray(sync_from, np.uint32), np.ascontiguousarray(sync_at, np.uint32)
-        assert len(tile_first) == len(desc) + 1 and (tu_at is None or len(tu_at) == len(tus))
-        assert (tu_guard is None or len(tu_guard) == len(tus)) and len(sf) == len(desc) and len(sa) == len(desc)
-        if coeff is None:
-            coeff = np.zeros(max(int(n_coeff_total), 1), np.int16 if int16 else np.int32)
-        if values is None:
-            values = np.zeros(max(len(plan), 1), np.uint32)
-        if info is None:
-            info = np.zeros(max(len(tus), 1), np.uint32)
-        assert coeff.dtype == (np.int16 if int16 else np.int32) and values.dtype == np.uint32 and info.dtype == np.uint32
-        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
-        rc = self.L.cabac_hip_plan_parse_rows_batch(
-            self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data, tus.ctypes.data,
-            tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
-            plan.ctypes.data, len(plan), coeff.ctypes.data, 2 if int16 else 4, int(n_coeff_total), values.ctypes.data,
-            info.ctypes.data, res.ctypes.data, len(lf) - 1, lf.ctypes.data, sf.ctypes.data, sa.ctypes.data)
-        self._check(rc, allow_substream=not check)
-        return coeff[: int(n_coeff_total)], values[: len(plan)], res[: len(desc)], info[: len(tus)]
+        return self._parse_plan_batch(self.L.cabac_hip_plan_parse_rows_batch, desc, data, tile_first, tus, tu_at, tu_guard, plan,
+                                      n_coeff_total, check, int16, coeff, values, info, rows=(level_first, sync_from, sync_at))
 
     def plan_write_sets_device(self, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff,
                                d_payload, payload_capacity, d_payload_offsets, d_results, d_values_out=0, d_tu_info=0, int16=False,
                                n_sets=0, d_state=0, d_rate=0, d_start_set=0, d_out_set=0, d_out_state=0, d_out_rate=0):
         """write_plan_device with substream s coded from set d_start_set[s] and its final contexts written as set d_out_set[s]."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_plan_write_sets_device(
-            self.h, n_sub, vp(d_desc), opt(d_plan), opt(d_values_in), vp(d_tile_first), n_tu, opt(d_tu), opt(d_tu_at), opt(d_tu_guard),
-            opt(d_coeff), 2 if int16 else 4, vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), opt(d_values_out),
-            opt(d_tu_info), *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate)))
+            self.h, n_sub, vp(d_desc), _opt(d_plan), _opt(d_values_in), vp(d_tile_first), n_tu, _opt(d_tu), _opt(d_tu_at), _opt(d_tu_guard),
+            _opt(d_coeff), 2 if int16 else 4, vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), _opt(d_values_out),
+            _opt(d_tu_info), *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate)))
 
     def plan_write_rows_device(self, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff,
                                d_payload, payload_capacity, d_payload_offsets, d_results, level_first, d_sync_from, d_sync_at,
                                d_values_out=0, d_tu_info=0, int16=False):
         """write_plan_device over WPP rows in level order; level_first: HOST, n_level + 1 entries; d_sync_at in plan entries."""
-        opt = lambda p: vp(p) if p else None
         lf = np.ascontiguousarray(level_first, np.uint32)
         self._check(self.L.cabac_hip_plan_write_rows_device(
-            self.h, n_sub, vp(d_desc), opt(d_plan), opt(d_values_in), vp(d_tile_first), n_tu, opt(d_tu), opt(d_tu_at), opt(d_tu_guard),
-            opt(d_coeff), 2 if int16 else 4, vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), opt(d_values_out),
-            opt(d_tu_info), len(lf) - 1, lf.ctypes.data, vp(d_sync_from), vp(d_sync_at)))
+            self.h, n_sub, vp(d_desc), _opt(d_plan), _opt(d_values_in), vp(d_tile_first), n_tu, _opt(d_tu), _opt(d_tu_at), _opt(d_tu_guard),
+            _opt(d_coeff), 2 if int16 else 4, vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), _opt(d_values_out),
+            _opt(d_tu_info), len(lf) - 1, lf.ctypes.data, vp(d_sync_from), vp(d_sync_at)))
 
     def plan_write_rows_batch(self, desc, plan, values, tile_first, tus, tu_at, tu_guard, coeff, payload, level_first, sync_from,
                               sync_at, check=True, values_out=None, info=None):
         """Host arrays through cabac_hip_plan_write_rows_batch (synchronous): as write_plan_batch."""
-        narrow = isinstance(coeff, np.ndarray) and coeff.dtype == np.int16
-        desc = np.ascontiguousarray(desc, DESC_DTYPE)
-        plan = np.ascontiguousarray(plan, np.uint32).reshape(-1, 2)
-        values = np.ascontiguousarray(values, np.uint32)
-        tile_first = np.ascontiguousarray(tile_first, np.uint32)
-        tus = np.ascontiguousarray(tus, TU_DTYPE)
-        tu_at = None if tu_at is None else np.ascontiguousarray(tu_at, np.uint32)
-        tu_guard = None if tu_guard is None else np.ascontiguousarray(tu_guard, np.uint32)
-        coeff = np.ascontiguousarray(coeff, np.int16 if narrow else np.int32)
-        lf = np.ascontiguousarray(level_first, np.uint32)
-        sf, sa = np.ascontiguousarray(sync_from, np.uint32), np.ascontiguousarray(sync_at, np.uint32)
-        n = len(desc)
-        assert len(tile_first) == n + 1 and len(values) >= len(plan) and (tu_at is None or len(tu_at) == len(tus))
-        assert (tu_guard is None or len(tu_guard) == len(tus)) and len(sf) == n and len(sa) == n
-        if values_out is None:
-            values_out = np.zeros(max(len(plan), 1), np.uint32)
-        if info is None:
-            info = np.zeros(max(len(tus), 1), np.uint32)
-        assert values_out.dtype == np.uint32 and len(values_out) >= len(plan) and info.dtype == np.uint32 and payload.dtype == np.uint8
-        offsets = np.zeros(n + 1, np.uint64)
-        res = np.zeros(max(n, 1), RESULT_DTYPE)
-        rc = self.L.cabac_hip_plan_write_rows_batch(
-            self.h, n, desc.ctypes.data, plan.ctypes.data, values.ctypes.data, len(plan), tile_first.ctypes.data, tus.ctypes.data,
-            tu_at.ctypes.data if tu_at is not None else None, tu_guard.ctypes.data if tu_guard is not None else None,
-            coeff.ctypes.data, 2 if narrow else 4, len(coeff), payload.ctypes.data, payload.nbytes, offsets.ctypes.data,
-            res.ctypes.data, values_out.ctypes.data, info.ctypes.data, len(lf) - 1, lf.ctypes.data, sf.ctypes.data, sa.ctypes.data)
-        self._check(rc, allow_substream=not check)
-        return payload[: int(offsets[n])], offsets, res[:n], values_out[: len(plan)], info[: len(tus)]
+        return self._write_plan_batch(self.L.cabac_hip_plan_write_rows_batch, desc, plan, values, tile_first, tus, tu_at, tu_guard,
+                                      coeff, payload, check, values_out, info, rows=(level_first, sync_from, sync_at))
 
     def residual_batch(self, tus, coeff, check=True):
         """Host arrays in, (records, offsets, info) out (cabac_hip_residual_batch: both passes, synchronous)."""
@@ -1263,23 +1208,21 @@ class CabacHip:
                                     n_sets=0, d_state=0, d_rate=0, d_start_set=0, d_out_set=0, d_out_state=0, d_out_rate=0):
         """encode_residual_device with substream s coded from set d_start_set[s] and the contexts after the last record of its
         expanded string written as set d_out_set[s]."""
-        opt = lambda p: vp(p) if p else None
         self._check(self.L.cabac_hip_encode_residual_sets_device(
-            self.h, n_sub, opt(d_desc), opt(d_records), opt(d_splice_first), opt(d_splices), n_splice, n_tu, opt(d_tu), opt(d_coeff),
-            2 if int16 else 4, opt(d_payload), payload_capacity, vp(d_payload_offsets), opt(d_results), opt(d_tu_info),
-            opt(d_bin_counts), *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate)))
+            self.h, n_sub, _opt(d_desc), _opt(d_records), _opt(d_splice_first), _opt(d_splices), n_splice, n_tu, _opt(d_tu), _opt(d_coeff),
+            2 if int16 else 4, _opt(d_payload), payload_capacity, vp(d_payload_offsets), _opt(d_results), _opt(d_tu_info),
+            _opt(d_bin_counts), *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate)))
 
     def encode_residual_rows_device(self, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff,
                                     d_payload, payload_capacity, d_payload_offsets, d_results, level_first, d_sync_from, d_sync_at,
                                     d_sync_splice=0, d_tu_info=0, d_bin_counts=0, int16=False):
         """encode_residual_device over WPP rows in level order; level_first: HOST, n_level + 1 entries; (d_sync_at, d_sync_splice):
         the hand-over pair of every substream (d_sync_splice 0: every block at the position goes in front)."""
-        opt = lambda p: vp(p) if p else None
         lf = np.ascontiguousarray(level_first, np.uint32)
         self._check(self.L.cabac_hip_encode_residual_rows_device(
-            self.h, n_sub, opt(d_desc), opt(d_records), opt(d_splice_first), opt(d_splices), n_splice, n_tu, opt(d_tu), opt(d_coeff),
-            2 if int16 else 4, opt(d_payload), payload_capacity, vp(d_payload_offsets), opt(d_results), opt(d_tu_info),
-            opt(d_bin_counts), len(lf) - 1, lf.ctypes.data, opt(d_sync_from), opt(d_sync_at), opt(d_sync_splice)))
+            self.h, n_sub, _opt(d_desc), _opt(d_records), _opt(d_splice_first), _opt(d_splices), n_splice, n_tu, _opt(d_tu), _opt(d_coeff),
+            2 if int16 else 4, _opt(d_payload), payload_capacity, vp(d_payload_offsets), _opt(d_results), _opt(d_tu_info),
+            _opt(d_bin_counts), len(lf) - 1, lf.ctypes.data, _opt(d_sync_from), _opt(d_sync_at), _opt(d_sync_splice)))
 
     def encode_residual_rows_batch(self, desc, records, splice_first, splices, tus, coeff, payload, level_first, sync_from, sync_at,
                                    sync_splice=None, check=True, offsets=None, results=None, info=None, counts=None):
@@ -1434,11 +1377,10 @@ class SearchLog:
         the host first with check=True (see validate); what only exists on the device cannot be."""
         if check and pick is not None and group_chain is not None:
             self.validate(pick, group_chain, n_cand, self.n_chain)
-        opt = lambda p: vp(p) if p else None
         narrow = self.int16 if int16 is None else bool(int16)
         self.hip._check(self.L.cabac_hip_search_log_append_device(
-            self.h, n_group, opt(d_pick), opt(d_group_chain), n_cand, opt(d_cand_first), opt(d_tu), opt(d_coeff), 2 if narrow else 4,
-            opt(d_rec_first), opt(d_records), opt(d_tu_at)))
+            self.h, n_group, _opt(d_pick), _opt(d_group_chain), n_cand, _opt(d_cand_first), _opt(d_tu), _opt(d_coeff), 2 if narrow else 4,
+            _opt(d_rec_first), _opt(d_records), _opt(d_tu_at)))
 
     def reset(self):
         """cabac_hip_search_log_reset_device (asynchronous): the log is empty again."""
@@ -1488,17 +1430,15 @@ class SearchLog:
                                       d_bin_counts=0, n_sets=0, d_state=0, d_rate=0, d_start_set=0, d_out_set=0, d_out_state=0,
                                       d_out_rate=0):
         """encode_device with chain k coded from set d_start_set[k] and its final contexts written as set d_out_set[k]."""
-        opt = lambda p: vp(p) if p else None
         self.hip._check(self.L.cabac_hip_search_log_encode_sets_device(
-            self.h, vp(d_desc), vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), opt(d_tu_info), opt(d_bin_counts),
+            self.h, vp(d_desc), vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), _opt(d_tu_info), _opt(d_bin_counts),
             *CabacHip._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate)))
 
     def search_log_encode_rows_device(self, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, level_first, d_sync_from,
                                       d_tu_info=0, d_bin_counts=0):
         """encode_device over WPP rows: the chains in level order (level_first: HOST, n_level + 1 entries), chain k coded from the
         contexts chain d_sync_from[k] holds at its mark."""
-        opt = lambda p: vp(p) if p else None
         lf = np.ascontiguousarray(level_first, np.uint32)
         self.hip._check(self.L.cabac_hip_search_log_encode_rows_device(
-            self.h, vp(d_desc), vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), opt(d_tu_info), opt(d_bin_counts),
-            len(lf) - 1, lf.ctypes.data, opt(d_sync_from)))
+            self.h, vp(d_desc), vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), _opt(d_tu_info), _opt(d_bin_counts),
+            len(lf) - 1, lf.ctypes.data, _opt(d_sync_from)))

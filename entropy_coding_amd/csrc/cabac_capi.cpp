@@ -4,6 +4,13 @@
 // blocks, a batch is cut into chunks whose H2D copy, kernel and D2H copy run on separate streams, and coded
 // substreams leave the device compacted (cabac_assemble.hip) in one copy per chunk.  There is no
 // CPU codec in this library — without a GPU cabac_hip_init fails.
+//
+// How the file is laid out: the slot table (every device staging buffer of a ctx, by name) and the ctx; the helpers every
+// section uses (fail / ensure, the event brackets Bracket, TIMED_LAUNCH and Timed, the PCIe path, the level / link checks and the
+// WPP and rows schedules); then one section per header.  The single-launch device calls go through TIMED_LAUNCH.  The four
+// host-pointer forms of the parser family (residual, unit, element and plan parse, the rows parse included) share their host
+// checks (check_substream_host, check_plan_host, check_coeff_ranges_host) and their staging (ParseStage); the pipelined
+// host-pointer forms each keep their own stream choreography.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +47,49 @@ hipError_t debug_read_parse_waves(unsigned long long *out);
 }
 #endif
 
+// Every device staging buffer of a ctx (index into d_buf / d_cap; grown on demand by ensure), in numeric order.  Names of one
+// value side by side: one buffer in two roles, in calls that never overlap.
+enum Slot {
+  // the codec's host-pointer forms (encode, decode, estimate, NAL and WPP batch), cabac_hip_residual_batch, the parser family
+  kDesc = 0,                                          // substream descriptors | residual_batch: block descriptors
+  kRecords = 1, kCoeff = 1,                           // bin records | parser family, residual_batch: coefficients
+  kBytes = 2, kOutRecords = 2,                        // byte slots | residual_batch: the records
+  kResults = 3, kFracBits = 3, kRecOffsets = 3, kFirstTus = 3,  // results | estimate_batch | residual_batch | parsers: tile_first, pad, tus
+  kBins = 4, kFlags = 4, kCounts = 4, kParseResults = 4,        // decoded bins | estimate_batch | residual_batch: counts, info | parsers
+  kResidualScratch = 5,                               // the residual binariser's scratch (every call that runs it)
+  kPayload = 6, kPackedBins = 6, kTuInfo = 6,         // compacted payload | decode_batch_packed | parsers: info words
+  kPayloadOffsets = 7,
+  // the spliced-residual path (also the plan write and the plan resolve), the staging of its host-pointer form (also the plan write's)
+  kSpCnt = 8, kSpPlan = 9, kSpDesc = 10, kSpTuOff = 11, kSpRec = 12, kSpBytes = 13, kSpFlag = 14,
+  kSpInDesc = 15, kSpInRec = 16, kSpInFirst = 17, kSpInSplice = 18, kSpInTu = 19, kSpInCoeff = 20, kSpOutRes = 21, kSpOutInfo = 22,
+  kSpOutCnt = 23,
+  // the fused residual estimator: the candidate order, the staging of its host-pointer form (also the search rounds')
+  kEstScratch = 24, kEstInFirst = 25, kEstInTu = 26, kEstInCoeff = 27, kEstInState = 28, kEstInRate = 29, kEstInSet = 30,
+  kEstOutBits = 31, kEstOutInfo = 32,
+  // emulation prevention: the chunk summaries and scans, the staging of the host-pointer forms
+  kNalScratch = 33, kNalIn = 34, kNalInOff = 35, kNalOut = 36, kNalOutOff = 37, kNalLoc = 38, kNalStatus = 39,
+  // the search rounds' host-pointer forms (the side records of cabac_hip_search_unit.h included; the plan round's resolved form)
+  kSearchInGroupFirst = 40, kSearchInOutSet = 41, kSearchInDist = 42, kSearchOutPick = 43, kSearchOutCost = 44, kSearchInRecords = 45,
+  kSearchInRecFirst = 46, kSearchInTuAt = 47,
+  // the winner log's emit
+  kLogScratch = 48, kLogDesc = 49, kLogFirst = 50, kLogRec = 51, kLogSplice = 52,
+  // the unit parse: runs, positions (also the element / plan parse, the plan write, the plan round), side bins
+  kUnitRecords = 53, kUnitTuAt = 54, kUnitBins = 55,
+  // the element and plan parse: plan, block guards, values (also the plan write and the plan round)
+  kElemPlan = 56, kElemGuard = 57, kElemValues = 58,
+  // the plan write: its per-substream words, the descriptor list of its records pass (also the plan round's resolved blocks)
+  kPwPlan = 59, kPwTu = 60,
+  // the plan resolve of the search rounds: counts (and flags where the caller gives none), staged ent_first, flags
+  kPsCnt = 61, kPsEnt = 62, kPsFlags = 63,
+  // a WPP call (the rows parse shares the sets): one set per substream, prefix descriptors, checked links and slot indices, the
+  // results of the prefix passes, and the links of every host-pointer form with rows
+  kWppState = 64, kWppRate = 65, kWppDesc = 66, kWppIndex = 67, kWppRes = 68, kWppFrom = 69, kWppAt = 70,
+  // the plan rows and the spliced rows: per substream the record index of its hand-over entry, then the out sets of the substreams
+  // that did not stop (the rows write); the hand-over splice counts of the spliced rows' host-pointer form
+  kRowsWords = 71, kSpInSync = 72,
+  kSlots
+};
+
 struct cabac_hip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -52,14 +102,7 @@ struct cabac_hip_ctx {
   std::vector<hipEvent_t> prof_ev;  // 2 per slot
   std::vector<int32_t> prof_kind;
   uint32_t prof_n = 0;
-  // device staging for the host-pointer entry points (grown on demand)
-  // [5]: scratch of the residual binariser, [6]: compacted payload, [7]: payload offsets; [8..]: the spliced-residual path
-  // (kSp* below); [24..]: the fused residual estimator (kEst* below); [33..]: emulation prevention (kNal* below); [40..]: the
-  // search rounds (kSearch* below, the side records of cabac_hip_search_unit.h included); [48..]: the winner log (kLog* below); [53..]: the
-  // unit parse (kUnit* below); [56..]: the element parse (kElem* below); [59..]: the plan write (kPw* below); [61..]: the plan
-  // resolve of the search rounds (kPs* below); [64..]: the WPP calls (kWpp* below); [71]: the plan rows and the spliced rows
-  // (kRowsWords below); [72]: the spliced rows' host-pointer form (kSpInSync below)
-  static constexpr int kSlots = 73;
+  // device staging (the Slot table above)
   void *d_buf[kSlots] = {};
   size_t d_cap[kSlots] = {};
   void *h_totals = nullptr;  // pinned, 64 bytes: what the spliced-residual path reads back in the middle
@@ -131,6 +174,14 @@ int ensure(cabac_hip_ctx *c, int slot, size_t bytes) {
   return CABAC_HIP_OK;
 }
 
+// a plain copy on the ctx stream, host to device and back (nothing for no bytes); the pipelined forms use h2d / d2h below
+hipError_t up(cabac_hip_ctx *c, void *dst, const void *src, size_t n) {
+  return n ? hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+}
+hipError_t down(cabac_hip_ctx *c, void *dst, const void *src, size_t n) {
+  return n ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+}
+
 // Event bracket of one launch: the ring slot when profiling is on, else the ctx's single pair.
 struct Bracket {
   hipEvent_t a, b;
@@ -143,6 +194,33 @@ Bracket bracket_for(cabac_hip_ctx *c, int kind) {
   }
   return {c->ev_start, c->ev_stop};
 }
+
+// One launch on the ctx stream between the events of its bracket; cabac_hip_last_kernel_ms reads the ctx's pair, so it has a time
+// only when the ring did not take the launch.  what: the launch as last_error names it when it fails.
+template <class F>
+int timed_launch(cabac_hip_ctx *c, int kind, const char *what, F &&launch) {
+  Bracket br = bracket_for(c, kind);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  if (hipError_t e = launch(); e != hipSuccess) return fail_hip(c, e, what);
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+#define TIMED_LAUNCH(c, kind, expr) timed_launch((c), (kind), #expr, [&] { return (expr); })
+
+struct Timed {  // profile-ring bracket around a group of launches (nothing when the ring is off or full)
+  cabac_hip_ctx *c;
+  Bracket br{nullptr, nullptr};
+  Timed(cabac_hip_ctx *ctx, int kind) : c(ctx) {
+    if (!c->prof_ev.empty() && c->prof_n < c->prof_kind.size()) {
+      br = bracket_for(c, kind);
+      (void)hipEventRecord(br.a, c->stream);
+    }
+  }
+  ~Timed() {
+    if (br.b) (void)hipEventRecord(br.b, c->stream);
+  }
+};
 
 struct DeviceGuard {
   int prev = -1;
@@ -169,6 +247,26 @@ int check_desc_host(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc
   return CABAC_HIP_OK;
 }
 
+// ---- the host checks of the parser family's host-pointer forms, in the order every form runs them: per substream the three
+// checks below and then the form's own, and behind all substreams the blocks' coefficient ranges -------------------------------
+// bytes_total: null where the descriptors' byte ranges are not input (the plan write, the plan round)
+int check_substream_host(cabac_hip_ctx *c, const cabac_substream_desc &d, const uint32_t *tile_first, uint32_t s, const uint64_t *bytes_total) {
+  if (tile_first[s] > tile_first[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "tile_first must not decrease");
+  if (bytes_total && (d.byte_offset > *bytes_total || d.byte_capacity > *bytes_total - d.byte_offset))
+    return fail(c, CABAC_HIP_ERR_INVALID, "bytes out of range");
+  if ((d.init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
+  return CABAC_HIP_OK;
+}
+
+int check_coeff_ranges_host(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_desc *tus, uint64_t n_coeff_total) {
+  for (uint32_t t = 0; t < n_tu; t++) {
+    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, writes nothing
+    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
+    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
+  }
+  return CABAC_HIP_OK;
+}
 
 // ---- pinned host memory handed out by cabac_hip_host_alloc / pinned in place by cabac_hip_host_register ----
 std::mutex g_host_mu;
@@ -410,6 +508,207 @@ std::vector<Chunk> plan_chunks(const cabac_hip_ctx *c, uint32_t n_sub, const cab
   return out;
 }
 
+// ---- levels, links and context sets: what the WPP calls (cabac_hip_ctx_sets.h), the plan rows and the spliced rows share ------
+// level_first as the WPP calls need it: n_level + 1 entries, non-decreasing, from 0 to n_sub
+int check_levels(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, const uint32_t *level_first) {
+  if (n_sub == 0) return CABAC_HIP_OK;
+  if (n_level == 0 || !level_first || level_first[0] != 0u || level_first[n_level] != n_sub)
+    return fail(c, CABAC_HIP_ERR_INVALID, "level_first must run from 0 to n_sub");
+  for (uint32_t l = 0; l < n_level; l++)
+    if (level_first[l] > level_first[l + 1]) {
+      char buf[96];
+      snprintf(buf, sizeof buf, "level_first decreases at level %u", l + 1);
+      return fail(c, CABAC_HIP_ERR_INVALID, buf);
+    }
+  return CABAC_HIP_OK;
+}
+
+// the links of a host-pointer form (level_first checked): every link points into an earlier level
+int check_links_host(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, const uint32_t *level_first, const uint32_t *sync_from) {
+  for (uint32_t l = 0; l < n_level; l++)
+    for (uint32_t s = level_first[l]; s < level_first[l + 1]; s++) {
+      const uint32_t from = sync_from[s];
+      if (from == CABAC_CTX_NO_SET || from < level_first[l]) continue;
+      char buf[128];
+      if (from >= n_sub) snprintf(buf, sizeof buf, "substream %u links to %u, beyond the batch", s, from);
+      else snprintf(buf, sizeof buf, "substream %u (level %u) links to %u in the same or a later level", s, l, from);
+      return fail(c, CABAC_HIP_ERR_INVALID, buf);
+    }
+  return CABAC_HIP_OK;
+}
+
+// the rows of a call of cabac_hip_plan_rows.h or cabac_hip_splice_rows.h: levels (HOST memory), links and hand-over positions
+// (device memory; host memory in the batch forms).  d_sync_splice: the spliced rows' alone, and null there too where every block at
+// the hand-over position goes in front
+struct Rows {
+  uint32_t n_level;
+  const uint32_t *level_first, *d_sync_from, *d_sync_at, *d_sync_splice;
+};
+
+// what a host-pointer form refuses about its rows (links in host memory)
+int check_rows_host(cabac_hip_ctx *c, uint32_t n_sub, const Rows &rows) {
+  if (int bad = check_levels(c, n_sub, rows.n_level, rows.level_first)) return bad;
+  return check_links_host(c, n_sub, rows.n_level, rows.level_first, rows.d_sync_from);
+}
+
+bool sets_args_ok(uint32_t n_sub, uint32_t n_sets, const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
+                  const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate) {
+  if (n_sub == 0) return true;
+  if (d_start_set && n_sets && (!d_state || !d_rate)) return false;
+  if (d_out_set && n_sets && (!d_out_state || !d_out_rate)) return false;
+  return true;
+}
+
+// The schedule of a WPP call on the ctx stream: per level the level kernel (prefix descriptors, checked links, slot indices), for
+// every level but the last its prefix pass into the slots, then the pass over all substreams from their slots.  encode: d_bins
+// null, the prefix pass is the context advance; decode: the sets decoder (its bins land in d_bins and are written again, the
+// same, by the last pass; its results go to a scratch).
+int wpp_device_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                    uint8_t *d_bytes, uint8_t *d_bins, cabac_substream_result *d_results, uint32_t n_level,
+                    const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
+  if (!c || (n_sub && (!d_desc || !d_records || !d_bytes || !d_results || (decode && !d_bins) || !d_sync_from || !d_sync_at)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  int rc = check_levels(c, n_sub, n_level, level_first);
+  if (rc) return rc;
+  DeviceGuard g(c->device);
+  const size_t set_words = size_t(n_sub) * CABAC_NUM_CONTEXTS;
+  if ((rc = ensure(c, kWppState, set_words * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kWppRate, set_words))) return rc;
+  if ((rc = ensure(c, kWppDesc, size_t(n_sub) * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kWppIndex, 2 * size_t(n_sub) * sizeof(uint32_t)))) return rc;
+  if (decode && (rc = ensure(c, kWppRes, size_t(n_sub) * sizeof(cabac_substream_result)))) return rc;
+  auto *slot_state = static_cast<uint32_t *>(c->d_buf[kWppState]);
+  auto *slot_rate = static_cast<uint8_t *>(c->d_buf[kWppRate]);
+  auto *pre_desc = static_cast<cabac_substream_desc *>(c->d_buf[kWppDesc]);
+  auto *start = static_cast<uint32_t *>(c->d_buf[kWppIndex]);
+  auto *slot = start + n_sub;
+  auto *pre_res = static_cast<cabac_substream_result *>(c->d_buf[kWppRes]);
+  for (uint32_t l = 0; l < n_level; l++) {
+    const uint32_t first = level_first[l], n = level_first[l + 1] - first;
+    if (n == 0) continue;
+    HIP_TRY(c, cabac::launch_wpp_level(c->stream, first, n, d_desc, d_sync_from, d_sync_at, pre_desc, start, slot));
+    if (l + 1 == n_level) break;
+    const cabac::CtxSets sets{n_sub, slot_state, slot_rate, start + first, slot + first, slot_state, slot_rate};
+    Timed t(c, 33);
+    if (decode)
+      HIP_TRY(c, cabac::launch_decode(c->stream, c->dec_variant, n, pre_desc + first, d_records, d_bytes, d_bins, pre_res + first, 0,
+                                      c->d_select, &sets));
+    else
+      HIP_TRY(c, cabac::launch_ctx_advance(c->stream, n, pre_desc + first, d_records, sets, nullptr));
+  }
+  const cabac::CtxSets sets{n_sub, slot_state, slot_rate, start, nullptr, nullptr, nullptr};
+  Bracket br = bracket_for(c, decode ? 31 : 30);
+  HIP_TRY(c, hipEventRecord(br.a, c->stream));
+  if (decode)
+    HIP_TRY(c, cabac::launch_decode(c->stream, c->dec_variant, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, 0, c->d_select, &sets));
+  else
+    HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, d_desc, d_records, d_bytes, d_results, 0, &sets));
+  HIP_TRY(c, hipEventRecord(br.b, c->stream));
+  c->timed = (br.a == c->ev_start);
+  return CABAC_HIP_OK;
+}
+
+// The schedule of a rows parse on the ctx stream: for every non-empty level ONE launch of the sets kernel over that level's
+// substreams.  A substream starts from the slot of its link (checked on the device against the level: it must lie below the
+// level's first substream) and writes its own slot at its hand-over entry; the last level writes none.
+int parse_rows_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                           const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at, const uint32_t *d_tu_guard,
+                           const uint32_t *d_plan, void *d_coeff, int coeff_bytes, uint32_t *d_values, uint32_t *d_tu_info,
+                           cabac_substream_result *d_results, const Rows &rows) {
+  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results || !rows.d_sync_from || !rows.d_sync_at)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  int rc = check_levels(c, n_sub, rows.n_level, rows.level_first);
+  if (rc) return rc;
+  DeviceGuard g(c->device);
+  const size_t set_words = size_t(n_sub) * CABAC_NUM_CONTEXTS;
+  if ((rc = ensure(c, kWppState, set_words * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kWppRate, set_words))) return rc;
+  auto *slot_state = static_cast<uint32_t *>(c->d_buf[kWppState]);
+  auto *slot_rate = static_cast<uint8_t *>(c->d_buf[kWppRate]);
+  uint32_t last = rows.n_level;  // the last non-empty level
+  while (last > 0 && rows.level_first[last - 1] == rows.level_first[last]) last--;
+  c->timed = false;
+  for (uint32_t l = 0; l < last; l++) {
+    const uint32_t first = rows.level_first[l], n = rows.level_first[l + 1] - first;
+    if (n == 0) continue;
+    const bool hands_over = l + 1 < last;
+    const cabac::CtxSets sets{n_sub, slot_state, slot_rate, rows.d_sync_from + first, nullptr, slot_state, slot_rate};
+    Timed t(c, 35);
+    HIP_TRY(c, cabac::launch_plan_parse_sets(c->stream, n, d_desc + first, d_bytes, d_tile_first + first, d_tu, d_tu_at, d_tu_guard, d_plan,
+                                             d_coeff, coeff_bytes, d_values, d_tu_info, d_results + first, sets, rows.d_sync_at + first,
+                                             first, hands_over ? first : 0xFFFFFFFFu));
+  }
+  return CABAC_HIP_OK;
+}
+
+// ---- what the host-pointer forms of the parser family (residual, unit, element and plan parse) stage alike: plain copies on the
+// ctx stream, no bounce ring, no second stream.  stage() uploads the common inputs and leaves the device views below; the form
+// adds its own arrays, launches, fetches its own outputs, and finish() brings back the common ones --------------------------------
+struct ParseStage {
+  cabac_hip_ctx *c;
+  uint32_t n_sub, n_tu;
+  int coeff_bytes;
+  uint64_t n_coeff_total;
+  bool blocks;  // the coefficients go up (int32) or are cleared (int16), and come back
+  const cabac_substream_desc *d_desc = nullptr;
+  const uint8_t *d_bytes = nullptr;
+  const uint32_t *d_tile_first = nullptr;
+  const cabac_tu_desc *d_tu = nullptr;
+  void *d_coeff = nullptr;
+  uint32_t *d_tu_info = nullptr;
+  cabac_substream_result *d_results = nullptr;
+
+  size_t tu_word_bytes() const { return size_t(n_tu) * sizeof(uint32_t); }  // one word per block: info words, positions, guards
+
+  // tu_info_in (may be null): the caller's info words go up, so that what the walk does not write comes back as it went in
+  int stage(const cabac_substream_desc *desc, const uint8_t *bytes, uint64_t bytes_total, const uint32_t *tile_first,
+            const cabac_tu_desc *tus, const void *coeff, const uint32_t *tu_info_in) {
+    int rc;
+    // kFirstTus: tile_first, padding to 16 bytes, the block descriptors; kBytes: room for the dword that holds the last byte
+    const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), first_pad = (first_bytes + 15) / 16 * 16;
+    if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
+    if ((rc = ensure(c, kBytes, bytes_total + 4))) return rc;
+    if ((rc = ensure(c, kFirstTus, first_pad + size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
+    if ((rc = ensure(c, kCoeff, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
+    if ((rc = ensure(c, kParseResults, n_sub * sizeof(cabac_substream_result)))) return rc;
+    if ((rc = ensure(c, kTuInfo, tu_word_bytes()))) return rc;
+    uint8_t *d_first = static_cast<uint8_t *>(c->d_buf[kFirstTus]);
+    d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[kDesc]);
+    d_bytes = static_cast<const uint8_t *>(c->d_buf[kBytes]);
+    d_tile_first = reinterpret_cast<const uint32_t *>(d_first);
+    d_tu = reinterpret_cast<const cabac_tu_desc *>(d_first + first_pad);
+    d_coeff = c->d_buf[kCoeff];
+    d_tu_info = static_cast<uint32_t *>(c->d_buf[kTuInfo]);
+    d_results = static_cast<cabac_substream_result *>(c->d_buf[kParseResults]);
+    HIP_TRY(c, up(c, c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc)));
+    HIP_TRY(c, up(c, c->d_buf[kBytes], bytes, bytes_total));
+    HIP_TRY(c, up(c, d_first, tile_first, first_bytes));
+    HIP_TRY(c, up(c, d_first + first_pad, tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
+    if (tu_info_in) HIP_TRY(c, up(c, d_tu_info, tu_info_in, tu_word_bytes()));
+    // int32: what the walk does not write (outside the coded region of 64-wide blocks, the blocks of a stopped substream) keeps
+    // the caller's values; int16: output only, zero where nothing is written
+    if (blocks && coeff_bytes == 4) HIP_TRY(c, up(c, d_coeff, coeff, n_coeff_total * sizeof(int32_t)));
+    if (blocks && n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(d_coeff, 0, n_coeff_total * sizeof(int16_t), c->stream));
+    return CABAC_HIP_OK;
+  }
+
+  // info words (where the caller wants them), coefficients and results back, the wait, and the flags as the status
+  int finish(void *coeff, uint32_t *tu_info, cabac_substream_result *results) {
+    if (tu_info) HIP_TRY(c, down(c, tu_info, d_tu_info, tu_word_bytes()));
+    if (blocks) HIP_TRY(c, down(c, coeff, d_coeff, n_coeff_total * size_t(coeff_bytes)));
+    HIP_TRY(c, down(c, results, d_results, n_sub * sizeof(cabac_substream_result)));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int status = CABAC_HIP_OK;
+    for (uint32_t s = 0; s < n_sub; s++)
+      if (results[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
+    if (status) c->last_error = "substream flag set (see results[].flags)";
+    return status;
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -452,7 +751,7 @@ void cabac_hip_destroy(cabac_hip_ctx *c) {
   DeviceGuard g(c->device);
   (void)hipStreamSynchronize(c->stream);
   while (!c->logs.empty()) (void)cabac_hip_search_log_destroy(c->logs.back());
-  for (int i = 0; i < cabac_hip_ctx::kSlots; i++)
+  for (int i = 0; i < kSlots; i++)
     if (c->d_buf[i]) (void)hipFree(c->d_buf[i]);
   if (c->h_totals) (void)hipHostFree(c->h_totals);
   if (c->d_select) (void)hipFree(c->d_select);
@@ -530,12 +829,7 @@ int cabac_hip_encode_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substr
                             const uint16_t *d_records, uint8_t *d_bytes, cabac_substream_result *d_results) {
   if (!c || (n_sub && (!d_desc || !d_records || !d_bytes || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 0);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, d_desc, d_records, d_bytes, d_results));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 0, cabac::launch_encode(c->stream, c->enc_variant, n_sub, d_desc, d_records, d_bytes, d_results));
 }
 
 int cabac_hip_decode_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc,
@@ -544,24 +838,14 @@ int cabac_hip_decode_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substr
   if (!c || (n_sub && (!d_desc || !d_records || !d_bytes || !d_bins || !d_results)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 1);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_decode(c->stream, c->dec_variant, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, 0, c->d_select));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 1, cabac::launch_decode(c->stream, c->dec_variant, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, 0, c->d_select));
 }
 
 int cabac_hip_estimate_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc,
                               const uint16_t *d_records, uint64_t *d_frac_bits, uint32_t *d_flags) {
   if (!c || (n_sub && (!d_desc || !d_records || !d_frac_bits))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 4);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_estimate(c->stream, n_sub, d_desc, d_records, d_frac_bits, d_flags));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 4, cabac::launch_estimate(c->stream, n_sub, d_desc, d_records, d_frac_bits, d_flags));
 }
 
 int cabac_hip_estimate_from_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc,
@@ -570,12 +854,7 @@ int cabac_hip_estimate_from_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac
   if (!c || (n_sub && (!d_desc || !d_records || !d_frac_bits || !d_state || !d_rate || !d_set)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 4);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_estimate(c->stream, n_sub, d_desc, d_records, d_frac_bits, d_flags, d_state, d_rate, d_set));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 4, cabac::launch_estimate(c->stream, n_sub, d_desc, d_records, d_frac_bits, d_flags, d_state, d_rate, d_set));
 }
 
 int cabac_hip_ctx_init_device(cabac_hip_ctx *c, uint32_t n_sub, const int32_t *d_qp, const uint32_t *d_init_id,
@@ -622,24 +901,14 @@ int cabac_hip_assemble_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subs
   if (!c || !d_offsets || (n_sub && (!d_desc || !d_results || !d_bytes || !d_payload)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 6);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_assemble(c->stream, n_sub, d_desc, d_results, d_bytes, d_payload, payload_capacity, d_offsets));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 6, cabac::launch_assemble(c->stream, n_sub, d_desc, d_results, d_bytes, d_payload, payload_capacity, d_offsets));
 }
 
 int cabac_hip_split_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint64_t *d_offsets,
                            const uint8_t *d_payload, uint8_t *d_bytes) {
   if (!c || (n_sub && (!d_desc || !d_offsets || !d_payload || !d_bytes))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 7);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_split(c->stream, n_sub, d_desc, d_offsets, d_payload, d_bytes));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 7, cabac::launch_split(c->stream, n_sub, d_desc, d_offsets, d_payload, d_bytes));
 }
 
 int cabac_hip_count_emulations_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc,
@@ -647,12 +916,7 @@ int cabac_hip_count_emulations_device(cabac_hip_ctx *c, uint32_t n_sub, const ca
                                       uint32_t *d_counts) {
   if (!c || (n_sub && (!d_desc || !d_results || !d_bytes || !d_counts))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 8);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_count_emulations(c->stream, n_sub, d_desc, d_results, d_bytes, d_counts));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 8, cabac::launch_count_emulations(c->stream, n_sub, d_desc, d_results, d_bytes, d_counts));
 }
 
 int cabac_hip_gather_records_device(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t *d_src_off, const uint64_t *d_dst_off,
@@ -688,29 +952,29 @@ static int encode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   if ((rc = pipe_init(c))) return rc;
   const std::vector<Chunk> chunks = plan_chunks(c, n_sub, desc);
   const uint32_t nc = uint32_t(chunks.size());
-  // device: [0] descriptors, [1] records, [2] byte slots, [3] results, [6] compacted payload (chunk k from its byte_lo),
-  // [7] payload offsets (chunk k: n_k + 1 entries from s0 + k).  pinned: [0] results then offsets, [1] payload.
+  // device: kPayload holds chunk k from its byte_lo, kPayloadOffsets n_k + 1 entries per chunk from s0 + k.  pinned: [0] results
+  // then offsets, [1] payload.
   const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result);
   const size_t off_count = size_t(n_sub) + nc;
-  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, 1, n_records_total * 2))) return rc;
-  if ((rc = ensure(c, 2, bytes_total))) return rc;
-  if ((rc = ensure(c, 3, res_bytes))) return rc;
-  if ((rc = ensure(c, 6, bytes_total))) return rc;
-  if ((rc = ensure(c, 7, off_count * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
+  if ((rc = ensure(c, kBytes, bytes_total))) return rc;
+  if ((rc = ensure(c, kResults, res_bytes))) return rc;
+  if ((rc = ensure(c, kPayload, bytes_total))) return rc;
+  if ((rc = ensure(c, kPayloadOffsets, off_count * sizeof(uint64_t)))) return rc;
   if ((rc = ensure_pinned(c, 0, res_bytes + off_count * sizeof(uint64_t)))) return rc;
-  auto *d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[0]);
-  auto *d_rec = static_cast<uint16_t *>(c->d_buf[1]);
-  auto *d_slots = static_cast<uint8_t *>(c->d_buf[2]);
-  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[3]);
-  auto *d_pay = static_cast<uint8_t *>(c->d_buf[6]);
-  auto *d_off = static_cast<uint64_t *>(c->d_buf[7]);
+  auto *d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[kDesc]);
+  auto *d_rec = static_cast<uint16_t *>(c->d_buf[kRecords]);
+  auto *d_slots = static_cast<uint8_t *>(c->d_buf[kBytes]);
+  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[kResults]);
+  auto *d_pay = static_cast<uint8_t *>(c->d_buf[kPayload]);
+  auto *d_off = static_cast<uint64_t *>(c->d_buf[kPayloadOffsets]);
   auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
   auto *h_off = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(c->h_pin[0]) + res_bytes);
 
   // what came before on the caller's stream is finished first; everything below runs on the library's own streams
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if ((rc = h2d(c, c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc), c->s_in))) return rc;
+  if ((rc = h2d(c, c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc), c->s_in))) return rc;
   for (uint32_t k = 0; k < nc; k++) {
     const Chunk &ch = chunks[k];
     const uint32_t n_k = ch.s1 - ch.s0;
@@ -796,19 +1060,19 @@ int cabac_hip_estimate_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   }
   DeviceGuard g(c->device);
   int rc;
-  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, 1, n_records_total * 2))) return rc;
-  if ((rc = ensure(c, 3, n_sub * sizeof(uint64_t)))) return rc;
-  if ((rc = ensure(c, 4, n_sub * sizeof(uint32_t)))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc), hipMemcpyHostToDevice, c->stream));
+  if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
+  if ((rc = ensure(c, kFracBits, n_sub * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kFlags, n_sub * sizeof(uint32_t)))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc), hipMemcpyHostToDevice, c->stream));
   if (n_records_total)
-    HIP_TRY(c, hipMemcpyAsync(c->d_buf[1], records, n_records_total * 2, hipMemcpyHostToDevice, c->stream));
-  rc = cabac_hip_estimate_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint16_t *)c->d_buf[1],
-                                 (uint64_t *)c->d_buf[3], (uint32_t *)c->d_buf[4]);
+    HIP_TRY(c, hipMemcpyAsync(c->d_buf[kRecords], records, n_records_total * 2, hipMemcpyHostToDevice, c->stream));
+  rc = cabac_hip_estimate_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[kDesc], (const uint16_t *)c->d_buf[kRecords],
+                                 (uint64_t *)c->d_buf[kFracBits], (uint32_t *)c->d_buf[kFlags]);
   if (rc) return rc;
   std::vector<uint32_t> fl(n_sub);
-  HIP_TRY(c, hipMemcpyAsync(frac_bits, c->d_buf[3], n_sub * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(fl.data(), c->d_buf[4], n_sub * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(frac_bits, c->d_buf[kFracBits], n_sub * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(fl.data(), c->d_buf[kFlags], n_sub * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   int status = CABAC_HIP_OK;
   for (uint32_t s = 0; s < n_sub; s++) {
@@ -833,22 +1097,22 @@ static int decode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   const uint32_t nc = uint32_t(chunks.size());
   const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result);
   // the kernel reads whole aligned dwords: room for the dword that holds the last byte
-  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, 1, n_records_total * 2))) return rc;
-  if ((rc = ensure(c, 2, bytes_total + 4))) return rc;
-  if ((rc = ensure(c, 3, res_bytes))) return rc;
-  if ((rc = ensure(c, 4, n_records_total + 8))) return rc;
-  if (packed && bins && (rc = ensure(c, 6, (n_records_total + 7) / 8 + 8))) return rc;
+  if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
+  if ((rc = ensure(c, kBytes, bytes_total + 4))) return rc;
+  if ((rc = ensure(c, kResults, res_bytes))) return rc;
+  if ((rc = ensure(c, kBins, n_records_total + 8))) return rc;
+  if (packed && bins && (rc = ensure(c, kPackedBins, (n_records_total + 7) / 8 + 8))) return rc;
   if ((rc = ensure_pinned(c, 0, res_bytes))) return rc;
-  auto *d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[0]);
-  auto *d_rec = static_cast<uint16_t *>(c->d_buf[1]);
-  auto *d_slots = static_cast<uint8_t *>(c->d_buf[2]);
-  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[3]);
-  auto *d_bins = static_cast<uint8_t *>(c->d_buf[4]);
+  auto *d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[kDesc]);
+  auto *d_rec = static_cast<uint16_t *>(c->d_buf[kRecords]);
+  auto *d_slots = static_cast<uint8_t *>(c->d_buf[kBytes]);
+  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[kResults]);
+  auto *d_bins = static_cast<uint8_t *>(c->d_buf[kBins]);
   auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
 
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if ((rc = h2d(c, c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc), c->s_in))) return rc;
+  if ((rc = h2d(c, c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc), c->s_in))) return rc;
   for (uint32_t k = 0; k < nc; k++) {
     const Chunk &ch = chunks[k];
     const uint32_t n_k = ch.s1 - ch.s0;
@@ -870,8 +1134,8 @@ static int decode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
     if (bins && !packed && (rc = d2h(c, bins + ch.rec_lo, d_bins + ch.rec_lo, ch.rec_hi - ch.rec_lo, c->s_out))) return rc;
   }
   if (bins && packed) {  // all chunks decoded (s_out waits for each of them above): eight bins to a byte, one small copy
-    HIP_TRY(c, cabac::launch_pack_bins(c->s_out, n_records_total, d_bins, static_cast<uint8_t *>(c->d_buf[6])));
-    if ((rc = d2h(c, bins, c->d_buf[6], (n_records_total + 7) / 8, c->s_out))) return rc;
+    HIP_TRY(c, cabac::launch_pack_bins(c->s_out, n_records_total, d_bins, static_cast<uint8_t *>(c->d_buf[kPackedBins])));
+    if ((rc = d2h(c, bins, c->d_buf[kPackedBins], (n_records_total + 7) / 8, c->s_out))) return rc;
   }
   if ((rc = d2h_drain(c))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->s_out));
@@ -902,12 +1166,7 @@ int cabac_hip_binarize_device(cabac_hip_ctx *c, uint32_t n_sub, const uint64_t *
   if (!c || (n_sub && (!d_se_offset || !d_se || !d_n_records || (d_records && !d_rec_offset))))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 2);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_binarize(c->stream, n_sub, d_se_offset, d_se, d_rec_offset, d_n_records, d_records));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 2, cabac::launch_binarize(c->stream, n_sub, d_se_offset, d_se, d_rec_offset, d_n_records, d_records));
 }
 
 int cabac_hip_residual_device(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_desc *d_tu, const int32_t *d_coeff,
@@ -916,14 +1175,9 @@ int cabac_hip_residual_device(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_de
   if (!c || (n_tu && (!d_tu || !d_coeff || !d_n_records || (d_records && !d_rec_offset))))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  if (int rc = ensure(c, 5, cabac::residual_scratch_bytes(n_tu))) return rc;
-  Bracket br = bracket_for(c, 5);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, 4, d_rec_offset, d_n_records, d_info, d_records,
-                                    c->d_buf[5]));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  if (int rc = ensure(c, kResidualScratch, cabac::residual_scratch_bytes(n_tu))) return rc;
+  return TIMED_LAUNCH(c, 5, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, 4, d_rec_offset, d_n_records, d_info, d_records,
+                                                   c->d_buf[kResidualScratch]));
 }
 
 int cabac_hip_residual_batch(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_desc *tus, const int32_t *coeff,
@@ -940,15 +1194,15 @@ int cabac_hip_residual_batch(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_des
   }
   DeviceGuard g(c->device);
   int rc;
-  // staging: [0] descriptors, [1] coefficients, [3] record offsets, [4] counts then info, [2] records
-  if ((rc = ensure(c, 0, n_tu * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, 1, n_coeff_total * sizeof(int32_t)))) return rc;
-  if ((rc = ensure(c, 3, n_tu * sizeof(uint64_t)))) return rc;
-  if ((rc = ensure(c, 4, 2 * size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[4]), *d_info = d_cnt + n_tu;
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[0], tus, n_tu * sizeof(cabac_tu_desc), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[1], coeff, n_coeff_total * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  rc = cabac_hip_residual_device(c, n_tu, (const cabac_tu_desc *)c->d_buf[0], (const int32_t *)c->d_buf[1], nullptr, d_cnt,
+  // staging: kCounts holds the counts, then the info words
+  if ((rc = ensure(c, kDesc, n_tu * sizeof(cabac_tu_desc)))) return rc;
+  if ((rc = ensure(c, kCoeff, n_coeff_total * sizeof(int32_t)))) return rc;
+  if ((rc = ensure(c, kRecOffsets, n_tu * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kCounts, 2 * size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kCounts]), *d_info = d_cnt + n_tu;
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kDesc], tus, n_tu * sizeof(cabac_tu_desc), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kCoeff], coeff, n_coeff_total * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  rc = cabac_hip_residual_device(c, n_tu, (const cabac_tu_desc *)c->d_buf[kDesc], (const int32_t *)c->d_buf[kCoeff], nullptr, d_cnt,
                                  d_info, nullptr);
   if (rc) return rc;
   std::vector<uint32_t> cnt(2 * size_t(n_tu));
@@ -964,12 +1218,12 @@ int cabac_hip_residual_batch(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_des
   if (!records) return status;
   if (records_capacity < offsets[n_tu]) return fail(c, CABAC_HIP_ERR_INVALID, "records_capacity too small");
   if (offsets[n_tu] == 0) return status;
-  if ((rc = ensure(c, 2, offsets[n_tu] * sizeof(uint16_t)))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[3], offsets, n_tu * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-  rc = cabac_hip_residual_device(c, n_tu, (const cabac_tu_desc *)c->d_buf[0], (const int32_t *)c->d_buf[1],
-                                 (const uint64_t *)c->d_buf[3], d_cnt, d_info, (uint16_t *)c->d_buf[2]);
+  if ((rc = ensure(c, kOutRecords, offsets[n_tu] * sizeof(uint16_t)))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kRecOffsets], offsets, n_tu * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  rc = cabac_hip_residual_device(c, n_tu, (const cabac_tu_desc *)c->d_buf[kDesc], (const int32_t *)c->d_buf[kCoeff],
+                                 (const uint64_t *)c->d_buf[kRecOffsets], d_cnt, d_info, (uint16_t *)c->d_buf[kOutRecords]);
   if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(records, c->d_buf[2], offsets[n_tu] * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(records, c->d_buf[kOutRecords], offsets[n_tu] * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return status;
 }
@@ -980,12 +1234,8 @@ static int residual_parse_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_tu || !d_coeff || !d_results)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 9);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_residual_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_coeff, coeff_bytes, d_tu_info, d_results));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 9, cabac::launch_residual_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_coeff, coeff_bytes, d_tu_info,
+                                                         d_results));
 }
 
 int cabac_hip_residual_parse_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
@@ -1006,50 +1256,18 @@ static int residual_parse_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cab
   if (!c || (n_sub && (!desc || !bytes || !tile_first || !tus || !coeff || !results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (n_sub == 0) return CABAC_HIP_OK;
   const uint32_t n_tu = tile_first[n_sub];
-  for (uint32_t s = 0; s < n_sub; s++) {
-    if (tile_first[s] > tile_first[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "tile_first must not decrease");
-    if (desc[s].byte_offset > bytes_total || desc[s].byte_capacity > bytes_total - desc[s].byte_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "bytes out of range");
-    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
-  }
-  for (uint32_t t = 0; t < n_tu; t++) {
-    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, writes nothing
-    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
-    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
-  }
-  DeviceGuard g(c->device);
-  int rc;
-  // staging: [0] substream descriptors, [2] bytes, [3] tile_first then block descriptors, [1] coefficients, [4] results
-  const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), first_pad = (first_bytes + 15) / 16 * 16;
-  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, 2, bytes_total))) return rc;
-  if ((rc = ensure(c, 3, first_pad + size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, 1, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
-  if ((rc = ensure(c, 4, n_sub * sizeof(cabac_substream_result)))) return rc;
-  if ((rc = ensure(c, 6, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  uint8_t *d_first = static_cast<uint8_t *>(c->d_buf[3]);
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc), hipMemcpyHostToDevice, c->stream));
-  if (bytes_total) HIP_TRY(c, hipMemcpyAsync(c->d_buf[2], bytes, bytes_total, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(d_first, tile_first, first_bytes, hipMemcpyHostToDevice, c->stream));
-  if (n_tu) HIP_TRY(c, hipMemcpyAsync(d_first + first_pad, tus, size_t(n_tu) * sizeof(cabac_tu_desc), hipMemcpyHostToDevice, c->stream));
-  // int32: what the parser does not write (outside the coded region of 64-wide blocks) keeps the caller's values;
-  // int16: output only, zero where nothing is written
-  if (n_coeff_total && coeff_bytes == 4) HIP_TRY(c, hipMemcpyAsync(c->d_buf[1], coeff, n_coeff_total * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  if (n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(c->d_buf[1], 0, n_coeff_total * sizeof(int16_t), c->stream));
-  rc = residual_parse_device_impl(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
-                                  (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad), c->d_buf[1], coeff_bytes,
-                                  (uint32_t *)c->d_buf[6], (cabac_substream_result *)c->d_buf[4]);
-  if (rc) return rc;
-  if (tu_info && n_tu) HIP_TRY(c, hipMemcpyAsync(tu_info, c->d_buf[6], size_t(n_tu) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  if (n_coeff_total) HIP_TRY(c, hipMemcpyAsync(coeff, c->d_buf[1], n_coeff_total * size_t(coeff_bytes), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(results, c->d_buf[4], n_sub * sizeof(cabac_substream_result), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  int status = CABAC_HIP_OK;
   for (uint32_t s = 0; s < n_sub; s++)
-    if (results[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
-  if (status) c->last_error = "substream flag set (see results[].flags)";
-  return status;
+    if (int bad = check_substream_host(c, desc[s], tile_first, s, &bytes_total)) return bad;
+  if (int bad = check_coeff_ranges_host(c, n_tu, tus, n_coeff_total)) return bad;
+  DeviceGuard g(c->device);
+  // (this form moves the coefficients whenever there are any, with or without blocks, and never sends the caller's info words up)
+  ParseStage st{c, n_sub, n_tu, coeff_bytes, n_coeff_total, n_coeff_total != 0};
+  int rc;
+  if ((rc = st.stage(desc, bytes, bytes_total, tile_first, tus, coeff, nullptr))) return rc;
+  if ((rc = residual_parse_device_impl(c, n_sub, st.d_desc, st.d_bytes, st.d_tile_first, st.d_tu, st.d_coeff, coeff_bytes, st.d_tu_info,
+                                       st.d_results)))
+    return rc;
+  return st.finish(coeff, tu_info, results);
 }
 
 int cabac_hip_residual_parse_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
@@ -1065,10 +1283,6 @@ int cabac_hip_residual_parse_batch16(cabac_hip_ctx *c, uint32_t n_sub, const cab
 }
 
 // ---- spliced substreams read back (declared in cabac_hip_parse_unit.h; the side-walking instantiation of the parser) ----------
-namespace {
-enum { kUnitRecords = 53, kUnitTuAt = 54, kUnitBins = 55 };
-}
-
 int cabac_hip_parse_unit_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
                                 const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
                                 const uint16_t *d_records, void *d_coeff, int coeff_bytes, uint8_t *d_side_bins, uint32_t *d_tu_info,
@@ -1078,13 +1292,8 @@ int cabac_hip_parse_unit_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_su
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (n_sub == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 25);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_unit_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_records, d_coeff, coeff_bytes,
-                                      d_side_bins, d_tu_info, d_results));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 25, cabac::launch_unit_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_records, d_coeff, coeff_bytes,
+                                                      d_side_bins, d_tu_info, d_results));
 }
 
 int cabac_hip_parse_unit_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
@@ -1098,10 +1307,7 @@ int cabac_hip_parse_unit_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
   if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (n_records_total && (!records || !side_bins)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   for (uint32_t s = 0; s < n_sub; s++) {
-    if (tile_first[s] > tile_first[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "tile_first must not decrease");
-    if (desc[s].byte_offset > bytes_total || desc[s].byte_capacity > bytes_total - desc[s].byte_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "bytes out of range");
-    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
+    if (int bad = check_substream_host(c, desc[s], tile_first, s, &bytes_total)) return bad;
     const uint64_t n_rec = desc[s].n_records;
     if (desc[s].rec_offset > n_records_total || n_rec > n_records_total - desc[s].rec_offset)
       return fail(c, CABAC_HIP_ERR_INVALID, "a side run leaves n_records_total");
@@ -1120,65 +1326,56 @@ int cabac_hip_parse_unit_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
       }
     }
   }
-  for (uint32_t t = 0; t < n_tu; t++) {
-    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, writes nothing
-    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
-    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
-  }
+  if (int bad = check_coeff_ranges_host(c, n_tu, tus, n_coeff_total)) return bad;
   DeviceGuard g(c->device);
+  // the common staging (the caller's info words do not go up); the runs, the positions and the side bins in slots of their own
+  ParseStage st{c, n_sub, n_tu, coeff_bytes, n_coeff_total, n_tu != 0};
   int rc;
-  // staging as cabac_hip_residual_parse_batch: [0] substream descriptors, [2] bytes, [3] tile_first then block descriptors, [1]
-  // coefficients, [4] results, [6] info words; the runs, the positions and the side bins in slots of their own
-  const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), first_pad = (first_bytes + 15) / 16 * 16;
-  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, 2, bytes_total + 4))) return rc;
-  if ((rc = ensure(c, 3, first_pad + size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, 1, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
-  if ((rc = ensure(c, 4, n_sub * sizeof(cabac_substream_result)))) return rc;
-  if ((rc = ensure(c, 6, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kUnitRecords, size_t(n_records_total) * sizeof(uint16_t)))) return rc;
-  if ((rc = ensure(c, kUnitTuAt, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kUnitBins, size_t(n_records_total)))) return rc;
-  uint8_t *d_first = static_cast<uint8_t *>(c->d_buf[3]);
-  auto up = [&](void *dst, const void *src, size_t n) {
-    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream) : hipSuccess;
-  };
-  auto down = [&](void *dst, const void *src, size_t n) {
-    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-  };
-  HIP_TRY(c, up(c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc)));
-  HIP_TRY(c, up(c->d_buf[2], bytes, bytes_total));
-  HIP_TRY(c, up(d_first, tile_first, first_bytes));
-  HIP_TRY(c, up(d_first + first_pad, tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
-  HIP_TRY(c, up(c->d_buf[kUnitRecords], records, size_t(n_records_total) * sizeof(uint16_t)));
-  if (tu_at) HIP_TRY(c, up(c->d_buf[kUnitTuAt], tu_at, size_t(n_tu) * sizeof(uint32_t)));
-  // what the walk does not write keeps the caller's values (int32 blocks, side bins) or is zero (int16 blocks: output only)
-  HIP_TRY(c, up(c->d_buf[kUnitBins], side_bins, size_t(n_records_total)));
-  if (n_tu && coeff_bytes == 4) HIP_TRY(c, up(c->d_buf[1], coeff, n_coeff_total * sizeof(int32_t)));
-  if (n_tu && n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(c->d_buf[1], 0, n_coeff_total * sizeof(int16_t), c->stream));
-  rc = cabac_hip_parse_unit_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
-                                   (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad),
+  if ((rc = st.stage(desc, bytes, bytes_total, tile_first, tus, coeff, nullptr))) return rc;
+  const size_t rec_bytes = size_t(n_records_total) * sizeof(uint16_t), bin_bytes = size_t(n_records_total);
+  if ((rc = ensure(c, kUnitRecords, rec_bytes))) return rc;
+  if ((rc = ensure(c, kUnitTuAt, st.tu_word_bytes()))) return rc;
+  if ((rc = ensure(c, kUnitBins, bin_bytes))) return rc;
+  HIP_TRY(c, up(c, c->d_buf[kUnitRecords], records, rec_bytes));
+  if (tu_at) HIP_TRY(c, up(c, c->d_buf[kUnitTuAt], tu_at, st.tu_word_bytes()));
+  HIP_TRY(c, up(c, c->d_buf[kUnitBins], side_bins, bin_bytes));  // what the walk does not write keeps the caller's values
+  rc = cabac_hip_parse_unit_device(c, n_sub, st.d_desc, st.d_bytes, st.d_tile_first, st.d_tu,
                                    tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr, (const uint16_t *)c->d_buf[kUnitRecords],
-                                   c->d_buf[1], coeff_bytes, (uint8_t *)c->d_buf[kUnitBins], (uint32_t *)c->d_buf[6],
-                                   (cabac_substream_result *)c->d_buf[4]);
+                                   st.d_coeff, coeff_bytes, (uint8_t *)c->d_buf[kUnitBins], st.d_tu_info, st.d_results);
   if (rc) return rc;
-  if (tu_info) HIP_TRY(c, down(tu_info, c->d_buf[6], size_t(n_tu) * sizeof(uint32_t)));
-  if (n_tu) HIP_TRY(c, down(coeff, c->d_buf[1], n_coeff_total * size_t(coeff_bytes)));
-  HIP_TRY(c, down(side_bins, c->d_buf[kUnitBins], size_t(n_records_total)));
-  HIP_TRY(c, down(results, c->d_buf[4], n_sub * sizeof(cabac_substream_result)));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  int status = CABAC_HIP_OK;
-  for (uint32_t s = 0; s < n_sub; s++)
-    if (results[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
-  if (status) c->last_error = "substream flag set (see results[].flags)";
-  return status;
+  HIP_TRY(c, down(c, side_bins, c->d_buf[kUnitBins], bin_bytes));
+  return st.finish(coeff, tu_info, results);
 }
 
 // ---- spliced substreams read back element by element (declared in cabac_hip_parse_elements.h; the element-walking instantiation) ----
-namespace {
-enum { kElemPlan = 56, kElemGuard = 57, kElemValues = 58 };
+int cabac_hip_parse_elements_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                    const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                    const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
+                                    uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results) {
+  // d_tu / d_coeff belong to the blocks, d_plan / d_values to the plans: either kind may be absent altogether
+  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  return TIMED_LAUNCH(c, 26, cabac::launch_element_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
+                                                         coeff_bytes, d_values, d_tu_info, d_results));
+}
 
+// ---- a whole transform unit in one walk (declared in cabac_hip_parse_plan.h; the plan-walking instantiation) ----
+int cabac_hip_parse_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
+                                uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results) {
+  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  return TIMED_LAUNCH(c, 27, cabac::launch_plan_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
+                                                      coeff_bytes, d_values, d_tu_info, d_results));
+}
+
+// what the host-pointer forms of the two refuse about a plan (the plan write and the plan round of the search use it too)
+namespace {
 // why a plan entry is bad (cabac_hip_parse_elements.h, "A BAD PLAN ENTRY"), or nullptr; i: its index in the substream's plan
 const char *bad_plan_entry(uint32_t w0, uint32_t gw, uint64_t i) {
   const uint32_t kind = w0 & 15u, p = w0 >> 4;
@@ -1210,131 +1407,7 @@ const char *bad_plan_entry(uint32_t w0, uint32_t gw, uint64_t i) {
   }
   return nullptr;
 }
-}  // namespace
 
-int cabac_hip_parse_elements_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
-                                    const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
-                                    const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
-                                    uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results) {
-  // d_tu / d_coeff belong to the blocks, d_plan / d_values to the plans: either kind may be absent altogether
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 26);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_element_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
-                                         coeff_bytes, d_values, d_tu_info, d_results));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
-}
-
-int cabac_hip_parse_elements_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                   uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
-                                   const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
-                                   int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
-                                   cabac_substream_result *results) {
-  if (!c || (n_sub && (!desc || !bytes || !tile_first || !results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  const uint32_t n_tu = tile_first[n_sub];
-  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (n_elements_total && (!plan || !values)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  char buf[200];
-  for (uint32_t s = 0; s < n_sub; s++) {
-    if (tile_first[s] > tile_first[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "tile_first must not decrease");
-    if (desc[s].byte_offset > bytes_total || desc[s].byte_capacity > bytes_total - desc[s].byte_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "bytes out of range");
-    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
-    const uint64_t n_el = desc[s].n_records;
-    if (desc[s].rec_offset > n_elements_total || n_el > n_elements_total - desc[s].rec_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "a plan leaves n_elements_total");
-    uint32_t at = 0;
-    for (uint32_t t = tile_first[s]; t < tile_first[s + 1]; t++) {
-      if (tu_at) {
-        if (tu_at[t] < at) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at decreases inside a substream");
-        if (tu_at[t] > n_el) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at exceeds the substream's plan length");
-        at = tu_at[t];
-      } else {
-        at = uint32_t(n_el);
-      }
-      if (tu_guard && ((tu_guard[t] & 0xfc00u) || (tu_guard[t] & 0xffu) > at)) {
-        snprintf(buf, sizeof buf, "bad block guard: substream %u, block %u of its blocks (guard 0x%x at element %u)", s,
-                 t - tile_first[s], tu_guard[t], at);
-        return fail(c, CABAC_HIP_ERR_INVALID, buf);
-      }
-    }
-    for (uint64_t i = 0; i < n_el; i++) {
-      const uint32_t *e = plan + 2 * (desc[s].rec_offset + i);
-      if (const char *why = bad_plan_entry(e[0], e[1], i)) {
-        snprintf(buf, sizeof buf, "bad plan entry: substream %u, element %llu of its plan (word0 0x%x, guard 0x%x): %s", s,
-                 (unsigned long long)i, e[0], e[1], why);
-        return fail(c, CABAC_HIP_ERR_INVALID, buf);
-      }
-    }
-  }
-  for (uint32_t t = 0; t < n_tu; t++) {
-    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, writes nothing
-    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
-    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
-  }
-  DeviceGuard g(c->device);
-  int rc;
-  // staging as cabac_hip_parse_unit_batch; the plan, the block guards and the values in slots of their own
-  const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), first_pad = (first_bytes + 15) / 16 * 16;
-  const size_t plan_bytes = size_t(n_elements_total) * 2 * sizeof(uint32_t), value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
-  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, 2, bytes_total + 4))) return rc;
-  if ((rc = ensure(c, 3, first_pad + size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, 1, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
-  if ((rc = ensure(c, 4, n_sub * sizeof(cabac_substream_result)))) return rc;
-  if ((rc = ensure(c, 6, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kUnitTuAt, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
-  if ((rc = ensure(c, kElemGuard, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
-  uint8_t *d_first = static_cast<uint8_t *>(c->d_buf[3]);
-  auto up = [&](void *dst, const void *src, size_t n) {
-    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream) : hipSuccess;
-  };
-  auto down = [&](void *dst, const void *src, size_t n) {
-    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-  };
-  HIP_TRY(c, up(c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc)));
-  HIP_TRY(c, up(c->d_buf[2], bytes, bytes_total));
-  HIP_TRY(c, up(d_first, tile_first, first_bytes));
-  HIP_TRY(c, up(d_first + first_pad, tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
-  HIP_TRY(c, up(c->d_buf[kElemPlan], plan, plan_bytes));
-  if (tu_at) HIP_TRY(c, up(c->d_buf[kUnitTuAt], tu_at, size_t(n_tu) * sizeof(uint32_t)));
-  if (tu_guard) HIP_TRY(c, up(c->d_buf[kElemGuard], tu_guard, size_t(n_tu) * sizeof(uint32_t)));
-  // what the walk does not write keeps the caller's values (int32 blocks, values, info words) or is zero (int16 blocks)
-  HIP_TRY(c, up(c->d_buf[kElemValues], values, value_bytes));
-  if (tu_info) HIP_TRY(c, up(c->d_buf[6], tu_info, size_t(n_tu) * sizeof(uint32_t)));
-  if (n_tu && coeff_bytes == 4) HIP_TRY(c, up(c->d_buf[1], coeff, n_coeff_total * sizeof(int32_t)));
-  if (n_tu && n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(c->d_buf[1], 0, n_coeff_total * sizeof(int16_t), c->stream));
-  rc = cabac_hip_parse_elements_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
-                                       (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad),
-                                       tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr,
-                                       tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr, (const uint32_t *)c->d_buf[kElemPlan],
-                                       c->d_buf[1], coeff_bytes, (uint32_t *)c->d_buf[kElemValues], (uint32_t *)c->d_buf[6],
-                                       (cabac_substream_result *)c->d_buf[4]);
-  if (rc) return rc;
-  if (tu_info) HIP_TRY(c, down(tu_info, c->d_buf[6], size_t(n_tu) * sizeof(uint32_t)));
-  if (n_tu) HIP_TRY(c, down(coeff, c->d_buf[1], n_coeff_total * size_t(coeff_bytes)));
-  HIP_TRY(c, down(values, c->d_buf[kElemValues], value_bytes));
-  HIP_TRY(c, down(results, c->d_buf[4], n_sub * sizeof(cabac_substream_result)));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  int status = CABAC_HIP_OK;
-  for (uint32_t s = 0; s < n_sub; s++)
-    if (results[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
-  if (status) c->last_error = "substream flag set (see results[].flags)";
-  return status;
-}
-
-// ---- a whole transform unit in one walk (declared in cabac_hip_parse_plan.h; the plan-walking instantiation) ----
-namespace {
 // why an entry of the plan parse is bad, or nullptr; i: its index in the substream's plan, nb: nb(i), the blocks in front of it
 const char *bad_computed_entry(uint32_t w0, uint32_t w1, uint64_t i, uint32_t nb) {
   const uint32_t kind = w0 & 15u, p = w0 >> 4;
@@ -1357,22 +1430,28 @@ const char *bad_computed_entry(uint32_t w0, uint32_t w1, uint64_t i, uint32_t nb
   if (shift + width > 32u) return "shift + width above 32";
   return nullptr;
 }
-}  // namespace
 
-namespace {
-// what the host-pointer forms of the plan parse and the plan write refuse about descriptors, plan, guards, tile_first, tu_at and
-// coefficient ranges; bytes_total: null where the descriptors' byte ranges are not input (the writer); unit: what the messages call
-// a descriptor's owner (the plan search describes its candidates this way)
+// the entry check of the element parse, which has no computed entries and calls word1 the guard
+const char *bad_element_entry(uint32_t w0, uint32_t gw, uint64_t i, uint32_t) { return bad_plan_entry(w0, gw, i); }
+
+// which plans a call takes: whether they may hold computed entries, the entry check, what its message calls an entry's second word
+struct PlanRules {
+  bool computed;
+  const char *(*bad_entry)(uint32_t w0, uint32_t w1, uint64_t i, uint32_t nb);
+  const char *word1;
+};
+constexpr PlanRules kElementRules{false, bad_element_entry, "guard"}, kPlanRules{true, bad_computed_entry, "word1"};
+
+// what the host-pointer forms of the element parse, the plan parse and the plan write refuse about descriptors, plan, guards,
+// tile_first, tu_at and coefficient ranges; bytes_total: null where the descriptors' byte ranges are not input (the writer); unit:
+// what the messages call a descriptor's owner (the plan search describes its candidates this way)
 int check_plan_host(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint64_t *bytes_total,
                     const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
-                    const uint32_t *plan, uint64_t n_elements_total, uint64_t n_coeff_total, const char *unit = "substream") {
-  const uint32_t n_tu = tile_first[n_sub];
+                    const uint32_t *plan, uint64_t n_elements_total, uint64_t n_coeff_total, const PlanRules &rules = kPlanRules,
+                    const char *unit = "substream") {
   char buf[200];
   for (uint32_t s = 0; s < n_sub; s++) {
-    if (tile_first[s] > tile_first[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "tile_first must not decrease");
-    if (bytes_total && (desc[s].byte_offset > *bytes_total || desc[s].byte_capacity > *bytes_total - desc[s].byte_offset))
-      return fail(c, CABAC_HIP_ERR_INVALID, "bytes out of range");
-    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
+    if (int bad = check_substream_host(c, desc[s], tile_first, s, bytes_total)) return bad;
     const uint64_t n_el = desc[s].n_records;
     if (desc[s].rec_offset > n_elements_total || n_el > n_elements_total - desc[s].rec_offset)
       return fail(c, CABAC_HIP_ERR_INVALID, "a plan leaves n_elements_total");
@@ -1396,64 +1475,24 @@ int check_plan_host(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc
     for (uint64_t i = 0; i < n_el; i++) {
       while (tu_at && t < tile_first[s + 1] && tu_at[t] <= i) t++;
       const uint32_t *e = plan + 2 * (desc[s].rec_offset + i);
-      if (const char *why = bad_computed_entry(e[0], e[1], i, t - tile_first[s])) {
-        snprintf(buf, sizeof buf, "bad plan entry: %s %u, element %llu of its plan (word0 0x%x, word1 0x%x): %s", unit, s,
-                 (unsigned long long)i, e[0], e[1], why);
+      if (const char *why = rules.bad_entry(e[0], e[1], i, t - tile_first[s])) {
+        snprintf(buf, sizeof buf, "bad plan entry: %s %u, element %llu of its plan (word0 0x%x, %s 0x%x): %s", unit, s,
+                 (unsigned long long)i, e[0], rules.word1, e[1], why);
         return fail(c, CABAC_HIP_ERR_INVALID, buf);
       }
     }
   }
-  for (uint32_t t = 0; t < n_tu; t++) {
-    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, writes nothing
-    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
-    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
-  }
-  return CABAC_HIP_OK;
+  return check_coeff_ranges_host(c, tile_first[n_sub], tus, n_coeff_total);
 }
 }  // namespace
 
-int cabac_hip_parse_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
-                                const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
-                                const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
-                                uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results) {
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 27);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_plan_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
-                                      coeff_bytes, d_values, d_tu_info, d_results));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
-}
-
-namespace {
-// the rows of a call of cabac_hip_plan_rows.h: levels (HOST memory) and links (device memory; host memory in the batch forms)
-struct PlanRows {
-  uint32_t n_level;
-  const uint32_t *level_first, *d_sync_from, *d_sync_at;
-};
-// device slot of the plan rows: per substream the record index of its hand-over entry, then the out sets of the substreams that
-// did not stop (the rows write); the slots of the rows parse and the links of the batch forms are the WPP calls' (kWpp* below)
-enum { kRowsWords = 71, kRowsState = 64, kRowsRate = 65, kRowsFrom = 69, kRowsAt = 70 };
-}  // namespace
-
-static int check_levels(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, const uint32_t *level_first);
-static int check_links_host(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, const uint32_t *level_first, const uint32_t *sync_from);
-static int parse_rows_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
-                                  const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
-                                  const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes, uint32_t *d_values,
-                                  uint32_t *d_tu_info, cabac_substream_result *d_results, const PlanRows &rows);
-
-// rows (may be null): the levels and the links, all in HOST memory here; the rows parse then takes the plan parse's place
+// The host-pointer form of the element parse (rules: kElementRules) and of the plan parse.  rows (may be null, the plan parse's
+// alone): the levels and the links, all in HOST memory here; the rows parse then takes the plan parse's place
 static int parse_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
                                  uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
                                  const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
                                  int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
-                                 cabac_substream_result *results, const PlanRows *rows) {
+                                 cabac_substream_result *results, const PlanRules &rules, const Rows *rows) {
   if (!c || (n_sub && (!desc || !bytes || !tile_first || !results)) || (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
@@ -1461,76 +1500,54 @@ static int parse_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   const uint32_t n_tu = tile_first[n_sub];
   if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (n_elements_total && (!plan || !values)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (int bad = check_plan_host(c, n_sub, desc, &bytes_total, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, n_coeff_total)) return bad;
-  if (rows) {
-    if (int bad = check_levels(c, n_sub, rows->n_level, rows->level_first)) return bad;
-    if (int bad = check_links_host(c, n_sub, rows->n_level, rows->level_first, rows->d_sync_from)) return bad;
-  }
+  if (int bad = check_plan_host(c, n_sub, desc, &bytes_total, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, n_coeff_total, rules))
+    return bad;
+  if (rows)
+    if (int bad = check_rows_host(c, n_sub, *rows)) return bad;
   DeviceGuard g(c->device);
+  // the common staging, the caller's info words with it: what the walk does not write keeps the caller's values (int32 blocks,
+  // values, info words) or is zero (int16 blocks); the positions, the plan, the block guards and the values in slots of their own
+  ParseStage st{c, n_sub, n_tu, coeff_bytes, n_coeff_total, n_tu != 0};
   int rc;
-  const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
-  if (rows && ((rc = ensure(c, kRowsFrom, link_bytes)) || (rc = ensure(c, kRowsAt, link_bytes)))) return rc;
-  // staged as cabac_hip_parse_elements_batch stages, in its slots
-  const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), first_pad = (first_bytes + 15) / 16 * 16;
+  if ((rc = st.stage(desc, bytes, bytes_total, tile_first, tus, coeff, tu_info))) return rc;
   const size_t plan_bytes = size_t(n_elements_total) * 2 * sizeof(uint32_t), value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
-  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, 2, bytes_total + 4))) return rc;
-  if ((rc = ensure(c, 3, first_pad + size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, 1, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
-  if ((rc = ensure(c, 4, n_sub * sizeof(cabac_substream_result)))) return rc;
-  if ((rc = ensure(c, 6, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kUnitTuAt, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
+  if ((rc = ensure(c, kUnitTuAt, st.tu_word_bytes()))) return rc;
   if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
-  if ((rc = ensure(c, kElemGuard, size_t(n_tu) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kElemGuard, st.tu_word_bytes()))) return rc;
   if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
-  uint8_t *d_first = static_cast<uint8_t *>(c->d_buf[3]);
-  auto up = [&](void *dst, const void *src, size_t n) {
-    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream) : hipSuccess;
-  };
-  auto down = [&](void *dst, const void *src, size_t n) {
-    return n ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-  };
-  HIP_TRY(c, up(c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc)));
-  HIP_TRY(c, up(c->d_buf[2], bytes, bytes_total));
-  HIP_TRY(c, up(d_first, tile_first, first_bytes));
-  HIP_TRY(c, up(d_first + first_pad, tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
-  HIP_TRY(c, up(c->d_buf[kElemPlan], plan, plan_bytes));
-  if (tu_at) HIP_TRY(c, up(c->d_buf[kUnitTuAt], tu_at, size_t(n_tu) * sizeof(uint32_t)));
-  if (tu_guard) HIP_TRY(c, up(c->d_buf[kElemGuard], tu_guard, size_t(n_tu) * sizeof(uint32_t)));
-  // what the walk does not write keeps the caller's values (int32 blocks, values, info words) or is zero (int16 blocks)
-  HIP_TRY(c, up(c->d_buf[kElemValues], values, value_bytes));
-  if (tu_info) HIP_TRY(c, up(c->d_buf[6], tu_info, size_t(n_tu) * sizeof(uint32_t)));
-  if (n_tu && coeff_bytes == 4) HIP_TRY(c, up(c->d_buf[1], coeff, n_coeff_total * sizeof(int32_t)));
-  if (n_tu && n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(c->d_buf[1], 0, n_coeff_total * sizeof(int16_t), c->stream));
+  if (rows && ((rc = ensure(c, kWppFrom, link_bytes)) || (rc = ensure(c, kWppAt, link_bytes)))) return rc;
+  HIP_TRY(c, up(c, c->d_buf[kElemPlan], plan, plan_bytes));
+  if (tu_at) HIP_TRY(c, up(c, c->d_buf[kUnitTuAt], tu_at, st.tu_word_bytes()));
+  if (tu_guard) HIP_TRY(c, up(c, c->d_buf[kElemGuard], tu_guard, st.tu_word_bytes()));
+  HIP_TRY(c, up(c, c->d_buf[kElemValues], values, value_bytes));
+  const uint32_t *d_tu_at = tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr;
+  const uint32_t *d_tu_guard = tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr;
+  const uint32_t *d_plan = (const uint32_t *)c->d_buf[kElemPlan];
+  uint32_t *d_values = (uint32_t *)c->d_buf[kElemValues];
   if (rows) {
-    HIP_TRY(c, up(c->d_buf[kRowsFrom], rows->d_sync_from, link_bytes));
-    HIP_TRY(c, up(c->d_buf[kRowsAt], rows->d_sync_at, link_bytes));
-    const PlanRows d_rows{rows->n_level, rows->level_first, (const uint32_t *)c->d_buf[kRowsFrom], (const uint32_t *)c->d_buf[kRowsAt]};
-    rc = parse_rows_device_impl(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
-                                (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad),
-                                tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr,
-                                tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr, (const uint32_t *)c->d_buf[kElemPlan],
-                                c->d_buf[1], coeff_bytes, (uint32_t *)c->d_buf[kElemValues], (uint32_t *)c->d_buf[6],
-                                (cabac_substream_result *)c->d_buf[4], d_rows);
+    HIP_TRY(c, up(c, c->d_buf[kWppFrom], rows->d_sync_from, link_bytes));
+    HIP_TRY(c, up(c, c->d_buf[kWppAt], rows->d_sync_at, link_bytes));
+    const Rows d_rows{rows->n_level, rows->level_first, (const uint32_t *)c->d_buf[kWppFrom], (const uint32_t *)c->d_buf[kWppAt]};
+    rc = parse_rows_device_impl(c, n_sub, st.d_desc, st.d_bytes, st.d_tile_first, st.d_tu, d_tu_at, d_tu_guard, d_plan, st.d_coeff,
+                                coeff_bytes, d_values, st.d_tu_info, st.d_results, d_rows);
   } else {
-    rc = cabac_hip_parse_plan_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[0], (const uint8_t *)c->d_buf[2],
-                                     (const uint32_t *)d_first, (const cabac_tu_desc *)(d_first + first_pad),
-                                     tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr,
-                                     tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr, (const uint32_t *)c->d_buf[kElemPlan],
-                                     c->d_buf[1], coeff_bytes, (uint32_t *)c->d_buf[kElemValues], (uint32_t *)c->d_buf[6],
-                                     (cabac_substream_result *)c->d_buf[4]);
+    rc = (rules.computed ? cabac_hip_parse_plan_device : cabac_hip_parse_elements_device)(
+        c, n_sub, st.d_desc, st.d_bytes, st.d_tile_first, st.d_tu, d_tu_at, d_tu_guard, d_plan, st.d_coeff, coeff_bytes, d_values,
+        st.d_tu_info, st.d_results);
   }
   if (rc) return rc;
-  if (tu_info) HIP_TRY(c, down(tu_info, c->d_buf[6], size_t(n_tu) * sizeof(uint32_t)));
-  if (n_tu) HIP_TRY(c, down(coeff, c->d_buf[1], n_coeff_total * size_t(coeff_bytes)));
-  HIP_TRY(c, down(values, c->d_buf[kElemValues], value_bytes));
-  HIP_TRY(c, down(results, c->d_buf[4], n_sub * sizeof(cabac_substream_result)));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  int status = CABAC_HIP_OK;
-  for (uint32_t s = 0; s < n_sub; s++)
-    if (results[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
-  if (status) c->last_error = "substream flag set (see results[].flags)";
-  return status;
+  HIP_TRY(c, down(c, values, d_values, value_bytes));
+  return st.finish(coeff, tu_info, results);
+}
+
+int cabac_hip_parse_elements_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                   uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                                   const uint32_t *tu_guard, const uint32_t *plan, uint64_t n_elements_total, void *coeff,
+                                   int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
+                                   cabac_substream_result *results) {
+  return parse_plan_batch_impl(c, n_sub, desc, bytes, bytes_total, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, coeff,
+                               coeff_bytes, n_coeff_total, values, tu_info, results, kElementRules, nullptr);
 }
 
 int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
@@ -1539,47 +1556,10 @@ int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
                                int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
                                cabac_substream_result *results) {
   return parse_plan_batch_impl(c, n_sub, desc, bytes, bytes_total, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, coeff,
-                               coeff_bytes, n_coeff_total, values, tu_info, results, nullptr);
+                               coeff_bytes, n_coeff_total, values, tu_info, results, kPlanRules, nullptr);
 }
 
 // ---- coefficients -> bytes (cabac_splice.hip) -------------------------------------------------------------------
-namespace {
-// device slots of the spliced-residual path
-enum { kSpCnt = 8, kSpPlan = 9, kSpDesc = 10, kSpTuOff = 11, kSpRec = 12, kSpBytes = 13, kSpFlag = 14,
-       // ... and the staging of its host-pointer form
-       kSpInDesc = 15, kSpInRec = 16, kSpInFirst = 17, kSpInSplice = 18, kSpInTu = 19, kSpInCoeff = 20, kSpOutRes = 21,
-       kSpOutInfo = 22, kSpOutCnt = 23,
-       // ... and the hand-over splice counts of its rows form (cabac_hip_splice_rows.h)
-       kSpInSync = 72 };
-
-struct Timed {  // profile-ring bracket around a group of launches (nothing when the ring is off or full)
-  cabac_hip_ctx *c;
-  Bracket br{nullptr, nullptr};
-  Timed(cabac_hip_ctx *ctx, int kind) : c(ctx) {
-    if (!c->prof_ev.empty() && c->prof_n < c->prof_kind.size()) {
-      br = bracket_for(c, kind);
-      (void)hipEventRecord(br.a, c->stream);
-    }
-  }
-  ~Timed() {
-    if (br.b) (void)hipEventRecord(br.b, c->stream);
-  }
-};
-}  // namespace
-
-namespace {
-// the rows of a call of cabac_hip_splice_rows.h: levels (HOST memory), links and hand-over pairs (device memory; d_sync_splice may be
-// null: every block at the hand-over position goes in front)
-struct SpliceRows {
-  uint32_t n_level;
-  const uint32_t *level_first, *d_sync_from, *d_sync_at, *d_sync_splice;
-};
-}  // namespace
-
-static int wpp_device_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
-                           uint8_t *d_bytes, uint8_t *d_bins, cabac_substream_result *d_results, uint32_t n_level,
-                           const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at);
-
 // sets (may be null): the encode launch starts from and writes context sets; rows (may be null): every substream's hand-over pair
 // becomes an index into its expanded string and the WPP encode schedule takes the encode launch's place.  Not both.  The plain
 // calls pass neither.
@@ -1588,7 +1568,7 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
                                        const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes, uint8_t *d_payload,
                                        uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
                                        uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets = nullptr,
-                                       const SpliceRows *rows = nullptr) {
+                                       const Rows *rows = nullptr) {
   if (!c || !d_payload_offsets || (n_sub && (!d_desc || !d_records || !d_splice_first || !d_payload || !d_results)) ||
       (n_splice && !d_splices) || (n_tu && (!d_tu || !d_coeff)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
@@ -1605,7 +1585,7 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
   const size_t plan32 = n_pre + 2 * size_t(n_sub) + size_t(n_tu ? n_tu : 1) + 2;  // pre, sub_n, sub_cap, seen, err (+ pad)
   const size_t plan32_pad = (plan32 + 1) & ~size_t(1);
   if ((rc = ensure(c, kSpCnt, 2 * size_t(n_tu ? n_tu : 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, 5, cabac::residual_scratch_bytes(n_tu)))) return rc;
+  if ((rc = ensure(c, kResidualScratch, cabac::residual_scratch_bytes(n_tu)))) return rc;
   if ((rc = ensure(c, kSpPlan, plan32_pad * sizeof(uint32_t) + (2 * size_t(n_sub) + 3) * sizeof(uint64_t)))) return rc;
   if ((rc = ensure(c, kSpDesc, size_t(n_sub ? n_sub : 1) * sizeof(cabac_substream_desc)))) return rc;
   if ((rc = ensure(c, kSpTuOff, size_t(n_tu ? n_tu : 1) * sizeof(uint64_t)))) return rc;
@@ -1620,7 +1600,7 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
   c->timed = false;
   {  // block sizes (pass 1 of the binariser)
     Timed t(c, 5);
-    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[5]));
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[kResidualScratch]));
   }
   {
     Timed t(c, 10);
@@ -1642,7 +1622,7 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
   }
   {  // block records (pass 2), straight into the expanded substreams
     Timed t(c, 5);
-    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[5],
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[kResidualScratch],
                                       /*order_ready=*/true));  // the block order of the sizes pass above: same tus[], same scratch
   }
   if (rows) {  // the hand-over indices, the context-advance prefix passes per level, then one encode launch from the slots
@@ -1697,14 +1677,13 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
                                       uint64_t n_records_total, const uint32_t *splice_first, const cabac_splice *splices, uint32_t n_tu,
                                       const cabac_tu_desc *tus, const void *coeff, int coeff_bytes, uint64_t n_coeff_total, uint8_t *payload,
                                       uint64_t payload_capacity, uint64_t *payload_offsets, cabac_substream_result *results,
-                                      uint32_t *tu_info, uint32_t *bin_counts, const SpliceRows *rows = nullptr) {
+                                      uint32_t *tu_info, uint32_t *bin_counts, const Rows *rows = nullptr) {
   if (!c || !payload_offsets || (n_sub && (!desc || !splice_first || !results || !payload)) || (n_tu && (!tus || !coeff || !splices)) ||
       (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (rows && n_sub) {  // refused before anything is touched, payload_offsets[0] included
-    if (int bad = check_levels(c, n_sub, rows->n_level, rows->level_first)) return bad;
-    if (int bad = check_links_host(c, n_sub, rows->n_level, rows->level_first, rows->d_sync_from)) return bad;
+    if (int bad = check_rows_host(c, n_sub, *rows)) return bad;
     for (uint32_t s = 0; s < n_sub; s++) {
       const char *what = nullptr;
       if (desc[s].rec_offset > n_records_total || desc[s].n_records > n_records_total - desc[s].rec_offset) what = "records out of range";
@@ -1741,11 +1720,11 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if ((rc = ensure(c, kSpOutRes, n_sub * sizeof(cabac_substream_result)))) return rc;
   if ((rc = ensure(c, kSpOutInfo, size_t(n_tu ? n_tu : 1) * sizeof(uint32_t)))) return rc;
   if (bin_counts && (rc = ensure(c, kSpOutCnt, size_t(n_sub) * CABAC_BIN_COUNT_WORDS * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, 6, payload_capacity ? payload_capacity : 16))) return rc;
-  if ((rc = ensure(c, 7, (size_t(n_sub) + 1) * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kPayload, payload_capacity ? payload_capacity : 16))) return rc;
+  if ((rc = ensure(c, kPayloadOffsets, (size_t(n_sub) + 1) * sizeof(uint64_t)))) return rc;
   if ((rc = ensure(c, kSpFlag, 64))) return rc;
   const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
-  if (rows && ((rc = ensure(c, kRowsFrom, link_bytes)) || (rc = ensure(c, kRowsAt, link_bytes)) || (rc = ensure(c, kSpInSync, link_bytes))))
+  if (rows && ((rc = ensure(c, kWppFrom, link_bytes)) || (rc = ensure(c, kWppAt, link_bytes)) || (rc = ensure(c, kSpInSync, link_bytes))))
     return rc;
   const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result), off_bytes = (size_t(n_sub) + 1) * sizeof(uint64_t);
   if ((rc = ensure_pinned(c, 0, res_bytes + off_bytes + 64))) return rc;
@@ -1768,13 +1747,13 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if ((rc = h2d(c, c->d_buf[kSpInSplice], splices, size_t(n_splice) * sizeof(cabac_splice), c->s_in))) return rc;
   if ((rc = h2d(c, c->d_buf[kSpInRec], records, n_records_total * sizeof(uint16_t), c->s_in))) return rc;
   if ((rc = h2d(c, c->d_buf[kSpInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), c->s_in))) return rc;
-  SpliceRows d_rows{};
+  Rows d_rows{};
   if (rows) {
-    if ((rc = h2d(c, c->d_buf[kRowsFrom], rows->d_sync_from, link_bytes, c->s_in))) return rc;
-    if ((rc = h2d(c, c->d_buf[kRowsAt], rows->d_sync_at, link_bytes, c->s_in))) return rc;
+    if ((rc = h2d(c, c->d_buf[kWppFrom], rows->d_sync_from, link_bytes, c->s_in))) return rc;
+    if ((rc = h2d(c, c->d_buf[kWppAt], rows->d_sync_at, link_bytes, c->s_in))) return rc;
     if (rows->d_sync_splice && (rc = h2d(c, c->d_buf[kSpInSync], rows->d_sync_splice, link_bytes, c->s_in))) return rc;
-    d_rows = SpliceRows{rows->n_level, rows->level_first, static_cast<const uint32_t *>(c->d_buf[kRowsFrom]),
-                        static_cast<const uint32_t *>(c->d_buf[kRowsAt]),
+    d_rows = Rows{rows->n_level, rows->level_first, static_cast<const uint32_t *>(c->d_buf[kWppFrom]),
+                        static_cast<const uint32_t *>(c->d_buf[kWppAt]),
                         rows->d_sync_splice ? static_cast<const uint32_t *>(c->d_buf[kSpInSync]) : nullptr};
   }
   HIP_TRY(c, hipEventRecord(c->ev_in[1], c->s_in));
@@ -1785,21 +1764,21 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
                                         static_cast<const uint16_t *>(c->d_buf[kSpInRec]), static_cast<const uint32_t *>(c->d_buf[kSpInFirst]),
                                         static_cast<const cabac_splice *>(c->d_buf[kSpInSplice]), n_splice, n_tu,
                                         static_cast<const cabac_tu_desc *>(c->d_buf[kSpInTu]), c->d_buf[kSpInCoeff], coeff_bytes,
-                                        static_cast<uint8_t *>(c->d_buf[6]), payload_capacity, static_cast<uint64_t *>(c->d_buf[7]),
+                                        static_cast<uint8_t *>(c->d_buf[kPayload]), payload_capacity, static_cast<uint64_t *>(c->d_buf[kPayloadOffsets]),
                                         static_cast<cabac_substream_result *>(c->d_buf[kSpOutRes]), static_cast<uint32_t *>(c->d_buf[kSpOutInfo]),
                                         bin_counts ? static_cast<uint32_t *>(c->d_buf[kSpOutCnt]) : nullptr, nullptr,
                                         rows ? &d_rows : nullptr);
   if (rc) return rc;
   HIP_TRY(c, cabac::launch_tu_info_any(c->stream, n_tu, static_cast<const uint32_t *>(c->d_buf[kSpOutInfo]), d_flag + 1));
   HIP_TRY(c, hipMemcpyAsync(h_res, c->d_buf[kSpOutRes], res_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h_off, c->d_buf[7], off_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h_off, c->d_buf[kPayloadOffsets], off_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(h_flag, d_flag + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev_k[1], c->stream));
   // the big things leave on the outgoing copy stream once the offsets are known
   HIP_TRY(c, hipEventSynchronize(c->ev_k[1]));
   const uint64_t n_pay = h_off[n_sub];
   if (n_pay > payload_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "payload_capacity too small");
-  if ((rc = d2h(c, payload, c->d_buf[6], n_pay, c->s_out))) return rc;
+  if ((rc = d2h(c, payload, c->d_buf[kPayload], n_pay, c->s_out))) return rc;
   if (tu_info && (rc = d2h(c, tu_info, c->d_buf[kSpOutInfo], size_t(n_tu) * sizeof(uint32_t), c->s_out))) return rc;
   if (bin_counts && (rc = d2h(c, bin_counts, c->d_buf[kSpOutCnt], size_t(n_sub) * CABAC_BIN_COUNT_WORDS * sizeof(uint32_t), c->s_out))) return rc;
   if ((rc = d2h_drain(c))) return rc;
@@ -1836,15 +1815,6 @@ int cabac_hip_encode_batch_residual16(cabac_hip_ctx *c, uint32_t n_sub, const ca
 }
 
 // ---- plan + values -> bytes (cabac_plan_write.hip; declared in cabac_hip_write_plan.h) --------------------------------------
-namespace {
-// device slots of the plan write: its per-substream words, and the descriptor list of the records pass
-enum { kPwPlan = 59, kPwTu = 60 };
-}  // namespace
-
-static int wpp_device_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
-                           uint8_t *d_bytes, uint8_t *d_bins, cabac_substream_result *d_results, uint32_t n_level,
-                           const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at);
-
 // sets (may be null): the encode launch starts from and writes context sets; rows (may be null): the emit walk notes each
 // substream's hand-over record and the WPP encode schedule takes the encode launch's place.  Not both.
 static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,
@@ -1852,7 +1822,7 @@ static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_
                                   const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes,
                                   uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_payload_offsets,
                                   cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info,
-                                  const cabac::CtxSets *sets, const PlanRows *rows) {
+                                  const cabac::CtxSets *sets, const Rows *rows) {
   if (!c || !d_payload_offsets || (n_sub && (!d_desc || !d_tile_first || !d_payload || !d_results)) || (n_tu && (!d_tu || !d_coeff)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
@@ -1872,7 +1842,7 @@ static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_
   const size_t n_blk = n_tu ? n_tu : 1, n_s = n_sub ? n_sub : 1;
   const size_t words = (3 * n_s + 2 + 1) & ~size_t(1);  // sub_n, sub_cap, sub_flag, err (+ pad)
   if ((rc = ensure(c, kSpCnt, 2 * n_blk * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, 5, cabac::residual_scratch_bytes(n_tu)))) return rc;
+  if ((rc = ensure(c, kResidualScratch, cabac::residual_scratch_bytes(n_tu)))) return rc;
   if ((rc = ensure(c, kPwPlan, words * sizeof(uint32_t) + (2 * n_s + 3) * sizeof(uint64_t)))) return rc;
   if ((rc = ensure(c, kPwTu, n_blk * sizeof(cabac_tu_desc)))) return rc;
   if ((rc = ensure(c, kSpDesc, n_s * sizeof(cabac_substream_desc)))) return rc;
@@ -1888,7 +1858,7 @@ static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_
   c->timed = false;
   {  // sizes and info words of ALL blocks: they do not depend on the guards, the guards depend on them
     Timed t(c, 5);
-    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[5]));
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[kResidualScratch]));
   }
   {
     Timed t(c, 28);
@@ -1912,7 +1882,7 @@ static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_
   {  // block records of the coded blocks, straight into the expanded substreams: in tus2 a skipped block is one the binariser
      // rejects, so it writes nothing whatever its coefficients hold (another list: the block order is made again)
     Timed t(c, 5);
-    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, tus2, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[5]));
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, tus2, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[kResidualScratch]));
   }
   if (rows) {  // the context-advance prefix passes per level, then one encode launch from the slots
     if (n_sub && (rc = wpp_device_impl(c, false, n_sub, desc2, exp_rec, slots, nullptr, d_results, rows->n_level, rows->level_first,
@@ -1954,7 +1924,7 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
                                  const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard, const void *coeff,
                                  int coeff_bytes, uint64_t n_coeff_total, uint8_t *payload, uint64_t payload_capacity,
                                  uint64_t *payload_offsets, cabac_substream_result *results, uint32_t *values_out, uint32_t *tu_info,
-                                 const PlanRows *rows = nullptr) {
+                                 const Rows *rows = nullptr) {
   if (!c || !payload_offsets || (n_sub && (!desc || !tile_first || !results || !payload)) ||
       (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
@@ -1967,16 +1937,14 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (n_elements_total && (!plan || !values_in)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (int bad = check_plan_host(c, n_sub, desc, nullptr, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, n_coeff_total)) return bad;
-  if (rows) {
-    if (int bad = check_levels(c, n_sub, rows->n_level, rows->level_first)) return bad;
-    if (int bad = check_links_host(c, n_sub, rows->n_level, rows->level_first, rows->d_sync_from)) return bad;
-  }
+  if (rows)
+    if (int bad = check_rows_host(c, n_sub, *rows)) return bad;
   DeviceGuard g(c->device);
   int rc;
   if ((rc = pipe_init(c))) return rc;
   const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), at_bytes = size_t(n_tu) * sizeof(uint32_t);
   const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
-  if (rows && ((rc = ensure(c, kRowsFrom, link_bytes)) || (rc = ensure(c, kRowsAt, link_bytes)))) return rc;
+  if (rows && ((rc = ensure(c, kWppFrom, link_bytes)) || (rc = ensure(c, kWppAt, link_bytes)))) return rc;
   const size_t plan_bytes = size_t(n_elements_total) * 2 * sizeof(uint32_t), value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
   if ((rc = ensure(c, kSpInDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
   if ((rc = ensure(c, kSpInFirst, first_bytes))) return rc;
@@ -1988,8 +1956,8 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   if ((rc = ensure(c, kElemGuard, at_bytes))) return rc;
   if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
   if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
-  if ((rc = ensure(c, 6, payload_capacity ? payload_capacity : 16))) return rc;
-  if ((rc = ensure(c, 7, (size_t(n_sub) + 1) * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kPayload, payload_capacity ? payload_capacity : 16))) return rc;
+  if ((rc = ensure(c, kPayloadOffsets, (size_t(n_sub) + 1) * sizeof(uint64_t)))) return rc;
   const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result), off_bytes = (size_t(n_sub) + 1) * sizeof(uint64_t);
   if ((rc = ensure_pinned(c, 0, res_bytes + off_bytes + 64))) return rc;
   auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
@@ -2006,12 +1974,12 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   if ((rc = h2d(c, c->d_buf[kElemPlan], plan, plan_bytes, c->s_in))) return rc;
   if ((rc = h2d(c, d_values, values_in, value_bytes, c->s_in))) return rc;
   if ((rc = h2d(c, c->d_buf[kSpInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), c->s_in))) return rc;
-  PlanRows d_rows{};
+  Rows d_rows{};
   if (rows) {
-    if ((rc = h2d(c, c->d_buf[kRowsFrom], rows->d_sync_from, link_bytes, c->s_in))) return rc;
-    if ((rc = h2d(c, c->d_buf[kRowsAt], rows->d_sync_at, link_bytes, c->s_in))) return rc;
-    d_rows = PlanRows{rows->n_level, rows->level_first, static_cast<const uint32_t *>(c->d_buf[kRowsFrom]),
-                      static_cast<const uint32_t *>(c->d_buf[kRowsAt])};
+    if ((rc = h2d(c, c->d_buf[kWppFrom], rows->d_sync_from, link_bytes, c->s_in))) return rc;
+    if ((rc = h2d(c, c->d_buf[kWppAt], rows->d_sync_at, link_bytes, c->s_in))) return rc;
+    d_rows = Rows{rows->n_level, rows->level_first, static_cast<const uint32_t *>(c->d_buf[kWppFrom]),
+                      static_cast<const uint32_t *>(c->d_buf[kWppAt])};
   }
   HIP_TRY(c, hipEventRecord(c->ev_in[0], c->s_in));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in[0], 0));
@@ -2021,18 +1989,19 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
                                    static_cast<const cabac_tu_desc *>(c->d_buf[kSpInTu]),
                                    tu_at ? static_cast<const uint32_t *>(c->d_buf[kUnitTuAt]) : nullptr,
                                    tu_guard ? static_cast<const uint32_t *>(c->d_buf[kElemGuard]) : nullptr, c->d_buf[kSpInCoeff],
-                                   coeff_bytes, static_cast<uint8_t *>(c->d_buf[6]), payload_capacity, static_cast<uint64_t *>(c->d_buf[7]),
+                                   coeff_bytes, static_cast<uint8_t *>(c->d_buf[kPayload]), payload_capacity,
+                                   static_cast<uint64_t *>(c->d_buf[kPayloadOffsets]),
                                    static_cast<cabac_substream_result *>(c->d_buf[kSpOutRes]), values_out ? d_values : nullptr,
                                    tu_info ? static_cast<uint32_t *>(c->d_buf[kSpOutInfo]) : nullptr, nullptr, rows ? &d_rows : nullptr);
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(h_res, c->d_buf[kSpOutRes], res_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h_off, c->d_buf[7], off_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h_off, c->d_buf[kPayloadOffsets], off_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev_k[1], c->stream));
   // the big things leave on the outgoing copy stream once the offsets are known
   HIP_TRY(c, hipEventSynchronize(c->ev_k[1]));
   const uint64_t n_pay = h_off[n_sub];
   if (n_pay > payload_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "payload_capacity too small");
-  if ((rc = d2h(c, payload, c->d_buf[6], n_pay, c->s_out))) return rc;
+  if ((rc = d2h(c, payload, c->d_buf[kPayload], n_pay, c->s_out))) return rc;
   // a stopped substream's values and info words are unspecified on the device: the caller's stay what they were
   int status = CABAC_HIP_OK;
   for (uint32_t s = 0; s < n_sub; s++) {
@@ -2069,12 +2038,6 @@ int cabac_hip_write_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
 
 // ---- pinned host memory for the caller's buffers ------------------------------------------------------------
 // ---- fused residual estimator (cabac_residual_estimate.hip) -------------------------------------------------------
-namespace {
-// device slots: the candidate order, and the staging of the host-pointer form
-enum { kEstScratch = 24, kEstInFirst = 25, kEstInTu = 26, kEstInCoeff = 27, kEstInState = 28, kEstInRate = 29, kEstInSet = 30,
-       kEstOutBits = 31, kEstOutInfo = 32 };
-}  // namespace
-
 static int estimate_residual_device_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
                                          const void *d_coeff, int coeff_bytes, const uint32_t *d_state, const uint8_t *d_rate,
                                          const uint32_t *d_set, uint64_t *d_frac_bits, uint64_t *d_tu_frac_bits, uint32_t *d_tu_info) {
@@ -2083,13 +2046,8 @@ static int estimate_residual_device_impl(cabac_hip_ctx *c, uint32_t n_cand, cons
   if (n_cand == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
   if (int rc = ensure(c, kEstScratch, cabac::residual_estimate_scratch_bytes(n_cand))) return rc;
-  Bracket br = bracket_for(c, 12);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_residual_estimate(c->stream, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state, d_rate, d_set,
-                                             d_frac_bits, d_tu_frac_bits, d_tu_info, c->d_buf[kEstScratch]));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 12, cabac::launch_residual_estimate(c->stream, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state, d_rate, d_set,
+                                                             d_frac_bits, d_tu_frac_bits, d_tu_info, c->d_buf[kEstScratch]));
 }
 
 int cabac_hip_estimate_residual_device(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
@@ -2171,9 +2129,6 @@ int cabac_hip_estimate_residual_batch(cabac_hip_ctx *c, uint32_t n_cand, const u
 
 // ---- emulation prevention (cabac_nal.hip; declared in cabac_hip_nal.h) ---------------------------------------------------
 namespace {
-// device slots: the chunk summaries and scans, and the staging of the host-pointer forms
-enum { kNalScratch = 33, kNalIn = 34, kNalInOff = 35, kNalOut = 36, kNalOutOff = 37, kNalLoc = 38, kNalStatus = 39 };
-
 int check_offsets_host(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t *offsets) {
   if (offsets[0] != 0) return fail(c, CABAC_HIP_ERR_INVALID, "offsets[0] must be 0");
   for (uint32_t s = 0; s < n_seg; s++)
@@ -2196,13 +2151,8 @@ int cabac_hip_nal_escape_device(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t
     return CABAC_HIP_OK;
   }
   if (int rc = ensure(c, kNalScratch, cabac::nal_scratch_bytes(payload_bytes_max))) return rc;
-  Bracket br = bracket_for(c, 13);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_nal_escape(c->stream, n_seg, d_offsets, d_payload, payload_bytes_max, d_nal, nal_capacity, d_nal_offsets,
-                                      d_status, c->d_buf[kNalScratch]));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 13, cabac::launch_nal_escape(c->stream, n_seg, d_offsets, d_payload, payload_bytes_max, d_nal, nal_capacity, d_nal_offsets,
+                                                      d_status, c->d_buf[kNalScratch]));
 }
 
 int cabac_hip_nal_unescape_device(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t *d_nal_offsets, const uint8_t *d_nal,
@@ -2217,13 +2167,8 @@ int cabac_hip_nal_unescape_device(cabac_hip_ctx *c, uint32_t n_seg, const uint64
     return CABAC_HIP_OK;
   }
   if (int rc = ensure(c, kNalScratch, cabac::nal_scratch_bytes(nal_bytes_max))) return rc;
-  Bracket br = bracket_for(c, 14);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_nal_unescape(c->stream, n_seg, d_nal_offsets, d_nal, nal_bytes_max, d_payload, payload_capacity, d_offsets,
-                                        d_locations, loc_capacity, loc_base, d_status, c->d_buf[kNalScratch]));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 14, cabac::launch_nal_unescape(c->stream, n_seg, d_nal_offsets, d_nal, nal_bytes_max, d_payload, payload_capacity, d_offsets,
+                                                        d_locations, loc_capacity, loc_base, d_status, c->d_buf[kNalScratch]));
 }
 
 int cabac_hip_nal_escape_batch(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t *offsets, const uint8_t *payload, uint8_t *nal,
@@ -2308,29 +2253,28 @@ int cabac_hip_encode_batch_nal(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
   int rc = check_desc_host(c, n_sub, desc, n_records_total, slots_end);
   if (rc) return rc;
   DeviceGuard g(c->device);
-  // device: [0] descriptors, [1] records, [2] byte slots, [3] results, [6] compacted payload, [7] payload offsets (the slots
-  // of cabac_hip_encode_batch), then the escape's own
+  // device: the slots of cabac_hip_encode_batch, then the escape's own
   const size_t off_bytes = (size_t(n_sub) + 1) * sizeof(uint64_t), res_bytes = size_t(n_sub) * sizeof(cabac_substream_result);
   const uint64_t cap = std::min<uint64_t>(nal_capacity, cabac_hip_nal_escape_bound(slots_end));
-  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, 1, n_records_total * 2))) return rc;
-  if ((rc = ensure(c, 2, slots_end))) return rc;
-  if ((rc = ensure(c, 3, res_bytes))) return rc;
-  if ((rc = ensure(c, 6, slots_end))) return rc;
-  if ((rc = ensure(c, 7, off_bytes))) return rc;
+  if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
+  if ((rc = ensure(c, kBytes, slots_end))) return rc;
+  if ((rc = ensure(c, kResults, res_bytes))) return rc;
+  if ((rc = ensure(c, kPayload, slots_end))) return rc;
+  if ((rc = ensure(c, kPayloadOffsets, off_bytes))) return rc;
   if ((rc = ensure(c, kNalOut, cap))) return rc;
   if ((rc = ensure(c, kNalOutOff, off_bytes))) return rc;
   if ((rc = ensure(c, kNalStatus, sizeof(cabac_nal_status)))) return rc;
-  auto *d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[0]);
-  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[3]);
+  auto *d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[kDesc]);
+  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[kResults]);
   auto *d_status = static_cast<cabac_nal_status *>(c->d_buf[kNalStatus]);
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[0], desc, n_sub * sizeof(cabac_substream_desc), hipMemcpyHostToDevice, c->stream));
-  if (n_records_total) HIP_TRY(c, hipMemcpyAsync(c->d_buf[1], records, n_records_total * 2, hipMemcpyHostToDevice, c->stream));
-  if ((rc = cabac_hip_encode_device(c, n_sub, d_desc, (const uint16_t *)c->d_buf[1], (uint8_t *)c->d_buf[2], d_res))) return rc;
-  if ((rc = cabac_hip_assemble_device(c, n_sub, d_desc, d_res, (const uint8_t *)c->d_buf[2], (uint8_t *)c->d_buf[6], slots_end,
-                                      (uint64_t *)c->d_buf[7])))
+  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc), hipMemcpyHostToDevice, c->stream));
+  if (n_records_total) HIP_TRY(c, hipMemcpyAsync(c->d_buf[kRecords], records, n_records_total * 2, hipMemcpyHostToDevice, c->stream));
+  if ((rc = cabac_hip_encode_device(c, n_sub, d_desc, (const uint16_t *)c->d_buf[kRecords], (uint8_t *)c->d_buf[kBytes], d_res))) return rc;
+  if ((rc = cabac_hip_assemble_device(c, n_sub, d_desc, d_res, (const uint8_t *)c->d_buf[kBytes], (uint8_t *)c->d_buf[kPayload], slots_end,
+                                      (uint64_t *)c->d_buf[kPayloadOffsets])))
     return rc;
-  if ((rc = cabac_hip_nal_escape_device(c, n_sub, (const uint64_t *)c->d_buf[7], (const uint8_t *)c->d_buf[6], slots_end,
+  if ((rc = cabac_hip_nal_escape_device(c, n_sub, (const uint64_t *)c->d_buf[kPayloadOffsets], (const uint8_t *)c->d_buf[kPayload], slots_end,
                                         (uint8_t *)c->d_buf[kNalOut], cap, (uint64_t *)c->d_buf[kNalOutOff], d_status)))
     return rc;
   HIP_TRY(c, hipMemcpyAsync(status, d_status, sizeof(cabac_nal_status), hipMemcpyDeviceToHost, c->stream));
@@ -2347,10 +2291,6 @@ int cabac_hip_encode_batch_nal(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
 
 // ---- search rounds (cabac_search.hip, cabac_residual_estimate.hip; declared in cabac_hip_search.h) -----------------------------
 namespace {
-// device slots: the staging of the host-pointer form (the rest of it goes through the estimator's kEst* slots)
-enum { kSearchInGroupFirst = 40, kSearchInOutSet = 41, kSearchInDist = 42, kSearchOutPick = 43, kSearchOutCost = 44,
-       kSearchInRecords = 45, kSearchInRecFirst = 46, kSearchInTuAt = 47 };
-
 // the side records of the host-pointer form of cabac_hip_search_unit.h (null: the round of cabac_hip_search.h)
 struct HostSide {
   const uint16_t *records;
@@ -2367,12 +2307,112 @@ struct HostPlan {
   const uint32_t *tu_at, *tu_guard;
   uint32_t *flags, *values_out;
 };
+
+// the most bins a value in its domain makes of an entry that is not bad (cabac_hip_search_plan.h, "THE MOST BINS")
+uint32_t plan_entry_max_bins(uint32_t w0) {
+  const uint32_t kind = w0 & 15u, p = w0 >> 4;
+  switch (kind) {
+  case CABAC_SE_CTX_BIN:
+  case CABAC_SE_TRM:
+  case CABAC_SE_ALIGN: return 1;
+  case CABAC_SE_EP_BINS:
+  case CABAC_SE_UNARY_EP: return p & 63u;
+  case CABAC_SE_UNARY_MAX: return (p >> 18) & 0xffu;
+  case CABAC_SE_TRUNC_BIN: {
+    uint32_t l = 0;
+    while ((p >> l) > 1u) l++;
+    return l + 1;
+  }
+  case CABAC_SE_EXP_GOLOMB: return 63u - (p & 31u);
+  case CABAC_SE_REM_ABS: {
+    const uint32_t rice = p & 31u, cutoff = (p >> 5) & 31u, longest = 32u - cutoff - ((p >> 10) & 63u);
+    return std::max(32u, cutoff + rice + (longest ? 2u * longest - 1u : 0u));
+  }
+  default: return 0;  // computed entries
+  }
+}
+
+// what cabac_hip_search_plan.h refuses on top of the other rounds; *record_bound: the most records the plans can resolve to
 int check_search_plan_host(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus, const HostPlan &hp,
-                           uint64_t n_coeff_total, uint64_t *record_bound);
+                           uint64_t n_coeff_total, uint64_t *record_bound) {
+  if (!hp.ent_first || (hp.n_entries_total && (!hp.plan || !hp.values_in))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  for (uint32_t k = 0; k < n_cand; k++)
+    if (hp.ent_first[k] > hp.ent_first[k + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "ent_first is not non-decreasing");
+  if (hp.ent_first[n_cand] > hp.n_entries_total) return fail(c, CABAC_HIP_ERR_INVALID, "ent_first ends past n_entries_total");
+  // the plans as the plan write's check sees them: one descriptor per candidate
+  std::vector<cabac_substream_desc> desc(n_cand);
+  for (uint32_t k = 0; k < n_cand; k++) {
+    const uint64_t n_ent = hp.ent_first[k + 1] - hp.ent_first[k];
+    if (n_ent > 0xffffffffull) return fail(c, CABAC_HIP_ERR_INVALID, "ent_first: a plan longer than 2^32 - 1 entries");
+    uint32_t at = 0;
+    for (uint32_t t = cand_first[k]; hp.tu_at && t < cand_first[k + 1]; t++) {
+      if (hp.tu_at[t] < at) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at decreases inside a candidate");
+      if (hp.tu_at[t] > n_ent) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at exceeds the candidate's plan length");
+      at = hp.tu_at[t];
+    }
+    desc[k] = cabac_substream_desc{};
+    desc[k].rec_offset = hp.ent_first[k];
+    desc[k].n_records = uint32_t(n_ent);
+  }
+  if (int bad = check_plan_host(c, n_cand, desc.data(), nullptr, cand_first, tus, hp.tu_at, hp.tu_guard, hp.plan, hp.n_entries_total,
+                                n_coeff_total, kPlanRules, "candidate"))
+    return bad;
+  uint64_t bound = 0;
+  for (uint64_t i = hp.ent_first[0]; i < hp.ent_first[n_cand]; i++) bound += plan_entry_max_bins(hp.plan[2 * i]);
+  *record_bound = bound;
+  return CABAC_HIP_OK;
+}
+
+// the plan inputs staged behind what search_round_batch_impl has staged, the resolved form in the library's own buffers (the
+// record buffer sized from the bound), and the round
 int search_plan_stage_and_run(cabac_hip_ctx *c, uint32_t n_group, uint32_t n_cand, uint32_t n_tu, int coeff_bytes, const HostPlan &hp,
                               uint64_t record_bound, bool has_out_set, bool has_dist, uint64_t lambda_q16, uint64_t *d_bits,
-                              uint64_t *d_tu_bits, uint32_t *d_info);
-int search_plan_fetch(cabac_hip_ctx *c, uint32_t n_cand, const HostPlan &hp, int *status);
+                              uint64_t *d_tu_bits, uint32_t *d_info) {
+  int rc;
+  const size_t at_bytes = size_t(n_tu) * sizeof(uint32_t), ent_bytes = (size_t(n_cand) + 1) * sizeof(uint64_t);
+  const size_t plan_bytes = size_t(hp.n_entries_total) * 2 * sizeof(uint32_t), value_bytes = size_t(hp.n_entries_total) * sizeof(uint32_t);
+  if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
+  if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
+  if ((rc = ensure(c, kUnitTuAt, at_bytes))) return rc;
+  if ((rc = ensure(c, kElemGuard, at_bytes))) return rc;
+  if ((rc = ensure(c, kPsEnt, ent_bytes))) return rc;
+  if ((rc = ensure(c, kPsFlags, size_t(n_cand ? n_cand : 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kSearchInRecords, size_t(record_bound) * sizeof(uint16_t)))) return rc;
+  if ((rc = ensure(c, kSearchInRecFirst, ent_bytes))) return rc;
+  if ((rc = ensure(c, kSearchInTuAt, at_bytes))) return rc;
+  if ((rc = ensure(c, kPwTu, size_t(n_tu ? n_tu : 1) * sizeof(cabac_tu_desc)))) return rc;
+  HIP_TRY(c, up(c, c->d_buf[kElemPlan], hp.plan, plan_bytes));
+  HIP_TRY(c, up(c, c->d_buf[kElemValues], hp.values_in, value_bytes));
+  HIP_TRY(c, up(c, c->d_buf[kPsEnt], hp.ent_first, ent_bytes));
+  if (hp.tu_at) HIP_TRY(c, up(c, c->d_buf[kUnitTuAt], hp.tu_at, at_bytes));
+  if (hp.tu_guard) HIP_TRY(c, up(c, c->d_buf[kElemGuard], hp.tu_guard, at_bytes));
+  return cabac_hip_search_plan_round_device(
+      c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand, (const uint32_t *)c->d_buf[kEstInFirst], n_tu,
+      (const cabac_tu_desc *)c->d_buf[kEstInTu], c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState],
+      (uint8_t *)c->d_buf[kEstInRate], (const uint32_t *)c->d_buf[kEstInSet], (const uint64_t *)c->d_buf[kPsEnt],
+      (const uint32_t *)c->d_buf[kElemPlan], (const uint32_t *)c->d_buf[kElemValues],
+      hp.tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr, hp.tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr,
+      has_out_set ? (const uint32_t *)c->d_buf[kSearchInOutSet] : nullptr, has_dist ? (const uint64_t *)c->d_buf[kSearchInDist] : nullptr,
+      lambda_q16, d_bits, (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info,
+      (uint32_t *)c->d_buf[kPsFlags], (uint64_t *)c->d_buf[kSearchInRecFirst], (uint16_t *)c->d_buf[kSearchInRecords], record_bound,
+      (uint32_t *)c->d_buf[kSearchInTuAt], (cabac_tu_desc *)c->d_buf[kPwTu], hp.values_out ? (uint32_t *)c->d_buf[kElemValues] : nullptr,
+      nullptr);
+}
+
+// the flags and the filled values back; *status: CABAC_HIP_ERR_SUBSTREAM when a candidate has a flag
+int search_plan_fetch(cabac_hip_ctx *c, uint32_t n_cand, const HostPlan &hp, int *status) {
+  std::vector<uint32_t> fl(n_cand);
+  if (n_cand) HIP_TRY(c, hipMemcpyAsync(fl.data(), c->d_buf[kPsFlags], size_t(n_cand) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (hp.values_out && hp.n_entries_total)
+    HIP_TRY(c, hipMemcpyAsync(hp.values_out, c->d_buf[kElemValues], size_t(hp.n_entries_total) * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                              c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (uint32_t k = 0; k < n_cand; k++) {
+    if (hp.flags) hp.flags[k] = fl[k];
+    if (fl[k]) *status = CABAC_HIP_ERR_SUBSTREAM;
+  }
+  return CABAC_HIP_OK;
+}
 
 int estimate_residual_ctx_device_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
                                       const void *d_coeff, int coeff_bytes, const uint32_t *d_state, const uint8_t *d_rate,
@@ -2384,14 +2424,9 @@ int estimate_residual_ctx_device_impl(cabac_hip_ctx *c, uint32_t n_cand, const u
   if (n_cand == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
   if (int rc = ensure(c, kEstScratch, cabac::residual_estimate_scratch_bytes(n_cand))) return rc;
-  Bracket br = bracket_for(c, 15);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_residual_estimate_export(c->stream, n_cand, nullptr, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state,
-                                                    d_rate, d_set, d_out_set, d_out_state, d_out_rate, d_frac_bits, d_tu_frac_bits,
-                                                    d_tu_info, c->d_buf[kEstScratch]));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 15, cabac::launch_residual_estimate_export(c->stream, n_cand, nullptr, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state,
+                                                                    d_rate, d_set, d_out_set, d_out_state, d_out_rate, d_frac_bits, d_tu_frac_bits,
+                                                                    d_tu_info, c->d_buf[kEstScratch]));
 }
 }  // namespace
 
@@ -2417,12 +2452,7 @@ int cabac_hip_search_select_device(cabac_hip_ctx *c, uint32_t n_group, const uin
   if (!c || (n_group && (!d_group_first || !d_frac_bits || !d_pick || !d_cost))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (n_group == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
-  Bracket br = bracket_for(c, 16);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_search_select(c->stream, n_group, 0xffffffffu, d_group_first, d_frac_bits, d_dist, lambda_q16, d_pick, d_cost));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 16, cabac::launch_search_select(c->stream, n_group, 0xffffffffu, d_group_first, d_frac_bits, d_dist, lambda_q16, d_pick, d_cost));
 }
 
 int cabac_hip_search_round_device(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *d_group_first, uint32_t n_cand,
@@ -2555,25 +2585,22 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
   if ((rc = ensure(c, kSearchOutCost, size_t(n_group) * sizeof(uint64_t)))) return rc;
   uint64_t *d_bits = static_cast<uint64_t *>(c->d_buf[kEstOutBits]), *d_tu_bits = d_bits + n_cand;
   uint32_t *d_info = static_cast<uint32_t *>(c->d_buf[kEstOutInfo]);
-  auto up = [&](int slot, const void *src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(c->d_buf[slot], src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
-  };
-  HIP_TRY(c, up(kEstInFirst, cand_first, (size_t(n_cand) + 1) * sizeof(uint32_t)));
-  HIP_TRY(c, up(kEstInTu, tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
-  HIP_TRY(c, up(kEstInCoeff, coeff, n_tu ? n_coeff_total * size_t(coeff_bytes) : 0));
-  HIP_TRY(c, up(kEstInState, state, n_cand ? set_words * sizeof(uint32_t) : 0));
-  HIP_TRY(c, up(kEstInRate, rate, n_cand ? set_words : 0));
-  HIP_TRY(c, up(kEstInSet, set, size_t(n_cand) * sizeof(uint32_t)));
-  HIP_TRY(c, up(kSearchInGroupFirst, group_first, (size_t(n_group) + 1) * sizeof(uint32_t)));
-  if (group_out_set) HIP_TRY(c, up(kSearchInOutSet, group_out_set, size_t(n_group) * sizeof(uint32_t)));
-  if (dist) HIP_TRY(c, up(kSearchInDist, dist, size_t(n_cand) * sizeof(uint64_t)));
+  HIP_TRY(c, up(c, c->d_buf[kEstInFirst], cand_first, (size_t(n_cand) + 1) * sizeof(uint32_t)));
+  HIP_TRY(c, up(c, c->d_buf[kEstInTu], tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
+  HIP_TRY(c, up(c, c->d_buf[kEstInCoeff], coeff, n_tu ? n_coeff_total * size_t(coeff_bytes) : 0));
+  HIP_TRY(c, up(c, c->d_buf[kEstInState], state, n_cand ? set_words * sizeof(uint32_t) : 0));
+  HIP_TRY(c, up(c, c->d_buf[kEstInRate], rate, n_cand ? set_words : 0));
+  HIP_TRY(c, up(c, c->d_buf[kEstInSet], set, size_t(n_cand) * sizeof(uint32_t)));
+  HIP_TRY(c, up(c, c->d_buf[kSearchInGroupFirst], group_first, (size_t(n_group) + 1) * sizeof(uint32_t)));
+  if (group_out_set) HIP_TRY(c, up(c, c->d_buf[kSearchInOutSet], group_out_set, size_t(n_group) * sizeof(uint32_t)));
+  if (dist) HIP_TRY(c, up(c, c->d_buf[kSearchInDist], dist, size_t(n_cand) * sizeof(uint64_t)));
   if (side) {
     if ((rc = ensure(c, kSearchInRecords, size_t(side->n_records_total) * sizeof(uint16_t)))) return rc;
     if ((rc = ensure(c, kSearchInRecFirst, (size_t(n_cand) + 1) * sizeof(uint64_t)))) return rc;
     if ((rc = ensure(c, kSearchInTuAt, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-    HIP_TRY(c, up(kSearchInRecords, side->records, size_t(side->n_records_total) * sizeof(uint16_t)));
-    HIP_TRY(c, up(kSearchInRecFirst, side->rec_first, (size_t(n_cand) + 1) * sizeof(uint64_t)));
-    if (side->tu_at) HIP_TRY(c, up(kSearchInTuAt, side->tu_at, size_t(n_tu) * sizeof(uint32_t)));
+    HIP_TRY(c, up(c, c->d_buf[kSearchInRecords], side->records, size_t(side->n_records_total) * sizeof(uint16_t)));
+    HIP_TRY(c, up(c, c->d_buf[kSearchInRecFirst], side->rec_first, (size_t(n_cand) + 1) * sizeof(uint64_t)));
+    if (side->tu_at) HIP_TRY(c, up(c, c->d_buf[kSearchInTuAt], side->tu_at, size_t(n_tu) * sizeof(uint32_t)));
   }
   if (n_tu) {  // blocks no candidate owns keep a defined value
     HIP_TRY(c, hipMemsetAsync(d_tu_bits, 0, size_t(n_tu) * sizeof(uint64_t), c->stream));
@@ -2600,14 +2627,11 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
                                        (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info);
   if (rc) return rc;
   std::vector<uint32_t> info(n_tu);
-  auto down = [&](void *dst, const void *src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-  };
-  HIP_TRY(c, down(frac_bits, d_bits, size_t(n_cand) * sizeof(uint64_t)));
-  if (tu_frac_bits) HIP_TRY(c, down(tu_frac_bits, d_tu_bits, size_t(n_tu) * sizeof(uint64_t)));
-  HIP_TRY(c, down(info.data(), d_info, size_t(n_tu) * sizeof(uint32_t)));
-  HIP_TRY(c, down(pick, c->d_buf[kSearchOutPick], size_t(n_group) * sizeof(uint32_t)));
-  HIP_TRY(c, down(cost, c->d_buf[kSearchOutCost], size_t(n_group) * sizeof(uint64_t)));
+  HIP_TRY(c, down(c, frac_bits, d_bits, size_t(n_cand) * sizeof(uint64_t)));
+  if (tu_frac_bits) HIP_TRY(c, down(c, tu_frac_bits, d_tu_bits, size_t(n_tu) * sizeof(uint64_t)));
+  HIP_TRY(c, down(c, info.data(), d_info, size_t(n_tu) * sizeof(uint32_t)));
+  HIP_TRY(c, down(c, pick, c->d_buf[kSearchOutPick], size_t(n_group) * sizeof(uint32_t)));
+  HIP_TRY(c, down(c, cost, c->d_buf[kSearchOutCost], size_t(n_group) * sizeof(uint64_t)));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   // the written sets: those of the groups that picked a candidate
   if (group_out_set && n_cand) {
@@ -2615,8 +2639,8 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
       const uint32_t o = group_out_set[k];
       if (o == CABAC_SEARCH_NO_SET || pick[k] == CABAC_SEARCH_NONE) continue;
       const size_t at = size_t(o) * CABAC_NUM_CONTEXTS;
-      HIP_TRY(c, down(state + at, (const uint32_t *)c->d_buf[kEstInState] + at, CABAC_NUM_CONTEXTS * sizeof(uint32_t)));
-      HIP_TRY(c, down(rate + at, (const uint8_t *)c->d_buf[kEstInRate] + at, CABAC_NUM_CONTEXTS));
+      HIP_TRY(c, down(c, state + at, (const uint32_t *)c->d_buf[kEstInState] + at, CABAC_NUM_CONTEXTS * sizeof(uint32_t)));
+      HIP_TRY(c, down(c, rate + at, (const uint8_t *)c->d_buf[kEstInRate] + at, CABAC_NUM_CONTEXTS));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
@@ -2657,14 +2681,9 @@ int cabac_hip_estimate_unit_device(cabac_hip_ctx *c, uint32_t n_cand, const uint
   if (n_cand == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
   if (int rc = ensure(c, kEstScratch, cabac::residual_estimate_scratch_bytes(n_cand))) return rc;
-  Bracket br = bracket_for(c, 19);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_unit_estimate(c->stream, n_cand, nullptr, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state, d_rate,
-                                         d_set, d_rec_first, d_records, d_tu_at, d_out_set, d_out_state, d_out_rate, d_frac_bits,
-                                         d_tu_frac_bits, d_tu_info, d_flags, c->d_buf[kEstScratch]));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 19, cabac::launch_unit_estimate(c->stream, n_cand, nullptr, n_cand, d_cand_first, d_tu, d_coeff, coeff_bytes, d_state, d_rate,
+                                                         d_set, d_rec_first, d_records, d_tu_at, d_out_set, d_out_state, d_out_rate, d_frac_bits,
+                                                         d_tu_frac_bits, d_tu_info, d_flags, c->d_buf[kEstScratch]));
 }
 
 int cabac_hip_search_unit_round_device(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *d_group_first, uint32_t n_cand,
@@ -2718,34 +2737,6 @@ int cabac_hip_search_unit_round_batch(cabac_hip_ctx *c, uint32_t n_group, const 
 
 // ---- search rounds over plans (declared in cabac_hip_search_plan.h; kernels in cabac_plan_search.hip) ---------------------------
 namespace {
-// device slots: the counts and (where the caller gives none) the flags of the resolve; the staging of the host-pointer form (the
-// rest of it goes through the slots of the other rounds, of the plan write and of the element parse)
-enum { kPsCnt = 61, kPsEnt = 62, kPsFlags = 63 };
-
-// the most bins a value in its domain makes of an entry that is not bad (cabac_hip_search_plan.h, "THE MOST BINS")
-uint32_t plan_entry_max_bins(uint32_t w0) {
-  const uint32_t kind = w0 & 15u, p = w0 >> 4;
-  switch (kind) {
-  case CABAC_SE_CTX_BIN:
-  case CABAC_SE_TRM:
-  case CABAC_SE_ALIGN: return 1;
-  case CABAC_SE_EP_BINS:
-  case CABAC_SE_UNARY_EP: return p & 63u;
-  case CABAC_SE_UNARY_MAX: return (p >> 18) & 0xffu;
-  case CABAC_SE_TRUNC_BIN: {
-    uint32_t l = 0;
-    while ((p >> l) > 1u) l++;
-    return l + 1;
-  }
-  case CABAC_SE_EXP_GOLOMB: return 63u - (p & 31u);
-  case CABAC_SE_REM_ABS: {
-    const uint32_t rice = p & 31u, cutoff = (p >> 5) & 31u, longest = 32u - cutoff - ((p >> 10) & 63u);
-    return std::max(32u, cutoff + rice + (longest ? 2u * longest - 1u : 0u));
-  }
-  default: return 0;  // computed entries
-  }
-}
-
 // sizes pass, count walk, scan, emit walk: the resolved form of every candidate.  d_flags: never null here
 int resolve_plan_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const uint64_t *d_ent_first, const uint32_t *d_plan,
                       const uint32_t *d_values_in, uint32_t n_tu, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
@@ -2755,14 +2746,14 @@ int resolve_plan_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_
   int rc;
   const size_t n_blk = n_tu ? n_tu : 1;
   if ((rc = ensure(c, kSpCnt, 2 * n_blk * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, 5, cabac::residual_scratch_bytes(n_tu)))) return rc;
+  if ((rc = ensure(c, kResidualScratch, cabac::residual_scratch_bytes(n_tu)))) return rc;
   uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kSpCnt]), *d_info = d_cnt + n_blk;
   uint32_t *cnt = static_cast<uint32_t *>(c->d_buf[kPsCnt]);
   const cabac::PlanResolveIn in{n_cand, d_cand_first, d_ent_first, d_plan, d_values_in, n_tu, d_tu, d_tu_at, d_tu_guard, d_info};
   const cabac::PlanResolveOut out{d_rec_first, d_records, d_tu_at_out, d_tu_out, d_values_out, d_tu_info};
   {  // info words of ALL blocks: they do not depend on the guards, the guards depend on them
     Timed t(c, 5);
-    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[5]));
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[kResidualScratch]));
   }
   {
     Timed t(c, 29);
@@ -2847,92 +2838,6 @@ int cabac_hip_search_plan_round_device(cabac_hip_ctx *c, uint32_t n_group, const
   return CABAC_HIP_OK;
 }
 
-namespace {
-int check_search_plan_host(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *cand_first, const cabac_tu_desc *tus, const HostPlan &hp,
-                           uint64_t n_coeff_total, uint64_t *record_bound) {
-  if (!hp.ent_first || (hp.n_entries_total && (!hp.plan || !hp.values_in))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  for (uint32_t k = 0; k < n_cand; k++)
-    if (hp.ent_first[k] > hp.ent_first[k + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "ent_first is not non-decreasing");
-  if (hp.ent_first[n_cand] > hp.n_entries_total) return fail(c, CABAC_HIP_ERR_INVALID, "ent_first ends past n_entries_total");
-  // the plans as the plan write's check sees them: one descriptor per candidate
-  std::vector<cabac_substream_desc> desc(n_cand);
-  for (uint32_t k = 0; k < n_cand; k++) {
-    const uint64_t n_ent = hp.ent_first[k + 1] - hp.ent_first[k];
-    if (n_ent > 0xffffffffull) return fail(c, CABAC_HIP_ERR_INVALID, "ent_first: a plan longer than 2^32 - 1 entries");
-    uint32_t at = 0;
-    for (uint32_t t = cand_first[k]; hp.tu_at && t < cand_first[k + 1]; t++) {
-      if (hp.tu_at[t] < at) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at decreases inside a candidate");
-      if (hp.tu_at[t] > n_ent) return fail(c, CABAC_HIP_ERR_INVALID, "tu_at exceeds the candidate's plan length");
-      at = hp.tu_at[t];
-    }
-    desc[k] = cabac_substream_desc{};
-    desc[k].rec_offset = hp.ent_first[k];
-    desc[k].n_records = uint32_t(n_ent);
-  }
-  if (int bad = check_plan_host(c, n_cand, desc.data(), nullptr, cand_first, tus, hp.tu_at, hp.tu_guard, hp.plan, hp.n_entries_total,
-                                n_coeff_total, "candidate"))
-    return bad;
-  uint64_t bound = 0;
-  for (uint64_t i = hp.ent_first[0]; i < hp.ent_first[n_cand]; i++) bound += plan_entry_max_bins(hp.plan[2 * i]);
-  *record_bound = bound;
-  return CABAC_HIP_OK;
-}
-
-// the plan inputs staged behind what search_round_batch_impl has staged, the resolved form in the library's own buffers (the
-// record buffer sized from the bound), and the round
-int search_plan_stage_and_run(cabac_hip_ctx *c, uint32_t n_group, uint32_t n_cand, uint32_t n_tu, int coeff_bytes, const HostPlan &hp,
-                              uint64_t record_bound, bool has_out_set, bool has_dist, uint64_t lambda_q16, uint64_t *d_bits,
-                              uint64_t *d_tu_bits, uint32_t *d_info) {
-  int rc;
-  const size_t at_bytes = size_t(n_tu) * sizeof(uint32_t), ent_bytes = (size_t(n_cand) + 1) * sizeof(uint64_t);
-  const size_t plan_bytes = size_t(hp.n_entries_total) * 2 * sizeof(uint32_t), value_bytes = size_t(hp.n_entries_total) * sizeof(uint32_t);
-  if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
-  if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
-  if ((rc = ensure(c, kUnitTuAt, at_bytes))) return rc;
-  if ((rc = ensure(c, kElemGuard, at_bytes))) return rc;
-  if ((rc = ensure(c, kPsEnt, ent_bytes))) return rc;
-  if ((rc = ensure(c, kPsFlags, size_t(n_cand ? n_cand : 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kSearchInRecords, size_t(record_bound) * sizeof(uint16_t)))) return rc;
-  if ((rc = ensure(c, kSearchInRecFirst, ent_bytes))) return rc;
-  if ((rc = ensure(c, kSearchInTuAt, at_bytes))) return rc;
-  if ((rc = ensure(c, kPwTu, size_t(n_tu ? n_tu : 1) * sizeof(cabac_tu_desc)))) return rc;
-  auto up = [&](int slot, const void *src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(c->d_buf[slot], src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
-  };
-  HIP_TRY(c, up(kElemPlan, hp.plan, plan_bytes));
-  HIP_TRY(c, up(kElemValues, hp.values_in, value_bytes));
-  HIP_TRY(c, up(kPsEnt, hp.ent_first, ent_bytes));
-  if (hp.tu_at) HIP_TRY(c, up(kUnitTuAt, hp.tu_at, at_bytes));
-  if (hp.tu_guard) HIP_TRY(c, up(kElemGuard, hp.tu_guard, at_bytes));
-  return cabac_hip_search_plan_round_device(
-      c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand, (const uint32_t *)c->d_buf[kEstInFirst], n_tu,
-      (const cabac_tu_desc *)c->d_buf[kEstInTu], c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState],
-      (uint8_t *)c->d_buf[kEstInRate], (const uint32_t *)c->d_buf[kEstInSet], (const uint64_t *)c->d_buf[kPsEnt],
-      (const uint32_t *)c->d_buf[kElemPlan], (const uint32_t *)c->d_buf[kElemValues],
-      hp.tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr, hp.tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr,
-      has_out_set ? (const uint32_t *)c->d_buf[kSearchInOutSet] : nullptr, has_dist ? (const uint64_t *)c->d_buf[kSearchInDist] : nullptr,
-      lambda_q16, d_bits, (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info,
-      (uint32_t *)c->d_buf[kPsFlags], (uint64_t *)c->d_buf[kSearchInRecFirst], (uint16_t *)c->d_buf[kSearchInRecords], record_bound,
-      (uint32_t *)c->d_buf[kSearchInTuAt], (cabac_tu_desc *)c->d_buf[kPwTu], hp.values_out ? (uint32_t *)c->d_buf[kElemValues] : nullptr,
-      nullptr);
-}
-
-// the flags and the filled values back; *status: CABAC_HIP_ERR_SUBSTREAM when a candidate has a flag
-int search_plan_fetch(cabac_hip_ctx *c, uint32_t n_cand, const HostPlan &hp, int *status) {
-  std::vector<uint32_t> fl(n_cand);
-  if (n_cand) HIP_TRY(c, hipMemcpyAsync(fl.data(), c->d_buf[kPsFlags], size_t(n_cand) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  if (hp.values_out && hp.n_entries_total)
-    HIP_TRY(c, hipMemcpyAsync(hp.values_out, c->d_buf[kElemValues], size_t(hp.n_entries_total) * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                              c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (uint32_t k = 0; k < n_cand; k++) {
-    if (hp.flags) hp.flags[k] = fl[k];
-    if (fl[k]) *status = CABAC_HIP_ERR_SUBSTREAM;
-  }
-  return CABAC_HIP_OK;
-}
-}  // namespace
-
 int cabac_hip_search_plan_round_batch(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *group_first, uint32_t n_cand,
                                       const uint32_t *cand_first, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
                                       uint64_t n_coeff_total, uint32_t *state, uint8_t *rate, uint32_t n_sets, const uint32_t *set,
@@ -2948,8 +2853,6 @@ int cabac_hip_search_plan_round_batch(cabac_hip_ctx *c, uint32_t n_group, const 
 
 // ---- the winner log (declared in cabac_hip_search_emit.h; kernels in cabac_search_emit.hip) -------------------------------------
 namespace {
-enum { kLogScratch = 48, kLogDesc = 49, kLogFirst = 50, kLogRec = 51, kLogSplice = 52 };
-
 void log_free(cabac_search_log *log) {
   void *p[] = {log->a.counters, log->a.entries, log->a.records, log->a.tu, log->a.tu_at, log->a.coeff, log->a.chain_rec, log->a.chain_tu,
                log->a.mark_rec, log->a.mark_tu};
@@ -3054,7 +2957,7 @@ int cabac_hip_search_log_view(const cabac_search_log *log, cabac_search_log_view
 // (its d_sync_at and d_sync_splice are not read)
 static int search_log_encode_impl(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
                                   uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
-                                  uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets, const SpliceRows *rows) {
+                                  uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets, const Rows *rows) {
   if (!log) return CABAC_HIP_ERR_INVALID;
   cabac_hip_ctx *c = log->ctx;
   if (!d_desc || !d_payload || !d_payload_offsets || !d_results) return fail(c, CABAC_HIP_ERR_INVALID, "null");
@@ -3090,8 +2993,8 @@ static int search_log_encode_impl(cabac_search_log *log, const cabac_substream_d
     Timed t(c, 24);
     HIP_TRY(c, cabac::launch_search_log_place(c->stream, a, d_desc, n_entry, cnt.n_record, n_tu, desc2, first, rec, splices));
   }
-  SpliceRows marked{};
-  if (rows) marked = SpliceRows{rows->n_level, rows->level_first, rows->d_sync_from, a.mark_rec, a.mark_tu};
+  Rows marked{};
+  if (rows) marked = Rows{rows->n_level, rows->level_first, rows->d_sync_from, a.mark_rec, a.mark_tu};
   return encode_residual_device_impl(c, a.n_chain, desc2, rec, first, splices, n_tu, n_tu, a.tu, a.coeff, log->coeff_bytes, d_payload,
                                      payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, sets,
                                      rows ? &marked : nullptr);
@@ -3104,21 +3007,7 @@ int cabac_hip_search_log_encode_device(cabac_search_log *log, const cabac_substr
                                 nullptr);
 }
 
-// ---- context sets and WPP (cabac_hip_ctx_sets.h) -------------------------------------------------------------------
-// device slots: the slots of a WPP call (one set per substream), its prefix descriptors, its checked links and slot indices,
-// the results of its prefix passes, and the links of the host-pointer forms
-enum { kWppState = 64, kWppRate = 65, kWppDesc = 66, kWppIndex = 67, kWppRes = 68, kWppFrom = 69, kWppAt = 70 };
-static_assert(kRowsState == kWppState && kRowsRate == kWppRate && kRowsFrom == kWppFrom && kRowsAt == kWppAt,
-              "the plan rows share the WPP calls' slots and link staging");
-
-static bool sets_args_ok(uint32_t n_sub, uint32_t n_sets, const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
-                         const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate) {
-  if (n_sub == 0) return true;
-  if (d_start_set && n_sets && (!d_state || !d_rate)) return false;
-  if (d_out_set && n_sets && (!d_out_state || !d_out_rate)) return false;
-  return true;
-}
-
+// ---- context sets and WPP (cabac_hip_ctx_sets.h; the schedule of a WPP call is wpp_device_impl above) ---------------------------
 int cabac_hip_encode_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
                                  uint8_t *d_bytes, cabac_substream_result *d_results, uint32_t n_sets, const uint32_t *d_state,
                                  const uint8_t *d_rate, const uint32_t *d_start_set, const uint32_t *d_out_set, uint32_t *d_out_state,
@@ -3128,12 +3017,7 @@ int cabac_hip_encode_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
-  Bracket br = bracket_for(c, 30);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, d_desc, d_records, d_bytes, d_results, 0, &sets));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 30, cabac::launch_encode(c->stream, c->enc_variant, n_sub, d_desc, d_records, d_bytes, d_results, 0, &sets));
 }
 
 int cabac_hip_decode_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
@@ -3145,12 +3029,7 @@ int cabac_hip_decode_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
-  Bracket br = bracket_for(c, 31);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_decode(c->stream, c->dec_variant, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, 0, c->d_select, &sets));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 31, cabac::launch_decode(c->stream, c->dec_variant, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, 0, c->d_select, &sets));
 }
 
 int cabac_hip_ctx_advance_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
@@ -3161,90 +3040,7 @@ int cabac_hip_ctx_advance_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
-  Bracket br = bracket_for(c, 32);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_ctx_advance(c->stream, n_sub, d_desc, d_records, sets, d_flags));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
-}
-
-// level_first as the WPP calls need it: n_level + 1 entries, non-decreasing, from 0 to n_sub
-static int check_levels(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, const uint32_t *level_first) {
-  if (n_sub == 0) return CABAC_HIP_OK;
-  if (n_level == 0 || !level_first || level_first[0] != 0u || level_first[n_level] != n_sub)
-    return fail(c, CABAC_HIP_ERR_INVALID, "level_first must run from 0 to n_sub");
-  for (uint32_t l = 0; l < n_level; l++)
-    if (level_first[l] > level_first[l + 1]) {
-      char buf[96];
-      snprintf(buf, sizeof buf, "level_first decreases at level %u", l + 1);
-      return fail(c, CABAC_HIP_ERR_INVALID, buf);
-    }
-  return CABAC_HIP_OK;
-}
-
-// the links of a host-pointer form (level_first checked): every link points into an earlier level
-static int check_links_host(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_level, const uint32_t *level_first, const uint32_t *sync_from) {
-  for (uint32_t l = 0; l < n_level; l++)
-    for (uint32_t s = level_first[l]; s < level_first[l + 1]; s++) {
-      const uint32_t from = sync_from[s];
-      if (from == CABAC_CTX_NO_SET || from < level_first[l]) continue;
-      char buf[128];
-      if (from >= n_sub) snprintf(buf, sizeof buf, "substream %u links to %u, beyond the batch", s, from);
-      else snprintf(buf, sizeof buf, "substream %u (level %u) links to %u in the same or a later level", s, l, from);
-      return fail(c, CABAC_HIP_ERR_INVALID, buf);
-    }
-  return CABAC_HIP_OK;
-}
-
-// The schedule of a WPP call on the ctx stream: per level the level kernel (prefix descriptors, checked links, slot indices), for
-// every level but the last its prefix pass into the slots, then the pass over all substreams from their slots.  encode: d_bins
-// null, the prefix pass is the context advance; decode: the sets decoder (its bins land in d_bins and are written again, the
-// same, by the last pass; its results go to a scratch).
-static int wpp_device_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
-                           uint8_t *d_bytes, uint8_t *d_bins, cabac_substream_result *d_results, uint32_t n_level,
-                           const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
-  if (!c || (n_sub && (!d_desc || !d_records || !d_bytes || !d_results || (decode && !d_bins) || !d_sync_from || !d_sync_at)))
-    return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  int rc = check_levels(c, n_sub, n_level, level_first);
-  if (rc) return rc;
-  DeviceGuard g(c->device);
-  const size_t set_words = size_t(n_sub) * CABAC_NUM_CONTEXTS;
-  if ((rc = ensure(c, kWppState, set_words * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kWppRate, set_words))) return rc;
-  if ((rc = ensure(c, kWppDesc, size_t(n_sub) * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, kWppIndex, 2 * size_t(n_sub) * sizeof(uint32_t)))) return rc;
-  if (decode && (rc = ensure(c, kWppRes, size_t(n_sub) * sizeof(cabac_substream_result)))) return rc;
-  auto *slot_state = static_cast<uint32_t *>(c->d_buf[kWppState]);
-  auto *slot_rate = static_cast<uint8_t *>(c->d_buf[kWppRate]);
-  auto *pre_desc = static_cast<cabac_substream_desc *>(c->d_buf[kWppDesc]);
-  auto *start = static_cast<uint32_t *>(c->d_buf[kWppIndex]);
-  auto *slot = start + n_sub;
-  auto *pre_res = static_cast<cabac_substream_result *>(c->d_buf[kWppRes]);
-  for (uint32_t l = 0; l < n_level; l++) {
-    const uint32_t first = level_first[l], n = level_first[l + 1] - first;
-    if (n == 0) continue;
-    HIP_TRY(c, cabac::launch_wpp_level(c->stream, first, n, d_desc, d_sync_from, d_sync_at, pre_desc, start, slot));
-    if (l + 1 == n_level) break;
-    const cabac::CtxSets sets{n_sub, slot_state, slot_rate, start + first, slot + first, slot_state, slot_rate};
-    Timed t(c, 33);
-    if (decode)
-      HIP_TRY(c, cabac::launch_decode(c->stream, c->dec_variant, n, pre_desc + first, d_records, d_bytes, d_bins, pre_res + first, 0,
-                                      c->d_select, &sets));
-    else
-      HIP_TRY(c, cabac::launch_ctx_advance(c->stream, n, pre_desc + first, d_records, sets, nullptr));
-  }
-  const cabac::CtxSets sets{n_sub, slot_state, slot_rate, start, nullptr, nullptr, nullptr};
-  Bracket br = bracket_for(c, decode ? 31 : 30);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  if (decode)
-    HIP_TRY(c, cabac::launch_decode(c->stream, c->dec_variant, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, 0, c->d_select, &sets));
-  else
-    HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, d_desc, d_records, d_bytes, d_results, 0, &sets));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 32, cabac::launch_ctx_advance(c->stream, n_sub, d_desc, d_records, sets, d_flags));
 }
 
 int cabac_hip_encode_wpp_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
@@ -3275,19 +3071,19 @@ static int wpp_batch_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const c
   DeviceGuard g(c->device);
   if ((rc = pipe_init(c))) return rc;
   const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result);
-  if ((rc = ensure(c, 0, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, 1, n_records_total * 2))) return rc;
-  if ((rc = ensure(c, 2, bytes_total + 4))) return rc;
-  if ((rc = ensure(c, 3, res_bytes))) return rc;
-  if (decode && (rc = ensure(c, 4, n_records_total + 8))) return rc;
+  if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
+  if ((rc = ensure(c, kBytes, bytes_total + 4))) return rc;
+  if ((rc = ensure(c, kResults, res_bytes))) return rc;
+  if (decode && (rc = ensure(c, kBins, n_records_total + 8))) return rc;
   if ((rc = ensure(c, kWppFrom, size_t(n_sub) * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(c, kWppAt, size_t(n_sub) * sizeof(uint32_t)))) return rc;
   if ((rc = ensure_pinned(c, 0, res_bytes))) return rc;
-  auto *d_desc = static_cast<cabac_substream_desc *>(c->d_buf[0]);
-  auto *d_rec = static_cast<uint16_t *>(c->d_buf[1]);
-  auto *d_slots = static_cast<uint8_t *>(c->d_buf[2]);
-  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[3]);
-  auto *d_bins = static_cast<uint8_t *>(c->d_buf[4]);
+  auto *d_desc = static_cast<cabac_substream_desc *>(c->d_buf[kDesc]);
+  auto *d_rec = static_cast<uint16_t *>(c->d_buf[kRecords]);
+  auto *d_slots = static_cast<uint8_t *>(c->d_buf[kBytes]);
+  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[kResults]);
+  auto *d_bins = static_cast<uint8_t *>(c->d_buf[kBins]);
   auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
   hipStream_t st = c->stream;
   HIP_TRY(c, hipStreamSynchronize(st));
@@ -3349,48 +3145,8 @@ int cabac_hip_plan_parse_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cab
   if (n_sub == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
-  Bracket br = bracket_for(c, 34);
-  HIP_TRY(c, hipEventRecord(br.a, c->stream));
-  HIP_TRY(c, cabac::launch_plan_parse_sets(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
-                                           coeff_bytes, d_values, d_tu_info, d_results, sets, d_out_at, n_sets, 0xFFFFFFFFu));
-  HIP_TRY(c, hipEventRecord(br.b, c->stream));
-  c->timed = (br.a == c->ev_start);
-  return CABAC_HIP_OK;
-}
-
-// The schedule of a rows parse on the ctx stream: for every non-empty level ONE launch of the sets kernel over that level's
-// substreams.  A substream starts from the slot of its link (checked on the device against the level: it must lie below the
-// level's first substream) and writes its own slot at its hand-over entry; the last level writes none.
-static int parse_rows_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
-                                  const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
-                                  const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes, uint32_t *d_values,
-                                  uint32_t *d_tu_info, cabac_substream_result *d_results, const PlanRows &rows) {
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results || !rows.d_sync_from || !rows.d_sync_at)))
-    return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  int rc = check_levels(c, n_sub, rows.n_level, rows.level_first);
-  if (rc) return rc;
-  DeviceGuard g(c->device);
-  const size_t set_words = size_t(n_sub) * CABAC_NUM_CONTEXTS;
-  if ((rc = ensure(c, kRowsState, set_words * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kRowsRate, set_words))) return rc;
-  auto *slot_state = static_cast<uint32_t *>(c->d_buf[kRowsState]);
-  auto *slot_rate = static_cast<uint8_t *>(c->d_buf[kRowsRate]);
-  uint32_t last = rows.n_level;  // the last non-empty level
-  while (last > 0 && rows.level_first[last - 1] == rows.level_first[last]) last--;
-  c->timed = false;
-  for (uint32_t l = 0; l < last; l++) {
-    const uint32_t first = rows.level_first[l], n = rows.level_first[l + 1] - first;
-    if (n == 0) continue;
-    const bool hands_over = l + 1 < last;
-    const cabac::CtxSets sets{n_sub, slot_state, slot_rate, rows.d_sync_from + first, nullptr, slot_state, slot_rate};
-    Timed t(c, 35);
-    HIP_TRY(c, cabac::launch_plan_parse_sets(c->stream, n, d_desc + first, d_bytes, d_tile_first + first, d_tu, d_tu_at, d_tu_guard, d_plan,
-                                             d_coeff, coeff_bytes, d_values, d_tu_info, d_results + first, sets, rows.d_sync_at + first,
-                                             first, hands_over ? first : 0xFFFFFFFFu));
-  }
-  return CABAC_HIP_OK;
+  return TIMED_LAUNCH(c, 34, cabac::launch_plan_parse_sets(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
+                                                           coeff_bytes, d_values, d_tu_info, d_results, sets, d_out_at, n_sets, 0xFFFFFFFFu));
 }
 
 int cabac_hip_plan_parse_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
@@ -3399,7 +3155,7 @@ int cabac_hip_plan_parse_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cab
                                      uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results, uint32_t n_level,
                                      const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
   return parse_rows_device_impl(c, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff, coeff_bytes, d_values,
-                                d_tu_info, d_results, PlanRows{n_level, level_first, d_sync_from, d_sync_at});
+                                d_tu_info, d_results, Rows{n_level, level_first, d_sync_from, d_sync_at});
 }
 
 int cabac_hip_plan_parse_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
@@ -3408,9 +3164,9 @@ int cabac_hip_plan_parse_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const caba
                                     int coeff_bytes, uint64_t n_coeff_total, uint32_t *values, uint32_t *tu_info,
                                     cabac_substream_result *results, uint32_t n_level, const uint32_t *level_first,
                                     const uint32_t *sync_from, const uint32_t *sync_at) {
-  const PlanRows rows{n_level, level_first, sync_from, sync_at};
+  const Rows rows{n_level, level_first, sync_from, sync_at};
   return parse_plan_batch_impl(c, n_sub, desc, bytes, bytes_total, tile_first, tus, tu_at, tu_guard, plan, n_elements_total, coeff,
-                               coeff_bytes, n_coeff_total, values, tu_info, results, &rows);
+                               coeff_bytes, n_coeff_total, values, tu_info, results, kPlanRules, &rows);
 }
 
 int cabac_hip_plan_write_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,
@@ -3433,7 +3189,7 @@ int cabac_hip_plan_write_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cab
                                      uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_payload_offsets,
                                      cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info, uint32_t n_level,
                                      const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
-  const PlanRows rows{n_level, level_first, d_sync_from, d_sync_at};
+  const Rows rows{n_level, level_first, d_sync_from, d_sync_at};
   return write_plan_device_impl(c, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, coeff_bytes,
                                 d_payload, payload_capacity, d_payload_offsets, d_results, d_values_out, d_tu_info, nullptr, &rows);
 }
@@ -3444,7 +3200,7 @@ int cabac_hip_plan_write_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const caba
                                     int coeff_bytes, uint64_t n_coeff_total, uint8_t *payload, uint64_t payload_capacity,
                                     uint64_t *payload_offsets, cabac_substream_result *results, uint32_t *values_out, uint32_t *tu_info,
                                     uint32_t n_level, const uint32_t *level_first, const uint32_t *sync_from, const uint32_t *sync_at) {
-  const PlanRows rows{n_level, level_first, sync_from, sync_at};
+  const Rows rows{n_level, level_first, sync_from, sync_at};
   return host_call_exit(c, write_plan_batch_impl(c, n_sub, desc, plan, values_in, n_elements_total, tile_first, tus, tu_at, tu_guard,
                                                  coeff, coeff_bytes, n_coeff_total, payload, payload_capacity, payload_offsets, results,
                                                  values_out, tu_info, &rows));
@@ -3471,7 +3227,7 @@ int cabac_hip_encode_residual_rows_device(cabac_hip_ctx *c, uint32_t n_sub, cons
                                           uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
                                           uint32_t *d_tu_info, uint32_t *d_bin_counts, uint32_t n_level, const uint32_t *level_first,
                                           const uint32_t *d_sync_from, const uint32_t *d_sync_at, const uint32_t *d_sync_splice) {
-  const SpliceRows rows{n_level, level_first, d_sync_from, d_sync_at, d_sync_splice};
+  const Rows rows{n_level, level_first, d_sync_from, d_sync_at, d_sync_splice};
   return encode_residual_device_impl(c, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes,
                                      d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr, &rows);
 }
@@ -3483,7 +3239,7 @@ int cabac_hip_encode_residual_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const
                                          cabac_substream_result *results, uint32_t *tu_info, uint32_t *bin_counts, uint32_t n_level,
                                          const uint32_t *level_first, const uint32_t *sync_from, const uint32_t *sync_at,
                                          const uint32_t *sync_splice) {
-  const SpliceRows rows{n_level, level_first, sync_from, sync_at, sync_splice};
+  const Rows rows{n_level, level_first, sync_from, sync_at, sync_splice};
   return host_call_exit(c, encode_batch_residual_impl(c, n_sub, desc, records, n_records_total, splice_first, splices, n_tu, tus, coeff,
                                                       coeff_bytes, n_coeff_total, payload, payload_capacity, payload_offsets, results,
                                                       tu_info, bin_counts, &rows));
@@ -3521,7 +3277,7 @@ int cabac_hip_search_log_encode_rows_device(cabac_search_log *log, const cabac_s
   if (!log) return CABAC_HIP_ERR_INVALID;
   if (!d_sync_from) return fail(log->ctx, CABAC_HIP_ERR_INVALID, "null");
   if (int bad = check_levels(log->ctx, log->a.n_chain, n_level, level_first)) return bad;  // before the first wait
-  const SpliceRows rows{n_level, level_first, d_sync_from, nullptr, nullptr};
+  const Rows rows{n_level, level_first, d_sync_from, nullptr, nullptr};
   return search_log_encode_impl(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr,
                                 &rows);
 }
