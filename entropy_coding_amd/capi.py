@@ -104,6 +104,20 @@ EXPORTS_SPLICE_ROWS = [
     "cabac_hip_encode_residual_sets_device", "cabac_hip_encode_residual_rows_device", "cabac_hip_encode_residual_rows_batch",
     "cabac_hip_search_log_mark_device", "cabac_hip_search_log_encode_sets_device", "cabac_hip_search_log_encode_rows_device",
 ]
+# include/cabac_hip_workspace.h (the fixed workspace: the nine calls that code a slice to bytes without a host wait;
+# tests/test_workspace_abi.py compares)
+EXPORTS_WORKSPACE = [
+    "cabac_hip_workspace_bound", "cabac_hip_workspace_fix", "cabac_hip_workspace_release", "cabac_hip_workspace_status_device",
+    "cabac_hip_workspace_status", "cabac_hip_workspace_waits",
+]
+WS_ROWS = 0x1                                                    # CABAC_WS_ROWS (cabac_workspace_sizes.flags)
+WS_OVER_RECORDS, WS_OVER_SLOTS, WS_BAD_SPLICES, WS_RECORDS_32BIT, WS_LOG_OVERFLOW, WS_LOG_DAMAGED = 1, 2, 4, 8, 16, 32   # status flags
+WS_NONE_VOIDED = 0xFFFFFFFF                                      # CABAC_WS_NONE_VOIDED
+WORKSPACE_SIZES_DTYPE = np.dtype([("n_sub", "<u4"), ("n_tu", "<u4"), ("n_entries", "<u8"), ("expanded_records", "<u8"),
+                                  ("slot_bytes", "<u8"), ("log_records", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])
+WORKSPACE_STATUS_DTYPE = np.dtype([("records_needed", "<u8"), ("slot_bytes_needed", "<u8"), ("flags", "<u4"), ("n_calls", "<u4"),
+                                   ("n_voided", "<u4"), ("first_voided", "<u4")])
+assert WORKSPACE_SIZES_DTYPE.itemsize == 48 and WORKSPACE_STATUS_DTYPE.itemsize == 32
 CTX_NO_SET = 0xFFFFFFFF                                          # CABAC_CTX_NO_SET
 RES_BAD_SET = 0x40                                               # CABAC_RES_BAD_SET
 PE_COND, PE_BLOCK_INFO = 9, 10                                   # CABAC_PE_COND, CABAC_PE_BLOCK_INFO
@@ -372,6 +386,14 @@ def load_library():
         L.cabac_hip_search_log_mark_device.argtypes = [vp, ctypes.c_uint32, vp]
         L.cabac_hip_search_log_encode_sets_device.argtypes = L.cabac_hip_search_log_encode_device.argtypes + sets7
         L.cabac_hip_search_log_encode_rows_device.argtypes = L.cabac_hip_search_log_encode_device.argtypes + [ctypes.c_uint32, vp, vp]
+    # (CABAC_HIP_LIBRARY may name a build from before cabac_hip_workspace.h)
+    if hasattr(L, "cabac_hip_workspace_fix"):
+        L.cabac_hip_workspace_bound.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, vp, vp]
+        L.cabac_hip_workspace_fix.argtypes = [vp, vp]
+        L.cabac_hip_workspace_release.argtypes = [vp]
+        L.cabac_hip_workspace_status_device.argtypes = [vp, vp]
+        L.cabac_hip_workspace_status.argtypes = [vp, vp]
+        L.cabac_hip_workspace_waits.argtypes = [vp, vp]
     L.cabac_hip_nal_escape_bound.restype = ctypes.c_size_t
     L.cabac_hip_nal_escape_bound.argtypes = [ctypes.c_uint64]
     L.cabac_hip_nal_escape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
@@ -455,6 +477,15 @@ def nal_escape_bound(n_bytes):
     return load_library().cabac_hip_nal_escape_bound(n_bytes)
 
 
+def workspace_bound(n_sub, n_host_records, n_tu, n_coded_coeff):
+    """cabac_hip_workspace_bound: (expanded_records, slot_bytes) that no call of that size can exceed.  Host arithmetic only."""
+    out = np.zeros(2, np.uint64)
+    rc = load_library().cabac_hip_workspace_bound(n_sub, n_host_records, n_tu, n_coded_coeff, vp(out.ctypes.data), vp(out.ctypes.data + 8))
+    if rc != 0:
+        raise CabacHipError(rc, "cabac_hip_workspace_bound")
+    return int(out[0]), int(out[1])
+
+
 class CabacHip:
     """One codec context = one device + one HIP stream (stream=None: a non-blocking stream of the ctx's own; otherwise the
     caller's stream handle, 0 being the device's default stream).  Raises if there is no GPU (no CPU fallback)."""
@@ -501,6 +532,35 @@ class CabacHip:
     def synchronize(self):
         self._check(self.L.cabac_hip_synchronize(self.h))
 
+    # ---- the fixed workspace (cabac_hip_workspace.h) ----
+    workspace_bound = staticmethod(workspace_bound)
+
+    def workspace_fix(self, n_sub, n_tu, expanded_records, slot_bytes, n_entries=0, log_records=0, rows=False):
+        """Fix the workspace: the nine calls of cabac_hip_workspace.h then queue their work and return.  May block and allocate."""
+        z = np.zeros(1, WORKSPACE_SIZES_DTYPE)
+        z["n_sub"], z["n_tu"], z["n_entries"], z["expanded_records"] = n_sub, n_tu, n_entries, expanded_records
+        z["slot_bytes"], z["log_records"], z["flags"] = slot_bytes, log_records, WS_ROWS if rows else 0
+        self._check(self.L.cabac_hip_workspace_fix(self.h, vp(z.ctypes.data)))
+
+    def workspace_release(self):
+        self._check(self.L.cabac_hip_workspace_release(self.h))
+
+    def workspace_status(self):
+        """The status (one WORKSPACE_STATUS_DTYPE record) once the ctx's stream has drained."""
+        st = np.zeros(1, WORKSPACE_STATUS_DTYPE)
+        self._check(self.L.cabac_hip_workspace_status(self.h, vp(st.ctypes.data)))
+        return st[0]
+
+    def workspace_status_device(self, d_out):
+        """Queue a copy of the status into d_out (device memory or pinned host memory): stream-ordered, no wait."""
+        self._check(self.L.cabac_hip_workspace_status_device(self.h, vp(d_out)))
+
+    def workspace_waits(self):
+        """Blocking runtime calls the library has issued for this ctx so far (never decreases)."""
+        n = ctypes.c_uint64(0)
+        self._check(self.L.cabac_hip_workspace_waits(self.h, ctypes.byref(n)))
+        return n.value
+
     def wait_event(self, hip_event):
         """The ctx's stream waits for `hip_event` (a hipEvent_t, e.g. torch.cuda.Event(...).cuda_event after record())."""
         self._check(self.L.cabac_hip_wait_event(self.h, vp(hip_event)))
@@ -525,7 +585,7 @@ class CabacHip:
         cabac_hip_search_plan.h; 30 encode with sets, 31 decode with sets, 32 context advance and 33 a WPP prefix pass in
         cabac_hip_ctx_sets.h; 34 plan parse with sets, 35 a level of a rows parse and 36 the encode launch of a plan write with sets
         in cabac_hip_plan_rows.h; 37 hand-over index, 38 log mark and 39 the encode launch of a spliced call with sets in
-        cabac_hip_splice_rows.h)."""
+        cabac_hip_splice_rows.h; 40 the gate of a call on a fixed workspace in cabac_hip_workspace.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)

@@ -15,18 +15,28 @@ namespace cabac {
 
 // exclusive scan of the substream sizes: one workgroup, tiles of 1024 with a running carry
 // (a substream whose encode overflowed its slot — CABAC_RES_OVERFLOW — counts on past byte_capacity; only what the slot
-// holds is assembled)
+// holds is assembled).  kGated (a call on a fixed workspace, cabac_hip_workspace.h): a VOIDED call — its slots have no capacity,
+// so every size is 0 — gets its results here too: {0, CABAC_RES_OVERFLOW} over whatever the encoder said of an empty string
+template <bool kGated>
 __global__ __launch_bounds__(1024) void sizes_scan_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
                                                           const cabac_substream_result *__restrict__ results,
-                                                          uint64_t *__restrict__ offsets) {
+                                                          uint64_t *__restrict__ offsets, const WsState *__restrict__ ws,
+                                                          cabac_substream_result *results_w) {
   __shared__ uint64_t wave_sum[16];
   __shared__ uint64_t carry;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const bool voided = kGated && ws->voided != 0u;
   if (tid == 0) carry = 0;
   __syncthreads();
   for (uint32_t tile = 0; tile < n_sub; tile += 1024) {
     const uint32_t s = tile + tid;
-    const uint64_t sz = s < n_sub ? (uint64_t)min((results[s].n_bits + 7u) >> 3, desc[s].byte_capacity) : 0;
+    if (kGated && voided && s < n_sub) {
+      cabac_substream_result r;
+      r.n_bits = 0u;
+      r.flags = CABAC_RES_OVERFLOW;
+      results_w[s] = r;
+    }
+    const uint64_t sz = (s < n_sub && !voided) ? (uint64_t)min(((kGated ? results_w : results)[s].n_bits + 7u) >> 3, desc[s].byte_capacity) : 0;
     uint64_t incl = sz;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -169,8 +179,9 @@ hipError_t launch_pack_bins(hipStream_t st, uint64_t n, const uint8_t *bins, uin
 
 hipError_t launch_assemble(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc,
                            const cabac_substream_result *results, const uint8_t *bytes, uint8_t *payload,
-                           uint64_t payload_capacity, uint64_t *offsets) {
-  hipLaunchKernelGGL(sizes_scan_kernel, dim3(1), dim3(1024), 0, st, n_sub, desc, results, offsets);
+                           uint64_t payload_capacity, uint64_t *offsets, const WsState *ws, cabac_substream_result *results_w) {
+  if (ws) hipLaunchKernelGGL(sizes_scan_kernel<true>, dim3(1), dim3(1024), 0, st, n_sub, desc, nullptr, offsets, ws, results_w);
+  else hipLaunchKernelGGL(sizes_scan_kernel<false>, dim3(1), dim3(1024), 0, st, n_sub, desc, results, offsets, nullptr, nullptr);
   if (n_sub)
     hipLaunchKernelGGL(copy_substreams_kernel<true>, dim3(n_sub), dim3(256), 0, st, n_sub, desc, offsets,
                        const_cast<uint8_t *>(bytes), payload, payload_capacity);

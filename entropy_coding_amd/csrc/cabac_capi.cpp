@@ -10,7 +10,9 @@
 // WPP and rows schedules); then one section per header.  The single-launch device calls go through TIMED_LAUNCH.  The four
 // host-pointer forms of the parser family (residual, unit, element and plan parse, the rows parse included) share their host
 // checks (check_substream_host, check_plan_host, check_coeff_ranges_host) and their staging (ParseStage); the pipelined
-// host-pointer forms each keep their own stream choreography.
+// host-pointer forms each keep their own stream choreography.  The blocking runtime calls go through counting helpers (wait_stream,
+// device_alloc, ...: cabac_hip_workspace_waits); on a ctx with a fixed workspace (cabac_hip_workspace.h) the three pipelines that wait
+// in the middle take a branch that queues a gate kernel instead.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +38,7 @@
 #include "cabac_hip_search_plan.h"
 #include "cabac_hip_search_unit.h"
 #include "cabac_hip_splice_rows.h"
+#include "cabac_hip_workspace.h"
 #include "cabac_hip_write_plan.h"
 #include "cabac_kernels.h"
 #include "cabac_nal_kernels.h"
@@ -125,6 +128,12 @@ struct cabac_hip_ctx {
   bool pipe_ready = false;
   int chunks_override = 0;  // CABAC_HIP_CHUNKS (experiments); 0 = by batch size
   std::vector<cabac_search_log *> logs;  // the winner logs that are alive (cabac_hip_search_emit.h): destroyed with the ctx
+  // ---- the fixed workspace (cabac_hip_workspace.h) -----------------------------------------------------
+  uint64_t n_waits = 0;               // blocking runtime calls issued for this ctx (the helpers below count them)
+  bool ws_fixed = false;
+  cabac_workspace_sizes ws = {};      // what the workspace was fixed to
+  cabac::WsState *d_ws = nullptr;     // its device words (allocated by the first fix, kept)
+  cabac_workspace_status ws_last = {0, 0, 0, 0, 0, CABAC_WS_NONE_VOIDED};  // the status as the last release found it
 };
 
 // a winner log: fixed device arrays (one allocation each, never grown) and the ctx whose stream orders everything done to them
@@ -156,16 +165,43 @@ int fail(cabac_hip_ctx *c, int status, const char *what) {
     if (_e != hipSuccess) return fail_hip((c), _e, #expr); \
   } while (0)
 
+// The blocking runtime calls of this file, counted for cabac_hip_workspace_waits where they are issued (c may be null).
+hipError_t wait_stream(cabac_hip_ctx *c, hipStream_t st) {
+  if (c) c->n_waits++;
+  return hipStreamSynchronize(st);
+}
+hipError_t wait_event(cabac_hip_ctx *c, hipEvent_t ev) {
+  if (c) c->n_waits++;
+  return hipEventSynchronize(ev);
+}
+template <class T>
+hipError_t device_alloc(cabac_hip_ctx *c, T **p, size_t bytes) {
+  if (c) c->n_waits++;
+  return hipMalloc(reinterpret_cast<void **>(p), bytes);
+}
+hipError_t device_free(cabac_hip_ctx *c, void *p) {
+  if (c) c->n_waits++;
+  return hipFree(p);
+}
+hipError_t pinned_alloc(cabac_hip_ctx *c, void **p, size_t bytes, unsigned flags) {
+  if (c) c->n_waits++;
+  return hipHostMalloc(p, bytes, flags);
+}
+hipError_t pinned_free(cabac_hip_ctx *c, void *p) {
+  if (c) c->n_waits++;
+  return hipHostFree(p);
+}
+
 int ensure(cabac_hip_ctx *c, int slot, size_t bytes) {
   if (bytes == 0) bytes = 16;
   if (c->d_cap[slot] >= bytes) return CABAC_HIP_OK;
   if (c->d_buf[slot]) {
-    HIP_TRY(c, hipFree(c->d_buf[slot]));
+    HIP_TRY(c, device_free(c, c->d_buf[slot]));
     c->d_buf[slot] = nullptr;
     c->d_cap[slot] = 0;
   }
   size_t want = bytes + bytes / 4 + 256;
-  hipError_t e = hipMalloc(&c->d_buf[slot], want);
+  hipError_t e = device_alloc(c, &c->d_buf[slot], want);
   if (e != hipSuccess) {
     c->last_error = "hipMalloc failed";
     return CABAC_HIP_ERR_NOMEM;
@@ -306,9 +342,9 @@ bool host_is_pinned(const void *p, size_t bytes) {
 // host-pointer call must leave behind when it returns early (the blocks' destinations point into the caller's buffers,
 // which the caller may free as soon as the call has returned — they are dropped, not copied).
 void pipe_quiesce(cabac_hip_ctx *c) {
-  (void)hipStreamSynchronize(c->stream);  // null = the adopted default stream: synchronised like any other
+  (void)wait_stream(c, c->stream);  // null = the adopted default stream: synchronised like any other
   for (hipStream_t st : {c->s_in, c->s_out, c->s_k[0], c->s_k[1], c->s_k[2], c->s_k[3]})
-    if (st) (void)hipStreamSynchronize(st);
+    if (st) (void)wait_stream(c, st);
   for (cabac_hip_ctx::Bounce *b : {&c->bounce_in, &c->bounce_out})
     for (int i = 0; i < cabac_hip_ctx::kBounceDepth; i++) {
       b->busy[i] = false;
@@ -339,11 +375,11 @@ void pipe_destroy(cabac_hip_ctx *c) {
       if (e) (void)hipEventDestroy(e);
   for (cabac_hip_ctx::Bounce *b : {&c->bounce_in, &c->bounce_out})
     for (int i = 0; i < cabac_hip_ctx::kBounceDepth; i++) {
-      if (b->blk[i]) (void)hipHostFree(b->blk[i]);
+      if (b->blk[i]) (void)pinned_free(c, b->blk[i]);
       if (b->ev[i]) (void)hipEventDestroy(b->ev[i]);
     }
   for (void *p : c->h_pin)
-    if (p) (void)hipHostFree(p);
+    if (p) (void)pinned_free(c, p);
   c->pipe_ready = false;
 }
 
@@ -359,7 +395,7 @@ int pipe_init(cabac_hip_ctx *c) {
   }
   for (cabac_hip_ctx::Bounce *b : {&c->bounce_in, &c->bounce_out})
     for (int i = 0; i < cabac_hip_ctx::kBounceDepth; i++) {
-      HIP_TRY(c, hipHostMalloc(&b->blk[i], cabac_hip_ctx::kBounceBlock, hipHostMallocDefault));
+      HIP_TRY(c, pinned_alloc(c, &b->blk[i], cabac_hip_ctx::kBounceBlock, hipHostMallocDefault));
       HIP_TRY(c, hipEventCreateWithFlags(&b->ev[i], hipEventDisableTiming));
     }
   if (const char *e = getenv("CABAC_HIP_CHUNKS")) c->chunks_override = atoi(e);
@@ -371,12 +407,12 @@ int ensure_pinned(cabac_hip_ctx *c, int slot, size_t bytes) {
   if (bytes == 0) bytes = 16;
   if (c->h_cap[slot] >= bytes) return CABAC_HIP_OK;
   if (c->h_pin[slot]) {
-    HIP_TRY(c, hipHostFree(c->h_pin[slot]));
+    HIP_TRY(c, pinned_free(c, c->h_pin[slot]));
     c->h_pin[slot] = nullptr;
     c->h_cap[slot] = 0;
   }
   const size_t want = bytes + bytes / 4 + 4096;
-  if (hipHostMalloc(&c->h_pin[slot], want, hipHostMallocDefault) != hipSuccess) {
+  if (pinned_alloc(c, &c->h_pin[slot], want, hipHostMallocDefault) != hipSuccess) {
     (void)hipGetLastError();
     c->last_error = "hipHostMalloc failed";
     return CABAC_HIP_ERR_NOMEM;
@@ -389,12 +425,12 @@ int ensure_pinned(cabac_hip_ctx *c, int slot, size_t bytes) {
 int ensure_pinned_keep(cabac_hip_ctx *c, int slot, size_t bytes, size_t keep) {
   if (c->h_cap[slot] >= bytes && c->h_pin[slot]) return CABAC_HIP_OK;
   void *old = c->h_pin[slot];
-  if (old && keep) HIP_TRY(c, hipStreamSynchronize(c->s_out));
+  if (old && keep) HIP_TRY(c, wait_stream(c, c->s_out));
   c->h_pin[slot] = nullptr;
   c->h_cap[slot] = 0;
   int rc = ensure_pinned(c, slot, bytes + bytes);  // chunks are about equal: leave room for the ones to come
   if (rc == CABAC_HIP_OK && old && keep) std::memcpy(c->h_pin[slot], old, keep);
-  if (old) (void)hipHostFree(old);
+  if (old) (void)pinned_free(c, old);
   return rc;
 }
 
@@ -411,7 +447,7 @@ int h2d(cabac_hip_ctx *c, void *dst, const void *src, size_t bytes, hipStream_t 
     const size_t n = std::min(cabac_hip_ctx::kBounceBlock, bytes - off);
     const int i = b.next;
     b.next = (i + 1) % cabac_hip_ctx::kBounceDepth;
-    if (b.busy[i]) HIP_TRY(c, hipEventSynchronize(b.ev[i]));
+    if (b.busy[i]) HIP_TRY(c, wait_event(c, b.ev[i]));
     std::memcpy(b.blk[i], static_cast<const uint8_t *>(src) + off, n);
     HIP_TRY(c, hipMemcpyAsync(static_cast<uint8_t *>(dst) + off, b.blk[i], n, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipEventRecord(b.ev[i], st));
@@ -424,7 +460,7 @@ int h2d(cabac_hip_ctx *c, void *dst, const void *src, size_t bytes, hipStream_t 
 int d2h_retire(cabac_hip_ctx *c, int i) {
   cabac_hip_ctx::Bounce &b = c->bounce_out;
   if (!b.busy[i]) return CABAC_HIP_OK;
-  HIP_TRY(c, hipEventSynchronize(b.ev[i]));
+  HIP_TRY(c, wait_event(c, b.ev[i]));
   std::memcpy(b.dst[i], b.blk[i], b.len[i]);
   b.busy[i] = false;
   return CABAC_HIP_OK;
@@ -549,6 +585,19 @@ struct Rows {
 int check_rows_host(cabac_hip_ctx *c, uint32_t n_sub, const Rows &rows) {
   if (int bad = check_levels(c, n_sub, rows.n_level, rows.level_first)) return bad;
   return check_links_host(c, n_sub, rows.n_level, rows.level_first, rows.d_sync_from);
+}
+
+// what a call on a fixed workspace (cabac_hip_workspace.h) may not exceed; checked before anything is queued.  (n_splice needs no
+// check of its own: the splice pipeline has refused n_splice != n_tu by then.  cabac_workspace_sizes.n_entries sizes nothing.)
+int check_workspace(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_tu, bool rows) {
+  if (n_sub > c->ws.n_sub) return fail(c, CABAC_HIP_ERR_INVALID, "n_sub exceeds the fixed workspace");
+  if (n_tu > c->ws.n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "n_tu exceeds the fixed workspace");
+  if (rows && !(c->ws.flags & CABAC_WS_ROWS)) return fail(c, CABAC_HIP_ERR_INVALID, "a rows call on a workspace fixed without CABAC_WS_ROWS");
+  return CABAC_HIP_OK;
+}
+int refuse_fixed_batch(cabac_hip_ctx *c) {
+  return fail(c, CABAC_HIP_ERR_INVALID,
+              "the workspace is fixed: the host-pointer forms of this pipeline share its buffers; call cabac_hip_workspace_release first");
 }
 
 bool sets_args_ok(uint32_t n_sub, uint32_t n_sets, const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
@@ -700,7 +749,7 @@ struct ParseStage {
     if (tu_info) HIP_TRY(c, down(c, tu_info, d_tu_info, tu_word_bytes()));
     if (blocks) HIP_TRY(c, down(c, coeff, d_coeff, n_coeff_total * size_t(coeff_bytes)));
     HIP_TRY(c, down(c, results, d_results, n_sub * sizeof(cabac_substream_result)));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, wait_stream(c, c->stream));
     int status = CABAC_HIP_OK;
     for (uint32_t s = 0; s < n_sub; s++)
       if (results[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
@@ -737,7 +786,7 @@ int cabac_hip_init(int device, cabac_hip_ctx **out) {
     return CABAC_HIP_ERR_HIP;
   }
   c->own_stream = true;
-  if (hipMalloc(&c->d_select, 256) != hipSuccess) {
+  if (device_alloc(c, &c->d_select, 256) != hipSuccess) {
     (void)hipGetLastError();
     cabac_hip_destroy(c);
     return CABAC_HIP_ERR_NOMEM;
@@ -749,12 +798,13 @@ int cabac_hip_init(int device, cabac_hip_ctx **out) {
 void cabac_hip_destroy(cabac_hip_ctx *c) {
   if (!c) return;
   DeviceGuard g(c->device);
-  (void)hipStreamSynchronize(c->stream);
+  (void)wait_stream(c, c->stream);
   while (!c->logs.empty()) (void)cabac_hip_search_log_destroy(c->logs.back());
   for (int i = 0; i < kSlots; i++)
-    if (c->d_buf[i]) (void)hipFree(c->d_buf[i]);
-  if (c->h_totals) (void)hipHostFree(c->h_totals);
-  if (c->d_select) (void)hipFree(c->d_select);
+    if (c->d_buf[i]) (void)device_free(c, c->d_buf[i]);
+  if (c->h_totals) (void)pinned_free(c, c->h_totals);
+  if (c->d_select) (void)device_free(c, c->d_select);
+  if (c->d_ws) (void)device_free(c, c->d_ws);
   pipe_destroy(c);
   for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
   if (c->ev_start) (void)hipEventDestroy(c->ev_start);
@@ -781,7 +831,7 @@ int cabac_hip_set_stream(cabac_hip_ctx *c, void *hip_stream) {
   if (!c) return CABAC_HIP_ERR_INVALID;
   DeviceGuard g(c->device);
   if (c->own_stream && c->stream) {
-    (void)hipStreamSynchronize(c->stream);
+    (void)wait_stream(c, c->stream);
     (void)hipStreamDestroy(c->stream);
     c->own_stream = false;
     c->stream = nullptr;
@@ -814,7 +864,7 @@ int cabac_hip_record_event(cabac_hip_ctx *c, void *hip_event) {
 int cabac_hip_synchronize(cabac_hip_ctx *c) {
   if (!c) return CABAC_HIP_ERR_INVALID;
   DeviceGuard g(c->device);
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   return CABAC_HIP_OK;
 }
 
@@ -868,7 +918,7 @@ int cabac_hip_ctx_init_device(cabac_hip_ctx *c, uint32_t n_sub, const int32_t *d
 int cabac_hip_profile_enable(cabac_hip_ctx *c, uint32_t capacity) {
   if (!c) return CABAC_HIP_ERR_INVALID;
   DeviceGuard g(c->device);
-  (void)hipStreamSynchronize(c->stream);
+  (void)wait_stream(c, c->stream);
   for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
   c->prof_ev.clear();
   c->prof_kind.clear();
@@ -885,7 +935,7 @@ int cabac_hip_profile_enable(cabac_hip_ctx *c, uint32_t capacity) {
 int cabac_hip_profile_read(cabac_hip_ctx *c, int32_t *kind, float *ms, uint32_t max_entries) {
   if (!c || !kind || !ms) return CABAC_HIP_ERR_INVALID;
   DeviceGuard g(c->device);
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   uint32_t n = c->prof_n < max_entries ? c->prof_n : max_entries;
   for (uint32_t i = 0; i < n; i++) {
     kind[i] = c->prof_kind[i];
@@ -931,7 +981,7 @@ int cabac_hip_gather_records_device(cabac_hip_ctx *c, uint32_t n_seg, const uint
 float cabac_hip_last_kernel_ms(cabac_hip_ctx *c) {
   if (!c || !c->timed) return -1.0f;
   DeviceGuard g(c->device);
-  if (hipEventSynchronize(c->ev_stop) != hipSuccess) return -1.0f;
+  if (wait_event(c, c->ev_stop) != hipSuccess) return -1.0f;
   float ms = -1.0f;
   if (hipEventElapsedTime(&ms, c->ev_start, c->ev_stop) != hipSuccess) return -1.0f;
   return ms;
@@ -973,7 +1023,7 @@ static int encode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   auto *h_off = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(c->h_pin[0]) + res_bytes);
 
   // what came before on the caller's stream is finished first; everything below runs on the library's own streams
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   if ((rc = h2d(c, c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc), c->s_in))) return rc;
   for (uint32_t k = 0; k < nc; k++) {
     const Chunk &ch = chunks[k];
@@ -1001,7 +1051,7 @@ static int encode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   std::vector<uint64_t> pay_base(nc + 1, 0);
   for (uint32_t k = 0; k < nc; k++) {
     const Chunk &ch = chunks[k];
-    HIP_TRY(c, hipEventSynchronize(c->ev_k[k]));
+    HIP_TRY(c, wait_event(c, c->ev_k[k]));
     const uint64_t n_pay = h_off[ch.s1 + k];
     pay_base[k + 1] = pay_base[k] + n_pay;
     if (payload) {  // straight into the caller's payload (DMA if it is pinned, else through the bounce ring)
@@ -1018,7 +1068,7 @@ static int encode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   int status = CABAC_HIP_OK;
   for (uint32_t k = 0; k < nc; k++) {
     const Chunk &ch = chunks[k];
-    HIP_TRY(c, hipEventSynchronize(c->ev_out[k]));
+    HIP_TRY(c, wait_event(c, c->ev_out[k]));
     const uint8_t *pay = payload ? payload + pay_base[k] : static_cast<const uint8_t *>(c->h_pin[1]) + pay_base[k];
     const uint64_t *off = h_off + ch.s0 + k;
     for (uint32_t s = ch.s0; s < ch.s1; s++) {
@@ -1073,7 +1123,7 @@ int cabac_hip_estimate_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   std::vector<uint32_t> fl(n_sub);
   HIP_TRY(c, hipMemcpyAsync(frac_bits, c->d_buf[kFracBits], n_sub * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(fl.data(), c->d_buf[kFlags], n_sub * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   int status = CABAC_HIP_OK;
   for (uint32_t s = 0; s < n_sub; s++) {
     if (flags) flags[s] = fl[s];
@@ -1111,7 +1161,7 @@ static int decode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   auto *d_bins = static_cast<uint8_t *>(c->d_buf[kBins]);
   auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
 
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   if ((rc = h2d(c, c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc), c->s_in))) return rc;
   for (uint32_t k = 0; k < nc; k++) {
     const Chunk &ch = chunks[k];
@@ -1138,8 +1188,8 @@ static int decode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
     if ((rc = d2h(c, bins, c->d_buf[kPackedBins], (n_records_total + 7) / 8, c->s_out))) return rc;
   }
   if ((rc = d2h_drain(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->s_out));
-  for (uint32_t k = 0; k < nc; k++) HIP_TRY(c, hipEventSynchronize(c->ev_k[k]));
+  HIP_TRY(c, wait_stream(c, c->s_out));
+  for (uint32_t k = 0; k < nc; k++) HIP_TRY(c, wait_event(c, c->ev_k[k]));
   int status = CABAC_HIP_OK;
   for (uint32_t s = 0; s < n_sub; s++) {
     results[s] = h_res[s];
@@ -1207,7 +1257,7 @@ int cabac_hip_residual_batch(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_des
   if (rc) return rc;
   std::vector<uint32_t> cnt(2 * size_t(n_tu));
   HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   int status = CABAC_HIP_OK;
   for (uint32_t t = 0; t < n_tu; t++) {
     offsets[t + 1] = offsets[t] + cnt[t];
@@ -1224,7 +1274,7 @@ int cabac_hip_residual_batch(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_des
                                  (const uint64_t *)c->d_buf[kRecOffsets], d_cnt, d_info, (uint16_t *)c->d_buf[kOutRecords]);
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(records, c->d_buf[kOutRecords], offsets[n_tu] * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   return status;
 }
 
@@ -1562,13 +1612,14 @@ int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
 // ---- coefficients -> bytes (cabac_splice.hip) -------------------------------------------------------------------
 // sets (may be null): the encode launch starts from and writes context sets; rows (may be null): every substream's hand-over pair
 // becomes an index into its expanded string and the WPP encode schedule takes the encode launch's place.  Not both.  The plain
-// calls pass neither.
+// calls pass neither.  d_n_live (the log's emit on a fixed workspace; else null): the device word that says how many of the n_tu
+// blocks and n_splice splices count.
 static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
                                        const uint32_t *d_splice_first, const cabac_splice *d_splices, uint32_t n_splice, uint32_t n_tu,
                                        const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes, uint8_t *d_payload,
                                        uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
                                        uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets = nullptr,
-                                       const Rows *rows = nullptr) {
+                                       const Rows *rows = nullptr, const uint64_t *d_n_live = nullptr) {
   if (!c || !d_payload_offsets || (n_sub && (!d_desc || !d_records || !d_splice_first || !d_payload || !d_results)) ||
       (n_splice && !d_splices) || (n_tu && (!d_tu || !d_coeff)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
@@ -1578,9 +1629,12 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
     if (!rows->d_sync_from || !rows->d_sync_at) return fail(c, CABAC_HIP_ERR_INVALID, "null");
     if (int bad = check_levels(c, n_sub, rows->n_level, rows->level_first)) return bad;
   }
+  const bool fixed = c->ws_fixed;  // cabac_hip_workspace.h: every ensure below finds its buffer, nothing waits
+  if (fixed)
+    if (int bad = check_workspace(c, n_sub, n_tu, rows != nullptr)) return bad;
   DeviceGuard g(c->device);
   int rc;
-  if (rows && (rc = ensure(c, kRowsWords, size_t(n_sub ? n_sub : 1) * sizeof(uint32_t)))) return rc;
+  if ((rows || (fixed && sets)) && (rc = ensure(c, kRowsWords, (fixed ? 2 : 1) * size_t(n_sub ? n_sub : 1) * sizeof(uint32_t)))) return rc;
   const size_t n_pre = size_t(n_splice) + n_sub + 1;
   const size_t plan32 = n_pre + 2 * size_t(n_sub) + size_t(n_tu ? n_tu : 1) + 2;  // pre, sub_n, sub_cap, seen, err (+ pad)
   const size_t plan32_pad = (plan32 + 1) & ~size_t(1);
@@ -1590,7 +1644,7 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
   if ((rc = ensure(c, kSpDesc, size_t(n_sub ? n_sub : 1) * sizeof(cabac_substream_desc)))) return rc;
   if ((rc = ensure(c, kSpTuOff, size_t(n_tu ? n_tu : 1) * sizeof(uint64_t)))) return rc;
   if ((rc = ensure(c, kSpFlag, 64))) return rc;
-  if (!c->h_totals) HIP_TRY(c, hipHostMalloc(&c->h_totals, 64, hipHostMallocDefault));
+  if (!fixed && !c->h_totals) HIP_TRY(c, pinned_alloc(c, &c->h_totals, 64, hipHostMallocDefault));
   uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kSpCnt]), *d_info = d_cnt + (n_tu ? n_tu : 1);
   uint32_t *pre = static_cast<uint32_t *>(c->d_buf[kSpPlan]), *sub_n = pre + n_pre, *sub_cap = sub_n + n_sub, *seen = sub_cap + n_sub,
            *err = seen + (n_tu ? n_tu : 1);
@@ -1602,35 +1656,58 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
     Timed t(c, 5);
     HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[kResidualScratch]));
   }
+  // fixed: the scan ends in the gate — good or voided, on the device (for a voided call it empties the binariser's block order,
+  // which order_ready makes the records pass take as it finds it)
+  const cabac::WsGate gate{c->d_ws, CABAC_WS_BAD_SPLICES, nullptr, static_cast<uint32_t *>(c->d_buf[kResidualScratch]),
+                           cabac::residual_scratch_bytes(n_tu)};
   {
     Timed t(c, 10);
     HIP_TRY(c, cabac::launch_splice_plan(c->stream, n_sub, n_tu, d_desc, d_splice_first, d_splices, n_splice, d_cnt, pre, sub_n, sub_cap, seen, err,
-                                         rec_base, byte_base, totals));
+                                         rec_base, byte_base, totals, d_n_live, fixed ? &gate : nullptr));
   }
-  uint64_t *h_tot = static_cast<uint64_t *>(c->h_totals);
-  HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the one wait: sizes decide the buffers of the second half
-  if (h_tot[2]) return fail(c, CABAC_HIP_ERR_INVALID, "splice list: not sorted, outside its substream, or a block not spliced exactly once");
-  if ((rc = ensure(c, kSpRec, (h_tot[0] + 64) * sizeof(uint16_t)))) return rc;
-  if ((rc = ensure(c, kSpBytes, h_tot[1] + 64))) return rc;
+  if (!fixed) {
+    uint64_t *h_tot = static_cast<uint64_t *>(c->h_totals);
+    HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, wait_stream(c, c->stream));  // the one wait: sizes decide the buffers of the second half
+    if (h_tot[2]) return fail(c, CABAC_HIP_ERR_INVALID, "splice list: not sorted, outside its substream, or a block not spliced exactly once");
+    if ((rc = ensure(c, kSpRec, (h_tot[0] + 64) * sizeof(uint16_t)))) return rc;
+    if ((rc = ensure(c, kSpBytes, h_tot[1] + 64))) return rc;
+  }
   auto *exp_rec = static_cast<uint16_t *>(c->d_buf[kSpRec]);
   auto *slots = static_cast<uint8_t *>(c->d_buf[kSpBytes]);
   {
     Timed t(c, 10);
-    HIP_TRY(c, cabac::launch_splice_expand(c->stream, n_sub, d_desc, d_records, d_splice_first, d_splices, pre, sub_n, sub_cap, rec_base,
-                                           byte_base, desc2, tu_off, exp_rec));
+    if (fixed)
+      HIP_TRY(c, cabac::launch_splice_expand_gated(c->stream, c->d_ws, n_sub, d_desc, d_records, d_splice_first, d_splices, pre, sub_n, sub_cap,
+                                                   rec_base, byte_base, desc2, tu_off, exp_rec));
+    else
+      HIP_TRY(c, cabac::launch_splice_expand(c->stream, n_sub, d_desc, d_records, d_splice_first, d_splices, pre, sub_n, sub_cap, rec_base,
+                                             byte_base, desc2, tu_off, exp_rec));
   }
   {  // block records (pass 2), straight into the expanded substreams
     Timed t(c, 5);
     HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[kResidualScratch],
                                       /*order_ready=*/true));  // the block order of the sizes pass above: same tus[], same scratch
   }
+  cabac::CtxSets live;  // fixed: a voided call writes no out set
+  if (fixed && sets && sets->out_set) {
+    uint32_t *out_live = static_cast<uint32_t *>(c->d_buf[kRowsWords]) + (n_sub ? n_sub : 1);
+    Timed t(c, 40);
+    HIP_TRY(c, cabac::launch_ws_out_sets(c->stream, c->d_ws, n_sub, sets->out_set, out_live));
+    live = *sets;
+    live.out_set = out_live;
+    sets = &live;
+  }
   if (rows) {  // the hand-over indices, the context-advance prefix passes per level, then one encode launch from the slots
     uint32_t *sync_rec = static_cast<uint32_t *>(c->d_buf[kRowsWords]);
     {
       Timed t(c, 37);
-      HIP_TRY(c, cabac::launch_splice_sync_index(c->stream, n_sub, d_desc, d_splice_first, d_splices, pre, rows->d_sync_at,
-                                                 rows->d_sync_splice, sync_rec));
+      if (fixed)
+        HIP_TRY(c, cabac::launch_splice_sync_index_gated(c->stream, c->d_ws, n_sub, d_desc, d_splice_first, d_splices, pre, rows->d_sync_at,
+                                                         rows->d_sync_splice, sync_rec));
+      else
+        HIP_TRY(c, cabac::launch_splice_sync_index(c->stream, n_sub, d_desc, d_splice_first, d_splices, pre, rows->d_sync_at,
+                                                   rows->d_sync_splice, sync_rec));
     }
     if (n_sub && (rc = wpp_device_impl(c, false, n_sub, desc2, exp_rec, slots, nullptr, d_results, rows->n_level, rows->level_first,
                                        rows->d_sync_from, sync_rec)))
@@ -1649,7 +1726,8 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
   }
   {
     Timed t(c, 6);
-    HIP_TRY(c, cabac::launch_assemble(c->stream, n_sub, desc2, d_results, slots, d_payload, payload_capacity, d_payload_offsets));
+    HIP_TRY(c, cabac::launch_assemble(c->stream, n_sub, desc2, d_results, slots, d_payload, payload_capacity, d_payload_offsets,
+                                      fixed ? c->d_ws : nullptr, d_results));  // fixed: a voided call's results too
   }
   if (d_tu_info && n_tu) HIP_TRY(c, hipMemcpyAsync(d_tu_info, d_info, size_t(n_tu) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
   return CABAC_HIP_OK;
@@ -1681,6 +1759,7 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if (!c || !payload_offsets || (n_sub && (!desc || !splice_first || !results || !payload)) || (n_tu && (!tus || !coeff || !splices)) ||
       (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (c->ws_fixed) return refuse_fixed_batch(c);
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (rows && n_sub) {  // refused before anything is touched, payload_offsets[0] included
     if (int bad = check_rows_host(c, n_sub, *rows)) return bad;
@@ -1734,7 +1813,7 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   uint32_t *d_flag = static_cast<uint32_t *>(c->d_buf[kSpFlag]);  // [0] descriptor range check, [1] empty / bad block
 
   // what came before on the caller's stream is finished first; uploads run on the copy stream, the kernels on the ctx's
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   // small things first: the block descriptors are checked on the device while the coefficients are still on the wire
   if ((rc = h2d(c, c->d_buf[kSpInTu], tus, size_t(n_tu) * sizeof(cabac_tu_desc), c->s_in))) return rc;
   HIP_TRY(c, hipEventRecord(c->ev_in[0], c->s_in));
@@ -1757,7 +1836,7 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
                         rows->d_sync_splice ? static_cast<const uint32_t *>(c->d_buf[kSpInSync]) : nullptr};
   }
   HIP_TRY(c, hipEventRecord(c->ev_in[1], c->s_in));
-  HIP_TRY(c, hipEventSynchronize(c->ev_k[0]));
+  HIP_TRY(c, wait_event(c, c->ev_k[0]));
   if (*h_flag) return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
   HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in[1], 0));
   rc = encode_residual_device_impl(c, n_sub, static_cast<const cabac_substream_desc *>(c->d_buf[kSpInDesc]),
@@ -1775,14 +1854,14 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   HIP_TRY(c, hipMemcpyAsync(h_flag, d_flag + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev_k[1], c->stream));
   // the big things leave on the outgoing copy stream once the offsets are known
-  HIP_TRY(c, hipEventSynchronize(c->ev_k[1]));
+  HIP_TRY(c, wait_event(c, c->ev_k[1]));
   const uint64_t n_pay = h_off[n_sub];
   if (n_pay > payload_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "payload_capacity too small");
   if ((rc = d2h(c, payload, c->d_buf[kPayload], n_pay, c->s_out))) return rc;
   if (tu_info && (rc = d2h(c, tu_info, c->d_buf[kSpOutInfo], size_t(n_tu) * sizeof(uint32_t), c->s_out))) return rc;
   if (bin_counts && (rc = d2h(c, bin_counts, c->d_buf[kSpOutCnt], size_t(n_sub) * CABAC_BIN_COUNT_WORDS * sizeof(uint32_t), c->s_out))) return rc;
   if ((rc = d2h_drain(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->s_out));
+  HIP_TRY(c, wait_stream(c, c->s_out));
   int status = *h_flag ? CABAC_HIP_ERR_SUBSTREAM : CABAC_HIP_OK;
   payload_offsets[0] = 0;
   for (uint32_t s = 0; s < n_sub; s++) {
@@ -1831,6 +1910,9 @@ static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_
     if (!rows->d_sync_from || !rows->d_sync_at) return fail(c, CABAC_HIP_ERR_INVALID, "null");
     if (int bad = check_levels(c, n_sub, rows->n_level, rows->level_first)) return bad;
   }
+  const bool fixed = c->ws_fixed;  // cabac_hip_workspace.h: every ensure below finds its buffer, nothing waits
+  if (fixed)
+    if (int bad = check_workspace(c, n_sub, n_tu, rows != nullptr)) return bad;
   DeviceGuard g(c->device);
   int rc;
   if ((sets || rows) && (rc = ensure(c, kRowsWords, 2 * size_t(n_sub ? n_sub : 1) * sizeof(uint32_t)))) return rc;
@@ -1847,7 +1929,7 @@ static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_
   if ((rc = ensure(c, kPwTu, n_blk * sizeof(cabac_tu_desc)))) return rc;
   if ((rc = ensure(c, kSpDesc, n_s * sizeof(cabac_substream_desc)))) return rc;
   if ((rc = ensure(c, kSpTuOff, n_blk * sizeof(uint64_t)))) return rc;
-  if (!c->h_totals) HIP_TRY(c, hipHostMalloc(&c->h_totals, 64, hipHostMallocDefault));
+  if (!fixed && !c->h_totals) HIP_TRY(c, pinned_alloc(c, &c->h_totals, 64, hipHostMallocDefault));
   uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kSpCnt]), *d_info = d_cnt + n_blk;
   uint32_t *sub_n = static_cast<uint32_t *>(c->d_buf[kPwPlan]), *sub_cap = sub_n + n_s, *sub_flag = sub_cap + n_s, *err = sub_flag + n_s;
   uint64_t *rec_base = reinterpret_cast<uint64_t *>(sub_n + words), *byte_base = rec_base + n_s, *totals = byte_base + n_s;
@@ -1863,14 +1945,19 @@ static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_
   {
     Timed t(c, 28);
     HIP_TRY(c, cabac::launch_plan_resolve(c->stream, n_sub, in, sub_n, sub_cap, sub_flag, err));
-    HIP_TRY(c, cabac::launch_splice_scan(c->stream, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals));
+    // fixed: the scan ends in the gate; a voided call's substreams all become stopped ones (CABAC_RES_OVERFLOW) of length 0,
+    // which the emit walk, the out sets, the records pass and the stops below already treat as the contract asks
+    const cabac::WsGate gate{c->d_ws, CABAC_WS_RECORDS_32BIT, sub_flag, nullptr, 0};
+    HIP_TRY(c, cabac::launch_splice_scan(c->stream, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals, fixed ? &gate : nullptr));
   }
-  uint64_t *h_tot = static_cast<uint64_t *>(c->h_totals);
-  HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the one wait: sizes decide the buffers of the second half
-  if (h_tot[2]) return fail(c, CABAC_HIP_ERR_INVALID, "a substream outgrows 32 bits of records");
-  if ((rc = ensure(c, kSpRec, (h_tot[0] + 64) * sizeof(uint16_t)))) return rc;
-  if ((rc = ensure(c, kSpBytes, h_tot[1] + 64))) return rc;
+  if (!fixed) {
+    uint64_t *h_tot = static_cast<uint64_t *>(c->h_totals);
+    HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, wait_stream(c, c->stream));  // the one wait: sizes decide the buffers of the second half
+    if (h_tot[2]) return fail(c, CABAC_HIP_ERR_INVALID, "a substream outgrows 32 bits of records");
+    if ((rc = ensure(c, kSpRec, (h_tot[0] + 64) * sizeof(uint16_t)))) return rc;
+    if ((rc = ensure(c, kSpBytes, h_tot[1] + 64))) return rc;
+  }
   auto *exp_rec = static_cast<uint16_t *>(c->d_buf[kSpRec]);
   auto *slots = static_cast<uint8_t *>(c->d_buf[kSpBytes]);
   {
@@ -1928,6 +2015,7 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   if (!c || !payload_offsets || (n_sub && (!desc || !tile_first || !results || !payload)) ||
       (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (c->ws_fixed) return refuse_fixed_batch(c);
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (n_sub == 0) {
     payload_offsets[0] = 0;
@@ -1965,7 +2053,7 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   uint32_t *d_values = static_cast<uint32_t *>(c->d_buf[kElemValues]);
 
   // what came before on the caller's stream is finished first; uploads run on the copy stream, the kernels on the ctx's
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   if ((rc = h2d(c, c->d_buf[kSpInTu], tus, size_t(n_tu) * sizeof(cabac_tu_desc), c->s_in))) return rc;
   if ((rc = h2d(c, c->d_buf[kSpInDesc], desc, n_sub * sizeof(cabac_substream_desc), c->s_in))) return rc;
   if ((rc = h2d(c, c->d_buf[kSpInFirst], tile_first, first_bytes, c->s_in))) return rc;
@@ -1998,7 +2086,7 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   HIP_TRY(c, hipMemcpyAsync(h_off, c->d_buf[kPayloadOffsets], off_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev_k[1], c->stream));
   // the big things leave on the outgoing copy stream once the offsets are known
-  HIP_TRY(c, hipEventSynchronize(c->ev_k[1]));
+  HIP_TRY(c, wait_event(c, c->ev_k[1]));
   const uint64_t n_pay = h_off[n_sub];
   if (n_pay > payload_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "payload_capacity too small");
   if ((rc = d2h(c, payload, c->d_buf[kPayload], n_pay, c->s_out))) return rc;
@@ -2016,7 +2104,7 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
       return rc;
   }
   if ((rc = d2h_drain(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->s_out));
+  HIP_TRY(c, wait_stream(c, c->s_out));
   for (uint32_t s = 0; s < n_sub; s++) {
     results[s] = h_res[s];
     payload_offsets[s + 1] = h_off[s + 1];
@@ -2117,7 +2205,7 @@ int cabac_hip_estimate_residual_batch(cabac_hip_ctx *c, uint32_t n_cand, const u
   if (n_tu && tu_frac_bits)
     HIP_TRY(c, hipMemcpyAsync(tu_frac_bits, d_tu_bits, size_t(n_tu) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   if (n_tu) HIP_TRY(c, hipMemcpyAsync(info.data(), d_info, size_t(n_tu) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   int status = CABAC_HIP_OK;
   for (uint32_t t = 0; t < n_tu; t++) {
     if (tu_info) tu_info[t] = info[t];
@@ -2194,10 +2282,10 @@ int cabac_hip_nal_escape_batch(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t 
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(status, d_status, sizeof(cabac_nal_status), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(nal_offsets, c->d_buf[kNalOutOff], off_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   const uint64_t got = std::min<uint64_t>(status->out_bytes, cap);
   if (got) HIP_TRY(c, hipMemcpyAsync(nal, c->d_buf[kNalOut], got, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   return CABAC_HIP_OK;
 }
 
@@ -2232,11 +2320,11 @@ int cabac_hip_nal_unescape_batch(cabac_hip_ctx *c, uint32_t n_seg, const uint64_
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(status, d_status, sizeof(cabac_nal_status), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(offsets, c->d_buf[kNalOutOff], off_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   const uint64_t got = std::min<uint64_t>(status->out_bytes, cap), got_loc = std::min<uint64_t>(status->n_changed, loc_cap);
   if (got) HIP_TRY(c, hipMemcpyAsync(payload, c->d_buf[kNalOut], got, hipMemcpyDeviceToHost, c->stream));
   if (got_loc) HIP_TRY(c, hipMemcpyAsync(locations, c->d_buf[kNalLoc], got_loc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   return CABAC_HIP_OK;
 }
 
@@ -2280,10 +2368,10 @@ int cabac_hip_encode_batch_nal(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
   HIP_TRY(c, hipMemcpyAsync(status, d_status, sizeof(cabac_nal_status), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(nal_offsets, c->d_buf[kNalOutOff], off_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(results, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   if (status->out_bytes > nal_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "nal_capacity too small (status->out_bytes is the size needed)");
   if (status->out_bytes) HIP_TRY(c, hipMemcpyAsync(nal, c->d_buf[kNalOut], status->out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   for (uint32_t s = 0; s < n_sub; s++)
     if (results[s].flags) return fail(c, CABAC_HIP_ERR_SUBSTREAM, "substream flag set (see results[].flags)");
   return CABAC_HIP_OK;
@@ -2406,7 +2494,7 @@ int search_plan_fetch(cabac_hip_ctx *c, uint32_t n_cand, const HostPlan &hp, int
   if (hp.values_out && hp.n_entries_total)
     HIP_TRY(c, hipMemcpyAsync(hp.values_out, c->d_buf[kElemValues], size_t(hp.n_entries_total) * sizeof(uint32_t), hipMemcpyDeviceToHost,
                               c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   for (uint32_t k = 0; k < n_cand; k++) {
     if (hp.flags) hp.flags[k] = fl[k];
     if (fl[k]) *status = CABAC_HIP_ERR_SUBSTREAM;
@@ -2632,7 +2720,7 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
   HIP_TRY(c, down(c, info.data(), d_info, size_t(n_tu) * sizeof(uint32_t)));
   HIP_TRY(c, down(c, pick, c->d_buf[kSearchOutPick], size_t(n_group) * sizeof(uint32_t)));
   HIP_TRY(c, down(c, cost, c->d_buf[kSearchOutCost], size_t(n_group) * sizeof(uint64_t)));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
   // the written sets: those of the groups that picked a candidate
   if (group_out_set && n_cand) {
     for (uint32_t k = 0; k < n_group; k++) {
@@ -2642,7 +2730,7 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
       HIP_TRY(c, down(c, state + at, (const uint32_t *)c->d_buf[kEstInState] + at, CABAC_NUM_CONTEXTS * sizeof(uint32_t)));
       HIP_TRY(c, down(c, rate + at, (const uint8_t *)c->d_buf[kEstInRate] + at, CABAC_NUM_CONTEXTS));
     }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, wait_stream(c, c->stream));
   }
   int status = CABAC_HIP_OK;
   if (hp) {  // the plan's info words: a block without records stops its candidate only where it is coded (see flags[])
@@ -2857,7 +2945,7 @@ void log_free(cabac_search_log *log) {
   void *p[] = {log->a.counters, log->a.entries, log->a.records, log->a.tu, log->a.tu_at, log->a.coeff, log->a.chain_rec, log->a.chain_tu,
                log->a.mark_rec, log->a.mark_tu};
   for (void *q : p)
-    if (q) (void)hipFree(q);
+    if (q) (void)device_free(log->ctx, q);
   delete log;
 }
 }  // namespace
@@ -2880,7 +2968,7 @@ int cabac_hip_search_log_create(cabac_hip_ctx *c, uint32_t n_chain, uint32_t ent
   a.record_cap = record_capacity;
   a.tu_cap = tu_capacity;
   a.coeff_cap = coeff_capacity;
-  auto alloc = [](auto **p, size_t bytes) { return hipMalloc(reinterpret_cast<void **>(p), bytes + 16) == hipSuccess; };  // + 16: never empty
+  auto alloc = [c](auto **p, size_t bytes) { return device_alloc(c, reinterpret_cast<void **>(p), bytes + 16) == hipSuccess; };  // + 16: never empty
   if (!alloc(&a.counters, sizeof(cabac_search_log_counters)) || !alloc(&a.entries, size_t(entry_capacity) * sizeof(cabac_search_log_entry)) ||
       !alloc(&a.records, record_capacity * sizeof(uint16_t)) || !alloc(&a.tu, size_t(tu_capacity) * sizeof(cabac_tu_desc)) ||
       !alloc(&a.tu_at, size_t(tu_capacity) * sizeof(uint32_t)) || !alloc(&a.coeff, coeff_capacity * size_t(coeff_bytes)) ||
@@ -2904,7 +2992,7 @@ int cabac_hip_search_log_destroy(cabac_search_log *log) {
   if (!log) return CABAC_HIP_OK;
   cabac_hip_ctx *c = log->ctx;
   DeviceGuard g(c->device);
-  (void)hipStreamSynchronize(c->stream);  // what is queued may still read or write the log
+  (void)wait_stream(c, c->stream);  // what is queued may still read or write the log
   c->logs.erase(std::remove(c->logs.begin(), c->logs.end(), log), c->logs.end());
   log_free(log);
   return CABAC_HIP_OK;
@@ -2953,6 +3041,46 @@ int cabac_hip_search_log_view(const cabac_search_log *log, cabac_search_log_view
   return CABAC_HIP_OK;
 }
 
+// The emit on a fixed workspace (cabac_hip_workspace.h): the counters stay on the device and every launch is sized from the log's
+// capacities; the place pass hands the binariser tu_cap descriptors, the unused ones rejected, and the splice kernels count the
+// logged blocks by the device's word.
+static int search_log_encode_fixed(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
+                                   uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
+                                   uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets, const Rows *rows) {
+  cabac_hip_ctx *c = log->ctx;
+  const cabac::SearchLogArrays &a = log->a;
+  if (int bad = check_workspace(c, a.n_chain, a.tu_cap, rows != nullptr)) return bad;
+  if (a.record_cap > c->ws.log_records)
+    return fail(c, CABAC_HIP_ERR_INVALID, "the log's record_capacity exceeds the fixed workspace (log_records)");
+  int rc;
+  if ((rc = ensure(c, kLogDesc, size_t(a.n_chain) * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kLogFirst, (size_t(a.n_chain) + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kLogRec, (a.record_cap + 8) * sizeof(uint16_t)))) return rc;
+  if ((rc = ensure(c, kLogSplice, size_t(a.tu_cap ? a.tu_cap : 1) * sizeof(cabac_splice)))) return rc;
+  if ((rc = ensure(c, kPwTu, size_t(a.tu_cap ? a.tu_cap : 1) * sizeof(cabac_tu_desc)))) return rc;
+  auto *desc2 = static_cast<cabac_substream_desc *>(c->d_buf[kLogDesc]);
+  auto *first = static_cast<uint32_t *>(c->d_buf[kLogFirst]);
+  auto *rec = static_cast<uint16_t *>(c->d_buf[kLogRec]);
+  auto *splices = static_cast<cabac_splice *>(c->d_buf[kLogSplice]);
+  auto *tus = static_cast<cabac_tu_desc *>(c->d_buf[kPwTu]);
+  {
+    Timed t(c, 24);
+    HIP_TRY(c, cabac::launch_search_log_place_fixed(c->stream, a, c->d_ws, d_desc, desc2, first, rec, splices, tus));
+  }
+  Rows marked{};
+  if (rows) marked = Rows{rows->n_level, rows->level_first, rows->d_sync_from, a.mark_rec, a.mark_tu};
+  if ((rc = encode_residual_device_impl(c, a.n_chain, desc2, rec, first, splices, a.tu_cap, a.tu_cap, tus, a.coeff, log->coeff_bytes,
+                                        d_payload, payload_capacity, d_payload_offsets, d_results, nullptr, d_bin_counts, sets,
+                                        rows ? &marked : nullptr, &c->d_ws->log_tu)))
+    return rc;
+  if (d_tu_info) {  // one word per LOGGED block: the count is the device's
+    Timed t(c, 40);
+    HIP_TRY(c, cabac::launch_ws_log_info(c->stream, c->d_ws, a.tu_cap, static_cast<uint32_t *>(c->d_buf[kSpCnt]) + (a.tu_cap ? a.tu_cap : 1),
+                                         d_tu_info));
+  }
+  return CABAC_HIP_OK;
+}
+
 // sets / rows (may be null, not both): handed on to the spliced encode; a rows call takes the chains' marks as the hand-over pairs
 // (its d_sync_at and d_sync_splice are not read)
 static int search_log_encode_impl(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
@@ -2963,10 +3091,12 @@ static int search_log_encode_impl(cabac_search_log *log, const cabac_substream_d
   if (!d_desc || !d_payload || !d_payload_offsets || !d_results) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
   const cabac::SearchLogArrays &a = log->a;
-  if (!c->h_totals) HIP_TRY(c, hipHostMalloc(&c->h_totals, 64, hipHostMallocDefault));
+  if (c->ws_fixed) return search_log_encode_fixed(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info,
+                                                  d_bin_counts, sets, rows);
+  if (!c->h_totals) HIP_TRY(c, pinned_alloc(c, &c->h_totals, 64, hipHostMallocDefault));
   static_assert(sizeof(cabac_search_log_counters) <= 64, "the pinned block of the ctx holds the counters");
   HIP_TRY(c, hipMemcpyAsync(c->h_totals, a.counters, sizeof(cabac_search_log_counters), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the first wait: the counters size everything below
+  HIP_TRY(c, wait_stream(c, c->stream));  // the first wait: the counters size everything below
   const cabac_search_log_counters cnt = *static_cast<const cabac_search_log_counters *>(c->h_totals);
   if (cnt.flags & CABAC_SEARCH_LOG_OVERFLOW) {
     std::string msg = "the log overflowed (an append was dropped):";
@@ -3086,7 +3216,7 @@ static int wpp_batch_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const c
   auto *d_bins = static_cast<uint8_t *>(c->d_buf[kBins]);
   auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
   hipStream_t st = c->stream;
-  HIP_TRY(c, hipStreamSynchronize(st));
+  HIP_TRY(c, wait_stream(c, st));
   if ((rc = h2d(c, d_desc, desc, n_sub * sizeof(cabac_substream_desc), st))) return rc;
   if ((rc = h2d(c, d_rec, records, n_records_total * 2, st))) return rc;
   if ((rc = h2d(c, c->d_buf[kWppFrom], sync_from, size_t(n_sub) * sizeof(uint32_t), st))) return rc;
@@ -3106,7 +3236,7 @@ static int wpp_batch_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const c
     if ((rc = d2h(c, bytes, d_slots, bytes_total, st))) return rc;
   }
   if ((rc = d2h_drain(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(st));
+  HIP_TRY(c, wait_stream(c, st));
   int status = CABAC_HIP_OK;
   for (uint32_t s = 0; s < n_sub; s++) {
     results[s] = h_res[s];
@@ -3280,6 +3410,122 @@ int cabac_hip_search_log_encode_rows_device(cabac_search_log *log, const cabac_s
   const Rows rows{n_level, level_first, d_sync_from, nullptr, nullptr};
   return search_log_encode_impl(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr,
                                 &rows);
+}
+
+// ---- the fixed workspace (cabac_hip_workspace.h; the gate and its kernels: cabac_workspace.hip) -------------------------------
+int cabac_hip_workspace_bound(uint32_t n_sub, uint64_t n_host_records, uint32_t n_tu, uint64_t n_coded_coeff, uint64_t *expanded_records,
+                              uint64_t *slot_bytes) {
+  if (!expanded_records || !slot_bytes) return CABAC_HIP_ERR_INVALID;
+  const uint64_t lim = uint64_t(1) << 60;
+  if (n_host_records > lim / 64 || n_coded_coeff > lim / 64) return CABAC_HIP_ERR_INVALID;
+  // the sum of CABAC_TU_MAX_RECORDS(n) = 33 + 38 n over the blocks; a slot: slot_bytes() of cabac_splice.hip, < 7 n / 8 + 24
+  const uint64_t rec = n_host_records + 33u * uint64_t(n_tu) + 38u * n_coded_coeff;
+  *expanded_records = rec;
+  *slot_bytes = (7u * rec + 7u) / 8u + 24u * uint64_t(n_sub);
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_workspace_fix(cabac_hip_ctx *c, const cabac_workspace_sizes *sizes) {
+  if (!c || !sizes) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  const cabac_workspace_sizes z = *sizes;
+  const uint64_t lim = uint64_t(1) << 60;
+  if (z.reserved != 0 || (z.flags & ~CABAC_WS_ROWS) != 0) return fail(c, CABAC_HIP_ERR_INVALID, "reserved or unknown flags");
+  if (z.n_entries > lim || z.expanded_records > lim || z.slot_bytes > lim || z.log_records > lim)
+    return fail(c, CABAC_HIP_ERR_INVALID, "a size beyond 2^60");
+  DeviceGuard g(c->device);
+  HIP_TRY(c, wait_stream(c, c->stream));  // what is queued may use the buffers that grow below
+  c->ws_fixed = false;
+  const size_t n_s = z.n_sub ? z.n_sub : 1, n_blk = z.n_tu ? z.n_tu : 1;
+  const size_t n_pre = size_t(z.n_tu) + z.n_sub + 1;
+  const size_t plan32 = ((n_pre + 2 * size_t(z.n_sub) + n_blk + 2) + 1) & ~size_t(1);  // encode_residual_device_impl's kSpPlan
+  const size_t pw32 = (3 * n_s + 2 + 1) & ~size_t(1);                                   // write_plan_device_impl's kPwPlan
+  const struct {
+    int slot;
+    size_t bytes;
+  } need[] = {
+      {kRowsWords, 2 * n_s * sizeof(uint32_t)},
+      {kSpCnt, 2 * n_blk * sizeof(uint32_t)},
+      {kResidualScratch, cabac::residual_scratch_bytes(z.n_tu)},
+      {kSpPlan, plan32 * sizeof(uint32_t) + (2 * size_t(z.n_sub) + 3) * sizeof(uint64_t)},
+      {kSpDesc, n_s * sizeof(cabac_substream_desc)},
+      {kSpTuOff, n_blk * sizeof(uint64_t)},
+      {kSpFlag, 64},
+      {kSpRec, (z.expanded_records + 64) * sizeof(uint16_t)},
+      {kSpBytes, z.slot_bytes + 64},
+      {kPwPlan, pw32 * sizeof(uint32_t) + (2 * n_s + 3) * sizeof(uint64_t)},
+      {kPwTu, n_blk * sizeof(cabac_tu_desc)},
+      {kLogDesc, n_s * sizeof(cabac_substream_desc)},
+      {kLogFirst, (n_s + 1) * sizeof(uint32_t)},
+      {kLogRec, (z.log_records + 8) * sizeof(uint16_t)},
+      {kLogSplice, n_blk * sizeof(cabac_splice)},
+  };
+  for (const auto &n : need)
+    if (int rc = ensure(c, n.slot, n.bytes)) return rc;
+  if (z.flags & CABAC_WS_ROWS) {  // wpp_device_impl's slots
+    const size_t set_words = n_s * CABAC_NUM_CONTEXTS;
+    int rc;
+    if ((rc = ensure(c, kWppState, set_words * sizeof(uint32_t))) || (rc = ensure(c, kWppRate, set_words)) ||
+        (rc = ensure(c, kWppDesc, n_s * sizeof(cabac_substream_desc))) || (rc = ensure(c, kWppIndex, 2 * n_s * sizeof(uint32_t))))
+      return rc;
+  }
+  if (!c->h_totals) HIP_TRY(c, pinned_alloc(c, &c->h_totals, 64, hipHostMallocDefault));
+  if (!c->d_ws && device_alloc(c, &c->d_ws, sizeof(cabac::WsState)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, CABAC_HIP_ERR_NOMEM, "hipMalloc failed");
+  }
+  cabac::WsState init = {};
+  init.status.first_voided = CABAC_WS_NONE_VOIDED;
+  init.rec_cap = z.expanded_records;
+  init.slot_cap = z.slot_bytes;
+  HIP_TRY(c, hipMemcpyAsync(c->d_ws, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));  // `init` leaves scope
+  c->ws = z;
+  c->ws_fixed = true;
+  return CABAC_HIP_OK;
+}
+
+namespace {
+// the status as it stands when the stream has drained (into *out)
+int read_status(cabac_hip_ctx *c, cabac_workspace_status *out) {
+  static_assert(sizeof(cabac_workspace_status) <= 64, "the pinned block of the ctx holds the status");
+  HIP_TRY(c, hipMemcpyAsync(c->h_totals, &c->d_ws->status, sizeof *out, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
+  memcpy(out, c->h_totals, sizeof *out);
+  return CABAC_HIP_OK;
+}
+}  // namespace
+
+int cabac_hip_workspace_release(cabac_hip_ctx *c) {
+  if (!c) return CABAC_HIP_ERR_INVALID;
+  if (!c->ws_fixed) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  if (int rc = read_status(c, &c->ws_last)) return rc;
+  c->ws_fixed = false;
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_workspace_status_device(cabac_hip_ctx *c, cabac_workspace_status *d_out) {
+  if (!c || !d_out) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (!c->ws_fixed) return fail(c, CABAC_HIP_ERR_INVALID, "the workspace is not fixed");
+  DeviceGuard g(c->device);
+  HIP_TRY(c, hipMemcpyAsync(d_out, &c->d_ws->status, sizeof *d_out, hipMemcpyDefault, c->stream));
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_workspace_status(cabac_hip_ctx *c, cabac_workspace_status *out) {
+  if (!c || !out) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (!c->ws_fixed) {
+    *out = c->ws_last;
+    return CABAC_HIP_OK;
+  }
+  DeviceGuard g(c->device);
+  return read_status(c, out);
+}
+
+int cabac_hip_workspace_waits(cabac_hip_ctx *c, uint64_t *n) {
+  if (!c || !n) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  *n = c->n_waits;
+  return CABAC_HIP_OK;
 }
 
 int cabac_hip_host_alloc(size_t bytes, void **out) {

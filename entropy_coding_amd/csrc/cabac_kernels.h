@@ -5,11 +5,15 @@
 #include <stdint.h>
 
 #include "cabac_hip.h"
+#include "cabac_hip_workspace.h"
 
 struct cabac_search_log_counters;  // cabac_hip_search_emit.h
 struct cabac_search_log_entry;
 
 namespace cabac {
+
+struct WsState;  // the fixed workspace, below
+struct WsGate;
 
 // Context sets of the codec calls (cabac_hip_ctx_sets.h): substream s starts from set start_set[s] of state / rate and writes the
 // contexts it leaves as set out_set[s] of out_state / out_rate (0xffffffff: Ctx::init / nothing; start_set / out_set null: all
@@ -203,7 +207,10 @@ hipError_t launch_plan_parse_sets(hipStream_t st, uint32_t n_sub, const cabac_su
 hipError_t launch_splice_plan(hipStream_t st, uint32_t n_sub, uint32_t n_tu, const cabac_substream_desc *desc,
                               const uint32_t *splice_first, const cabac_splice *splices, uint32_t n_splice,
                               const uint32_t *tu_n_records, uint32_t *pre, uint32_t *sub_n, uint32_t *sub_cap, uint32_t *seen, uint32_t *err,
-                              uint64_t *rec_base, uint64_t *byte_base, uint64_t *totals);
+                              uint64_t *rec_base, uint64_t *byte_base, uint64_t *totals, const uint64_t *n_dev = nullptr,
+                              const WsGate *gate = nullptr);
+// n_dev (null: n_tu and n_splice as given): a device word that holds the number of blocks and splices that count — the log's emit
+// on a fixed workspace, whose arrays are sized by the log's capacities; n_tu and n_splice then only bound the arrays
 hipError_t launch_splice_expand(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *host_records,
                                 const uint32_t *splice_first, const cabac_splice *splices, const uint32_t *pre,
                                 const uint32_t *sub_n, const uint32_t *sub_cap, const uint64_t *rec_base, const uint64_t *byte_base,
@@ -220,8 +227,8 @@ hipError_t launch_bin_count(hipStream_t st, uint32_t n_sub, const cabac_substrea
                             uint32_t *counts);
 
 // the scan of launch_splice_plan alone: rec_base / byte_base (n_sub each) from sub_n / sub_cap, totals = {records, bytes, *err != 0}
-hipError_t launch_splice_scan(hipStream_t st, uint32_t n_sub, const uint32_t *sub_n, const uint32_t *sub_cap, uint64_t *rec_base,
-                              uint64_t *byte_base, const uint32_t *err, uint64_t *totals);
+hipError_t launch_splice_scan(hipStream_t st, uint32_t n_sub, uint32_t *sub_n, uint32_t *sub_cap, uint64_t *rec_base,
+                              uint64_t *byte_base, const uint32_t *err, uint64_t *totals, const WsGate *gate = nullptr);
 
 // the plan writer (cabac_plan_write.hip; cabac_hip_write_plan.h): the plan walk on the writer's side, once for the sizes and once
 // for the records.  What both walks read: the plan and the real values, the blocks with the sizes and info words of the residual
@@ -284,10 +291,57 @@ hipError_t launch_plan_resolve_emit(hipStream_t st, const PlanResolveIn &in, uin
 // frac_bits[c] = UINT64_MAX where flags[c] != 0
 hipError_t launch_plan_flag_cost(hipStream_t st, uint32_t n_cand, const uint32_t *flags, uint64_t *frac_bits);
 
+// the fixed workspace (cabac_workspace.hip; cabac_hip_workspace.h): the device words of a ctx whose workspace is fixed.  One
+// block serves every call: the calls of a ctx run in stream order.
+struct WsState {
+  cabac_workspace_status status;
+  uint64_t rec_cap, slot_cap;               // the room for expanded records and byte slots the gate compares the totals with
+  uint64_t log_entry, log_record, log_tu;   // the log's counters as the fixed place pass took them (all 0 for a log it refuses)
+  uint32_t voided;                          // the gate's decision for the call in flight
+  uint32_t log_flags;                       // CABAC_WS_LOG_* of the call in flight; the gate takes them and clears them
+};
+// The residual binariser's scratch (cabac_residual.hip): kResidualScratchHeader words of class counts, cursors and the
+// transform-skip flag, then the block order, 0xffffffff where a slot holds no block.  The gate EMPTIES it for a voided call —
+// header 0, order 0xffffffff — so that the records pass behind it (order_ready: it takes the order as it finds it) walks no block
+// and writes nothing; the binariser's kernels are what they were.
+constexpr uint32_t kResidualScratchHeader = 24;
+// THE GATE is the tail of the scan of a call on a fixed workspace (launch_splice_plan / launch_splice_scan with a WsGate): the
+// call is VOIDED when the scan's error word is set (reported as err_flag), the log's place pass left flags, or a total exceeds its
+// room; the status takes the needs, the flags and the counts.  A voided call's tables are emptied — sub_n, sub_cap, rec_base,
+// byte_base 0, sub_flag (may be null) CABAC_RES_OVERFLOW, residual_scratch (may be null; of residual_scratch_bytes(n_tu) bytes)
+// emptied as said above — so that what follows finds empty substreams with zero-capacity slots and no block; launch_assemble with ws writes its results, {0, CABAC_RES_OVERFLOW}.
+struct WsGate {
+  WsState *ws;
+  uint32_t err_flag;
+  uint32_t *sub_flag, *residual_scratch;
+  size_t residual_scratch_bytes;
+};
+// out_set_live[s] = out_set[s], or 0xffffffff for every substream of a voided call
+hipError_t launch_ws_out_sets(hipStream_t st, const WsState *ws, uint32_t n_sub, const uint32_t *out_set, uint32_t *out_set_live);
+// dst[t] = src[t] for the blocks the log holds (t < ws->log_tu, at most cap)
+hipError_t launch_ws_log_info(hipStream_t st, const WsState *ws, uint32_t cap, const uint32_t *src, uint32_t *dst);
+// the gated forms of launch_splice_expand and launch_splice_sync_index: a voided call writes its (empty) descriptors and zero
+// hand-over indices and reads nothing of the splice list
+hipError_t launch_splice_expand_gated(hipStream_t st, const WsState *ws, uint32_t n_sub, const cabac_substream_desc *desc,
+                                      const uint16_t *host_records, const uint32_t *splice_first, const cabac_splice *splices,
+                                      const uint32_t *pre, const uint32_t *sub_n, const uint32_t *sub_cap, const uint64_t *rec_base,
+                                      const uint64_t *byte_base, cabac_substream_desc *desc_out, uint64_t *tu_offset, uint16_t *records);
+hipError_t launch_splice_sync_index_gated(hipStream_t st, const WsState *ws, uint32_t n_sub, const cabac_substream_desc *desc,
+                                          const uint32_t *splice_first, const cabac_splice *splices, const uint32_t *pre,
+                                          const uint32_t *sync_at, const uint32_t *sync_splice, uint32_t *sync_rec);
+// launch_search_log_place sized from the log's capacities: the counters are read on the device (ws->log_* and ws->log_flags
+// receive them); tus_out receives tu_cap descriptors, the logged ones copied and the unused tail ones the binariser rejects;
+// the splice list is the logged blocks' (launch_splice_plan takes their number from &ws->log_tu)
+hipError_t launch_search_log_place_fixed(hipStream_t st, const SearchLogArrays &log, WsState *ws, const cabac_substream_desc *desc,
+                                         cabac_substream_desc *desc_out, uint32_t *splice_first, uint16_t *records,
+                                         cabac_splice *splices, cabac_tu_desc *tus_out);
+
 // substream assembly (cabac_assemble.hip)
 hipError_t launch_assemble(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc,
                            const cabac_substream_result *results, const uint8_t *bytes, uint8_t *payload,
-                           uint64_t payload_capacity, uint64_t *offsets);
+                           uint64_t payload_capacity, uint64_t *offsets, const WsState *ws = nullptr,
+                           cabac_substream_result *results_w = nullptr);
+// ws (a call on a fixed workspace; then results_w = results, writable): a voided call's results are written by the sizes scan
 hipError_t launch_pack_bins(hipStream_t st, uint64_t n, const uint8_t *bins, uint8_t *packed);
 hipError_t launch_gather_records(hipStream_t st, uint32_t n_seg, const uint64_t *src_off, const uint64_t *dst_off, const uint32_t *len,
                                  const uint16_t *src, uint16_t *dst);

@@ -54,6 +54,7 @@ constexpr uint32_t kClasses = 8;
 // coded, [24..] permutation (padded per class)
 constexpr uint32_t kScratchHeader = 24;
 constexpr uint32_t kScratchAnyTs = 16;
+static_assert(kScratchHeader == kResidualScratchHeader, "the gate of a fixed workspace empties this layout (cabac_kernels.h)");
 
 // Pre-pass: each thread looks at kSortItems descriptors and keeps its per-class counts as 4-bit fields of one word
 // (a count is at most 8); counts meet through wave shuffles of 16-bit pairs, then one LDS add per wave and class,

@@ -17,6 +17,8 @@
 //                      hundred 4 x 4 winners share one or two.  Memory bound: every logged byte is read once and written once.
 // PLACE, at encode time: log_place_scan_kernel (exclusive sums over the chains' record and block counts: descriptors and
 // splice_first) and log_place_move_kernel (a row per entry: its records to their place in the chain's string, its splices).
+// On a ctx with a fixed workspace (cabac_hip_workspace.h) the place pass is log_place_scan_fixed_kernel / log_place_move_fixed_kernel:
+// the same layout from counters that stay on the device, launched over the log's capacities.
 // MARK (cabac_hip_splice_rows.h): log_mark_kernel copies the listed chains' cursors into their hand-over words.
 // No MFMA anywhere: there is no arithmetic to speak of.
 #include <hip/hip_runtime.h>
@@ -384,6 +386,90 @@ __global__ __launch_bounds__(256) void log_place_move_kernel(uint32_t n_entry, S
   }
 }
 
+// ---- place, sized from the log's capacities (cabac_hip_workspace.h) -------------------------------------------------------------
+// The counters stay on the device.  log_place_scan_fixed_kernel takes them (a log that overflowed or whose counters exceed its
+// capacities counts as empty and leaves its flags for the gate), log_place_move_fixed_kernel runs a row per entry the log could
+// hold and gives the binariser tu_cap descriptors: the logged ones, then ones it rejects.  The splice list is the logged blocks'
+// alone: the splice kernels take their number from ws->log_tu.
+__global__ __launch_bounds__(1024) void log_place_scan_fixed_kernel(SearchLogArrays log, WsState *__restrict__ ws,
+                                                                    const cabac_substream_desc *__restrict__ desc,
+                                                                    cabac_substream_desc *__restrict__ desc_out,
+                                                                    uint32_t *__restrict__ splice_first, cabac_splice *__restrict__ splices) {
+  __shared__ uint64_t wave_sum[2][16];
+  __shared__ uint64_t carry[2];
+  const uint32_t tid = threadIdx.x, n_chain = log.n_chain;
+  const cabac_search_log_counters cnt = *log.counters;
+  uint32_t flags = (cnt.flags & CABAC_SEARCH_LOG_OVERFLOW) ? CABAC_WS_LOG_OVERFLOW : 0u;
+  if (cnt.n_entry > log.entry_cap || cnt.n_record > log.record_cap || cnt.n_tu > log.tu_cap || cnt.n_coeff > log.coeff_cap)
+    flags |= CABAC_WS_LOG_DAMAGED;
+  const uint64_t n_tu_total = flags ? 0u : cnt.n_tu;
+  if (tid == 0u) {
+    carry[0] = carry[1] = 0;
+    ws->log_entry = flags ? 0u : cnt.n_entry;
+    ws->log_record = flags ? 0u : cnt.n_record;
+    ws->log_tu = n_tu_total;
+    ws->log_flags = flags;
+  }
+  __syncthreads();
+  for (uint32_t tile = 0; tile < n_chain; tile += 1024u) {
+    const uint32_t k = tile + tid;
+    uint64_t v[2] = {0, 0}, excl[2];
+    if (k < n_chain && flags == 0u) {
+      v[0] = log.chain_rec[k];
+      v[1] = log.chain_tu[k];
+    }
+    scan_tile1024<2>(v, excl, wave_sum, carry);
+    if (k < n_chain) {
+      cabac_substream_desc o;
+      o.rec_offset = min(excl[0], log.record_cap);  // a chain count the log cannot hold: the move leaves its entries out
+      o.byte_offset = 0;
+      o.n_records = (uint32_t)min(v[0], log.record_cap - o.rec_offset);
+      o.byte_capacity = 0;
+      o.qp = desc[k].qp;
+      o.init_id = desc[k].init_id;
+      desc_out[k] = o;
+      splice_first[k] = (uint32_t)min(excl[1], n_tu_total);
+    }
+  }
+  if (tid == 0u) splice_first[n_chain] = (uint32_t)min(carry[1], n_tu_total);
+  // a splice of a logged block that no entry fills names no block: the pipeline refuses the list (those behind are never read)
+  cabac_splice none;
+  none.at = none.tu = 0xffffffffu;
+  for (uint64_t t = tid; t < n_tu_total; t += 1024u) splices[t] = none;
+}
+
+__global__ __launch_bounds__(256) void log_place_move_fixed_kernel(SearchLogArrays log, const WsState *__restrict__ ws,
+                                                                   const cabac_substream_desc *__restrict__ desc_out,
+                                                                   const uint32_t *__restrict__ splice_first, uint16_t *__restrict__ records,
+                                                                   cabac_splice *__restrict__ splices, cabac_tu_desc *__restrict__ tus_out) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;  // a descriptor per thread: a copy (the log is not written), or a rejected one
+  if (t < log.tu_cap) {
+    cabac_tu_desc d{};
+    d.log2_width = d.log2_height = 7;
+    if (t < ws->log_tu) d = log.tu[t];
+    tus_out[t] = d;
+  }
+  const uint32_t l = threadIdx.x & 15u;
+  const uint32_t i = blockIdx.x * kRows + (threadIdx.x >> 4);
+  if (i >= ws->log_entry) return;
+  const uint64_t n_record_total = ws->log_record, n_tu_total = ws->log_tu;
+  const cabac_search_log_entry e = log.entries[i];
+  if (e.chain >= log.n_chain) return;
+  if ((uint64_t)e.chain_rec_first + e.n_rec > desc_out[e.chain].n_records || (uint64_t)e.chain_tu_first + e.n_tu > log.chain_tu[e.chain] ||
+      e.rec_first + e.n_rec > n_record_total || (uint64_t)e.tu_first + e.n_tu > n_tu_total)
+    return;
+  const uint64_t rec_to = desc_out[e.chain].rec_offset + e.chain_rec_first;
+  for (uint64_t k = l; k < e.n_rec; k += 16u) records[rec_to + k] = log.records[e.rec_first + k];
+  const uint64_t sp_to = (uint64_t)splice_first[e.chain] + e.chain_tu_first;
+  if (sp_to + e.n_tu > n_tu_total) return;  // chain counts that do not add up: the list stays incomplete and is refused
+  for (uint32_t k = l; k < e.n_tu; k += 16u) {
+    cabac_splice sp;
+    sp.at = e.chain_rec_first + log.tu_at[e.tu_first + k];
+    sp.tu = e.tu_first + k;
+    splices[sp_to + k] = sp;
+  }
+}
+
 // ---- mark (cabac_hip_splice_rows.h) --------------------------------------------------------------------------------------------
 // the hand-over point of every listed chain: its cursors as they stand in stream order (a dropped append left them unchanged)
 __global__ __launch_bounds__(256) void log_mark_kernel(uint32_t n, const uint32_t *__restrict__ chain, SearchLogArrays log) {
@@ -447,6 +533,16 @@ hipError_t launch_search_log_place(hipStream_t st, const SearchLogArrays &log, c
   if (n_entry)
     hipLaunchKernelGGL(log_place_move_kernel, dim3((n_entry + kRows - 1u) / kRows), dim3(256), 0, st, n_entry, log, n_record, (uint64_t)n_tu,
                        desc_out, splice_first, records, splices);
+  return hipGetLastError();
+}
+
+hipError_t launch_search_log_place_fixed(hipStream_t st, const SearchLogArrays &log, WsState *ws, const cabac_substream_desc *desc,
+                                         cabac_substream_desc *desc_out, uint32_t *splice_first, uint16_t *records,
+                                         cabac_splice *splices, cabac_tu_desc *tus_out) {
+  hipLaunchKernelGGL(log_place_scan_fixed_kernel, dim3(1), dim3(1024), 0, st, log, ws, desc, desc_out, splice_first, splices);
+  const uint32_t grid = std::max((log.entry_cap + kRows - 1u) / kRows, (log.tu_cap + 255u) / 256u);  // rows of entries; descriptors
+  if (grid)
+    hipLaunchKernelGGL(log_place_move_fixed_kernel, dim3(grid), dim3(256), 0, st, log, ws, desc_out, splice_first, records, splices, tus_out);
   return hipGetLastError();
 }
 

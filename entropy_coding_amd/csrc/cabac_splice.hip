@@ -50,8 +50,11 @@ __device__ __forceinline__ uint64_t slot_bytes(uint64_t n_records) { return ((7u
 
 }  // namespace
 
-// pre[j + s] = records of the substream's blocks spliced in before splice j (pre[j1 + s] = of all of them)
-__global__ __launch_bounds__(256) void splice_plan_kernel(uint32_t n_sub, uint32_t n_tu, uint32_t n_splice, const cabac_substream_desc *__restrict__ desc,
+// pre[j + s] = records of the substream's blocks spliced in before splice j (pre[j1 + s] = of all of them).  kDevCount (the
+// log's emit on a fixed workspace): the blocks and splices that count are the first *n_dev, a number only the device knows
+template <bool kDevCount>
+__global__ __launch_bounds__(256) void splice_plan_kernel(const uint64_t *__restrict__ n_dev, uint32_t n_sub, uint32_t n_tu, uint32_t n_splice,
+                                                          const cabac_substream_desc *__restrict__ desc,
                                                           const uint32_t *__restrict__ splice_first,
                                                           const cabac_splice *__restrict__ splices,
                                                           const uint32_t *__restrict__ tu_n_records, uint32_t *__restrict__ pre,
@@ -60,6 +63,7 @@ __global__ __launch_bounds__(256) void splice_plan_kernel(uint32_t n_sub, uint32
   __shared__ uint64_t wave_sum[4];
   const uint32_t s = blockIdx.x;
   if (s >= n_sub) return;
+  if (kDevCount) n_tu = n_splice = (uint32_t)*n_dev;
   uint32_t j0 = splice_first[s], j1 = splice_first[s + 1];
   const uint32_t n_host = desc[s].n_records;
   uint64_t carry = 0;
@@ -96,19 +100,19 @@ __global__ __launch_bounds__(256) void splice_plan_kernel(uint32_t n_sub, uint32
 }
 
 // every block spliced exactly once (the whole grid looks: one workgroup doing it alone took 0.26 ms for 1.6 M blocks)
-__global__ __launch_bounds__(256) void splice_seen_kernel(uint32_t n_tu, const uint32_t *__restrict__ seen, uint32_t *__restrict__ err) {
+template <bool kDevCount>
+__global__ __launch_bounds__(256) void splice_seen_kernel(const uint64_t *__restrict__ n_dev, uint32_t n_tu, const uint32_t *__restrict__ seen,
+                                                          uint32_t *__restrict__ err) {
+  if (kDevCount) n_tu = (uint32_t)*n_dev;
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;
   const bool bad = t < n_tu && seen[t] != 1u;
   if (__ballot(bad) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(err, 1u);
 }
 
-// one workgroup: exclusive scans over the substreams and the totals {records, bytes, error}
-__global__ __launch_bounds__(1024) void splice_scan_kernel(uint32_t n_sub, const uint32_t *__restrict__ sub_n,
-                                                           const uint32_t *__restrict__ sub_cap,
-                                                           uint64_t *__restrict__ rec_base, uint64_t *__restrict__ byte_base,
-                                                           const uint32_t *__restrict__ err, uint64_t *__restrict__ totals) {
-  __shared__ uint64_t wave_a[16], wave_b[16];
-  __shared__ uint64_t carry_a, carry_b;
+// one workgroup: exclusive scans over the substreams; the totals {records, bytes} are left in the two shared words
+__device__ __forceinline__ void scan_substreams(uint32_t n_sub, const uint32_t *sub_n, const uint32_t *sub_cap, uint64_t *rec_base,
+                                                uint64_t *byte_base, uint64_t (&wave_a)[16], uint64_t (&wave_b)[16], uint64_t &carry_a,
+                                                uint64_t &carry_b) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   if (tid == 0) carry_a = carry_b = 0;
   __syncthreads();
@@ -145,15 +149,80 @@ __global__ __launch_bounds__(1024) void splice_scan_kernel(uint32_t n_sub, const
     }
     __syncthreads();
   }
-  if (tid == 0) {
+}
+
+// ... and the totals {records, bytes, error}
+__global__ __launch_bounds__(1024) void splice_scan_kernel(uint32_t n_sub, const uint32_t *__restrict__ sub_n,
+                                                           const uint32_t *__restrict__ sub_cap,
+                                                           uint64_t *__restrict__ rec_base, uint64_t *__restrict__ byte_base,
+                                                           const uint32_t *__restrict__ err, uint64_t *__restrict__ totals) {
+  __shared__ uint64_t wave_a[16], wave_b[16];
+  __shared__ uint64_t carry_a, carry_b;
+  scan_substreams(n_sub, sub_n, sub_cap, rec_base, byte_base, wave_a, wave_b, carry_a, carry_b);
+  if (threadIdx.x == 0) {
     totals[0] = carry_a;
     totals[1] = carry_b;
     totals[2] = *err ? 1u : 0u;
   }
 }
 
-// the expanded substream: descriptor, block destinations, host records moved to their places
-__global__ __launch_bounds__(256) void splice_expand_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+// The scan of a call on a fixed workspace (cabac_hip_workspace.h), with THE GATE as its tail: no host reads the totals, so the
+// workgroup that has them decides.  The call is VOIDED when the error word is set (reported as g.err_flag), the log's place pass
+// left flags, or a total exceeds its room; the status takes the needs, the flags and the counts; and a voided call's tables are
+// emptied — length, slot size and bases 0, the plan write's stop word CABAC_RES_OVERFLOW, the binariser's block order — so that
+// everything behind finds empty substreams with zero-capacity slots.
+__global__ __launch_bounds__(1024) void splice_scan_gate_kernel(uint32_t n_sub, uint32_t *sub_n, uint32_t *sub_cap, uint64_t *rec_base,
+                                                                uint64_t *byte_base, const uint32_t *err, uint64_t *totals, WsGate g) {
+  __shared__ uint64_t wave_a[16], wave_b[16];
+  __shared__ uint64_t carry_a, carry_b;
+  __shared__ uint32_t voided;
+  scan_substreams(n_sub, sub_n, sub_cap, rec_base, byte_base, wave_a, wave_b, carry_a, carry_b);
+  if (threadIdx.x == 0) {
+    const uint64_t rec = carry_a, bytes = carry_b;
+    WsState *ws = g.ws;
+    uint32_t flags = (*err ? g.err_flag : 0u) | ws->log_flags;
+    totals[0] = rec;
+    totals[1] = bytes;
+    totals[2] = *err ? 1u : 0u;
+    cabac_workspace_status st = ws->status;
+    if (flags == 0u) {  // the totals of a refused list or log say nothing
+      st.records_needed = max(st.records_needed, rec);
+      st.slot_bytes_needed = max(st.slot_bytes_needed, bytes);
+      if (rec > ws->rec_cap) flags |= CABAC_WS_OVER_RECORDS;
+      if (bytes > ws->slot_cap) flags |= CABAC_WS_OVER_SLOTS;
+    }
+    st.flags |= flags;
+    if (flags != 0u) {
+      st.n_voided += 1u;
+      if (st.first_voided == CABAC_WS_NONE_VOIDED) st.first_voided = st.n_calls;
+    }
+    st.n_calls += 1u;
+    ws->status = st;
+    ws->voided = flags != 0u ? 1u : 0u;
+    ws->log_flags = 0u;
+    voided = flags;
+  }
+  __syncthreads();
+  if (voided == 0u) return;
+  if (g.residual_scratch) {  // no block left in the binariser's order: its records pass walks nothing
+    const size_t words = g.residual_scratch_bytes / sizeof(uint32_t);
+    for (size_t i = threadIdx.x; i < words; i += 1024u) g.residual_scratch[i] = i < kResidualScratchHeader ? 0u : 0xffffffffu;
+  }
+  for (uint32_t s = threadIdx.x; s < n_sub; s += 1024u) {
+    sub_n[s] = 0u;
+    sub_cap[s] = 0u;
+    rec_base[s] = 0u;
+    byte_base[s] = 0u;
+    if (g.sub_flag) g.sub_flag[s] = CABAC_RES_OVERFLOW;
+  }
+}
+
+// the expanded substream: descriptor, block destinations, host records moved to their places.  kGated (a ctx with a fixed
+// workspace, cabac_hip_workspace.h): a voided call writes its descriptors — empty: the gate has emptied sub_n, sub_cap and the bases —
+// and leaves before anything of the splice list is read
+template <bool kGated>
+__global__ __launch_bounds__(256) void splice_expand_kernel(const WsState *__restrict__ ws, uint32_t n_sub,
+                                                            const cabac_substream_desc *__restrict__ desc,
                                                             const uint16_t *__restrict__ host_records,
                                                             const uint32_t *__restrict__ splice_first,
                                                             const cabac_splice *__restrict__ splices, const uint32_t *__restrict__ pre,
@@ -174,6 +243,7 @@ __global__ __launch_bounds__(256) void splice_expand_kernel(uint32_t n_sub, cons
     o.byte_capacity = sub_cap[s];
     desc_out[s] = o;
   }
+  if (kGated && ws->voided != 0u) return;
   const cabac_splice *sp = splices + j0;
   const uint32_t *p = pre + j0 + s;
   for (uint32_t k = threadIdx.x; k < ns; k += 256u) tu_offset[sp[k].tu] = base + sp[k].at + p[k];
@@ -192,14 +262,21 @@ __global__ __launch_bounds__(256) void splice_expand_kernel(uint32_t n_sub, cons
 
 // the hand-over point of every substream (cabac_hip_splice_rows.h) as an index into its expanded string: k host records and m of
 // its splices in front, m clipped to [#{at < k}, #{at <= k}] — two bisections of the sorted splices — and the records of those m
-// blocks from the running sums of splice_plan_kernel.  One thread per substream; nothing is shared.
-__global__ __launch_bounds__(256) void splice_sync_index_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+// blocks from the running sums of splice_plan_kernel.  One thread per substream; nothing is shared.  kGated: index 0 for every
+// substream of a voided call, whose list may be anything
+template <bool kGated>
+__global__ __launch_bounds__(256) void splice_sync_index_kernel(const WsState *__restrict__ ws, uint32_t n_sub,
+                                                                const cabac_substream_desc *__restrict__ desc,
                                                                 const uint32_t *__restrict__ splice_first,
                                                                 const cabac_splice *__restrict__ splices, const uint32_t *__restrict__ pre,
                                                                 const uint32_t *__restrict__ sync_at, const uint32_t *__restrict__ sync_splice,
                                                                 uint32_t *__restrict__ sync_rec) {
   const uint32_t s = blockIdx.x * 256u + threadIdx.x;
   if (s >= n_sub) return;
+  if (kGated && ws->voided != 0u) {
+    sync_rec[s] = 0u;
+    return;
+  }
   const uint32_t j0 = splice_first[s], ns = splice_first[s + 1] - j0;
   const uint32_t k = min(sync_at[s], desc[s].n_records);
   const cabac_splice *sp = splices + j0;
@@ -276,22 +353,27 @@ hipError_t launch_tu_info_any(hipStream_t st, uint32_t n_tu, const uint32_t *inf
 hipError_t launch_splice_plan(hipStream_t st, uint32_t n_sub, uint32_t n_tu, const cabac_substream_desc *desc,
                               const uint32_t *splice_first, const cabac_splice *splices, uint32_t n_splice,
                               const uint32_t *tu_n_records, uint32_t *pre, uint32_t *sub_n, uint32_t *sub_cap, uint32_t *seen, uint32_t *err,
-                              uint64_t *rec_base, uint64_t *byte_base, uint64_t *totals) {
+                              uint64_t *rec_base, uint64_t *byte_base, uint64_t *totals, const uint64_t *n_dev, const WsGate *gate) {
   hipError_t e = hipMemsetAsync(seen, 0, sizeof(uint32_t) * (n_tu ? n_tu : 1u), st);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(err, 0, sizeof(uint32_t), st);
   if (e != hipSuccess) return e;
-  if (n_sub)
-    hipLaunchKernelGGL(splice_plan_kernel, dim3(n_sub), dim3(256), 0, st, n_sub, n_tu, n_splice, desc, splice_first, splices, tu_n_records,
-                       pre, sub_n, sub_cap, seen, err);
-  if (n_tu) hipLaunchKernelGGL(splice_seen_kernel, dim3((n_tu + 255u) / 256u), dim3(256), 0, st, n_tu, seen, err);
-  hipLaunchKernelGGL(splice_scan_kernel, dim3(1), dim3(1024), 0, st, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals);
-  return hipGetLastError();
+  const dim3 seen_grid((n_tu + 255u) / 256u);
+  if (n_sub && n_dev)
+    hipLaunchKernelGGL(splice_plan_kernel<true>, dim3(n_sub), dim3(256), 0, st, n_dev, n_sub, n_tu, n_splice, desc, splice_first, splices,
+                       tu_n_records, pre, sub_n, sub_cap, seen, err);
+  else if (n_sub)
+    hipLaunchKernelGGL(splice_plan_kernel<false>, dim3(n_sub), dim3(256), 0, st, nullptr, n_sub, n_tu, n_splice, desc, splice_first, splices,
+                       tu_n_records, pre, sub_n, sub_cap, seen, err);
+  if (n_tu && n_dev) hipLaunchKernelGGL(splice_seen_kernel<true>, seen_grid, dim3(256), 0, st, n_dev, n_tu, seen, err);
+  else if (n_tu) hipLaunchKernelGGL(splice_seen_kernel<false>, seen_grid, dim3(256), 0, st, nullptr, n_tu, seen, err);
+  return launch_splice_scan(st, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals, gate);
 }
 
-hipError_t launch_splice_scan(hipStream_t st, uint32_t n_sub, const uint32_t *sub_n, const uint32_t *sub_cap, uint64_t *rec_base,
-                              uint64_t *byte_base, const uint32_t *err, uint64_t *totals) {
-  hipLaunchKernelGGL(splice_scan_kernel, dim3(1), dim3(1024), 0, st, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals);
+hipError_t launch_splice_scan(hipStream_t st, uint32_t n_sub, uint32_t *sub_n, uint32_t *sub_cap, uint64_t *rec_base,
+                              uint64_t *byte_base, const uint32_t *err, uint64_t *totals, const WsGate *gate) {
+  if (gate) hipLaunchKernelGGL(splice_scan_gate_kernel, dim3(1), dim3(1024), 0, st, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals, *gate);
+  else hipLaunchKernelGGL(splice_scan_kernel, dim3(1), dim3(1024), 0, st, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals);
   return hipGetLastError();
 }
 
@@ -300,7 +382,17 @@ hipError_t launch_splice_expand(hipStream_t st, uint32_t n_sub, const cabac_subs
                                 const uint32_t *sub_n, const uint32_t *sub_cap, const uint64_t *rec_base, const uint64_t *byte_base,
                                 cabac_substream_desc *desc_out, uint64_t *tu_offset, uint16_t *records) {
   if (n_sub)
-    hipLaunchKernelGGL(splice_expand_kernel, dim3(n_sub), dim3(256), 0, st, n_sub, desc, host_records, splice_first, splices, pre,
+    hipLaunchKernelGGL(splice_expand_kernel<false>, dim3(n_sub), dim3(256), 0, st, nullptr, n_sub, desc, host_records, splice_first, splices,
+                       pre, sub_n, sub_cap, rec_base, byte_base, desc_out, tu_offset, records);
+  return hipGetLastError();
+}
+
+hipError_t launch_splice_expand_gated(hipStream_t st, const WsState *ws, uint32_t n_sub, const cabac_substream_desc *desc,
+                                      const uint16_t *host_records, const uint32_t *splice_first, const cabac_splice *splices,
+                                      const uint32_t *pre, const uint32_t *sub_n, const uint32_t *sub_cap, const uint64_t *rec_base,
+                                      const uint64_t *byte_base, cabac_substream_desc *desc_out, uint64_t *tu_offset, uint16_t *records) {
+  if (n_sub)
+    hipLaunchKernelGGL(splice_expand_kernel<true>, dim3(n_sub), dim3(256), 0, st, ws, n_sub, desc, host_records, splice_first, splices, pre,
                        sub_n, sub_cap, rec_base, byte_base, desc_out, tu_offset, records);
   return hipGetLastError();
 }
@@ -309,8 +401,17 @@ hipError_t launch_splice_sync_index(hipStream_t st, uint32_t n_sub, const cabac_
                                     const cabac_splice *splices, const uint32_t *pre, const uint32_t *sync_at,
                                     const uint32_t *sync_splice, uint32_t *sync_rec) {
   if (n_sub)
-    hipLaunchKernelGGL(splice_sync_index_kernel, dim3((n_sub + 255u) / 256u), dim3(256), 0, st, n_sub, desc, splice_first, splices, pre,
-                       sync_at, sync_splice, sync_rec);
+    hipLaunchKernelGGL(splice_sync_index_kernel<false>, dim3((n_sub + 255u) / 256u), dim3(256), 0, st, nullptr, n_sub, desc, splice_first,
+                       splices, pre, sync_at, sync_splice, sync_rec);
+  return hipGetLastError();
+}
+
+hipError_t launch_splice_sync_index_gated(hipStream_t st, const WsState *ws, uint32_t n_sub, const cabac_substream_desc *desc,
+                                          const uint32_t *splice_first, const cabac_splice *splices, const uint32_t *pre,
+                                          const uint32_t *sync_at, const uint32_t *sync_splice, uint32_t *sync_rec) {
+  if (n_sub)
+    hipLaunchKernelGGL(splice_sync_index_kernel<true>, dim3((n_sub + 255u) / 256u), dim3(256), 0, st, ws, n_sub, desc, splice_first,
+                       splices, pre, sync_at, sync_splice, sync_rec);
   return hipGetLastError();
 }
 
