@@ -110,6 +110,16 @@ EXPORTS_WORKSPACE = [
     "cabac_hip_workspace_bound", "cabac_hip_workspace_fix", "cabac_hip_workspace_release", "cabac_hip_workspace_status_device",
     "cabac_hip_workspace_status", "cabac_hip_workspace_waits",
 ]
+# include/cabac_hip_sparse.h (the sparse coefficient transport: blocks as lists of their non-zero coefficients;
+# tests/test_sparse_abi.py compares)
+EXPORTS_SPARSE = [
+    "cabac_hip_sparse_pack_host", "cabac_hip_sparse_unpack_host", "cabac_hip_sparse_expand_device", "cabac_hip_sparse_compact_device",
+    "cabac_hip_sparse_encode_batch", "cabac_hip_sparse_parse_batch",
+]
+SPARSE_STATUS_DTYPE = np.dtype([("n_entries", "<u8"), ("flags", "<u4"), ("first_bad", "<u4")])   # cabac_sparse_status
+assert SPARSE_STATUS_DTYPE.itemsize == 16
+SPARSE_OVERFLOW, SPARSE_RANGE, SPARSE_BAD_POS, SPARSE_BAD_FIRST, SPARSE_BAD_BLOCK = 1, 2, 4, 8, 16   # CABAC_SPARSE_*
+SPARSE_NO_BAD = 0xFFFFFFFF                                       # CABAC_SPARSE_NO_BAD
 WS_ROWS = 0x1                                                    # CABAC_WS_ROWS (cabac_workspace_sizes.flags)
 WS_OVER_RECORDS, WS_OVER_SLOTS, WS_BAD_SPLICES, WS_RECORDS_32BIT, WS_LOG_OVERFLOW, WS_LOG_DAMAGED = 1, 2, 4, 8, 16, 32   # status flags
 WS_NONE_VOIDED = 0xFFFFFFFF                                      # CABAC_WS_NONE_VOIDED
@@ -395,6 +405,14 @@ def load_library():
         L.cabac_hip_workspace_status.argtypes = [vp, vp]
         L.cabac_hip_workspace_waits.argtypes = [vp, vp]
     L.cabac_hip_nal_escape_bound.restype = ctypes.c_size_t
+    if hasattr(L, "cabac_hip_sparse_pack_host"):
+        u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+        L.cabac_hip_sparse_pack_host.argtypes = [u32, vp, vp, ctypes.c_int, u64, vp, vp, u64, vp]
+        L.cabac_hip_sparse_unpack_host.argtypes = [u32, vp, vp, vp, u64, vp, ctypes.c_int, u64, vp]
+        L.cabac_hip_sparse_expand_device.argtypes = [vp, u32, vp, vp, vp, u64, vp, ctypes.c_int, u64, vp]
+        L.cabac_hip_sparse_compact_device.argtypes = [vp, u32, vp, vp, ctypes.c_int, u64, vp, vp, u64, vp]
+        L.cabac_hip_sparse_encode_batch.argtypes = [vp, u32, vp, vp, u64, vp, vp, u32, vp, vp, vp, u64, u64, vp, u64, vp, vp, vp, vp]
+        L.cabac_hip_sparse_parse_batch.argtypes = [vp, u32, vp, vp, u64, vp, vp, vp, vp, u64, u64, vp, vp, vp]
     L.cabac_hip_nal_escape_bound.argtypes = [ctypes.c_uint64]
     L.cabac_hip_nal_escape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
     L.cabac_hip_nal_unescape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp,
@@ -484,6 +502,41 @@ def workspace_bound(n_sub, n_host_records, n_tu, n_coded_coeff):
     if rc != 0:
         raise CabacHipError(rc, "cabac_hip_workspace_bound")
     return int(out[0]), int(out[1])
+
+
+def sparse_pack_host(tus, coeff, entry_capacity=None, entries=None, ent_first=None):
+    """cabac_hip_sparse_pack_host (CPU, no GPU): dense blocks (int16 or int32 array) -> (ent_first uint32[n_tu + 1], entries, status
+    record).  entry_capacity None: room for every element; `entries` / `ent_first` (optional): the caller's arrays, written in place."""
+    tus = np.ascontiguousarray(tus, TU_DTYPE)
+    assert coeff.dtype in (np.int16, np.int32) and coeff.flags.c_contiguous
+    if entries is None:
+        entries = np.zeros(max(len(coeff) if entry_capacity is None else int(entry_capacity), 1), np.uint32)
+    cap = len(entries) if entry_capacity is None else int(entry_capacity)
+    if ent_first is None:
+        ent_first = np.zeros(len(tus) + 1, np.uint32)
+    assert entries.dtype == np.uint32 and ent_first.dtype == np.uint32 and cap <= len(entries) and len(ent_first) >= len(tus) + 1
+    status = np.zeros(1, SPARSE_STATUS_DTYPE)
+    rc = load_library().cabac_hip_sparse_pack_host(len(tus), tus.ctypes.data, coeff.ctypes.data, coeff.itemsize, len(coeff),
+                                                   ent_first.ctypes.data, entries.ctypes.data, cap, status.ctypes.data)
+    if rc != 0:
+        raise CabacHipError(rc, "cabac_hip_sparse_pack_host")
+    return ent_first, entries[: min(int(status[0]["n_entries"]), cap)], status[0]
+
+
+def sparse_unpack_host(tus, ent_first, entries, coeff, n_entries=None):
+    """cabac_hip_sparse_unpack_host (CPU, no GPU): the lists written into the dense array `coeff` (int16 or int32, in place);
+    returns the status record."""
+    tus = np.ascontiguousarray(tus, TU_DTYPE)
+    ent_first = np.ascontiguousarray(ent_first, np.uint32)
+    entries = np.ascontiguousarray(entries, np.uint32)
+    assert coeff.dtype in (np.int16, np.int32) and coeff.flags.c_contiguous and len(ent_first) >= len(tus) + 1
+    status = np.zeros(1, SPARSE_STATUS_DTYPE)
+    rc = load_library().cabac_hip_sparse_unpack_host(len(tus), tus.ctypes.data, ent_first.ctypes.data, entries.ctypes.data,
+                                                     len(entries) if n_entries is None else int(n_entries), coeff.ctypes.data,
+                                                     coeff.itemsize, len(coeff), status.ctypes.data)
+    if rc != 0:
+        raise CabacHipError(rc, "cabac_hip_sparse_unpack_host")
+    return status[0]
 
 
 class CabacHip:
@@ -585,7 +638,8 @@ class CabacHip:
         cabac_hip_search_plan.h; 30 encode with sets, 31 decode with sets, 32 context advance and 33 a WPP prefix pass in
         cabac_hip_ctx_sets.h; 34 plan parse with sets, 35 a level of a rows parse and 36 the encode launch of a plan write with sets
         in cabac_hip_plan_rows.h; 37 hand-over index, 38 log mark and 39 the encode launch of a spliced call with sets in
-        cabac_hip_splice_rows.h; 40 the gate of a call on a fixed workspace in cabac_hip_workspace.h)."""
+        cabac_hip_splice_rows.h; 40 the gate of a call on a fixed workspace in cabac_hip_workspace.h; 41 coefficient expand and
+        42 coefficient compact in cabac_hip_sparse.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -1376,6 +1430,82 @@ class CabacHip:
                                                         len(locations) if locations is not None else 0, loc_base,
                                                         status.ctypes.data))
         return offsets, status[0]
+
+    # ---- sparse coefficient transport (include/cabac_hip_sparse.h) ------
+    sparse_pack_host = staticmethod(sparse_pack_host)
+    sparse_unpack_host = staticmethod(sparse_unpack_host)
+
+    def sparse_expand_device(self, n_tu, d_tu, d_ent_first, d_entries, n_entries_max, d_coeff, coeff_bytes, n_coeff_total, d_status):
+        """cabac_hip_sparse_expand_device: lists -> dense blocks in d_coeff (coeff_bytes 2 or 4); asynchronous on the ctx's stream."""
+        self._check(self.L.cabac_hip_sparse_expand_device(self.h, n_tu, _opt(d_tu), vp(d_ent_first), _opt(d_entries), n_entries_max,
+                                                          _opt(d_coeff), coeff_bytes, n_coeff_total, vp(d_status)))
+
+    def sparse_compact_device(self, n_tu, d_tu, d_coeff, coeff_bytes, n_coeff_total, d_ent_first, d_entries, entry_capacity, d_status):
+        """cabac_hip_sparse_compact_device: dense blocks -> d_ent_first (n_tu + 1 words) and at most entry_capacity entries."""
+        self._check(self.L.cabac_hip_sparse_compact_device(self.h, n_tu, _opt(d_tu), _opt(d_coeff), coeff_bytes, n_coeff_total,
+                                                           vp(d_ent_first), _opt(d_entries), entry_capacity, vp(d_status)))
+
+    def sparse_encode_batch(self, desc, records, splice_first, splices, tus, ent_first, entries, n_coeff_total, payload, check=True,
+                            with_info=False, with_counts=False, offsets=None, results=None):
+        """cabac_hip_sparse_encode_batch (host arrays, synchronous): encode_batch_residual with the int16 blocks given as their
+        lists; (offsets uint64[n + 1], results[, tu_info][, counts]).  `offsets` / `results` (optional): the caller's arrays."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        records = np.ascontiguousarray(records, np.uint16)
+        splice_first = np.ascontiguousarray(splice_first, np.uint32)
+        splices = np.ascontiguousarray(splices, SPLICE_DTYPE)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        ent_first = np.ascontiguousarray(ent_first, np.uint32)
+        entries = np.ascontiguousarray(entries, np.uint32)
+        n = len(desc)
+        assert len(ent_first) >= len(tus) + 1
+        offsets = np.zeros(n + 1, np.uint64) if offsets is None else offsets
+        res = np.zeros(max(n, 1), RESULT_DTYPE) if results is None else results
+        info = np.zeros(max(len(tus), 1), np.uint32) if with_info else None
+        counts = np.zeros((max(n, 1), BIN_COUNT_WORDS), np.uint32) if with_counts else None
+        rc = self.L.cabac_hip_sparse_encode_batch(
+            self.h, n, desc.ctypes.data, records.ctypes.data, len(records), splice_first.ctypes.data, splices.ctypes.data, len(tus),
+            tus.ctypes.data, ent_first.ctypes.data, entries.ctypes.data, len(entries), int(n_coeff_total), payload.ctypes.data,
+            payload.nbytes, offsets.ctypes.data, res.ctypes.data, _ptr(info), _ptr(counts))
+        self._check(rc, allow_substream=not check)
+        out = [offsets, res[:n]]
+        if with_info:
+            out.append(info[: len(tus)])
+        if with_counts:
+            out.append(counts[:n])
+        return tuple(out)
+
+    def sparse_parse_batch(self, desc, data, tile_first, tus, n_coeff_total, entries=None, entry_capacity=None, check=True,
+                           ent_first=None):
+        """cabac_hip_sparse_parse_batch (host arrays, synchronous): residual_parse_batch(int16=True) with the blocks coming back as
+        their lists; (ent_first, entries, results, tu_info, status record).  `entries` / `ent_first` (optional): the caller's uint32
+        arrays, e.g. pinned; entry_capacity defaults to the length of `entries` (n_coeff_total without it).  A capacity that is too small raises with status
+        CABAC_HIP_ERR_INVALID; the error's `sparse_status["n_entries"]` then tells the need, and `sparse_outputs` holds
+        (ent_first, results, tu_info)."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        data = np.ascontiguousarray(data, np.uint8)
+        tile_first = np.ascontiguousarray(tile_first, np.uint32)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        assert len(tile_first) == len(desc) + 1
+        if entries is None:
+            entries = np.zeros(max(int(n_coeff_total) if entry_capacity is None else int(entry_capacity), 1), np.uint32)
+        cap = len(entries) if entry_capacity is None else int(entry_capacity)
+        assert entries.dtype == np.uint32 and cap <= len(entries)
+        if ent_first is None:
+            ent_first = np.zeros(len(tus) + 1, np.uint32)
+        assert ent_first.dtype == np.uint32 and len(ent_first) >= len(tus) + 1
+        res = np.zeros(max(len(desc), 1), RESULT_DTYPE)
+        info = np.zeros(max(len(tus), 1), np.uint32)
+        status = np.zeros(1, SPARSE_STATUS_DTYPE)
+        rc = self.L.cabac_hip_sparse_parse_batch(self.h, len(desc), desc.ctypes.data, data.ctypes.data, len(data), tile_first.ctypes.data,
+                                                 tus.ctypes.data, ent_first.ctypes.data, entries.ctypes.data, cap, int(n_coeff_total),
+                                                 info.ctypes.data, res.ctypes.data, status.ctypes.data)
+        try:
+            self._check(rc, allow_substream=not check)
+        except CabacHipError as e:
+            e.sparse_status = status[0]
+            e.sparse_outputs = (ent_first, res[: len(desc)], info[: len(tus)])
+            raise
+        return ent_first, entries[: int(status[0]["n_entries"])], res[: len(desc)], info[: len(tus)], status[0]
 
     def encode_batch_nal(self, desc, records, nal, check=True):
         """cabac_hip_encode_batch_nal: records -> NAL-ready payload in `nal` (uint8 array, e.g. pinned); returns (nal_offsets

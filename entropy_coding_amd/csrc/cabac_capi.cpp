@@ -22,6 +22,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -37,11 +38,13 @@
 #include "cabac_hip_search_emit.h"
 #include "cabac_hip_search_plan.h"
 #include "cabac_hip_search_unit.h"
+#include "cabac_hip_sparse.h"
 #include "cabac_hip_splice_rows.h"
 #include "cabac_hip_workspace.h"
 #include "cabac_hip_write_plan.h"
 #include "cabac_kernels.h"
 #include "cabac_nal_kernels.h"
+#include "cabac_sparse_kernels.h"
 
 #ifdef CABAC_PARSE_PROFILE
 namespace cabac {
@@ -90,6 +93,9 @@ enum Slot {
   // the plan rows and the spliced rows: per substream the record index of its hand-over entry, then the out sets of the substreams
   // that did not stop (the rows write); the hand-over splice counts of the spliced rows' host-pointer form
   kRowsWords = 71, kSpInSync = 72,
+  // the sparse coefficient transport (cabac_hip_sparse.h): the error words and workgroup counts of its kernels, and the firsts,
+  // entries and status of its host-pointer forms
+  kSparseScratch = 73, kSparseFirst = 74, kSparseEnt = 75, kSparseStatus = 76,
   kSlots
 };
 
@@ -689,6 +695,68 @@ int parse_rows_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substre
     HIP_TRY(c, cabac::launch_plan_parse_sets(c->stream, n, d_desc + first, d_bytes, d_tile_first + first, d_tu, d_tu_at, d_tu_guard, d_plan,
                                              d_coeff, coeff_bytes, d_values, d_tu_info, d_results + first, sets, rows.d_sync_at + first,
                                              first, hands_over ? first : 0xFFFFFFFFu));
+  }
+  return CABAC_HIP_OK;
+}
+
+// ---- the lists of cabac_hip_sparse_encode_batch (cabac_hip_sparse.h) and what that form refuses about them ------------------------
+struct SparseSrc {
+  const uint32_t *ent_first, *entries;
+  uint64_t n_entries;
+};
+
+// the first block of [t0, t1) the form refuses, and why (t1: none)
+uint32_t first_refused_block(uint32_t t0, uint32_t t1, const cabac_tu_desc *tus, const SparseSrc &sp, const char **why) {
+  for (uint32_t t = t0; t < t1; t++) {
+    const uint32_t lo = sp.ent_first[t], hi = sp.ent_first[t + 1];
+    const char *what = nullptr;
+    if (lo > hi) what = "ent_first descends";
+    else if (hi > sp.n_entries) what = "ent_first passes n_entries_total";
+    else if (tus[t].max_log2_tr_range > 15) what = "max_log2_tr_range above 15 is not carried in the sparse form";
+    else if (tus[t].log2_width <= 6 && tus[t].log2_height <= 6) {  // (other sizes: flagged by the binariser, no entry is used)
+      const uint32_t n = 1u << (tus[t].log2_width + tus[t].log2_height);
+      uint32_t bad = 0;
+      for (uint32_t k = lo; k < hi; k++) bad |= uint32_t((sp.entries[k] & 0xFFFFu) >= n);
+      if (bad) what = "an entry's pos lies outside the block";
+    }
+    if (what) {
+      *why = what;
+      return t;
+    }
+  }
+  return t1;
+}
+
+// A large batch is checked by up to eight threads, a slice of the blocks each: the walk is a few nanoseconds per block, which for
+// the 1.6 M blocks of the residual tiles is more than the whole upload of their lists takes.
+int check_sparse_host(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_desc *tus, const SparseSrc &sp) {
+  char buf[128];
+  if (sp.ent_first[0] != 0u) return fail(c, CABAC_HIP_ERR_INVALID, "block 0: ent_first must start at 0");
+  const uint32_t kSlice = 1u << 16;
+  const uint32_t n_thread = std::max(1u, std::min({8u, std::thread::hardware_concurrency(), n_tu / kSlice}));
+  std::vector<uint32_t> bad(n_thread, n_tu);
+  std::vector<const char *> why(n_thread, nullptr);
+  auto slice = [&](uint32_t i) {
+    const uint32_t t0 = uint32_t(uint64_t(n_tu) * i / n_thread), t1 = uint32_t(uint64_t(n_tu) * (i + 1) / n_thread);
+    const uint32_t t = first_refused_block(t0, t1, tus, sp, &why[i]);
+    bad[i] = t < t1 ? t : n_tu;
+  };
+  std::vector<std::thread> workers;
+  try {
+    for (uint32_t i = 1; i < n_thread; i++) workers.emplace_back(slice, i);
+  } catch (...) {  // no thread to be had: the slices that got none are walked here
+    for (uint32_t i = (uint32_t)workers.size() + 1; i < n_thread; i++) slice(i);
+  }
+  slice(0);
+  for (std::thread &w : workers) w.join();
+  for (uint32_t i = 0; i < n_thread; i++)
+    if (bad[i] != n_tu) {  // slices are in block order: the first hit is the lowest block
+      snprintf(buf, sizeof buf, "block %u: %s", bad[i], why[i]);
+      return fail(c, CABAC_HIP_ERR_INVALID, buf);
+    }
+  if (sp.ent_first[n_tu] != sp.n_entries) {
+    snprintf(buf, sizeof buf, "block %u: ent_first must end at n_entries_total", n_tu);
+    return fail(c, CABAC_HIP_ERR_INVALID, buf);
   }
   return CABAC_HIP_OK;
 }
@@ -1755,8 +1823,10 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
                                       uint64_t n_records_total, const uint32_t *splice_first, const cabac_splice *splices, uint32_t n_tu,
                                       const cabac_tu_desc *tus, const void *coeff, int coeff_bytes, uint64_t n_coeff_total, uint8_t *payload,
                                       uint64_t payload_capacity, uint64_t *payload_offsets, cabac_substream_result *results,
-                                      uint32_t *tu_info, uint32_t *bin_counts, const Rows *rows = nullptr) {
-  if (!c || !payload_offsets || (n_sub && (!desc || !splice_first || !results || !payload)) || (n_tu && (!tus || !coeff || !splices)) ||
+                                      uint32_t *tu_info, uint32_t *bin_counts, const Rows *rows = nullptr,
+                                      const SparseSrc *sparse = nullptr) {
+  if (!c || !payload_offsets || (n_sub && (!desc || !splice_first || !results || !payload)) ||
+      (n_tu && (!tus || (!coeff && !sparse) || !splices)) ||
       (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (c->ws_fixed) return refuse_fixed_batch(c);
@@ -1776,7 +1846,7 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
     }
     if (splice_first[0] != 0 || splice_first[n_sub] != n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "every block must be spliced exactly once");
   }
-  if (!rows || n_sub == 0) payload_offsets[0] = 0;  // (the rows form writes no output before it has run)
+  if ((!rows && !sparse) || n_sub == 0) payload_offsets[0] = 0;  // (the rows and the sparse form write no output before they have run)
   if (n_sub == 0) return n_tu ? fail(c, CABAC_HIP_ERR_INVALID, "blocks without a substream") : CABAC_HIP_OK;
   for (uint32_t s = 0; s < n_sub; s++) {
     if (desc[s].rec_offset > n_records_total || desc[s].n_records > n_records_total - desc[s].rec_offset)
@@ -1802,6 +1872,11 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if ((rc = ensure(c, kPayload, payload_capacity ? payload_capacity : 16))) return rc;
   if ((rc = ensure(c, kPayloadOffsets, (size_t(n_sub) + 1) * sizeof(uint64_t)))) return rc;
   if ((rc = ensure(c, kSpFlag, 64))) return rc;
+  const size_t ent_first_bytes = (size_t(n_tu) + 1) * sizeof(uint32_t);
+  if (sparse && ((rc = ensure(c, kSparseFirst, ent_first_bytes)) || (rc = ensure(c, kSparseEnt, sparse->n_entries * sizeof(uint32_t))) ||
+                 (rc = ensure(c, kSparseScratch, cabac::sparse_scratch_bytes(n_tu))) ||
+                 (rc = ensure(c, kSparseStatus, sizeof(cabac_sparse_status)))))
+    return rc;
   const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
   if (rows && ((rc = ensure(c, kWppFrom, link_bytes)) || (rc = ensure(c, kWppAt, link_bytes)) || (rc = ensure(c, kSpInSync, link_bytes))))
     return rc;
@@ -1825,7 +1900,10 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if ((rc = h2d(c, c->d_buf[kSpInFirst], splice_first, first_bytes, c->s_in))) return rc;
   if ((rc = h2d(c, c->d_buf[kSpInSplice], splices, size_t(n_splice) * sizeof(cabac_splice), c->s_in))) return rc;
   if ((rc = h2d(c, c->d_buf[kSpInRec], records, n_records_total * sizeof(uint16_t), c->s_in))) return rc;
-  if ((rc = h2d(c, c->d_buf[kSpInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), c->s_in))) return rc;
+  if (sparse) {  // the lists go up in the coefficients' place
+    if ((rc = h2d(c, c->d_buf[kSparseFirst], sparse->ent_first, ent_first_bytes, c->s_in))) return rc;
+    if ((rc = h2d(c, c->d_buf[kSparseEnt], sparse->entries, sparse->n_entries * sizeof(uint32_t), c->s_in))) return rc;
+  } else if ((rc = h2d(c, c->d_buf[kSpInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), c->s_in))) return rc;
   Rows d_rows{};
   if (rows) {
     if ((rc = h2d(c, c->d_buf[kWppFrom], rows->d_sync_from, link_bytes, c->s_in))) return rc;
@@ -1836,9 +1914,19 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
                         rows->d_sync_splice ? static_cast<const uint32_t *>(c->d_buf[kSpInSync]) : nullptr};
   }
   HIP_TRY(c, hipEventRecord(c->ev_in[1], c->s_in));
+  // the lists are checked while they are on the wire: nothing of the pipeline has run and no output is touched when they are refused
+  if (sparse && (rc = check_sparse_host(c, n_tu, tus, *sparse))) return rc;
   HIP_TRY(c, wait_event(c, c->ev_k[0]));
   if (*h_flag) return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
   HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in[1], 0));
+  if (sparse) {  // every block that lies inside the buffer (checked above) is written whole: zeros, then its entries
+    Timed t(c, 41);
+    HIP_TRY(c, cabac::launch_sparse_expand(c->stream, n_tu, static_cast<const cabac_tu_desc *>(c->d_buf[kSpInTu]),
+                                           static_cast<const uint32_t *>(c->d_buf[kSparseFirst]),
+                                           static_cast<const uint32_t *>(c->d_buf[kSparseEnt]), sparse->n_entries, c->d_buf[kSpInCoeff],
+                                           coeff_bytes, n_coeff_total, static_cast<cabac_sparse_status *>(c->d_buf[kSparseStatus]),
+                                           c->d_buf[kSparseScratch]));
+  }
   rc = encode_residual_device_impl(c, n_sub, static_cast<const cabac_substream_desc *>(c->d_buf[kSpInDesc]),
                                         static_cast<const uint16_t *>(c->d_buf[kSpInRec]), static_cast<const uint32_t *>(c->d_buf[kSpInFirst]),
                                         static_cast<const cabac_splice *>(c->d_buf[kSpInSplice]), n_splice, n_tu,
@@ -3410,6 +3498,98 @@ int cabac_hip_search_log_encode_rows_device(cabac_search_log *log, const cabac_s
   const Rows rows{n_level, level_first, d_sync_from, nullptr, nullptr};
   return search_log_encode_impl(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr,
                                 &rows);
+}
+
+// ---- sparse coefficient transport (cabac_hip_sparse.h; kernels: cabac_sparse.hip, the CPU forms: cabac_sparse_host.cpp) ----------
+namespace {
+int sparse_args(cabac_hip_ctx *c, int coeff_bytes, uint64_t n_coeff_total) {
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_coeff_total >> 32) return fail(c, CABAC_HIP_ERR_INVALID, "n_coeff_total must be below 2^32 (ent_first is 32-bit)");
+  return CABAC_HIP_OK;
+}
+}  // namespace
+
+int cabac_hip_sparse_expand_device(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_desc *d_tu, const uint32_t *d_ent_first,
+                                   const uint32_t *d_entries, uint64_t n_entries_max, void *d_coeff, int coeff_bytes,
+                                   uint64_t n_coeff_total, cabac_sparse_status *d_status) {
+  if (!c || !d_status || !d_ent_first || (n_tu && !d_tu) || (n_entries_max && !d_entries) || (n_coeff_total && !d_coeff))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (int bad = sparse_args(c, coeff_bytes, n_coeff_total)) return bad;
+  DeviceGuard g(c->device);
+  if (int rc = ensure(c, kSparseScratch, cabac::sparse_scratch_bytes(n_tu))) return rc;
+  return TIMED_LAUNCH(c, 41, cabac::launch_sparse_expand(c->stream, n_tu, d_tu, d_ent_first, d_entries, n_entries_max, d_coeff, coeff_bytes,
+                                                         n_coeff_total, d_status, c->d_buf[kSparseScratch]));
+}
+
+int cabac_hip_sparse_compact_device(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes,
+                                    uint64_t n_coeff_total, uint32_t *d_ent_first, uint32_t *d_entries, uint64_t entry_capacity,
+                                    cabac_sparse_status *d_status) {
+  if (!c || !d_status || !d_ent_first || (n_tu && !d_tu) || (entry_capacity && !d_entries) || (n_coeff_total && !d_coeff))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (int bad = sparse_args(c, coeff_bytes, n_coeff_total)) return bad;
+  DeviceGuard g(c->device);
+  if (int rc = ensure(c, kSparseScratch, cabac::sparse_scratch_bytes(n_tu))) return rc;
+  return TIMED_LAUNCH(c, 42, cabac::launch_sparse_compact(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, n_coeff_total, d_ent_first, d_entries,
+                                                          entry_capacity, d_status, c->d_buf[kSparseScratch]));
+}
+
+int cabac_hip_sparse_encode_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                  uint64_t n_records_total, const uint32_t *splice_first, const cabac_splice *splices, uint32_t n_tu,
+                                  const cabac_tu_desc *tus, const uint32_t *ent_first, const uint32_t *entries, uint64_t n_entries_total,
+                                  uint64_t n_coeff_total, uint8_t *payload, uint64_t payload_capacity, uint64_t *payload_offsets,
+                                  cabac_substream_result *results, uint32_t *tu_info, uint32_t *bin_counts) {
+  if (!c || !ent_first || (n_entries_total && !entries)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (int bad = sparse_args(c, 2, n_coeff_total)) return bad;
+  const SparseSrc sparse{ent_first, entries, n_entries_total};
+  return host_call_exit(c, encode_batch_residual_impl(c, n_sub, desc, records, n_records_total, splice_first, splices, n_tu, tus, nullptr, 2,
+                                                      n_coeff_total, payload, payload_capacity, payload_offsets, results, tu_info,
+                                                      bin_counts, nullptr, &sparse));
+}
+
+int cabac_hip_sparse_parse_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                 uint64_t bytes_total, const uint32_t *tile_first, const cabac_tu_desc *tus, uint32_t *ent_first,
+                                 uint32_t *entries, uint64_t entry_capacity, uint64_t n_coeff_total, uint32_t *tu_info,
+                                 cabac_substream_result *results, cabac_sparse_status *status) {
+  if (!c || !status || !ent_first || (entry_capacity && !entries) || (n_sub && (!desc || !bytes || !tile_first || !tus || !results)))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (int bad = sparse_args(c, 2, n_coeff_total)) return bad;
+  if (n_sub == 0) {
+    ent_first[0] = 0;
+    *status = cabac_sparse_status{0, 0, CABAC_SPARSE_NO_BAD};
+    return CABAC_HIP_OK;
+  }
+  const uint32_t n_tu = tile_first[n_sub];
+  for (uint32_t s = 0; s < n_sub; s++)
+    if (int bad = check_substream_host(c, desc[s], tile_first, s, &bytes_total)) return bad;
+  if (int bad = check_coeff_ranges_host(c, n_tu, tus, n_coeff_total)) return bad;
+  const uint64_t cap = std::min(entry_capacity, n_coeff_total);  // blocks that do not overlap hold no more entries than elements
+  DeviceGuard g(c->device);
+  ParseStage st{c, n_sub, n_tu, 2, n_coeff_total, n_coeff_total != 0};
+  int rc;
+  if ((rc = st.stage(desc, bytes, bytes_total, tile_first, tus, nullptr, nullptr))) return rc;  // 16-bit blocks: cleared, nothing goes up
+  const size_t first_bytes = (size_t(n_tu) + 1) * sizeof(uint32_t);
+  if ((rc = ensure(c, kSparseFirst, first_bytes)) || (rc = ensure(c, kSparseEnt, cap * sizeof(uint32_t))) ||
+      (rc = ensure(c, kSparseScratch, cabac::sparse_scratch_bytes(n_tu))) || (rc = ensure(c, kSparseStatus, sizeof(cabac_sparse_status))))
+    return rc;
+  if ((rc = residual_parse_device_impl(c, n_sub, st.d_desc, st.d_bytes, st.d_tile_first, st.d_tu, st.d_coeff, 2, st.d_tu_info, st.d_results)))
+    return rc;
+  if ((rc = TIMED_LAUNCH(c, 42, cabac::launch_sparse_compact(c->stream, n_tu, st.d_tu, st.d_coeff, 2, n_coeff_total,
+                                                             static_cast<uint32_t *>(c->d_buf[kSparseFirst]),
+                                                             static_cast<uint32_t *>(c->d_buf[kSparseEnt]), cap,
+                                                             static_cast<cabac_sparse_status *>(c->d_buf[kSparseStatus]),
+                                                             c->d_buf[kSparseScratch]))))
+    return rc;
+  HIP_TRY(c, down(c, status, c->d_buf[kSparseStatus], sizeof(cabac_sparse_status)));
+  HIP_TRY(c, down(c, ent_first, c->d_buf[kSparseFirst], first_bytes));
+  st.blocks = false;  // the blocks stay on the device: the entries leave in their place, once their number is known
+  const int flagged = st.finish(nullptr, tu_info, results);  // the first wait
+  if (flagged != CABAC_HIP_OK && flagged != CABAC_HIP_ERR_SUBSTREAM) return flagged;
+  if (status->n_entries > entry_capacity)
+    return fail(c, CABAC_HIP_ERR_INVALID, "entry_capacity too small (status->n_entries is the size needed)");
+  if (status->n_entries > cap) return fail(c, CABAC_HIP_ERR_INVALID, "more entries than coefficients: blocks overlap");
+  HIP_TRY(c, down(c, entries, c->d_buf[kSparseEnt], status->n_entries * sizeof(uint32_t)));
+  HIP_TRY(c, wait_stream(c, c->stream));  // the second
+  return flagged;
 }
 
 // ---- the fixed workspace (cabac_hip_workspace.h; the gate and its kernels: cabac_workspace.hip) -------------------------------
