@@ -360,7 +360,9 @@ void pipe_quiesce(cabac_hip_ctx *c) {
 }
 
 // the exit of every host-pointer entry point: an error other than "a substream has a flag set" may have come from the middle
-// of the pipeline
+// of the pipeline.  The contract of such a return ("payload_capacity too small" is the one a caller meets
+// in ordinary use): the outputs' contents are unspecified, the library does not write to caller memory on behalf of the call once
+// it has returned, and the ctx is usable as before.  Only error paths wait here: a call that returns CABAC_HIP_OK never does.
 int host_call_exit(cabac_hip_ctx *c, int rc) {
   if (c && c->pipe_ready && rc != CABAC_HIP_OK && rc != CABAC_HIP_ERR_SUBSTREAM) {
     const std::string keep = c->last_error;

@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import assemble_model as M
 import helpers as H
 from entropy_coding_amd import capi
 
@@ -115,3 +116,170 @@ def test_pack_shard_gathers_on_the_device():
         torch.cuda.synchronize()
         assert np.array_equal(got_d, want_d) and got_t == want_t
         assert np.array_equal(got_r.cpu().numpy().view(np.uint16), want_r)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Below: every kernel of csrc/cabac_assemble.hip against tests/assemble_model.py, bit for bit, on batches made by writing results and
+# slot bytes directly (tests/test_assemble_model.py checks on the CPU that they reach the branches they are made for).  Every
+# device buffer a kernel writes, and every one it reads, is a view into a larger tensor of sentinel bytes that is compared whole
+# afterwards: nothing outside the view, and nothing inside it that the model leaves alone, may change.
+GUARD = 4096
+
+
+class Guarded:
+    """`content` (a numpy array) on the device between two guards of `sentinel` bytes: GUARD bytes in front (plus `shift`, to
+    misalign the view) and `after` bytes behind"""
+
+    def __init__(self, content, sentinel, after=GUARD, shift=0):
+        import torch
+        self.content = np.ascontiguousarray(content).view(np.uint8).reshape(-1).copy()
+        self.front, self.after, self.sentinel = GUARD + shift, after, sentinel
+        self.t = torch.from_numpy(self.expect(self.content)).cuda()
+        self.ptr = self.t.data_ptr() + self.front
+        assert self.t.data_ptr() % 256 == 0
+
+    def expect(self, content):
+        content = np.ascontiguousarray(content).view(np.uint8).reshape(-1)
+        assert len(content) == len(self.content)
+        return np.concatenate([np.full(self.front, self.sentinel, np.uint8), content, np.full(self.after, self.sentinel, np.uint8)])
+
+    def check(self, want=None, what=""):
+        """The whole tensor is the guards around `want` (default: what went in)"""
+        got, full = self.t.cpu().numpy(), self.expect(self.content if want is None else want)
+        bad = np.nonzero(got != full)[0]
+        assert len(bad) == 0, "%s: %d bytes differ, the first at %d of the view (%d bytes long): %d for %d" % (
+            what, len(bad), int(bad[0]) - self.front, len(self.content), int(got[bad[0]]), int(full[bad[0]]))
+
+
+def _inputs(batch):
+    return Guarded(batch["desc"], 0x3C), Guarded(batch["results"], 0x3C), Guarded(batch["slots"], 0x3C)
+
+
+@pytest.mark.parametrize("n_sub", M.N_SUBS)
+def test_assemble_clips_at_the_capacity_and_keeps_its_bounds(n_sub):
+    """cabac_hip_assemble_device on the shared batch with the payload as large as the total, with every clipping capacity of
+    assemble_model.clip_capacities and with the payload 1, 2 and 3 bytes off its alignment: the offsets are the unclipped sums
+    whatever the capacity, the payload is the model's up to the capacity and untouched behind it (the guard there is larger
+    than the whole unclipped payload), the slots, descriptors and results are as they were."""
+    hip = H.gpu_ctx()
+    b = M.shared_batch(n_sub)
+    offs = M.offsets(b["desc"], b["results"])
+    total = int(offs[-1])
+    caps = M.clip_capacities(offs)
+    g_desc, g_res, g_slots = _inputs(b)
+    runs = [(name, cap, 0) for name, cap in caps.items()]
+    runs += [(name, caps[name], shift) for name in ("total", "total-1", "into+2") if name in caps for shift in (1, 2, 3)]
+    for name, cap, shift in runs:
+        init = np.full(cap, M.PAY_SENTINEL, np.uint8)
+        g_pay = Guarded(init, M.PAY_SENTINEL, after=max(GUARD, total) + 8, shift=shift)
+        g_off = Guarded(np.full(n_sub + 1, 0xA7A7A7A7A7A7A7A7, np.uint64), 0xA7)
+        hip.assemble_device(n_sub, g_desc.ptr, g_res.ptr, g_slots.ptr, g_pay.ptr, cap, g_off.ptr)
+        hip.synchronize()
+        what = "n_sub %d, capacity %s = %d of %d, payload + %d" % (n_sub, name, cap, total, shift)
+        g_off.check(offs, what + ": offsets")
+        g_pay.check(M.assemble(b["desc"], b["results"], b["slots"], cap, init), what + ": payload")
+        g_slots.check(what=what + ": slots")
+    g_desc.check(what="descriptors")
+    g_res.check(what="results")
+    hip.close()
+
+
+@pytest.mark.parametrize("n_sub", M.N_SUBS)
+def test_split_is_the_inverse_and_stays_inside_the_slots(n_sub):
+    """cabac_hip_split_device of the assembled payload (the model's) back into slots full of sentinels: every slot holds its
+    substream again and its sentinel behind it, from the first byte behind the size on; then with hand-made entry points whose
+    spans exceed the slots they go to: no more than byte_capacity arrives, the neighbouring slot stays as it was.  Both with
+    the payload at every alignment."""
+    hip = H.gpu_ctx()
+    b = M.shared_batch(n_sub)
+    desc, res, slots = b["desc"], b["results"], b["slots"]
+    offs = M.offsets(desc, res)
+    payload = M.assemble(desc, res, slots, int(offs[-1]), np.zeros(int(offs[-1]), np.uint8))
+    g_desc = Guarded(desc, 0x3C)
+    empty = np.full(len(slots), M.SLOT_SENTINEL, np.uint8)
+    for what, o, p in (("inverse", offs, payload), ("wide spans",) + M.wide_offsets(b)):
+        g_off = Guarded(o, 0x3C)
+        want = M.split(desc, o, p, empty)
+        if what == "inverse":                                      # the batch's own slots again, slack and padding included
+            assert np.array_equal(want, slots)
+        for shift in range(4):
+            g_pay, g_slots = Guarded(p, M.PAY_SENTINEL, shift=shift), Guarded(empty, 0x3C)
+            hip.split_device(n_sub, g_desc.ptr, g_off.ptr, g_pay.ptr, g_slots.ptr)
+            hip.synchronize()
+            g_slots.check(want, "n_sub %d, %s, payload + %d: slots" % (n_sub, what, shift))
+            g_pay.check(what="payload")
+        g_off.check(what="offsets")
+    g_desc.check(what="descriptors")
+    hip.close()
+
+
+@pytest.mark.parametrize("n_sub", M.COUNT_N_SUBS + ("long runs",))
+def test_count_takes_the_whole_bytes_inside_the_slot(n_sub):
+    """cabac_hip_count_emulations_device over substreams that end in a partial byte (not part of the reference's FIFO: not
+    counted, though it would complete a match), that overflowed (counted up to byte_capacity, though matches follow) and whole
+    ones, four to a workgroup; "long runs": zero runs of 65 535 .. 100 000 bytes, ending 0 .. 3 bytes before a partial byte."""
+    hip = H.gpu_ctx()
+    b = M.long_run_batch() if n_sub == "long runs" else M.count_batch(n_sub)
+    n = len(b["desc"])
+    g_desc, g_res, g_slots = _inputs(b)
+    g_cnt = Guarded(np.full(n, 0x91919191, np.uint32), 0x91)
+    hip.count_emulations_device(n, g_desc.ptr, g_res.ptr, g_slots.ptr, g_cnt.ptr)
+    hip.synchronize()
+    got = g_cnt.t.cpu().numpy()[g_cnt.front: g_cnt.front + 4 * n].view(np.uint32)
+    want = M.counts_of(b)
+    assert np.array_equal(got, want), [(int(s), int(got[s]), int(want[s]), int(b["kind"][s])) for s in np.nonzero(got != want)[0][:10]]
+    g_cnt.check(want, "counts")
+    for g in (g_desc, g_res, g_slots):
+        g.check(what="inputs")
+    hip.close()
+
+
+@pytest.mark.parametrize("n_seg", [0, 1, 300])
+def test_gather_at_every_parity_and_leaves_the_gaps(n_seg):
+    """cabac_hip_gather_records_device itself: runs of 0 .. 513 records with source and destination offsets of either parity,
+    the destination runs apart from each other; n_seg 1: each of the 32 combinations alone."""
+    import torch
+    hip = H.gpu_ctx()
+    for first in range(32 if n_seg == 1 else 1):
+        c = M.gather_case(n_seg, first)
+        if n_seg:
+            assert c["length"][0] == M.GATHER_LENGTHS[first % 8]
+            assert (int(c["src_off"][0]) & 1, int(c["dst_off"][0]) & 1) == (first >> 3 & 1, first >> 4 & 1)
+        if n_seg == 300:
+            assert len({(int(n), int(s) & 1, int(d) & 1) for n, s, d in zip(c["length"], c["src_off"], c["dst_off"])}) == 32
+            ends = c["dst_off"][:-1].astype(np.int64) + c["length"][:-1]
+            assert (c["dst_off"][1:].astype(np.int64) - ends >= 1).all()
+        init = np.full(c["n_dst"], 0xBEEF, np.uint16)
+        g_src, g_dst = Guarded(c["src"], 0x3C), Guarded(init, 0xE1)
+        t_so, t_do, t_len = (torch.from_numpy(np.concatenate([c[k], np.zeros(1, c[k].dtype)]).view(np.uint8)).cuda()
+                             for k in ("src_off", "dst_off", "length"))
+        hip.gather_records_device(n_seg, t_so.data_ptr(), t_do.data_ptr(), t_len.data_ptr(), g_src.ptr, g_dst.ptr)
+        hip.synchronize()
+        g_dst.check(M.gather(c["src_off"], c["dst_off"], c["length"], c["src"], init), "n_seg %d from %d: destination" % (n_seg, first))
+        g_src.check(what="source")
+    hip.close()
+
+
+def test_packed_bins_byte_for_byte():
+    """cabac_hip_decode_batch_packed on batches whose substreams cover every record: all (n + 7) // 8 bytes are the model's, the
+    bits behind the last bin zero, the caller's bytes behind them untouched."""
+    hip = capi.CabacHip(0)
+    orc = H.load_oracle()
+    rng = np.random.default_rng(8)
+    for n in (1, 7, 8, 9, 2047, 2048, 2049):
+        parts = [n] if n < 7 else [n // 3, n // 3, n - 2 * (n // 3)]
+        recs = [H.random_records(rng, k - 1) for k in parts]
+        records = np.concatenate(recs)
+        desc, total = H.make_desc(parts, rng.integers(0, 64, size=len(parts)), [2] * len(parts), H.SUB_FINISH | H.SUB_ALIGN_RBSP)
+        out, res = orc.encode_batch(desc, records, total)
+        assert len(records) == n and int(desc["n_records"].sum()) == n and not res["flags"].any()
+        dd = desc.copy()
+        dd["byte_capacity"] = (res["n_bits"] + 7) // 8
+        mine = np.full((n + 7) // 8 + 64, 0xEE, np.uint8)
+        packed, rp = hip.decode_batch_packed(dd, records, out, packed=mine)
+        bins_o, ro = orc.decode_batch(dd, records, out)
+        assert not rp["flags"].any() and np.array_equal(rp["n_bits"], ro["n_bits"]) and np.array_equal(bins_o, records >> 15)
+        want = M.pack_bins(records >> 15)
+        assert len(want) == (n + 7) // 8 and np.array_equal(packed, want), n
+        assert np.array_equal(mine[: len(want)], want) and (mine[len(want):] == 0xEE).all(), n
+    hip.close()

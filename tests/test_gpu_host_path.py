@@ -178,3 +178,128 @@ def test_early_error_return_leaves_the_pipeline_idle(pinned):
         hip.close()
     finally:
         del os.environ["CABAC_HIP_CHUNKS"]
+
+
+# ---- "payload_capacity too small" ("A payload that is too small"): CABAC_HIP_ERR_INVALID with that text, the
+# payload's contents unspecified, no write to caller memory on behalf of the call once it has returned, the ctx usable ----
+TOO_SMALL = "payload_capacity too small"
+MINE = 0xD7
+
+
+def _first_chunk_substreams(desc, chunks):
+    """How many substreams the first of `chunks` chunks holds: a batch is cut at substream boundaries into runs of about equal
+    record counts, the first one ending with the substream at which the records so far reach total / chunks"""
+    done = np.cumsum(desc["n_records"].astype(np.int64))
+    return len(desc) if chunks == 1 else int(np.searchsorted(done, int(done[-1]) // chunks, side="left")) + 1
+
+
+def _caller_bytes(n, pinned, keep):
+    """n bytes of the caller's, all MINE, in pinned or in pageable memory"""
+    if pinned:
+        keep.append(capi.PinnedArray((n,), np.uint8))
+        a = keep[-1].array
+    else:
+        a = np.zeros(n, np.uint8)
+    a[:] = MINE
+    assert capi.host_is_pinned(a) == pinned
+    return a
+
+
+@pytest.mark.parametrize("chunks", [1, 2, 3])
+@pytest.mark.parametrize("pinned", [False, True])
+def test_refused_payload_is_left_alone_once_the_call_has_returned(chunks, pinned):
+    """cabac_hip_encode_batch_payload with a payload of 0 bytes, of 1, of one byte less than needed and of exactly the first
+    chunk's size (so that with two and three chunks the refusal comes after earlier chunks were queued towards the caller's memory,
+    through the bounce ring if it is pageable).  After every refusal a sufficient call on the same ctx, with another payload, gives
+    the oracle's bytes — and every refused array, kept alive, is byte for byte what it was when its call returned.  (With the drain
+    of the error exits taken out of the library — host_call_exit in csrc/cabac_capi.cpp — the pageable cases with two and three
+    chunks fail here: the next call hands the stale bounce blocks to the refused payload.)"""
+    os.environ["CABAC_HIP_CHUNKS"] = str(chunks)   # read when the ctx sets up its streams
+    keep = []
+    try:
+        hip = capi.CabacHip(0)
+        rng = np.random.default_rng(4000 + chunks)
+        desc, records, total = _ragged_batch(rng, 600, 400)
+        out_o, res_o = H.load_oracle().encode_batch(desc, records, total)
+        nbytes = np.minimum((res_o["n_bits"].astype(np.int64) + 7) // 8, desc["byte_capacity"].astype(np.int64))
+        want_off = np.concatenate([[0], np.cumsum(nbytes)]).astype(np.uint64)
+        need = int(nbytes.sum())
+        first = int(want_off[_first_chunk_substreams(desc, chunks)])
+        assert (first == need) == (chunks == 1) and 1 < first
+        refused = []
+        for cap in (0, 1, need - 1, first):
+            mine = _caller_bytes(cap + 64, pinned, keep)            # the payload is its first `cap` bytes
+            if cap == need:                                         # one chunk: the first chunk's size is the whole batch's
+                hip.encode_batch_payload(desc, records, mine[:cap], check=False)
+                assert (mine[cap:] == MINE).all()
+                continue
+            with pytest.raises(capi.CabacHipError) as e:
+                hip.encode_batch_payload(desc, records, mine[:cap], check=False)
+            assert e.value.status == -2 and TOO_SMALL in str(e.value), (cap, str(e.value))
+            refused.append((mine, mine.copy()))
+            assert (mine[cap:] == MINE).all()                       # (contents unspecified, but never more than the capacity)
+            payload = _caller_bytes(need + 64, pinned, keep)
+            offs, res = hip.encode_batch_payload(desc, records, payload[:need], check=False)
+            assert np.array_equal(res["n_bits"], res_o["n_bits"]) and np.array_equal(res["flags"], res_o["flags"])
+            assert np.array_equal(offs, want_off)
+            for s in range(len(desc)):
+                o = int(desc["byte_offset"][s])
+                assert np.array_equal(payload[int(offs[s]): int(offs[s + 1])], out_o[o:o + int(nbytes[s])]), (cap, s)
+            assert (payload[need:] == MINE).all()
+            for k, (a, snapshot) in enumerate(refused):
+                assert np.array_equal(a, snapshot), "refused payload %d written to after its call had returned (capacity %d)" % (k, cap)
+        hip.close()
+    finally:
+        del os.environ["CABAC_HIP_CHUNKS"]
+        for k in keep:
+            k.close()
+
+
+@pytest.mark.parametrize("narrow", [False, True])
+def test_spliced_residual_refuses_a_short_payload(narrow):
+    """cabac_hip_encode_batch_residual / _residual16: the same refusal, the ctx usable, the next call the oracle's"""
+    from test_gpu_splice import build_case, expected
+    hip = capi.CabacHip(0)
+    rng = np.random.default_rng(0x5111CE + 9)
+    desc, records, first, splices, tus, coeff, expanded = build_case(rng, 40, 12)
+    coeff = coeff.astype(np.int16 if narrow else np.int32)
+    want, want_bits = expected(desc, expanded)
+    need = sum(len(b) for b in want)
+    for cap in (0, 1, need - 1):
+        mine = np.full(cap + 64, MINE, np.uint8)
+        with pytest.raises(capi.CabacHipError) as e:
+            hip.encode_batch_residual(desc, records, first, splices, tus, coeff, mine[:cap])
+        assert e.value.status == -2 and TOO_SMALL in str(e.value), (cap, str(e.value))
+        snapshot = mine.copy()
+        payload = np.full(need + 64, MINE, np.uint8)
+        offs, res = hip.encode_batch_residual(desc, records, first, splices, tus, coeff, payload[:need])
+        assert np.array_equal(res["n_bits"], want_bits) and not res["flags"].any() and int(offs[-1]) == need
+        for s in range(len(desc)):
+            assert np.array_equal(payload[int(offs[s]): int(offs[s + 1])], want[s]), (cap, s)
+        assert (payload[need:] == MINE).all() and (mine[cap:] == MINE).all() and np.array_equal(mine, snapshot)
+    hip.close()
+
+
+def test_plan_write_refuses_a_short_payload():
+    """cabac_hip_write_plan_batch: the same refusal, the ctx usable, the next call the model's"""
+    from test_gpu_write_plan import batch_args, tu_subs
+    subs = tu_subs(3)[:5]
+    P, a = batch_args(subs)
+    want = np.concatenate([x["want"]["data"] for x in subs])
+    need = len(want)
+    hip = capi.CabacHip(0)
+    try:
+        for cap in (0, 1, need - 1):
+            mine = np.full(cap + 64, MINE, np.uint8)
+            with pytest.raises(capi.CabacHipError) as e:
+                hip.write_plan_batch(payload=mine[:cap], **a)
+            assert e.value.status == -2 and TOO_SMALL in str(e.value), (cap, str(e.value))
+            snapshot = mine.copy()
+            payload = np.full(need + 64, MINE, np.uint8)
+            pay, off, res, values, info = hip.write_plan_batch(payload=payload[:need], **a)
+            assert np.array_equal(pay, want) and int(off[-1]) == need and not res["flags"].any()
+            assert res["n_bits"].tolist() == [x["want"]["n_bits"] for x in subs]
+            assert values.tolist() == [v for x in subs for v in x["want"]["values"]]
+            assert (payload[need:] == MINE).all() and (mine[cap:] == MINE).all() and np.array_equal(mine, snapshot)
+    finally:
+        hip.close()
