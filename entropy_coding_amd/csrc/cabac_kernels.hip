@@ -53,9 +53,11 @@ hipError_t launch_encode(hipStream_t st, int variant, uint32_t n_sub, const caba
                          const CtxSets *sets) {
   if (n_sub == 0) return hipSuccess;
   const int kind = variant & 0xff;
-  // auto (measured, DESIGN.md section 3, tools/enc_scaling.py): from 3 072 substreams the lane-serial encoder (v7: C4 0.64, C5 10.3 ms,
-  // 16 384 substreams 1.90 ms against v6's 0.82 / 12.8 / 2.81); below, one unit per workgroup, the four-wave quad encoder (v6:
-  // C2 0.61, C3 12.8 ms, 1 024 substreams 0.43, 2 048: 0.57 ms against v7's 0.78 / 16.5 / 0.65 / 0.64)
+  // auto (measured, DESIGN.md section 3, tools/enc_scaling.py): from 3 072 substreams the lane-serial encoder (v7: C4 0.53, C5 8.6 ms,
+  // 16 384 substreams 1.66 ms against v6's 0.82 / 12.8 / 2.81); below, one unit per workgroup, the four-wave quad encoder (v6:
+  // C2 0.61, C3 12.8 ms, 1 024 substreams 0.43, 2 048: 0.57 ms against v7's 0.54 at 1 024 and 0.55 at 2 048 — v7's figures are those
+  // of profiles/encode_chain_fields.json, after its chain wave came down to nine instructions per bin; C2 and C3 under v7 and the
+  // threshold itself have not been measured again since v7 took 0.78 and 16.5 ms on them)
   if (kind == 7 || (kind == 0 && max(n_sub, in_flight) >= 3072u)) return launch_encode_v7(st, n_sub, desc, records, bytes, results, in_flight, sets);
   if (kind == 6 || kind == 0) return launch_encode_v6(st, n_sub, desc, records, bytes, results, in_flight, sets);
   if (kind == 4) return launch_encode_v4(st, n_sub, desc, records, bytes, results, sets);

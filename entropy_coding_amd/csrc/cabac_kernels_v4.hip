@@ -91,18 +91,6 @@ __device__ __forceinline__ void lds_read4(const uint32_t *p, int q, uint32_t (&d
   dst[4 * q + 2] = v.z;
   dst[4 * q + 3] = v.w;
 }
-__device__ __forceinline__ void lds_read16(const uint32_t *p, uint32_t (&dst)[16]) {
-  const uint4 *q = reinterpret_cast<const uint4 *>(p);
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const uint4 v = q[i];
-    dst[4 * i] = v.x;
-    dst[4 * i + 1] = v.y;
-    dst[4 * i + 2] = v.z;
-    dst[4 * i + 3] = v.w;
-  }
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // encode
@@ -352,7 +340,7 @@ __device__ __forceinline__ uint32_t quad_phase_a(uint32_t r, bool active, uint32
 // The same as separate words for the lane-serial encoder (v7), which parks them in LDS field by field: no packing here and
 // no unpacking there.
 struct QuadFields {
-  uint32_t k, c2, lpsm, lp9, ep, alm;
+  uint32_t k, c2, lpsm, lp9, ep;
 };
 template <bool kLds = false>
 __device__ __forceinline__ QuadFields quad_phase_fields(uint32_t r, bool active, uint32_t lane, uint32_t row, uint32_t *rctx,
@@ -363,11 +351,14 @@ __device__ __forceinline__ QuadFields quad_phase_fields(uint32_t r, bool active,
   const uint32_t binm = 0u - q.bin;                               // 0 / ~0: the bin
   QuadFields f;
   f.k = ((sum >> 10) ^ sx) & 31u & q.ctxm;
-  f.c2 = (8u & q.ctxm) | (4u & q.trmm);                           // terminate == LPS width 2 (arith_codec.cpp:460-478)
-  f.lpsm = ((binm ^ sx) & q.ctxm) | (binm & q.trmm);              // the LPS path: bin != MPS, or a terminate bin 1
-  f.lp9 = (f.lpsm | (binm & q.epm)) & 0x1ffu;                     // the bin adds its MPS sub-range to low: LPS, or a bypass bin 1
+  // terminate == LPS width 2 (arith_codec.cpp:460-478).  align() == an LPS of width 256 (k = 0, c2 = 512: t = 256, the
+  // chain takes t, clz(256) - 23 = 0 shifts, range = 256) that adds nothing to low (lp9 = 0, ep = 0): the chain and the
+  // low wave need no case of their own for it
+  f.c2 = (8u & q.ctxm) | (4u & q.trmm) | (512u & q.alnm);
+  const uint32_t lpsm = ((binm ^ sx) & q.ctxm) | (binm & q.trmm); // the LPS path: bin != MPS, or a terminate bin 1
+  f.lp9 = (lpsm | (binm & q.epm)) & 0x1ffu;                       // the bin adds its MPS sub-range to low: LPS, or a bypass bin 1
+  f.lpsm = lpsm | q.alnm;                                         // (after lp9: an align record's stays 0)
   f.ep = q.epm & 1u;
-  f.alm = q.alnm;
   return f;
 }
 
@@ -1105,25 +1096,29 @@ __global__ __launch_bounds__(256 * U) void encode_kernel_v6(uint32_t n_sub, cons
 // that total, not by any one wave.  What needs the lanes of a row is only the context wave's work (which earlier bins of
 // the step share my context).  Everything downstream of it is a per-substream recurrence with nothing to share, so here
 // it runs one substream per LANE: per workgroup of S = 4U substreams
-//   U context waves   (v6's, four substreams each, lane = bin): per bin the fields of the chain and of the code value,
-//                      written to LDS field by field, [substream][bin];
-//   1 chain wave       lane = substream: reads its sixteen bins of each field with 16-byte reads and runs the range
-//                      recurrence — 9 instructions per bin for ALL substreams of the workgroup instead of 13 per four;
-//   1 output wave      lane = substream: the code value (low = (low << s) + term, 64-bit), its 16-bit units, the
-//                      delayed carry and the byte stores, exactly v4's per-row code, one step behind the chain.
-// One workgroup barrier per step; fields live in a ring of four steps (context waves one step ahead, output one behind).
+//   U context waves   (v6's, four substreams each, lane = bin): per bin the fields of the chain (k, c2, lpsm) and of the
+//                      code value (lp9, ep), written to LDS field by field, [substream][bin] — five planes.  An align()
+//                      record is given the fields of an LPS of width 256, so nothing downstream knows of it;
+//   1 chain wave       lane = substream: reads its sixteen bins of the three chain fields with twelve 16-byte reads and
+//                      runs the range recurrence — 9 vector instructions per bin (as compiled: bfe, mad, shift, sub,
+//                      select, ffbh, sub, shift, shift-add) for ALL substreams of the workgroup instead of 13 per four —
+//                      and posts rm | shift << 9 per bin with four 16-byte writes;
+//   1 low wave         lane = substream: the code value (low = (low << s) + term, 64-bit), one step behind the chain;
+//   U / 2 output waves eight lanes per substream: the 16-bit units, the delayed carry and the byte stores, two steps
+//                      behind the chain.
+// One workgroup barrier per step; fields live in a ring of four steps (context waves one step ahead, low one behind).
 constexpr uint32_t kV7Pad = 20;  // words per substream and field: 16 bins + 4, so that neighbouring lanes' 16-byte reads spread over the banks
-enum : uint32_t { kV7K = 0, kV7C2, kV7Lpsm, kV7Lp9, kV7Ep, kV7Alm, kV7Fields };
+enum : uint32_t { kV7K = 0, kV7C2, kV7Lpsm, kV7Lp9, kV7Ep, kV7Fields };
 
-template <bool kAlign>
-__device__ __forceinline__ uint32_t lane_rng_step(uint32_t k, uint32_t c2, uint32_t lpsm, uint32_t alm, uint32_t &range) {
+// One bin of the range recurrence, nine instructions.  No case for align(): its fields (quad_phase_fields) make it an LPS
+// of width 256 — t = 256, rm = range - 256 in 0..255, x = 256, no shift, range = 256.
+__device__ __forceinline__ uint32_t lane_rng_step(uint32_t k, uint32_t c2, uint32_t lpsm, uint32_t &range) {
   const uint32_t t = (__umul24((range >> 5) & 15u, k) + c2) >> 1;  // LPS width: ((r>>5)*k>>1) + c
   const uint32_t rm = range - t;
   const uint32_t x = sel(lpsm, t, rm);                              // see quad_rng_step
   const uint32_t nb = (uint32_t)(__builtin_clz(x) - 23);
   range = x << nb;
-  if (kAlign) range = sel(alm, 256u, range);
-  return rm | (nb << 9);
+  return (nb << 9) + rm;                                            // rm < 512: the sum is the OR, and one shift-add
 }
 
 template <int U, class... Sets>
@@ -1136,7 +1131,7 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
   __shared__ uint32_t ctx_all[S * kQuadCtxStride];
   __shared__ __attribute__((aligned(16))) uint32_t fld[4][kV7Fields][S * kV7Pad];  // context waves -> chain / low wave
   // chain -> low: rm | shift << 9 per bin; one row per substream and one that all lanes past the last substream share (they
-  // mirror it: same values) — LDS is what decides whether two workgroups fit on a CU (76 KB each)
+  // mirror it: same values) — LDS is what decides whether two workgroups fit on a CU (74 KB each, five field planes)
   __shared__ __attribute__((aligned(16))) uint32_t wpost[2][(S + 1) * kV7Pad];
   __shared__ uint32_t post_lo[U][2][4 * kQuadSubs], post_hi[U][2][4 * kQuadSubs], post_pend[U][2][4 * kQuadSubs];  // low -> output (v5's posts)
   __shared__ uint32_t fin_lo[S], fin_hi[S], fin_pend[S];
@@ -1150,19 +1145,24 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
   // same-id lanes of the context waves through LDS (C4 0.81 -> 0.65 ms)
   constexpr bool kLdsMatch = true;
   for (uint32_t k = threadIdx.x; k < U * kMatchWords; k += blockDim.x) (&match_all[0][0])[k] = 0u;
-  // Roles by wave number.  Waves are dealt to the CU's four SIMDs in turn and a SIMD's vector pipe is what bounds this
-  // kernel (SQ counters: 318 vector instructions per SIMD and step x 2 ns = the step), so the roles are ordered to load
-  // the four SIMDs evenly.  For U = 4, eight waves: context 0, context 1, chain, low | context 2, context 3, output 0,
-  // output 1 — two context waves on SIMD 0 and on SIMD 1, chain + output on SIMD 2, low + output on SIMD 3 (~300 each;
-  // with the four context waves first, SIMD 0 had context + chain = 340).  For U = 1: context, chain, low, output.
+  // Roles by wave number.  Waves are dealt to the CU's four SIMDs in turn.  For U = 4, eight waves: context 0, context 1,
+  // chain, low | output 0, output 1, context 2, context 3 — a context and an output wave on SIMD 0 and on SIMD 1, chain +
+  // context on SIMD 2, low + context on SIMD 3.  By vector instructions per step (context ~118, chain ~178, low ~175, output
+  // ~70) this is NOT the even deal: that is context + context | chain + output | low + output, which this kernel had while the
+  // chain wave was 230 instructions.  Measured with the role stamps (profiles/encode_chain_fields.json), the wave that came
+  // last to the barrier there was the output wave that shares the chain wave's SIMD — it waits for LDS and for its stores
+  // between few instructions, and the chain wave (s_setprio 3) takes the issue slots it could use; next to a context wave
+  // it is 13 % shorter and the kernel 10 % (4 096 substreams: 0.59 -> 0.53 ms).  Chain and low wave on one SIMD is the deal
+  // not to make (+ 13 %).  Last at the barrier now: the context wave next to the chain wave.
+  // For U = 1: context, chain, low, output.
   // Context waves: lane = (row, bin) of one unit's four substreams; chain and low wave: lane = substream; output waves:
   // EIGHT lanes per substream (eight substreams = two units per wave).
   const uint32_t role_slot = U == 4 ? wave : (wave == 0 ? 0u : wave + 1u);   // U = 1: 0 context, 2 chain, 3 low, 4+ output
-  const bool is_ctx = role_slot < 2u || (U == 4 && (role_slot == 4u || role_slot == 5u));
+  const bool is_ctx = role_slot < 2u || (U == 4 && role_slot >= 6u);
   const bool is_chain = role_slot == 2u, is_low = role_slot == 3u;
   const bool is_out = !is_ctx && !is_chain && !is_low;
-  const uint32_t ctx_unit = role_slot < 2u ? role_slot : role_slot - 2u;          // context waves 0, 1 | 4, 5 -> units 0 .. 3
-  const uint32_t out_index = U == 4 ? role_slot - 6u : 0u;
+  const uint32_t ctx_unit = role_slot < 2u ? role_slot : role_slot - 4u;          // context waves 0, 1 | 6, 7 -> units 0 .. 3
+  const uint32_t out_index = U == 4 ? role_slot - 4u : 0u;
   // the substream of this thread
   uint32_t row, j, unit, local;
   bool in_range = true;
@@ -1217,7 +1217,6 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
       fld[slot][kV7Lpsm][at] = f.lpsm;
       fld[slot][kV7Lp9][at] = f.lp9;
       fld[slot][kV7Ep][at] = f.ep;
-      fld[slot][kV7Alm][at] = f.alm;
     };
     const uint32_t cur_rec = rec_safe[min(j, last_rec)];
     uint32_t next_rec = rec_safe[min(16u + j, last_rec)];
@@ -1269,12 +1268,8 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
         lds_read4(&fld[slot][kV7C2][local * kV7Pad], q, c2);
         lds_read4(&fld[slot][kV7Lpsm][local * kV7Pad], q, lm);
       }
-      // always with the align() handling (one select per bin): asking whether the step has such a record would cost the
-      // context waves — which everything waits for — a ballot and a store per step
-      uint32_t al[16];
-      lds_read16(&fld[slot][kV7Alm][local * kV7Pad], al);
 #pragma unroll
-      for (int i = 0; i < 16; i++) w[i] = lane_rng_step<true>(kk[i], c2[i], lm[i], al[i], range);
+      for (int i = 0; i < 16; i++) w[i] = lane_rng_step(kk[i], c2[i], lm[i], range);
       uint4 *dst = reinterpret_cast<uint4 *>(&wpost[k & 1u][min(lane, S) * kV7Pad]);
 #pragma unroll
       for (int i = 0; i < 4; i++) dst[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
