@@ -120,6 +120,17 @@ SPARSE_STATUS_DTYPE = np.dtype([("n_entries", "<u8"), ("flags", "<u4"), ("first_
 assert SPARSE_STATUS_DTYPE.itemsize == 16
 SPARSE_OVERFLOW, SPARSE_RANGE, SPARSE_BAD_POS, SPARSE_BAD_FIRST, SPARSE_BAD_BLOCK = 1, 2, 4, 8, 16   # CABAC_SPARSE_*
 SPARSE_NO_BAD = 0xFFFFFFFF                                       # CABAC_SPARSE_NO_BAD
+# include/cabac_hip_rec10.h (the packed bin records: 64 records in 80 bytes; tests/test_rec10_abi.py compares)
+EXPORTS_REC10 = [
+    "cabac_hip_rec10_bytes", "cabac_hip_rec10_pack_host", "cabac_hip_rec10_unpack_host", "cabac_hip_rec10_unpack_device",
+    "cabac_hip_rec10_pack_device", "cabac_hip_rec10_encode_batch", "cabac_hip_rec10_encode_batch_payload",
+    "cabac_hip_rec10_decode_batch",
+]
+REC10_STATUS_DTYPE = np.dtype([("first_bad", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])   # cabac_rec10_status
+assert REC10_STATUS_DTYPE.itemsize == 16
+REC10_BAD_BITS, REC10_OVERFLOW = 1, 2                            # CABAC_REC10_*
+REC10_NO_BAD = 0xFFFFFFFFFFFFFFFF                                # first_bad with no bad record (UINT64_MAX)
+REC10_BLOCK_RECORDS, REC10_BLOCK_BYTES = 64, 80                  # CABAC_REC10_BLOCK_*
 WS_ROWS = 0x1                                                    # CABAC_WS_ROWS (cabac_workspace_sizes.flags)
 WS_OVER_RECORDS, WS_OVER_SLOTS, WS_BAD_SPLICES, WS_RECORDS_32BIT, WS_LOG_OVERFLOW, WS_LOG_DAMAGED = 1, 2, 4, 8, 16, 32   # status flags
 WS_NONE_VOIDED = 0xFFFFFFFF                                      # CABAC_WS_NONE_VOIDED
@@ -413,6 +424,16 @@ def load_library():
         L.cabac_hip_sparse_compact_device.argtypes = [vp, u32, vp, vp, ctypes.c_int, u64, vp, vp, u64, vp]
         L.cabac_hip_sparse_encode_batch.argtypes = [vp, u32, vp, vp, u64, vp, vp, u32, vp, vp, vp, u64, u64, vp, u64, vp, vp, vp, vp]
         L.cabac_hip_sparse_parse_batch.argtypes = [vp, u32, vp, vp, u64, vp, vp, vp, vp, u64, u64, vp, vp, vp]
+    if hasattr(L, "cabac_hip_rec10_bytes"):
+        u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+        L.cabac_hip_rec10_bytes.argtypes = [u64, vp]
+        L.cabac_hip_rec10_pack_host.argtypes = [vp, u64, vp, u64, vp]
+        L.cabac_hip_rec10_unpack_host.argtypes = [vp, u64, u64, vp]
+        L.cabac_hip_rec10_unpack_device.argtypes = [vp, vp, u64, u64, vp]
+        L.cabac_hip_rec10_pack_device.argtypes = [vp, vp, u64, vp, u64, vp]
+        L.cabac_hip_rec10_encode_batch.argtypes = [vp, u32, vp, vp, u64, u64, vp, u64, vp]
+        L.cabac_hip_rec10_encode_batch_payload.argtypes = [vp, u32, vp, vp, u64, u64, vp, u64, vp, vp]
+        L.cabac_hip_rec10_decode_batch.argtypes = [vp, u32, vp, vp, u64, u64, vp, u64, vp, ctypes.c_int, vp]
     L.cabac_hip_nal_escape_bound.argtypes = [ctypes.c_uint64]
     L.cabac_hip_nal_escape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
     L.cabac_hip_nal_unescape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp,
@@ -539,6 +560,49 @@ def sparse_unpack_host(tus, ent_first, entries, coeff, n_entries=None):
     return status[0]
 
 
+def rec10_bytes(n_records):
+    """cabac_hip_rec10_bytes: CABAC_REC10_BYTES(n_records), the size of n_records packed records."""
+    out = ctypes.c_uint64(0)
+    rc = load_library().cabac_hip_rec10_bytes(int(n_records), ctypes.byref(out))
+    if rc != 0:
+        raise CabacHipError(rc, "cabac_hip_rec10_bytes")
+    return out.value
+
+
+def rec10_pack_host(records, packed=None, packed_capacity=None):
+    """cabac_hip_rec10_pack_host (CPU, no GPU): uint16 records -> packed uint8[rec10_bytes(n)].  `packed` (optional): the caller's
+    array (e.g. pinned), written in place; packed_capacity defaults to its size.  A capacity that is too small or a record with
+    reserved bits set raises with status CABAC_HIP_ERR_INVALID; the error's `first_bad` is then the smallest bad index
+    (REC10_NO_BAD for the capacity)."""
+    records = np.ascontiguousarray(records, np.uint16)
+    if packed is None:
+        packed = np.zeros(max(rec10_bytes(len(records)) if packed_capacity is None else int(packed_capacity), 1), np.uint8)
+    cap = packed.nbytes if packed_capacity is None else int(packed_capacity)
+    assert packed.dtype == np.uint8 and packed.flags.c_contiguous and cap <= packed.nbytes
+    first_bad = ctypes.c_uint64(0)
+    rc = load_library().cabac_hip_rec10_pack_host(records.ctypes.data, len(records), packed.ctypes.data, cap, ctypes.byref(first_bad))
+    if rc != 0:
+        e = CabacHipError(rc, "cabac_hip_rec10_pack_host")
+        e.first_bad = first_bad.value
+        raise e
+    return packed[: rec10_bytes(len(records))]
+
+
+def rec10_unpack_host(packed, first, n, records=None):
+    """cabac_hip_rec10_unpack_host (CPU, no GPU): records first .. first + n - 1 of `packed` into records[first ..] (`records`:
+    the caller's uint16 array of at least first + n, written in place, else a fresh zeroed one); returns `records`."""
+    packed = np.ascontiguousarray(packed, np.uint8)
+    first, n = int(first), int(n)
+    assert n == 0 or rec10_bytes(first + n) <= packed.nbytes
+    if records is None:
+        records = np.zeros(first + n, np.uint16)
+    assert records.dtype == np.uint16 and records.flags.c_contiguous and len(records) >= first + n
+    rc = load_library().cabac_hip_rec10_unpack_host(packed.ctypes.data, first, n, records.ctypes.data)
+    if rc != 0:
+        raise CabacHipError(rc, "cabac_hip_rec10_unpack_host")
+    return records
+
+
 class CabacHip:
     """One codec context = one device + one HIP stream (stream=None: a non-blocking stream of the ctx's own; otherwise the
     caller's stream handle, 0 being the device's default stream).  Raises if there is no GPU (no CPU fallback)."""
@@ -639,7 +703,7 @@ class CabacHip:
         cabac_hip_ctx_sets.h; 34 plan parse with sets, 35 a level of a rows parse and 36 the encode launch of a plan write with sets
         in cabac_hip_plan_rows.h; 37 hand-over index, 38 log mark and 39 the encode launch of a spliced call with sets in
         cabac_hip_splice_rows.h; 40 the gate of a call on a fixed workspace in cabac_hip_workspace.h; 41 coefficient expand and
-        42 coefficient compact in cabac_hip_sparse.h)."""
+        42 coefficient compact in cabac_hip_sparse.h; 43 record unpack and 44 record pack in cabac_hip_rec10.h)."""
         cap = getattr(self, "_prof_cap", 0)
         kind = np.zeros(max(cap, 1), np.int32)
         ms = np.zeros(max(cap, 1), np.float32)
@@ -1506,6 +1570,67 @@ class CabacHip:
             e.sparse_outputs = (ent_first, res[: len(desc)], info[: len(tus)])
             raise
         return ent_first, entries[: int(status[0]["n_entries"])], res[: len(desc)], info[: len(tus)], status[0]
+
+    # ---- packed bin records (include/cabac_hip_rec10.h) ------
+    rec10_bytes = staticmethod(rec10_bytes)
+    rec10_pack_host = staticmethod(rec10_pack_host)
+    rec10_unpack_host = staticmethod(rec10_unpack_host)
+
+    def rec10_unpack_device(self, d_packed, first, n, d_records):
+        """cabac_hip_rec10_unpack_device: d_records[first .. first + n) from the packed blocks at d_packed (16-byte aligned);
+        asynchronous on the ctx's stream."""
+        self._check(self.L.cabac_hip_rec10_unpack_device(self.h, _opt(d_packed), int(first), int(n), _opt(d_records)))
+
+    def rec10_pack_device(self, d_records, n_records, d_packed, packed_capacity, d_status):
+        """cabac_hip_rec10_pack_device: n_records records -> rec10_bytes(n_records) bytes at d_packed (16-byte aligned); *d_status
+        receives a REC10_STATUS_DTYPE record; asynchronous on the ctx's stream."""
+        self._check(self.L.cabac_hip_rec10_pack_device(self.h, _opt(d_records), int(n_records), _opt(d_packed), int(packed_capacity),
+                                                       _opt(d_status)))
+
+    def rec10_encode_batch(self, desc, packed, n_records_total, bytes_total, check=True, out=None, packed_bytes=None):
+        """cabac_hip_rec10_encode_batch: encode_batch with the records as packed blocks (uint8 array, e.g. pinned; packed_bytes
+        defaults to its size)."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        assert packed is None or (packed.dtype == np.uint8 and packed.flags.c_contiguous)
+        if out is None:
+            out = np.zeros(max(int(bytes_total), 1), np.uint8)
+        res = np.zeros(len(desc), RESULT_DTYPE)
+        rc = self.L.cabac_hip_rec10_encode_batch(self.h, len(desc), desc.ctypes.data, _ptr(packed),
+                                                 packed.nbytes if packed_bytes is None else int(packed_bytes), int(n_records_total),
+                                                 out.ctypes.data, int(bytes_total), res.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return out, res
+
+    def rec10_encode_batch_payload(self, desc, packed, n_records_total, payload, check=True, packed_bytes=None, payload_capacity=None):
+        """cabac_hip_rec10_encode_batch_payload: encode_batch_payload with the records as packed blocks; (offsets uint64[n + 1],
+        results)."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        assert packed is None or (packed.dtype == np.uint8 and packed.flags.c_contiguous)
+        offsets = np.zeros(len(desc) + 1, np.uint64)
+        res = np.zeros(len(desc), RESULT_DTYPE)
+        rc = self.L.cabac_hip_rec10_encode_batch_payload(
+            self.h, len(desc), desc.ctypes.data, _ptr(packed), packed.nbytes if packed_bytes is None else int(packed_bytes),
+            int(n_records_total), _ptr(payload), payload.nbytes if payload_capacity is None else int(payload_capacity),
+            offsets.ctypes.data, res.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return offsets, res
+
+    def rec10_decode_batch(self, desc, packed, n_records_total, data, bins_packed=False, check=True, bins=None, packed_bytes=None):
+        """cabac_hip_rec10_decode_batch: decode_batch (bins_packed False: one bin per byte) or decode_batch_packed (True: eight to
+        a byte) with the records as packed blocks; (bins, results)."""
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        data = np.ascontiguousarray(data, np.uint8)
+        assert packed is None or (packed.dtype == np.uint8 and packed.flags.c_contiguous)
+        n = int(n_records_total)
+        n_out = (n + 7) // 8 if bins_packed else n
+        if bins is None:
+            bins = np.zeros(n_out + 1, np.uint8)
+        res = np.zeros(len(desc), RESULT_DTYPE)
+        rc = self.L.cabac_hip_rec10_decode_batch(self.h, len(desc), desc.ctypes.data, _ptr(packed),
+                                                 packed.nbytes if packed_bytes is None else int(packed_bytes), n, data.ctypes.data,
+                                                 len(data), bins.ctypes.data, 1 if bins_packed else 0, res.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return bins[:n_out], res
 
     def encode_batch_nal(self, desc, records, nal, check=True):
         """cabac_hip_encode_batch_nal: records -> NAL-ready payload in `nal` (uint8 array, e.g. pinned); returns (nal_offsets

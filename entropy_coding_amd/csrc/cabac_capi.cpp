@@ -34,6 +34,7 @@
 #include "cabac_hip_parse_plan.h"
 #include "cabac_hip_parse_unit.h"
 #include "cabac_hip_plan_rows.h"
+#include "cabac_hip_rec10.h"
 #include "cabac_hip_search.h"
 #include "cabac_hip_search_emit.h"
 #include "cabac_hip_search_plan.h"
@@ -44,6 +45,7 @@
 #include "cabac_hip_write_plan.h"
 #include "cabac_kernels.h"
 #include "cabac_nal_kernels.h"
+#include "cabac_rec10_kernels.h"
 #include "cabac_sparse_kernels.h"
 
 #ifdef CABAC_PARSE_PROFILE
@@ -96,6 +98,8 @@ enum Slot {
   // the sparse coefficient transport (cabac_hip_sparse.h): the error words and workgroup counts of its kernels, and the firsts,
   // entries and status of its host-pointer forms
   kSparseScratch = 73, kSparseFirst = 74, kSparseEnt = 75, kSparseStatus = 76,
+  // the packed bin records (cabac_hip_rec10.h): the blocks of the host-pointer forms as they came up, unpacked into kRecords
+  kRec10 = 77,
   kSlots
 };
 
@@ -550,6 +554,27 @@ std::vector<Chunk> plan_chunks(const cabac_hip_ctx *c, uint32_t n_sub, const cab
     out.push_back(ch);
   }
   return out;
+}
+
+// The records of one chunk on their way to d_rec (kRecords).  16-bit records go up as they are.  Packed records (cabac_hip_rec10.h)
+// go up as the whole blocks that hold [rec_lo, rec_hi), into kRec10 at the offset they have in the caller's buffer; a block that
+// two chunks share goes up with both.  The unpack below then runs on the chunk's kernel stream, behind the chunk's ev_in and in
+// front of its encode or decode launch, and writes [rec_lo, rec_hi) alone.
+int upload_chunk_records(cabac_hip_ctx *c, const Chunk &ch, const void *records, bool rec10, uint16_t *d_rec) {
+  if (!rec10)
+    return h2d(c, d_rec + ch.rec_lo, static_cast<const uint16_t *>(records) + ch.rec_lo, (ch.rec_hi - ch.rec_lo) * 2, c->s_in);
+  if (ch.rec_hi == ch.rec_lo) return CABAC_HIP_OK;
+  const uint64_t lo = ch.rec_lo / CABAC_REC10_BLOCK_RECORDS * CABAC_REC10_BLOCK_BYTES, hi = CABAC_REC10_BYTES(ch.rec_hi);
+  return h2d(c, static_cast<uint8_t *>(c->d_buf[kRec10]) + lo, static_cast<const uint8_t *>(records) + lo, hi - lo, c->s_in);
+}
+
+int unpack_chunk_records(cabac_hip_ctx *c, const Chunk &ch, hipStream_t ks, uint16_t *d_rec) {
+  const bool ring = !c->prof_ev.empty() && c->prof_n < c->prof_kind.size();
+  Bracket br = ring ? bracket_for(c, 43) : Bracket{nullptr, nullptr};
+  if (ring) HIP_TRY(c, hipEventRecord(br.a, ks));
+  HIP_TRY(c, cabac::launch_rec10_unpack(ks, static_cast<const uint8_t *>(c->d_buf[kRec10]), ch.rec_lo, ch.rec_hi - ch.rec_lo, d_rec));
+  if (ring) HIP_TRY(c, hipEventRecord(br.b, ks));
+  return CABAC_HIP_OK;
 }
 
 // ---- levels, links and context sets: what the WPP calls (cabac_hip_ctx_sets.h), the plan rows and the spliced rows share ------
@@ -1059,10 +1084,11 @@ float cabac_hip_last_kernel_ms(cabac_hip_ctx *c) {
 
 // bytes != NULL: every substream's bytes at its byte_offset (the reference's FIFOs); payload != NULL: the substreams back to
 // back in descriptor order with payload_offsets[0..n_sub] (what OutputBitstream::addSubstream makes of byte-aligned
-// substreams, bit_stream.cpp:139-150)
-static int encode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+// substreams, bit_stream.cpp:139-150).  rec10: `records` are the packed blocks of cabac_hip_rec10.h, CABAC_REC10_BYTES(n_records_total)
+// bytes of them, instead of uint16_t[n_records_total]
+static int encode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const void *records,
                              uint64_t n_records_total, uint8_t *bytes, uint64_t bytes_total, uint8_t *payload,
-                             uint64_t payload_capacity, uint64_t *payload_offsets, cabac_substream_result *results) {
+                             uint64_t payload_capacity, uint64_t *payload_offsets, cabac_substream_result *results, bool rec10 = false) {
   if (!c || (n_sub && (!desc || !results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (payload_offsets) payload_offsets[0] = 0;
   if (n_sub == 0) return CABAC_HIP_OK;
@@ -1078,6 +1104,7 @@ static int encode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   const size_t off_count = size_t(n_sub) + nc;
   if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
   if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
+  if (rec10 && (rc = ensure(c, kRec10, CABAC_REC10_BYTES(n_records_total)))) return rc;
   if ((rc = ensure(c, kBytes, bytes_total))) return rc;
   if ((rc = ensure(c, kResults, res_bytes))) return rc;
   if ((rc = ensure(c, kPayload, bytes_total))) return rc;
@@ -1098,10 +1125,11 @@ static int encode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   for (uint32_t k = 0; k < nc; k++) {
     const Chunk &ch = chunks[k];
     const uint32_t n_k = ch.s1 - ch.s0;
-    if ((rc = h2d(c, d_rec + ch.rec_lo, records + ch.rec_lo, (ch.rec_hi - ch.rec_lo) * 2, c->s_in))) return rc;
+    if ((rc = upload_chunk_records(c, ch, records, rec10, d_rec))) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_in[k], c->s_in));
     hipStream_t ks = c->s_k[k % cabac_hip_ctx::kKernelStreams];
     HIP_TRY(c, hipStreamWaitEvent(ks, c->ev_in[k], 0));
+    if (rec10 && (rc = unpack_chunk_records(c, ch, ks, d_rec))) return rc;
     // (timed only through the profile ring: the ctx's single event pair would tie the chunk streams together)
     const bool ring = !c->prof_ev.empty() && c->prof_n < c->prof_kind.size();
     Bracket br = ring ? bracket_for(c, 0) : Bracket{nullptr, nullptr};
@@ -1204,9 +1232,10 @@ int cabac_hip_estimate_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
 }
 
 // packed: `bins` receives (n_records_total + 7) / 8 bytes, bit (r & 7) of byte r >> 3 = the bin of record r
-static int decode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+// rec10: as for encode_batch_impl
+static int decode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const void *records,
                              uint64_t n_records_total, const uint8_t *bytes, uint64_t bytes_total, uint8_t *bins,
-                             cabac_substream_result *results, bool packed) {
+                             cabac_substream_result *results, bool packed, bool rec10 = false) {
   if (!c || (n_sub && (!desc || !results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (n_sub == 0) return CABAC_HIP_OK;
   int rc = check_desc_host(c, n_sub, desc, n_records_total, bytes_total);
@@ -1219,6 +1248,7 @@ static int decode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   // the kernel reads whole aligned dwords: room for the dword that holds the last byte
   if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
   if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
+  if (rec10 && (rc = ensure(c, kRec10, CABAC_REC10_BYTES(n_records_total)))) return rc;
   if ((rc = ensure(c, kBytes, bytes_total + 4))) return rc;
   if ((rc = ensure(c, kResults, res_bytes))) return rc;
   if ((rc = ensure(c, kBins, n_records_total + 8))) return rc;
@@ -1236,11 +1266,12 @@ static int decode_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
   for (uint32_t k = 0; k < nc; k++) {
     const Chunk &ch = chunks[k];
     const uint32_t n_k = ch.s1 - ch.s0;
-    if ((rc = h2d(c, d_rec + ch.rec_lo, records + ch.rec_lo, (ch.rec_hi - ch.rec_lo) * 2, c->s_in))) return rc;
+    if ((rc = upload_chunk_records(c, ch, records, rec10, d_rec))) return rc;
     if (bytes && (rc = h2d(c, d_slots + ch.byte_lo, bytes + ch.byte_lo, ch.byte_hi - ch.byte_lo, c->s_in))) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_in[k], c->s_in));
     hipStream_t ks = c->s_k[k % cabac_hip_ctx::kKernelStreams];
     HIP_TRY(c, hipStreamWaitEvent(ks, c->ev_in[k], 0));
+    if (rec10 && (rc = unpack_chunk_records(c, ch, ks, d_rec))) return rc;
     const bool ring = !c->prof_ev.empty() && c->prof_n < c->prof_kind.size();
     Bracket br = ring ? bracket_for(c, 1) : Bracket{nullptr, nullptr};
     if (ring) HIP_TRY(c, hipEventRecord(br.a, ks));
@@ -3592,6 +3623,62 @@ int cabac_hip_sparse_parse_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   HIP_TRY(c, down(c, entries, c->d_buf[kSparseEnt], status->n_entries * sizeof(uint32_t)));
   HIP_TRY(c, wait_stream(c, c->stream));  // the second
   return flagged;
+}
+
+// ---- packed bin records (cabac_hip_rec10.h; kernels: cabac_rec10.hip, the CPU forms: cabac_rec10_host.cpp) ----------------------
+namespace {
+bool misaligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+// what the three host-pointer forms refuse before they look at anything else
+int rec10_host_args(cabac_hip_ctx *c, const uint8_t *packed, uint64_t packed_bytes, uint64_t n_records_total) {
+  if (!c || (n_records_total && !packed)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_records_total > UINT64_MAX - 63u || packed_bytes < CABAC_REC10_BYTES(n_records_total))
+    return fail(c, CABAC_HIP_ERR_INVALID, "packed_bytes below CABAC_REC10_BYTES(n_records_total)");
+  return CABAC_HIP_OK;
+}
+}  // namespace
+
+int cabac_hip_rec10_unpack_device(cabac_hip_ctx *c, const uint8_t *d_packed, uint64_t first, uint64_t n, uint16_t *d_records) {
+  if (!c || (n && (!d_packed || !d_records))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (misaligned16(d_packed)) return fail(c, CABAC_HIP_ERR_INVALID, "d_packed must be 16-byte aligned");
+  if (first > UINT64_MAX - 7u || n > UINT64_MAX - 7u - first) return fail(c, CABAC_HIP_ERR_INVALID, "first + n out of range");
+  DeviceGuard g(c->device);
+  return TIMED_LAUNCH(c, 43, cabac::launch_rec10_unpack(c->stream, d_packed, first, n, d_records));
+}
+
+int cabac_hip_rec10_pack_device(cabac_hip_ctx *c, const uint16_t *d_records, uint64_t n_records, uint8_t *d_packed,
+                                uint64_t packed_capacity, cabac_rec10_status *d_status) {
+  if (!c || !d_status || (n_records && (!d_records || !d_packed))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (misaligned16(d_packed)) return fail(c, CABAC_HIP_ERR_INVALID, "d_packed must be 16-byte aligned");
+  if (n_records > UINT64_MAX - 63u) return fail(c, CABAC_HIP_ERR_INVALID, "n_records out of range");
+  DeviceGuard g(c->device);
+  return TIMED_LAUNCH(c, 44, cabac::launch_rec10_pack(c->stream, d_records, n_records, d_packed, packed_capacity, d_status));
+}
+
+int cabac_hip_rec10_encode_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *packed,
+                                 uint64_t packed_bytes, uint64_t n_records_total, uint8_t *bytes, uint64_t bytes_total,
+                                 cabac_substream_result *results) {
+  if (int bad = rec10_host_args(c, packed, packed_bytes, n_records_total)) return bad;
+  return host_call_exit(c, encode_batch_impl(c, n_sub, desc, packed, n_records_total, bytes, bytes_total, nullptr, 0, nullptr, results, true));
+}
+
+int cabac_hip_rec10_encode_batch_payload(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *packed,
+                                         uint64_t packed_bytes, uint64_t n_records_total, uint8_t *payload, uint64_t payload_capacity,
+                                         uint64_t *payload_offsets, cabac_substream_result *results) {
+  if (!payload || !payload_offsets) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (int bad = rec10_host_args(c, packed, packed_bytes, n_records_total)) return bad;
+  uint64_t slots_end = 0;  // as in cabac_hip_encode_batch_payload
+  for (uint32_t s = 0; s < n_sub && desc; s++) slots_end = std::max<uint64_t>(slots_end, desc[s].byte_offset + desc[s].byte_capacity);
+  return host_call_exit(c, encode_batch_impl(c, n_sub, desc, packed, n_records_total, nullptr, slots_end, payload, payload_capacity,
+                                             payload_offsets, results, true));
+}
+
+int cabac_hip_rec10_decode_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *packed,
+                                 uint64_t packed_bytes, uint64_t n_records_total, const uint8_t *bytes, uint64_t bytes_total,
+                                 uint8_t *bins, int bins_packed, cabac_substream_result *results) {
+  if (int bad = rec10_host_args(c, packed, packed_bytes, n_records_total)) return bad;
+  return host_call_exit(c, decode_batch_impl(c, n_sub, desc, packed, n_records_total, bytes, bytes_total, bins, results, bins_packed != 0,
+                                             true));
 }
 
 // ---- the fixed workspace (cabac_hip_workspace.h; the gate and its kernels: cabac_workspace.hip) -------------------------------
