@@ -221,6 +221,7 @@ __device__ __forceinline__ void quad_enc_steps(const QuadEncInfo &f, QuadEnc &e,
 struct QuadRecord {  // one bin record of a 16-bin step, with the context state it sees
   uint32_t id, bin, st;
   uint32_t ctxm, epm, trmm, alnm;  // 0 / ~0: what kind of record it is (all zero: none — past the end of the substream)
+  uint32_t kind;                   // quad_resolve<.., kKindTab>: the kind word of the id's table row, in place of epm, trmm, alnm
 };
 
 // Written with 0 / ~0 masks throughout (round 2): as booleans the record kinds became lane masks in SGPRs, and the
@@ -234,23 +235,45 @@ constexpr uint32_t kMatchWords = 1024;  // per wave: which lanes of a row hold w
 // `rates` (kRateTab, LDS, 512 entries): the packed shift amounts and addends of the two estimators of every context, looked
 // up instead of derived from the state word's rate bits with ten vector instructions (they depend on the context only:
 // the fourth row of the init table; the estimator, which may start from given rates, derives them)
-template <uint32_t kLowestSpecial = CABAC_REC_ALIGN, bool kLds = false, bool kRateTab = false>  // ids from kLowestSpecial up to 0x1FF are not "bad" (the estimator has two more)
+// `kinds` (kKindTab, LDS, kKindRows rows of 16 bytes, quad_kind_tab_init; it takes the place of `rates`): what a record id
+// means, looked up with the rates in one 16-byte read instead of derived from the id with compares and masks for every bin
+// — {rate shifts, rate addends, ctxm, kind word}.  An inactive lane reads the row behind the 512 ids, which is all zero
+// ("nothing"), so nothing here asks again whether the lane is active; and the match bitmap has kMatchWordsCtx words per
+// wave: a word per context and pair of rows, and one that every other record shares (only contexts use the answer).
+constexpr uint32_t kKindNone = 512;             // the row of an inactive lane
+constexpr uint32_t kKindRows = 513;
+constexpr uint32_t kMatchWordsCtx = 768;        // 2 x (379 contexts + the shared word), rounded up
+enum : uint32_t {                               // the kind word
+  kKindC2Mask = 0x3ffu,                         // bits 9..0: 2 * constant term of the LPS width: 8 context, 4 terminate, 512 align, 0 otherwise
+  kKindEpBit = 10,                              // a bypass bin
+  kKindBadBit = 11,                             // no record id
+  kKindLpsBit = 12,                             // context or terminate: a bin off the MPS (a terminate bin 1) takes the LPS path
+  kKindAlignBit = 13,                           // align: the LPS path whatever the bin
+  kKindLp9Shift = 16,                           // bits 24..16: 0x1ff for context, terminate and bypass — what such a bin may add to low
+};
+template <uint32_t kLowestSpecial = CABAC_REC_ALIGN, bool kLds = false, bool kRateTab = false, bool kKindTab = false>  // ids from kLowestSpecial up to 0x1FF are not "bad" (the estimator has two more)
 __device__ __forceinline__ QuadRecord quad_resolve(uint32_t r, bool active, uint32_t lane, uint32_t row, uint32_t *rctx,
-                                                   uint32_t &bad, uint32_t *match = nullptr, const uint2 *rates = nullptr) {
+                                                   uint32_t &bad, uint32_t *match = nullptr, const uint2 *rates = nullptr,
+                                                   const uint4 *kinds = nullptr) {
+  static_assert(!kKindTab || (kLds && !kRateTab && kLowestSpecial == CABAC_REC_ALIGN), "the kind table: the encoder's ids, with the LDS match");
   QuadRecord q;
   uint32_t actm = active ? ~0u : 0u;
-  asm volatile("" : "+v"(actm));   // opaque: hipcc otherwise turns the mask arithmetic below back into lane-mask booleans
-  const uint32_t id = sel(actm, r & CABAC_REC_ID_MASK, CABAC_REC_ID_MASK);
+  if constexpr (!kKindTab) asm volatile("" : "+v"(actm));   // opaque: hipcc otherwise turns the mask arithmetic below back into lane-mask booleans
+  const uint32_t id = kKindTab ? (active ? r & CABAC_REC_ID_MASK : kKindNone) : sel(actm, r & CABAC_REC_ID_MASK, CABAC_REC_ID_MASK);
   const uint32_t bin = (r >> 15) & 1u;
-  const uint32_t ctxm = neg_mask(id - (uint32_t)kNumCtx);                         // id < 379 (an inactive lane's id is 0x1FF)
-  const uint32_t epm = actm & neg_mask((id ^ CABAC_REC_EP) - 1u);
+  uint4 kind = make_uint4(0u, 0u, 0u, 0u);
+  if constexpr (kKindTab) kind = kinds[id];
+  const uint32_t ctxm = kKindTab ? kind.z : neg_mask(id - (uint32_t)kNumCtx);     // id < 379 (an inactive lane's id is 0x1FF)
+  const uint32_t epm = actm & neg_mask((id ^ CABAC_REC_EP) - 1u);                 // (these three: not with kKindTab, where kind.w says it)
   const uint32_t trmm = actm & neg_mask((id ^ CABAC_REC_TRM) - 1u);
   const uint32_t alnm = actm & neg_mask((id ^ CABAC_REC_ALIGN) - 1u);
-  bad |= actm & ~ctxm & neg_mask(id - kLowestSpecial) & 1u;
+  if constexpr (kKindTab) bad |= kind.w & (1u << kKindBadBit);
+  else bad |= actm & ~ctxm & neg_mask(id - kLowestSpecial) & 1u;
   const uint32_t j = lane & 15u;
   uint32_t same;
   if (kLds) {   // (a template parameter, not `match != nullptr`: an LDS address may be 0, so that test survives to run time)
     uint32_t *word = match + ((row >> 1) << 9) + id;
+    if constexpr (kKindTab) word = match + (row >> 1) * (kMatchWordsCtx / 2u) + min(id, (uint32_t)kNumCtx);
     const uint32_t shift = ((row & 1u) << 4);
     atomicOr(word, 1u << (shift + j));
     asm volatile("" ::: "memory");                 // one wave: LDS executes its instructions in order
@@ -271,7 +294,10 @@ __device__ __forceinline__ QuadRecord quad_resolve(uint32_t r, bool active, uint
   // once with packed 16-bit math as in the decoder (the rates of a context never change).
   typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
   u16x2 rate2, add2;
-  if (kRateTab) {
+  if (kKindTab) {
+    rate2 = __builtin_bit_cast(u16x2, kind.x);
+    add2 = __builtin_bit_cast(u16x2, kind.y);
+  } else if (kRateTab) {
     const uint2 ra = rates[id];
     rate2 = __builtin_bit_cast(u16x2, ra.x);
     add2 = __builtin_bit_cast(u16x2, ra.y);
@@ -312,7 +338,9 @@ __device__ __forceinline__ QuadRecord quad_resolve(uint32_t r, bool active, uint
       }
     }
   }
-  rctx[sel(ctxm & lastm, id, (uint32_t)kNumCtx)] = updated(st, bin);  // others write the pad word
+  // others write the pad word (with kKindTab: min(id, kNumCtx) is the pad word already for all that is no context)
+  if constexpr (kKindTab) rctx[((same >> j) & 0xffffu) == 1u ? min(id, (uint32_t)kNumCtx) : (uint32_t)kNumCtx] = updated(st, bin);
+  else rctx[sel(ctxm & lastm, id, (uint32_t)kNumCtx)] = updated(st, bin);
   q.id = id;
   q.bin = bin;
   q.st = st;
@@ -320,6 +348,7 @@ __device__ __forceinline__ QuadRecord quad_resolve(uint32_t r, bool active, uint
   q.epm = epm;
   q.trmm = trmm;
   q.alnm = alnm;
+  q.kind = kind.w;
   return q;
 }
 
@@ -342,14 +371,26 @@ __device__ __forceinline__ uint32_t quad_phase_a(uint32_t r, bool active, uint32
 struct QuadFields {
   uint32_t k, c2, lpsm, lp9, ep;
 };
-template <bool kLds = false>
+template <bool kLds = false, bool kKindTab = false>
 __device__ __forceinline__ QuadFields quad_phase_fields(uint32_t r, bool active, uint32_t lane, uint32_t row, uint32_t *rctx,
-                                                        uint32_t &bad, uint32_t *match = nullptr, const uint2 *rates = nullptr) {
-  const QuadRecord q = quad_resolve<CABAC_REC_ALIGN, kLds, kLds>(r, active, lane, row, rctx, bad, match, rates);
+                                                        uint32_t &bad, uint32_t *match = nullptr, const uint2 *rates = nullptr,
+                                                        const uint4 *kinds = nullptr) {
+  const QuadRecord q = quad_resolve<CABAC_REC_ALIGN, kLds, kLds && !kKindTab, kKindTab>(r, active, lane, row, rctx, bad, match, rates, kinds);
   const uint32_t sum = (q.st & kMask0) + (q.st >> 16);            // state(), contexts.cpp:939-950
   const uint32_t sx = (uint32_t)((int32_t)(sum << 16) >> 31);     // 0 / ~0: the MPS
   const uint32_t binm = 0u - q.bin;                               // 0 / ~0: the bin
   QuadFields f;
+  if constexpr (kKindTab) {
+    // the same fields from the kind word.  Only a context has a state (q.st is 0 otherwise, so sum and sx are): off_mps is
+    // the bin itself for every other record, and k needs no mask
+    const uint32_t off_mps = binm ^ sx;                           // 0 / ~0: the bin is not the MPS
+    f.k = ((sum >> 10) ^ sx) & 31u;
+    f.c2 = q.kind & kKindC2Mask;
+    f.lpsm = (off_mps & bit_mask<kKindLpsBit>(q.kind)) | bit_mask<kKindAlignBit>(q.kind);
+    f.lp9 = off_mps & (q.kind >> kKindLp9Shift);
+    f.ep = (q.kind >> kKindEpBit) & 1u;
+    return f;
+  }
   f.k = ((sum >> 10) ^ sx) & 31u & q.ctxm;
   // terminate == LPS width 2 (arith_codec.cpp:460-478).  align() == an LPS of width 256 (k = 0, c2 = 512: t = 256, the
   // chain takes t, clz(256) - 23 = 0 shifts, range = 256) that adds nothing to low (lp9 = 0, ep = 0): the chain and the
@@ -415,6 +456,31 @@ __device__ __forceinline__ void quad_rate_tab_init(uint2 *tab, uint32_t tid, uin
       const uint32_t r0 = (rates & 3u) + 2u, r1 = ((rates >> 2) & 7u) + 5u;
       v.x = r0 | (r1 << 16);
       v.y = ((0x7fffu >> r0) & kMask0) | (((0x7fffu >> r1) & kMask1) << 16);
+    }
+    tab[id] = v;
+  }
+}
+
+// the table quad_resolve<.., kKindTab> reads: the same two rate words, the context mask and the kind word (above) per record
+// id, and the all-zero row of an inactive lane behind them
+__device__ __forceinline__ void quad_kind_tab_init(uint4 *tab, uint32_t tid, uint32_t n_threads) {
+  for (uint32_t id = tid; id < kKindRows; id += n_threads) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (id < (uint32_t)kNumCtx) {
+      const uint32_t rates = ctx2_init(0, c_init_tables[id], c_init_tables[3 * kNumCtx + id]) & 31u;
+      const uint32_t r0 = (rates & 3u) + 2u, r1 = ((rates >> 2) & 7u) + 5u;
+      v.x = r0 | (r1 << 16);
+      v.y = ((0x7fffu >> r0) & kMask0) | (((0x7fffu >> r1) & kMask1) << 16);
+      v.z = ~0u;
+      v.w = 8u | (1u << kKindLpsBit) | (0x1ffu << kKindLp9Shift);
+    } else if (id == CABAC_REC_TRM) {
+      v.w = 4u | (1u << kKindLpsBit) | (0x1ffu << kKindLp9Shift);
+    } else if (id == CABAC_REC_EP) {
+      v.w = (1u << kKindEpBit) | (0x1ffu << kKindLp9Shift);
+    } else if (id == CABAC_REC_ALIGN) {
+      v.w = 512u | (1u << kKindAlignBit);
+    } else if (id < kKindNone) {
+      v.w = 1u << kKindBadBit;
     }
     tab[id] = v;
   }
@@ -655,6 +721,9 @@ __device__ unsigned long long g_v5_prof[16];
 #else
 #define V5_TICK(var)
 #define V5_ADD(slot, t0, t1)
+#endif
+#ifndef CABAC_V5_STAMP_UNIT   // v7: the unit whose context and output wave are stamped (0, or 2: the waves of the second half)
+#define CABAC_V5_STAMP_UNIT 0
 #endif
 
 // (encode_kernel_v5, the three-wave encoder described above, was retired in round 3: v6 and v7 below grew out of it and it
@@ -1136,24 +1205,33 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
   __shared__ uint32_t post_lo[U][2][4 * kQuadSubs], post_hi[U][2][4 * kQuadSubs], post_pend[U][2][4 * kQuadSubs];  // low -> output (v5's posts)
   __shared__ uint32_t fin_lo[S], fin_hi[S], fin_pend[S];
   __shared__ uint32_t unit_list[U][kQuadSubs][kUnitSlots];
-  __shared__ uint32_t match_all[U][kMatchWords];   // the context waves' same-id bitmaps (quad_resolve)
-  __shared__ uint2 rate_tab[512];
+  // What a record id means comes from a table (quad_resolve<.., kKindTab>) where context waves share a SIMD with the chain
+  // and the low wave, U = 4: 22 of the context wave's 137 instructions per step less, 4 096 substreams 0.530 -> 0.514 ms
+  // (profiles/encode_kind_table.json).  With U = 1 every wave has a SIMD of its own and the low wave sets the pace; there
+  // the 16-byte rows measured 1.7 % slower (16 to 256 substreams), so it keeps the rates table and the masks from compares.
+  constexpr bool kKinds = U == 4;
+  constexpr uint32_t kMatch = kKinds ? kMatchWordsCtx : kMatchWords;
+  __shared__ uint32_t match_all[U][kMatch];   // the context waves' same-id bitmaps (quad_resolve)
+  __shared__ __attribute__((aligned(16))) uint4 kind_tab[kKinds ? kKindRows : 1];   // what a record id means, and its rates
+  __shared__ uint2 rate_tab[kKinds ? 1 : 512];
   __shared__ uint32_t bad_rows[U];
   __shared__ uint32_t wg_max_n;
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  quad_rate_tab_init(rate_tab, threadIdx.x, blockDim.x);
+  if constexpr (kKinds) quad_kind_tab_init(kind_tab, threadIdx.x, blockDim.x);
+  else quad_rate_tab_init(rate_tab, threadIdx.x, blockDim.x);
   // same-id lanes of the context waves through LDS (C4 0.81 -> 0.65 ms)
   constexpr bool kLdsMatch = true;
-  for (uint32_t k = threadIdx.x; k < U * kMatchWords; k += blockDim.x) (&match_all[0][0])[k] = 0u;
+  for (uint32_t k = threadIdx.x; k < U * kMatch; k += blockDim.x) (&match_all[0][0])[k] = 0u;
   // Roles by wave number.  Waves are dealt to the CU's four SIMDs in turn.  For U = 4, eight waves: context 0, context 1,
   // chain, low | output 0, output 1, context 2, context 3 — a context and an output wave on SIMD 0 and on SIMD 1, chain +
-  // context on SIMD 2, low + context on SIMD 3.  By vector instructions per step (context ~118, chain ~178, low ~175, output
-  // ~70) this is NOT the even deal: that is context + context | chain + output | low + output, which this kernel had while the
+  // context on SIMD 2, low + context on SIMD 3.  By vector instructions per step (context ~96 since the kind table, chain ~178, low ~175,
+  // output ~70) this is NOT the even deal: that is context + context | chain + output | low + output, which this kernel had while the
   // chain wave was 230 instructions.  Measured with the role stamps (profiles/encode_chain_fields.json), the wave that came
   // last to the barrier there was the output wave that shares the chain wave's SIMD — it waits for LDS and for its stores
   // between few instructions, and the chain wave (s_setprio 3) takes the issue slots it could use; next to a context wave
   // it is 13 % shorter and the kernel 10 % (4 096 substreams: 0.59 -> 0.53 ms).  Chain and low wave on one SIMD is the deal
-  // not to make (+ 13 %).  Last at the barrier now: the context wave next to the chain wave.
+  // not to make (+ 13 %).  Last at the barrier now, as before the kind table: the context wave next to the chain wave (it
+  // waits 69 ticks there, every other role 170 to 325).
   // For U = 1: context, chain, low, output.
   // Context waves: lane = (row, bin) of one unit's four substreams; chain and low wave: lane = substream; output waves:
   // EIGHT lanes per substream (eight substreams = two units per wave).
@@ -1221,7 +1299,7 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
     const uint32_t cur_rec = rec_safe[min(j, last_rec)];
     uint32_t next_rec = rec_safe[min(16u + j, last_rec)];
     uint32_t ahead1 = rec_safe[min(32u + j, last_rec)], ahead2 = rec_safe[min(48u + j, last_rec)], ahead3 = rec_safe[min(64u + j, last_rec)];
-    post(0, quad_phase_fields<kLdsMatch>(cur_rec, j < n, lane, row, rctx, bad, match_all[unit], rate_tab));  // step 0
+    post(0, quad_phase_fields<kLdsMatch, kKinds>(cur_rec, j < n, lane, row, rctx, bad, match_all[unit], rate_tab, kind_tab));  // step 0
     __syncthreads();
     for (uint32_t k = 0; k < n_steps; k++) {
       const uint32_t base = 16u * k;
@@ -1231,12 +1309,12 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
       ahead2 = ahead3;
       ahead3 = rec_safe[min(base + 80u + j, last_rec)];
       V5_TICK(t0);
-      post((k + 1u) & 3u, quad_phase_fields<kLdsMatch>(r, base + 16u + j < n, lane, row, rctx, bad, match_all[unit], rate_tab));
+      post((k + 1u) & 3u, quad_phase_fields<kLdsMatch, kKinds>(r, base + 16u + j < n, lane, row, rctx, bad, match_all[unit], rate_tab, kind_tab));
       V5_TICK(t1);
       __syncthreads();
       V5_TICK(t2);
-      if (unit == 0) V5_ADD(0, t0, t1);
-      if (unit == 0) V5_ADD(1, t1, t2);
+      if (unit == CABAC_V5_STAMP_UNIT) V5_ADD(0, t0, t1);
+      if (unit == CABAC_V5_STAMP_UNIT) V5_ADD(1, t1, t2);
     }
     const uint64_t bad_mask = __ballot(bad != 0);
     if (lane == 0) {
@@ -1366,8 +1444,8 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
       V5_TICK(t1);
       __syncthreads();
       V5_TICK(t2);
-      if (unit == 0) V5_ADD(6, t0, t1);
-      if (unit == 0) V5_ADD(7, t1, t2);
+      if (unit == CABAC_V5_STAMP_UNIT) V5_ADD(6, t0, t1);
+      if (unit == CABAC_V5_STAMP_UNIT) V5_ADD(7, t1, t2);
     }
     if (listed) quad_emit_units(e, units, j, list, writer);
     if (n_steps >= 2u) {
