@@ -126,6 +126,11 @@ EXPORTS_REC10 = [
     "cabac_hip_rec10_pack_device", "cabac_hip_rec10_encode_batch", "cabac_hip_rec10_encode_batch_payload",
     "cabac_hip_rec10_decode_batch",
 ]
+# include/cabac_hip_probe.h (probe points: written and estimated bits inside a substream; tests/test_probe_abi.py compares)
+EXPORTS_PROBE = [
+    "cabac_hip_written_bits_device", "cabac_hip_estimate_probes_device", "cabac_hip_encode_residual_probes_device",
+    "cabac_hip_written_bits_batch", "cabac_hip_estimate_probes_batch", "cabac_hip_encode_residual_probes_batch",
+]
 REC10_STATUS_DTYPE = np.dtype([("first_bad", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])   # cabac_rec10_status
 assert REC10_STATUS_DTYPE.itemsize == 16
 REC10_BAD_BITS, REC10_OVERFLOW = 1, 2                            # CABAC_REC10_*
@@ -434,6 +439,20 @@ def load_library():
         L.cabac_hip_rec10_encode_batch.argtypes = [vp, u32, vp, vp, u64, u64, vp, u64, vp]
         L.cabac_hip_rec10_encode_batch_payload.argtypes = [vp, u32, vp, vp, u64, u64, vp, u64, vp, vp]
         L.cabac_hip_rec10_decode_batch.argtypes = [vp, u32, vp, vp, u64, u64, vp, u64, vp, ctypes.c_int, vp]
+    # (CABAC_HIP_LIBRARY may name a build from before cabac_hip_probe.h)
+    if hasattr(L, "cabac_hip_written_bits_device"):
+        u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+        probes = [vp, vp, u32]                      # probe_first, probe_at, n_probe
+        sets4 = [u32, vp, vp, vp]                   # n_sets, state, rate, start_set
+        L.cabac_hip_written_bits_device.argtypes = [vp, u32, vp, vp] + probes + sets4 + [vp, vp]
+        L.cabac_hip_estimate_probes_device.argtypes = [vp, u32, vp, vp] + probes + sets4 + [vp, vp]
+        L.cabac_hip_written_bits_batch.argtypes = [vp, u32, vp, vp, u64] + probes + sets4 + [vp, vp]
+        L.cabac_hip_estimate_probes_batch.argtypes = [vp, u32, vp, vp, u64] + probes + sets4 + [vp, vp]
+        plain = L.cabac_hip_encode_residual_device.argtypes
+        plain_b = L.cabac_hip_encode_batch_residual.argtypes
+        tail = [vp, vp, vp, u32, vp]                # probe_first, probe_at, probe_splice, n_probe, bits
+        L.cabac_hip_encode_residual_probes_device.argtypes = plain[:10] + [ctypes.c_int] + plain[10:] + tail
+        L.cabac_hip_encode_residual_probes_batch.argtypes = plain_b[:10] + [ctypes.c_int] + plain_b[10:] + tail
     L.cabac_hip_nal_escape_bound.argtypes = [ctypes.c_uint64]
     L.cabac_hip_nal_escape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp]
     L.cabac_hip_nal_unescape_device.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp,
@@ -1374,6 +1393,106 @@ class CabacHip:
             res.ctypes.data, info.ctypes.data if with_info else None, counts.ctypes.data if with_counts else None)
         self._check(rc, allow_substream=not check)
         out = [offsets, res[:n]]
+        if with_info:
+            out.append(info[: len(tus)])
+        if with_counts:
+            out.append(counts[:n])
+        return tuple(out)
+
+    # ---- probe points: written and estimated bits inside a substream (include/cabac_hip_probe.h) ------
+    def written_bits_device(self, n_sub, d_desc, d_records, d_probe_first, d_probe_at, n_probe, d_bits, d_flags=0, n_sets=0,
+                            d_state=0, d_rate=0, d_start_set=0):
+        """cabac_hip_written_bits_device: d_bits[p] (uint32) = getNumWrittenBits() after the first d_probe_at[p] records of the
+        substream that owns probe p.  Asynchronous on the ctx stream."""
+        self._check(self.L.cabac_hip_written_bits_device(self.h, n_sub, _opt(d_desc), _opt(d_records), _opt(d_probe_first), _opt(d_probe_at),
+                                                         n_probe, n_sets, _opt(d_state), _opt(d_rate), _opt(d_start_set), _opt(d_bits),
+                                                         _opt(d_flags)))
+
+    def estimate_probes_device(self, n_sub, d_desc, d_records, d_probe_first, d_probe_at, n_probe, d_frac_bits, d_flags=0, n_sets=0,
+                               d_state=0, d_rate=0, d_start_set=0):
+        """cabac_hip_estimate_probes_device: d_frac_bits[p] (uint64, 1/32768 bit) = the estimator's total after the first
+        d_probe_at[p] records.  Asynchronous on the ctx stream."""
+        self._check(self.L.cabac_hip_estimate_probes_device(self.h, n_sub, _opt(d_desc), _opt(d_records), _opt(d_probe_first),
+                                                            _opt(d_probe_at), n_probe, n_sets, _opt(d_state), _opt(d_rate),
+                                                            _opt(d_start_set), _opt(d_frac_bits), _opt(d_flags)))
+
+    def _probes_batch(self, fn, dtype, desc, records, probe_first, probe_at, state, rate, start_set, check, out):
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        records = np.ascontiguousarray(records, np.uint16)
+        probe_first = np.ascontiguousarray(probe_first, np.uint32)
+        probe_at = np.ascontiguousarray(probe_at, np.uint32)
+        n = len(desc)
+        if len(probe_first) != n + 1:
+            raise ValueError("probe_first holds n_sub + 1 entries")
+        n_sets = 0
+        if start_set is not None:
+            state = np.ascontiguousarray(state, np.uint32).reshape(-1, NUM_CTX)
+            rate = np.ascontiguousarray(rate, np.uint8).reshape(-1, NUM_CTX)
+            start_set = np.ascontiguousarray(start_set, np.uint32)
+            n_sets = len(state)
+            if len(rate) != n_sets or len(start_set) != n:
+                raise ValueError("state and rate hold the same sets; start_set holds n_sub entries")
+        values = np.zeros(max(len(probe_at), 1), dtype) if out is None else out
+        flags = np.zeros(max(n, 1), np.uint32)
+        rc = fn(self.h, n, desc.ctypes.data, records.ctypes.data, len(records), probe_first.ctypes.data, probe_at.ctypes.data,
+                len(probe_at), n_sets, state.ctypes.data if n_sets else None, rate.ctypes.data if n_sets else None,
+                start_set.ctypes.data if start_set is not None else None, values.ctypes.data, flags.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        return values[: len(probe_at)], flags[:n]
+
+    def written_bits_batch(self, desc, records, probe_first, probe_at, state=None, rate=None, start_set=None, check=True, out=None):
+        """cabac_hip_written_bits_batch (host arrays, synchronous): (bits uint32[n_probe], flags uint32[n_sub])."""
+        return self._probes_batch(self.L.cabac_hip_written_bits_batch, np.uint32, desc, records, probe_first, probe_at, state, rate,
+                                  start_set, check, out)
+
+    def estimate_probes_batch(self, desc, records, probe_first, probe_at, state=None, rate=None, start_set=None, check=True, out=None):
+        """cabac_hip_estimate_probes_batch (host arrays, synchronous): (frac_bits uint64[n_probe], flags uint32[n_sub])."""
+        return self._probes_batch(self.L.cabac_hip_estimate_probes_batch, np.uint64, desc, records, probe_first, probe_at, state, rate,
+                                  start_set, check, out)
+
+    def encode_residual_probes_device(self, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff,
+                                      d_payload, payload_capacity, d_payload_offsets, d_results, d_probe_first, d_probe_at, n_probe,
+                                      d_bits, d_probe_splice=0, d_tu_info=0, d_bin_counts=0, int16=False):
+        """cabac_hip_encode_residual_probes_device: encode_residual_device that also answers probes (k host records, m splices in
+        front) with the written bits of the expanded string in front of each."""
+        self._check(self.L.cabac_hip_encode_residual_probes_device(
+            self.h, n_sub, _opt(d_desc), _opt(d_records), _opt(d_splice_first), _opt(d_splices), n_splice, n_tu, _opt(d_tu), _opt(d_coeff),
+            2 if int16 else 4, _opt(d_payload), payload_capacity, _opt(d_payload_offsets), _opt(d_results), _opt(d_tu_info),
+            _opt(d_bin_counts), _opt(d_probe_first), _opt(d_probe_at), _opt(d_probe_splice), n_probe, _opt(d_bits)))
+
+    def encode_residual_probes_batch(self, desc, records, splice_first, splices, tus, coeff, payload, probe_first, probe_at,
+                                     probe_splice=None, check=True, with_info=False, with_counts=False):
+        """cabac_hip_encode_residual_probes_batch (host arrays, synchronous): (offsets, results, bits uint32[n_probe][, tu_info]
+        [, counts]); int16 coefficients go through with coeff_bytes = 2."""
+        narrow = isinstance(coeff, np.ndarray) and coeff.dtype == np.int16
+        desc = np.ascontiguousarray(desc, DESC_DTYPE)
+        records = np.ascontiguousarray(records, np.uint16)
+        splice_first = np.ascontiguousarray(splice_first, np.uint32)
+        splices = np.ascontiguousarray(splices, SPLICE_DTYPE)
+        tus = np.ascontiguousarray(tus, TU_DTYPE)
+        coeff = np.ascontiguousarray(coeff, np.int16 if narrow else np.int32)
+        probe_first = np.ascontiguousarray(probe_first, np.uint32)
+        probe_at = np.ascontiguousarray(probe_at, np.uint32)
+        n = len(desc)
+        if len(probe_first) != n + 1:
+            raise ValueError("probe_first holds n_sub + 1 entries")
+        if probe_splice is not None:
+            probe_splice = np.ascontiguousarray(probe_splice, np.uint32)
+            if len(probe_splice) != len(probe_at):
+                raise ValueError("probe_splice holds one entry per probe")
+        offsets = np.zeros(n + 1, np.uint64)
+        res = np.zeros(max(n, 1), RESULT_DTYPE)
+        bits = np.zeros(max(len(probe_at), 1), np.uint32)
+        info = np.zeros(max(len(tus), 1), np.uint32) if with_info else None
+        counts = np.zeros((max(n, 1), BIN_COUNT_WORDS), np.uint32) if with_counts else None
+        rc = self.L.cabac_hip_encode_residual_probes_batch(
+            self.h, n, desc.ctypes.data, records.ctypes.data, len(records), splice_first.ctypes.data, splices.ctypes.data, len(tus),
+            tus.ctypes.data, coeff.ctypes.data, 2 if narrow else 4, len(coeff), payload.ctypes.data, payload.nbytes, offsets.ctypes.data,
+            res.ctypes.data, info.ctypes.data if with_info else None, counts.ctypes.data if with_counts else None,
+            probe_first.ctypes.data, probe_at.ctypes.data, probe_splice.ctypes.data if probe_splice is not None else None, len(probe_at),
+            bits.ctypes.data)
+        self._check(rc, allow_substream=not check)
+        out = [offsets, res[:n], bits[: len(probe_at)]]
         if with_info:
             out.append(info[: len(tus)])
         if with_counts:

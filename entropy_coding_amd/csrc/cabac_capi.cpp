@@ -34,6 +34,7 @@
 #include "cabac_hip_parse_plan.h"
 #include "cabac_hip_parse_unit.h"
 #include "cabac_hip_plan_rows.h"
+#include "cabac_hip_probe.h"
 #include "cabac_hip_rec10.h"
 #include "cabac_hip_search.h"
 #include "cabac_hip_search_emit.h"
@@ -100,6 +101,9 @@ enum Slot {
   kSparseScratch = 73, kSparseFirst = 74, kSparseEnt = 75, kSparseStatus = 76,
   // the packed bin records (cabac_hip_rec10.h): the blocks of the host-pointer forms as they came up, unpacked into kRecords
   kRec10 = 77,
+  // probe points (cabac_hip_probe.h): the probes of a spliced call as positions in the expanded strings; the lists, the splice
+  // counts and the values of the host-pointer forms (which stage the rest as the estimator's and the spliced call's forms do)
+  kProbeRec = 78, kProbeFirst = 79, kProbeAt = 80, kProbeSplice = 81, kProbeOut = 82,
   kSlots
 };
 
@@ -613,6 +617,35 @@ struct Rows {
   uint32_t n_level;
   const uint32_t *level_first, *d_sync_from, *d_sync_at, *d_sync_splice;
 };
+
+// the probes of a spliced call (cabac_hip_probe.h): the lists (device memory; host memory in the batch form; splice may be null)
+// and where the values go
+struct SpliceProbes {
+  const uint32_t *first, *at, *splice;
+  uint32_t n;
+  uint32_t *bits;
+};
+
+// what the host-pointer forms of cabac_hip_probe.h refuse about a probe list (host memory)
+int check_probes_host(cabac_hip_ctx *c, uint32_t n_sub, const uint32_t *probe_first, const uint32_t *probe_at, uint32_t n_probe) {
+  if (n_sub == 0) return CABAC_HIP_OK;
+  if (!probe_first || (n_probe && !probe_at)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (probe_first[0] != 0) return fail(c, CABAC_HIP_ERR_INVALID, "probe_first must start at 0");
+  for (uint32_t s = 0; s < n_sub; s++) {
+    const char *what = nullptr;
+    if (probe_first[s] > probe_first[s + 1]) what = "probe_first must not decrease";
+    else if (probe_first[s + 1] > n_probe) what = "probe_first ends behind n_probe";
+    else
+      for (uint32_t p = probe_first[s] + 1; p < probe_first[s + 1] && !what; p++)
+        if (probe_at[p] < probe_at[p - 1]) what = "probe positions go backwards";
+    if (what) {
+      char buf[96];
+      snprintf(buf, sizeof buf, "substream %u: %s", s, what);
+      return fail(c, CABAC_HIP_ERR_INVALID, buf);
+    }
+  }
+  return CABAC_HIP_OK;
+}
 
 // what a host-pointer form refuses about its rows (links in host memory)
 int check_rows_host(cabac_hip_ctx *c, uint32_t n_sub, const Rows &rows) {
@@ -1720,10 +1753,13 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
                                        const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes, uint8_t *d_payload,
                                        uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
                                        uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets = nullptr,
-                                       const Rows *rows = nullptr, const uint64_t *d_n_live = nullptr) {
+                                       const Rows *rows = nullptr, const uint64_t *d_n_live = nullptr,
+                                       const SpliceProbes *probes = nullptr) {
   if (!c || !d_payload_offsets || (n_sub && (!d_desc || !d_records || !d_splice_first || !d_payload || !d_results)) ||
       (n_splice && !d_splices) || (n_tu && (!d_tu || !d_coeff)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (probes && n_sub && (!probes->first || (probes->n && (!probes->at || !probes->bits)))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (probes && c->ws_fixed) return fail(c, CABAC_HIP_ERR_INVALID, "the workspace is fixed: the spliced call has no probe form there");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (n_splice != n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "every block must be spliced exactly once (n_splice != n_tu)");
   if (rows && n_sub) {
@@ -1745,6 +1781,7 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
   if ((rc = ensure(c, kSpDesc, size_t(n_sub ? n_sub : 1) * sizeof(cabac_substream_desc)))) return rc;
   if ((rc = ensure(c, kSpTuOff, size_t(n_tu ? n_tu : 1) * sizeof(uint64_t)))) return rc;
   if ((rc = ensure(c, kSpFlag, 64))) return rc;
+  if (probes && (rc = ensure(c, kProbeRec, size_t(probes->n ? probes->n : 1) * sizeof(uint32_t)))) return rc;
   if (!fixed && !c->h_totals) HIP_TRY(c, pinned_alloc(c, &c->h_totals, 64, hipHostMallocDefault));
   uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kSpCnt]), *d_info = d_cnt + (n_tu ? n_tu : 1);
   uint32_t *pre = static_cast<uint32_t *>(c->d_buf[kSpPlan]), *sub_n = pre + n_pre, *sub_cap = sub_n + n_sub, *seen = sub_cap + n_sub,
@@ -1789,6 +1826,17 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
     Timed t(c, 5);
     HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[kResidualScratch],
                                       /*order_ready=*/true));  // the block order of the sizes pass above: same tus[], same scratch
+  }
+  if (probes && n_sub && probes->n) {  // the pairs as positions in the expanded strings, then the written-bits walk over those strings
+    uint32_t *probe_rec = static_cast<uint32_t *>(c->d_buf[kProbeRec]);
+    {
+      Timed t(c, 47);
+      HIP_TRY(c, cabac::launch_splice_probe_index(c->stream, n_sub, probes->n, d_desc, d_splice_first, d_splices, pre, probes->first,
+                                                  probes->at, probes->splice, probe_rec));
+    }
+    Timed t(c, 45);
+    HIP_TRY(c, cabac::launch_written_bits(c->stream, n_sub, desc2, exp_rec, cabac::ProbeList{probes->first, probe_rec, 0u}, nullptr, nullptr,
+                                          nullptr, probes->bits, nullptr));
   }
   cabac::CtxSets live;  // fixed: a voided call writes no out set
   if (fixed && sets && sets->out_set) {
@@ -1857,13 +1905,15 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
                                       const cabac_tu_desc *tus, const void *coeff, int coeff_bytes, uint64_t n_coeff_total, uint8_t *payload,
                                       uint64_t payload_capacity, uint64_t *payload_offsets, cabac_substream_result *results,
                                       uint32_t *tu_info, uint32_t *bin_counts, const Rows *rows = nullptr,
-                                      const SparseSrc *sparse = nullptr) {
+                                      const SparseSrc *sparse = nullptr, const SpliceProbes *probes = nullptr) {
   if (!c || !payload_offsets || (n_sub && (!desc || !splice_first || !results || !payload)) ||
       (n_tu && (!tus || (!coeff && !sparse) || !splices)) ||
-      (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)))
+      (rows && n_sub && (!rows->d_sync_from || !rows->d_sync_at)) || (probes && probes->n && !probes->bits))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (c->ws_fixed) return refuse_fixed_batch(c);
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (probes)  // refused before anything is touched, payload_offsets[0] included
+    if (int bad = check_probes_host(c, n_sub, probes->first, probes->at, probes->n)) return bad;
   if (rows && n_sub) {  // refused before anything is touched, payload_offsets[0] included
     if (int bad = check_rows_host(c, n_sub, *rows)) return bad;
     for (uint32_t s = 0; s < n_sub; s++) {
@@ -1913,6 +1963,10 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
   if (rows && ((rc = ensure(c, kWppFrom, link_bytes)) || (rc = ensure(c, kWppAt, link_bytes)) || (rc = ensure(c, kSpInSync, link_bytes))))
     return rc;
+  const size_t probe_bytes = probes ? size_t(probes->n) * sizeof(uint32_t) : 0;
+  if (probes && ((rc = ensure(c, kProbeFirst, first_bytes)) || (rc = ensure(c, kProbeAt, probe_bytes)) ||
+                 (rc = ensure(c, kProbeSplice, probe_bytes)) || (rc = ensure(c, kProbeOut, probe_bytes))))
+    return rc;
   const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result), off_bytes = (size_t(n_sub) + 1) * sizeof(uint64_t);
   if ((rc = ensure_pinned(c, 0, res_bytes + off_bytes + 64))) return rc;
   auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
@@ -1946,6 +2000,15 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
                         static_cast<const uint32_t *>(c->d_buf[kWppAt]),
                         rows->d_sync_splice ? static_cast<const uint32_t *>(c->d_buf[kSpInSync]) : nullptr};
   }
+  SpliceProbes d_probes{};
+  if (probes) {
+    if ((rc = h2d(c, c->d_buf[kProbeFirst], probes->first, first_bytes, c->s_in))) return rc;
+    if ((rc = h2d(c, c->d_buf[kProbeAt], probes->at, probe_bytes, c->s_in))) return rc;
+    if (probes->splice && (rc = h2d(c, c->d_buf[kProbeSplice], probes->splice, probe_bytes, c->s_in))) return rc;
+    d_probes = SpliceProbes{static_cast<const uint32_t *>(c->d_buf[kProbeFirst]), static_cast<const uint32_t *>(c->d_buf[kProbeAt]),
+                            probes->splice ? static_cast<const uint32_t *>(c->d_buf[kProbeSplice]) : nullptr, probes->n,
+                            static_cast<uint32_t *>(c->d_buf[kProbeOut])};
+  }
   HIP_TRY(c, hipEventRecord(c->ev_in[1], c->s_in));
   // the lists are checked while they are on the wire: nothing of the pipeline has run and no output is touched when they are refused
   if (sparse && (rc = check_sparse_host(c, n_tu, tus, *sparse))) return rc;
@@ -1967,7 +2030,7 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
                                         static_cast<uint8_t *>(c->d_buf[kPayload]), payload_capacity, static_cast<uint64_t *>(c->d_buf[kPayloadOffsets]),
                                         static_cast<cabac_substream_result *>(c->d_buf[kSpOutRes]), static_cast<uint32_t *>(c->d_buf[kSpOutInfo]),
                                         bin_counts ? static_cast<uint32_t *>(c->d_buf[kSpOutCnt]) : nullptr, nullptr,
-                                        rows ? &d_rows : nullptr);
+                                        rows ? &d_rows : nullptr, nullptr, probes ? &d_probes : nullptr);
   if (rc) return rc;
   HIP_TRY(c, cabac::launch_tu_info_any(c->stream, n_tu, static_cast<const uint32_t *>(c->d_buf[kSpOutInfo]), d_flag + 1));
   HIP_TRY(c, hipMemcpyAsync(h_res, c->d_buf[kSpOutRes], res_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1981,6 +2044,7 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if ((rc = d2h(c, payload, c->d_buf[kPayload], n_pay, c->s_out))) return rc;
   if (tu_info && (rc = d2h(c, tu_info, c->d_buf[kSpOutInfo], size_t(n_tu) * sizeof(uint32_t), c->s_out))) return rc;
   if (bin_counts && (rc = d2h(c, bin_counts, c->d_buf[kSpOutCnt], size_t(n_sub) * CABAC_BIN_COUNT_WORDS * sizeof(uint32_t), c->s_out))) return rc;
+  if (probes && (rc = d2h(c, probes->bits, c->d_buf[kProbeOut], size_t(probes->first[n_sub]) * sizeof(uint32_t), c->s_out))) return rc;
   if ((rc = d2h_drain(c))) return rc;
   HIP_TRY(c, wait_stream(c, c->s_out));
   int status = *h_flag ? CABAC_HIP_ERR_SUBSTREAM : CABAC_HIP_OK;
@@ -3795,6 +3859,151 @@ int cabac_hip_workspace_waits(cabac_hip_ctx *c, uint64_t *n) {
   if (!c || !n) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   *n = c->n_waits;
   return CABAC_HIP_OK;
+}
+
+// ---- probe points (cabac_probe.hip, the estimator's probe instantiation; declared in cabac_hip_probe.h) ----------------------
+namespace {
+bool probe_args_ok(uint32_t n_sub, const void *d_desc, const void *d_records, const uint32_t *d_probe_first, const uint32_t *d_probe_at,
+                   uint32_t n_probe, uint32_t n_sets, const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
+                   const void *d_out) {
+  if (n_sub == 0) return true;
+  if (!d_desc || !d_records || !d_probe_first || (n_probe && (!d_probe_at || !d_out))) return false;
+  return sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, nullptr, nullptr, nullptr);
+}
+
+// the two host-pointer forms: one staging, the walk chosen by `estimate` (out: uint64_t[n_probe] then, else uint32_t[n_probe])
+int probes_batch_impl(cabac_hip_ctx *c, bool estimate, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                      uint64_t n_records_total, const uint32_t *probe_first, const uint32_t *probe_at, uint32_t n_probe, uint32_t n_sets,
+                      const uint32_t *state, const uint8_t *rate, const uint32_t *start_set, void *out, uint32_t *flags) {
+  if (!c || (n_sub && (!desc || (n_records_total && !records))) || (n_sub && n_probe && !out)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  if (start_set && n_sets && (!state || !rate)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  for (uint32_t s = 0; s < n_sub; s++) {
+    if (desc[s].rec_offset > n_records_total || desc[s].n_records > n_records_total - desc[s].rec_offset)
+      return fail(c, CABAC_HIP_ERR_INVALID, "records out of range");
+    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
+    if (start_set && start_set[s] != CABAC_CTX_NO_SET && start_set[s] >= n_sets) {
+      char buf[96];
+      snprintf(buf, sizeof buf, "substream %u: start set >= n_sets", s);
+      return fail(c, CABAC_HIP_ERR_INVALID, buf);
+    }
+  }
+  if (int bad = check_probes_host(c, n_sub, probe_first, probe_at, n_probe)) return bad;
+  DeviceGuard g(c->device);
+  int rc;
+  const size_t set_entries = size_t(n_sets) * CABAC_NUM_CONTEXTS, out_bytes = size_t(n_probe) * (estimate ? sizeof(uint64_t) : sizeof(uint32_t));
+  if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
+  if ((rc = ensure(c, kFlags, n_sub * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kProbeFirst, (size_t(n_sub) + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kProbeAt, size_t(n_probe) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kProbeOut, out_bytes))) return rc;
+  if (start_set && ((rc = ensure(c, kEstInState, set_entries * sizeof(uint32_t))) || (rc = ensure(c, kEstInRate, set_entries)) ||
+                    (rc = ensure(c, kEstInSet, n_sub * sizeof(uint32_t)))))
+    return rc;
+  HIP_TRY(c, up(c, c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc)));
+  HIP_TRY(c, up(c, c->d_buf[kRecords], records, n_records_total * 2));
+  HIP_TRY(c, up(c, c->d_buf[kProbeFirst], probe_first, (size_t(n_sub) + 1) * sizeof(uint32_t)));
+  HIP_TRY(c, up(c, c->d_buf[kProbeAt], probe_at, size_t(n_probe) * sizeof(uint32_t)));
+  if (start_set) {
+    HIP_TRY(c, up(c, c->d_buf[kEstInState], state, set_entries * sizeof(uint32_t)));
+    HIP_TRY(c, up(c, c->d_buf[kEstInRate], rate, set_entries));
+    HIP_TRY(c, up(c, c->d_buf[kEstInSet], start_set, n_sub * sizeof(uint32_t)));
+  }
+  auto *d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[kDesc]);
+  auto *d_rec = static_cast<const uint16_t *>(c->d_buf[kRecords]);
+  auto *d_first = static_cast<const uint32_t *>(c->d_buf[kProbeFirst]), *d_at = static_cast<const uint32_t *>(c->d_buf[kProbeAt]);
+  auto *d_state = start_set ? static_cast<const uint32_t *>(c->d_buf[kEstInState]) : nullptr;
+  auto *d_rate = start_set ? static_cast<const uint8_t *>(c->d_buf[kEstInRate]) : nullptr;
+  auto *d_set = start_set ? static_cast<const uint32_t *>(c->d_buf[kEstInSet]) : nullptr;
+  auto *d_flags = static_cast<uint32_t *>(c->d_buf[kFlags]);
+  if (estimate)
+    rc = cabac_hip_estimate_probes_device(c, n_sub, d_desc, d_rec, d_first, d_at, n_probe, n_sets, d_state, d_rate, d_set,
+                                          static_cast<uint64_t *>(c->d_buf[kProbeOut]), d_flags);
+  else
+    rc = cabac_hip_written_bits_device(c, n_sub, d_desc, d_rec, d_first, d_at, n_probe, n_sets, d_state, d_rate, d_set,
+                                       static_cast<uint32_t *>(c->d_buf[kProbeOut]), d_flags);
+  if (rc) return rc;
+  // the values come back into the ctx's own memory first: a caller's array holds only what the list's probes own
+  std::vector<uint32_t> fl(n_sub);
+  std::vector<uint8_t> vals(out_bytes);
+  HIP_TRY(c, down(c, vals.data(), c->d_buf[kProbeOut], out_bytes));
+  HIP_TRY(c, down(c, fl.data(), d_flags, n_sub * sizeof(uint32_t)));
+  HIP_TRY(c, wait_stream(c, c->stream));
+  const size_t each = estimate ? sizeof(uint64_t) : sizeof(uint32_t);
+  std::memcpy(out, vals.data(), size_t(probe_first[n_sub]) * each);
+  int status = CABAC_HIP_OK;
+  for (uint32_t s = 0; s < n_sub; s++) {
+    if (flags) flags[s] = fl[s];
+    if (fl[s]) status = CABAC_HIP_ERR_SUBSTREAM;
+  }
+  if (status) c->last_error = "substream flag set (see flags[])";
+  return status;
+}
+}  // namespace
+
+int cabac_hip_written_bits_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                  const uint32_t *d_probe_first, const uint32_t *d_probe_at, uint32_t n_probe, uint32_t n_sets,
+                                  const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set, uint32_t *d_bits,
+                                  uint32_t *d_flags) {
+  if (!c || !probe_args_ok(n_sub, d_desc, d_records, d_probe_first, d_probe_at, n_probe, n_sets, d_state, d_rate, d_start_set, d_bits))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  DeviceGuard g(c->device);
+  return TIMED_LAUNCH(c, 45, cabac::launch_written_bits(c->stream, n_sub, d_desc, d_records, cabac::ProbeList{d_probe_first, d_probe_at, n_sets},
+                                                         d_state, d_rate, d_start_set, d_bits, d_flags));
+}
+
+int cabac_hip_estimate_probes_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                     const uint32_t *d_probe_first, const uint32_t *d_probe_at, uint32_t n_probe, uint32_t n_sets,
+                                     const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set, uint64_t *d_frac_bits,
+                                     uint32_t *d_flags) {
+  if (!c || !probe_args_ok(n_sub, d_desc, d_records, d_probe_first, d_probe_at, n_probe, n_sets, d_state, d_rate, d_start_set, d_frac_bits))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  DeviceGuard g(c->device);
+  return TIMED_LAUNCH(c, 46, cabac::launch_estimate_probes(c->stream, n_sub, d_desc, d_records,
+                                                            cabac::ProbeList{d_probe_first, d_probe_at, n_sets}, d_state, d_rate, d_start_set,
+                                                            d_frac_bits, d_flags));
+}
+
+int cabac_hip_written_bits_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                 uint64_t n_records_total, const uint32_t *probe_first, const uint32_t *probe_at, uint32_t n_probe,
+                                 uint32_t n_sets, const uint32_t *state, const uint8_t *rate, const uint32_t *start_set, uint32_t *bits,
+                                 uint32_t *flags) {
+  return probes_batch_impl(c, false, n_sub, desc, records, n_records_total, probe_first, probe_at, n_probe, n_sets, state, rate, start_set,
+                           bits, flags);
+}
+
+int cabac_hip_estimate_probes_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                    uint64_t n_records_total, const uint32_t *probe_first, const uint32_t *probe_at, uint32_t n_probe,
+                                    uint32_t n_sets, const uint32_t *state, const uint8_t *rate, const uint32_t *start_set,
+                                    uint64_t *frac_bits, uint32_t *flags) {
+  return probes_batch_impl(c, true, n_sub, desc, records, n_records_total, probe_first, probe_at, n_probe, n_sets, state, rate, start_set,
+                           frac_bits, flags);
+}
+
+int cabac_hip_encode_residual_probes_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                            const uint32_t *d_splice_first, const cabac_splice *d_splices, uint32_t n_splice, uint32_t n_tu,
+                                            const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes, uint8_t *d_payload,
+                                            uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
+                                            uint32_t *d_tu_info, uint32_t *d_bin_counts, const uint32_t *d_probe_first,
+                                            const uint32_t *d_probe_at, const uint32_t *d_probe_splice, uint32_t n_probe, uint32_t *d_bits) {
+  const SpliceProbes probes{d_probe_first, d_probe_at, d_probe_splice, n_probe, d_bits};
+  return encode_residual_device_impl(c, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes,
+                                     d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr, nullptr,
+                                     nullptr, &probes);
+}
+
+int cabac_hip_encode_residual_probes_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                           uint64_t n_records_total, const uint32_t *splice_first, const cabac_splice *splices,
+                                           uint32_t n_tu, const cabac_tu_desc *tus, const void *coeff, int coeff_bytes,
+                                           uint64_t n_coeff_total, uint8_t *payload, uint64_t payload_capacity, uint64_t *payload_offsets,
+                                           cabac_substream_result *results, uint32_t *tu_info, uint32_t *bin_counts,
+                                           const uint32_t *probe_first, const uint32_t *probe_at, const uint32_t *probe_splice,
+                                           uint32_t n_probe, uint32_t *bits) {
+  const SpliceProbes probes{probe_first, probe_at, probe_splice, n_probe, bits};
+  return host_call_exit(c, encode_batch_residual_impl(c, n_sub, desc, records, n_records_total, splice_first, splices, n_tu, tus, coeff,
+                                                      coeff_bytes, n_coeff_total, payload, payload_capacity, payload_offsets, results,
+                                                      tu_info, bin_counts, nullptr, nullptr, &probes));
 }
 
 int cabac_hip_host_alloc(size_t bytes, void **out) {

@@ -59,6 +59,30 @@ hipError_t launch_estimate(hipStream_t st, uint32_t n_sub, const cabac_substream
                            uint64_t *frac_bits, uint32_t *flags, const uint32_t *start_state = nullptr,
                            const uint8_t *start_rate = nullptr, const uint32_t *start_set = nullptr);
 
+// probe points (cabac_hip_probe.h): running totals at caller-chosen positions inside the substreams.  The probe list: substream
+// s owns at[first[s] .. first[s + 1]), each "after the first k records", non-decreasing, clipped to the substream's length; n_sets:
+// the sets state / rate hold (substream s starts from set start_set[s]; 0xffffffff or start_set null: Ctx::init; an index >=
+// n_sets: CABAC_RES_BAD_SET, its values 0).  flags (may be null): 0, CABAC_RES_BAD_RECORD or CABAC_RES_BAD_SET per substream
+struct ProbeList {
+  const uint32_t *first, *at;
+  uint32_t n_sets;
+};
+// written bits (cabac_probe.hip): bits[p] = getNumWrittenBits() after the probe's records — the range half of the encoder's chain
+hipError_t launch_written_bits(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                               const ProbeList &probes, const uint32_t *start_state, const uint8_t *start_rate,
+                               const uint32_t *start_set, uint32_t *bits, uint32_t *flags);
+// estimated bits (cabac_kernels_v4.hip): the probe instantiation of the estimator's walk, frac_bits[p] per probe
+hipError_t launch_estimate_probes(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                  const ProbeList &probes, const uint32_t *start_state, const uint8_t *start_rate,
+                                  const uint32_t *start_set, uint64_t *frac_bits, uint32_t *flags);
+// the probes of a spliced call (cabac_splice.hip) as positions in the expanded strings: probe_rec[p] = k + pre[m], as
+// launch_splice_sync_index, for the pair (probe_at[p], probe_splice[p]) of the substream that owns probe p (probe_splice null: the
+// upper end).  One thread per probe.  After launch_splice_plan accepted the list.
+hipError_t launch_splice_probe_index(hipStream_t st, uint32_t n_sub, uint32_t n_probe, const cabac_substream_desc *desc,
+                                     const uint32_t *splice_first, const cabac_splice *splices, const uint32_t *pre,
+                                     const uint32_t *probe_first, const uint32_t *probe_at, const uint32_t *probe_splice,
+                                     uint32_t *probe_rec);
+
 // context advance (cabac_kernels_v4.hip; cabac_hip_ctx_sets.h): update() for every context-coded record of the runs, sets in, sets
 // out; nothing is coded.  flags (may be null): CABAC_RES_BAD_RECORD, CABAC_RES_BAD_SET or 0 per substream
 hipError_t launch_ctx_advance(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,

@@ -260,6 +260,30 @@ __global__ __launch_bounds__(256) void splice_expand_kernel(const WsState *__res
   }
 }
 
+// a point (at, splice[i]; splice null: the upper end) of substream s as an index into its expanded string: what the two kernels below say of it
+__device__ __forceinline__ uint32_t splice_point_index(uint32_t s, const cabac_substream_desc *__restrict__ desc,
+                                                       const uint32_t *__restrict__ splice_first, const cabac_splice *__restrict__ splices,
+                                                       const uint32_t *__restrict__ pre, uint32_t at, const uint32_t *__restrict__ splice, uint32_t i) {
+  const uint32_t j0 = splice_first[s], ns = splice_first[s + 1] - j0;
+  const uint32_t k = min(at, desc[s].n_records);
+  const cabac_splice *sp = splices + j0;
+  uint32_t lo = 0, hi = ns;  // #{at < k}
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (sp[mid].at < k) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint32_t below = lo;
+  hi = ns;  // #{at <= k}, from there on
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (sp[mid].at <= k) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint32_t m = splice ? min(max(splice[i], below), lo) : lo;
+  return k + pre[j0 + s + m];
+}
+
 // the hand-over point of every substream (cabac_hip_splice_rows.h) as an index into its expanded string: k host records and m of
 // its splices in front, m clipped to [#{at < k}, #{at <= k}] — two bisections of the sorted splices — and the records of those m
 // blocks from the running sums of splice_plan_kernel.  One thread per substream; nothing is shared.  kGated: index 0 for every
@@ -277,24 +301,32 @@ __global__ __launch_bounds__(256) void splice_sync_index_kernel(const WsState *_
     sync_rec[s] = 0u;
     return;
   }
-  const uint32_t j0 = splice_first[s], ns = splice_first[s + 1] - j0;
-  const uint32_t k = min(sync_at[s], desc[s].n_records);
-  const cabac_splice *sp = splices + j0;
-  uint32_t lo = 0, hi = ns;  // #{at < k}
+  sync_rec[s] = splice_point_index(s, desc, splice_first, splices, pre, sync_at[s], sync_splice, s);
+}
+
+// The same for a LIST of points per substream (cabac_hip_probe.h): probe p of substream s, probe_first[s] <= p < probe_first[s + 1],
+// is the pair (probe_at[p], probe_splice[p]).  One thread per probe: a bisection of probe_first for its substream (the last s
+// with probe_first[s] <= p — substreams without probes are stepped over), then the two bisections above.
+__global__ __launch_bounds__(256) void splice_probe_index_kernel(uint32_t n_sub, uint32_t n_probe,
+                                                                 const cabac_substream_desc *__restrict__ desc,
+                                                                 const uint32_t *__restrict__ splice_first,
+                                                                 const cabac_splice *__restrict__ splices, const uint32_t *__restrict__ pre,
+                                                                 const uint32_t *__restrict__ probe_first,
+                                                                 const uint32_t *__restrict__ probe_at,
+                                                                 const uint32_t *__restrict__ probe_splice, uint32_t *__restrict__ probe_rec) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_probe) return;
+  uint32_t lo = 0, hi = n_sub;  // #{s in 1 .. n_sub: probe_first[s] <= p}
   while (lo < hi) {
     const uint32_t mid = (lo + hi) >> 1;
-    if (sp[mid].at < k) lo = mid + 1;
+    if (probe_first[mid + 1u] <= p) lo = mid + 1;
     else hi = mid;
   }
-  const uint32_t below = lo;
-  hi = ns;  // #{at <= k}, from there on
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (sp[mid].at <= k) lo = mid + 1;
-    else hi = mid;
+  if (lo >= n_sub) {  // behind probe_first[n_sub]: no substream owns it
+    probe_rec[p] = 0u;
+    return;
   }
-  const uint32_t m = sync_splice ? min(max(sync_splice[s], below), lo) : lo;
-  sync_rec[s] = k + pre[j0 + s + m];
+  probe_rec[p] = splice_point_index(lo, desc, splice_first, splices, pre, probe_at[p], probe_splice, p);
 }
 
 // BinCounter totals of the expanded substreams (arith_codec.cpp:281-316): per substream 379 context-bin counts, then the
@@ -412,6 +444,16 @@ hipError_t launch_splice_sync_index_gated(hipStream_t st, const WsState *ws, uin
   if (n_sub)
     hipLaunchKernelGGL(splice_sync_index_kernel<true>, dim3((n_sub + 255u) / 256u), dim3(256), 0, st, ws, n_sub, desc, splice_first,
                        splices, pre, sync_at, sync_splice, sync_rec);
+  return hipGetLastError();
+}
+
+hipError_t launch_splice_probe_index(hipStream_t st, uint32_t n_sub, uint32_t n_probe, const cabac_substream_desc *desc,
+                                     const uint32_t *splice_first, const cabac_splice *splices, const uint32_t *pre,
+                                     const uint32_t *probe_first, const uint32_t *probe_at, const uint32_t *probe_splice,
+                                     uint32_t *probe_rec) {
+  if (n_sub && n_probe)
+    hipLaunchKernelGGL(splice_probe_index_kernel, dim3((n_probe + 255u) / 256u), dim3(256), 0, st, n_sub, n_probe, desc, splice_first,
+                       splices, pre, probe_first, probe_at, probe_splice, probe_rec);
   return hipGetLastError();
 }
 
