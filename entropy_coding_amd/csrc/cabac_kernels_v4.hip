@@ -293,20 +293,22 @@ struct QuadUnits {
   uint64_t store_lanes;  // lanes that will store a unit
 };
 
-// Part 1: lanes 0..3 of a row list the units of posts 0..3 in stream order.  kHalfRows: a substream has EIGHT lanes (two
-// substreams per 16-lane DPP row, j = lane & 7) — eight is the most units a step can produce, and lanes 4..7 of a group
-// count nothing, so the row shifts never carry a count across the two groups of a row.
-template <bool kHalfRows = false>
+// Part 1: lanes 0..3 of a row list the units of posts 0..3 in stream order.  kLanes = 4: a substream has FOUR lanes (a DPP
+// quad, four substreams per 16-lane row, j = lane & 3), one per post, so the counts a row shift brings in from the
+// neighbouring substream are masked away.  Lane j then stores unit j: a step with more than four units — it can produce
+// eight, an all-LPS run; an ordinary mix produces about one — is "not plain" and takes the serial path.
+template <int kLanes = 16>
 __device__ __forceinline__ QuadUnits quad_list_units(const QuadEnc &e, const uint32_t *plo, const uint32_t *phi,
                                                      const uint32_t *ppend, uint32_t row, uint32_t j, bool live,
-                                                     uint32_t *list, uint32_t lane = 0) {
+                                                     uint32_t *list) {
+  static_assert(kLanes == 16 || kLanes == 4, "a row or a quad per substream");
   const uint32_t c = (j & 3u) * kQuadSubs + row;  // lanes >= 4 read along, and count nothing
   const uint64_t low = ((uint64_t)phi[c] << 32) | plo[c];
   const uint32_t pend = ppend[c];
-  const uint32_t nun = (pend >> 4) & neg_mask(j - 4u);  // 0, 1 or 2 units
+  const uint32_t nun = kLanes == 4 ? pend >> 4 : (pend >> 4) & neg_mask(j - 4u);  // 0, 1 or 2 units
   const uint64_t v = low >> (9u + (pend & 15u));         // carry, then the units
-  uint32_t incl = nun + row_shr<1>(nun);
-  incl += row_shr<2>(incl);
+  uint32_t incl = nun + (kLanes == 4 ? row_shr<1>(nun) & neg_mask(0u - j) : row_shr<1>(nun));
+  incl += kLanes == 4 ? row_shr<2>(incl) & neg_mask(1u - j) : row_shr<2>(incl);
   const uint32_t idx = incl - nun;
   const uint32_t first = (uint32_t)(v >> (((nun - 1u) & 1u) << 4));  // carry + first unit (nun >= 1)
   const uint32_t second = (uint32_t)v & 0xffffu;                      // second unit (nun == 2)
@@ -315,10 +317,10 @@ __device__ __forceinline__ QuadUnits quad_list_units(const QuadEnc &e, const uin
   list[sel(has1, idx, kUnitDump)] = first;
   list[sel(has2, idx + 1u, kUnitDump)] = second;
   QuadUnits u;
-  if (kHalfRows) u.m = (lane & 8u) ? row_bcast<11>(incl) : row_bcast<3>(incl);
-  else u.m = row_bcast<3>(incl);
+  u.m = group_bcast<kLanes, 3>(incl);
   const uint32_t room = e.cap - e.pos - 2u * u.m;                     // negative: the buffer would overflow
-  const uint32_t rowodd = neg_mask(0u - u.m) & (neg_mask(0u - ((uint32_t)e.nbuf ^ 1u)) | neg_mask(room));
+  uint32_t rowodd = neg_mask(0u - u.m) & (neg_mask(0u - ((uint32_t)e.nbuf ^ 1u)) | neg_mask(room));
+  if (kLanes == 4) rowodd |= neg_mask(4u - u.m);                      // five to eight units: more than the lanes
   u.odd_rows = __ballot(live && rowodd != 0);   // (rows without a substream never store: nothing to be careful about)
   u.store_lanes = __ballot(live && j < u.m);
   return u;
@@ -363,15 +365,19 @@ __device__ __forceinline__ void quad_emit_units(QuadEnc &e, const QuadUnits &u, 
 // All units of a workgroup run the same number of steps (the longest substream's) so that the barrier counts
 // match; surplus steps are no-ops.
 #ifdef CABAC_V5_PROFILE  // tools/ubench_v5.hip: where the two waves of workgroup 0 spend their cycles
-__device__ unsigned long long g_v5_prof[16];
+__device__ unsigned long long g_v5_prof[32];
 #define V5_TICK(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
 #define V5_ADD(slot, t0, t1) \
   if (blockIdx.x == 0 && lane == 0) g_v5_prof[slot] += (t1) - (t0)
+// where the hardware put wave `w` of workgroup 0: the whole HW_ID register (id 4, 32 bits; its bits 5..4 are the SIMD), one read
+#define V5_HW_ID(w) \
+  if (blockIdx.x == 0 && lane == 0) g_v5_prof[16 + (w)] = 0x100000000ull | (uint32_t)__builtin_amdgcn_s_getreg(4 | (31 << 11))
 #else
 #define V5_TICK(var)
 #define V5_ADD(slot, t0, t1)
+#define V5_HW_ID(w)
 #endif
-#ifndef CABAC_V5_STAMP_UNIT   // v7: the unit whose context and output wave are stamped (0, or 2: the waves of the second half)
+#ifndef CABAC_V5_STAMP_UNIT   // v7: the unit whose context wave is stamped (unit 0 shares its SIMD with unit 3's, 1 with the low wave, 2 with the output wave)
 #define CABAC_V5_STAMP_UNIT 0
 #endif
 
@@ -821,9 +827,13 @@ __global__ __launch_bounds__(256 * U) void encode_kernel_v6(uint32_t n_sub, cons
 //                      runs the range recurrence — 9 vector instructions per bin (as compiled: bfe, mad, shift, sub,
 //                      select, ffbh, sub, shift, shift-add) for ALL substreams of the workgroup instead of 13 per four —
 //                      and posts rm | shift << 9 per bin with four 16-byte writes;
-//   1 low wave         lane = substream: the code value (low = (low << s) + term, 64-bit), one step behind the chain;
-//   U / 2 output waves eight lanes per substream: the 16-bit units, the delayed carry and the byte stores, two steps
-//                      behind the chain.
+//   1 low wave         FOUR lanes per substream, a quarter of the step's bins each: the code value (low = (low << s) + term,
+//                      64-bit), one step behind the chain — a quarter's bins folded into one update per lane, the four
+//                      updates applied in order over the DPP quad (~108 instructions a step; one lane per substream and
+//                      sixteen updates in a row were 175);
+//   1 output wave      four lanes per substream, a post each: the 16-bit units, the delayed carry and the byte stores, two
+//                      steps behind the chain.  A step of more than four units (an all-LPS run) takes the serial path.
+// U + 3 waves: for U = 4 seven, dealt so that the chain wave is alone on its SIMD (see the roles below).
 // One workgroup barrier per step; fields live in a ring of four steps (context waves one step ahead, low one behind).
 constexpr uint32_t kV7Pad = 20;  // words per substream and field: 16 bins + 4, so that neighbouring lanes' 16-byte reads spread over the banks
 enum : uint32_t { kV7K = 0, kV7C2, kV7Lpsm, kV7Lp9, kV7Ep, kV7Fields };
@@ -840,7 +850,7 @@ __device__ __forceinline__ uint32_t lane_rng_step(uint32_t k, uint32_t c2, uint3
 }
 
 template <int U, class... Sets>
-__global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+__global__ __launch_bounds__(64 * (U + 3)) void encode_kernel_v7(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
                                                                       const uint16_t *__restrict__ records,
                                                                       uint8_t *__restrict__ bytes,
                                                                       cabac_substream_result *__restrict__ results, Sets... sets) {
@@ -866,51 +876,47 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
   __shared__ uint32_t bad_rows[U];
   __shared__ uint32_t wg_max_n;
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  V5_HW_ID(wave);
   if constexpr (kKinds) quad_kind_tab_init(kind_tab, threadIdx.x, blockDim.x);
   else quad_rate_tab_init(rate_tab, threadIdx.x, blockDim.x);
   // same-id lanes of the context waves through LDS (C4 0.81 -> 0.65 ms)
   constexpr bool kLdsMatch = true;
   for (uint32_t k = threadIdx.x; k < U * kMatch; k += blockDim.x) (&match_all[0][0])[k] = 0u;
-  // Roles by wave number.  Waves are dealt to the CU's four SIMDs in turn.  For U = 4, eight waves: context 0, context 1,
-  // chain, low | output 0, output 1, context 2, context 3 — a context and an output wave on SIMD 0 and on SIMD 1, chain +
-  // context on SIMD 2, low + context on SIMD 3.  By vector instructions per step (context ~96 since the kind table, chain ~178, low ~175,
-  // output ~70) this is NOT the even deal: that is context + context | chain + output | low + output, which this kernel had while the
-  // chain wave was 230 instructions.  Measured with the role stamps (profiles/encode_chain_fields.json), the wave that came
-  // last to the barrier there was the output wave that shares the chain wave's SIMD — it waits for LDS and for its stores
-  // between few instructions, and the chain wave (s_setprio 3) takes the issue slots it could use; next to a context wave
-  // it is 13 % shorter and the kernel 10 % (4 096 substreams: 0.59 -> 0.53 ms).  Chain and low wave on one SIMD is the deal
-  // not to make (+ 13 %).  Last at the barrier now, as before the kind table: the context wave next to the chain wave (it
-  // waits 69 ticks there, every other role 170 to 325).
-  // For U = 1: context, chain, low, output.
-  // Context waves: lane = (row, bin) of one unit's four substreams; chain and low wave: lane = substream; output waves:
-  // EIGHT lanes per substream (eight substreams = two units per wave).
-  const uint32_t role_slot = U == 4 ? wave : (wave == 0 ? 0u : wave + 1u);   // U = 1: 0 context, 2 chain, 3 low, 4+ output
-  const bool is_ctx = role_slot < 2u || (U == 4 && role_slot >= 6u);
-  const bool is_chain = role_slot == 2u, is_low = role_slot == 3u;
-  const bool is_out = !is_ctx && !is_chain && !is_low;
-  const uint32_t ctx_unit = role_slot < 2u ? role_slot : role_slot - 4u;          // context waves 0, 1 | 6, 7 -> units 0 .. 3
-  const uint32_t out_index = U == 4 ? role_slot - 4u : 0u;
+  // Roles by wave number: U + 3 waves.  The hardware deals the waves of a workgroup to the CU's four SIMDs in turn (wave w
+  // and wave w + 4 share one; which SIMD wave 0 gets varies — read from HW_ID in the profiled build, tools/ubench_v5.hip), so
+  // with seven waves, U = 4, wave 3 has a SIMD to itself.  That is the chain wave: a wave alone issues an instruction every
+  // ~4.8 ticks whatever depends on what (tools/ubench_lat.hip: the bin of lane_rng_step with eight, and two rewrites of it with
+  // six, dependent instructions all take 43 ticks), so its ~177 instructions a step are the floor of the step, and any wave
+  // that shares its SIMD comes late to the barrier (before this deal: the context wave beside it).
+  //   U = 4: context 0, context 1, context 2, chain | context 3, low, output   ->   context + context | context + low |
+  //          context + output | chain
+  //   U = 1: context, chain, low, output — a SIMD each.
+  // Context waves: lane = (row, bin) of one unit's four substreams; chain wave: lane = substream; low and output wave: FOUR
+  // lanes per substream, a DPP quad (the low wave: a quarter of the step's bins each; the output wave: a post each).
+  constexpr uint32_t kChainWave = U == 4 ? 3u : 1u, kLowWave = U == 4 ? 5u : 2u, kOutWave = U == 4 ? 6u : 3u;
+  const bool is_chain = wave == kChainWave, is_low = wave == kLowWave, is_out = wave == kOutWave;
+  const bool is_ctx = !is_chain && !is_low && !is_out;
   // the substream of this thread
   uint32_t row, j, unit, local;
   bool in_range = true;
   if (is_ctx) {
     row = lane >> 4;
     j = lane & 15u;
-    unit = ctx_unit;
+    unit = min(wave, U - 1u);                          // context waves 0, 1, 2 | 4 -> units 0 .. 3
     local = unit * kQuadSubs + row;
-  } else if (is_out) {
-    const uint32_t g = out_index * 8u + (lane >> 3);   // substream of the workgroup
-    in_range = g < S;
-    local = min(g, S - 1u);
-    unit = local >> 2;
-    row = local & 3u;
-    j = lane & 7u;
-  } else {
+  } else if (is_chain) {
     row = lane >> 4;
     j = lane & 15u;
     unit = 0;
     in_range = lane < S;
     local = min(lane, S - 1u);
+  } else {
+    const uint32_t g = lane >> 2;                      // substream of the workgroup
+    in_range = g < S;
+    local = min(g, S - 1u);
+    unit = local >> 2;
+    row = local & 3u;
+    j = lane & 3u;
   }
   const uint32_t sub = blockIdx.x * S + local;
   const QuadSetUse su = quad_set_use(sub, sub < n_sub, sets...);
@@ -1009,43 +1015,65 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
     __syncthreads();
     __syncthreads();
   } else if (is_low) {
-    // ---- low wave: lane = substream, the code value one step behind the chain; every 4th bin it posts (low, pend) and
-    // keeps only the pend % 16 bits that are not yet a whole unit (v5's chain wave did the same, see quad_enc_step) ----
-    uint64_t low = 0;
+    // ---- low wave: the code value, one step behind the chain, FOUR lanes per substream.  Lane (substream, quarter q) takes
+    // bins 4q .. 4q + 3 of the step with three 16-byte reads and folds them into one update of the code value,
+    //   low' = (low << S) + P,   S = sh_0 + .. + sh_3,   P = sum of term_i << (sh_(i+1) + .. + sh_3)   (P < 2^40, S <= 32),
+    // which needs nothing from the quarters before it.  The quarters are then joined in order over the DPP quad: in round r
+    // every lane takes the state its left neighbour holds (quarter 0: the state the step began with), applies its update,
+    // and cuts — what a lane holds is right from round q on and does not change after, because its input does not.  What a
+    // quarter posts, (low, pend) before the cut, and where (slot q * kQuadSubs + row) is what the serial form posted after
+    // bins 3, 7, 11, 15; it keeps only the pend % 16 bits that are not yet a whole unit (v5's chain wave did the same, see
+    // quad_enc_step).  low < 2^58 before a cut, as there. ----
+    uint64_t low = 0;       // the state behind the last quarter, in all four lanes of a substream
     uint32_t pend = 0;
-    const uint32_t pu = local >> 2, pr = local & 3u;
+    const uint32_t pu = local >> 2, pr = local & 3u, q = j;
+    auto quad_from_left = [](uint32_t v) {   // lane q of a quad gets lane q - 1 (quad_perm:[0,0,1,2]; quarter 0 does not use it)
+      return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x90, 0xf, 0xf, true);
+    };
     auto low_step = [&](uint32_t k) {
       const uint32_t slot = k & 3u;
-      uint32_t w[16], lp9[16], ep[16];
+      const uint4 w4 = reinterpret_cast<const uint4 *>(&wpost[k & 1u][local * kV7Pad])[q];
+      const uint4 l4 = reinterpret_cast<const uint4 *>(&fld[slot][kV7Lp9][local * kV7Pad])[q];
+      const uint4 e4 = reinterpret_cast<const uint4 *>(&fld[slot][kV7Ep][local * kV7Pad])[q];
+      const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w}, lp9[4] = {l4.x, l4.y, l4.z, l4.w}, ep[4] = {e4.x, e4.y, e4.z, e4.w};
+      // low = (low + (LPS ? rm : 0)) << shift for a context / terminate bin, (low << 1) + (bin ? range : 0) for a bypass
+      // bin (arith_codec.cpp:389-399, :426-478); a bypass bin does not renormalise (nb = 0), so both are (rm << nb)
+      uint32_t term[4], sh[4];
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        lds_read4(&wpost[k & 1u][min(lane, S) * kV7Pad], q, w);
-        lds_read4(&fld[slot][kV7Lp9][local * kV7Pad], q, lp9);
-        lds_read4(&fld[slot][kV7Ep][local * kV7Pad], q, ep);
-      }
-#pragma unroll
-      for (int i = 0; i < 16; i++) {
-        // low = (low + (LPS ? rm : 0)) << shift for a context / terminate bin, (low << 1) + (bin ? range : 0) for a bypass
-        // bin (arith_codec.cpp:389-399, :426-478); a bypass bin does not renormalise (nb = 0), so both are (rm << nb)
+      for (int i = 0; i < 4; i++) {
         const uint32_t nb = w[i] >> 9;
-        const uint32_t term = (w[i] & lp9[i]) << nb;
-        const uint32_t sh = nb + ep[i];
-        low = (low << sh) + term;
-        pend += sh;
-        if ((i & 3) == 3) {
-          const uint32_t c = (uint32_t)(i >> 2) * kQuadSubs + pr;
-          // (no `if (lane < S)`: the lanes past the last substream mirror it — same fields, same values — and an `if`
-          // is a compare the scalar unit waits for, four times per step)
-          post_lo[pu][k & 1u][c] = (uint32_t)low;
-          post_hi[pu][k & 1u][c] = (uint32_t)(low >> 32);
-          post_pend[pu][k & 1u][c] = pend;
-          // whole units, and the carry above them, now belong to the post; without a whole unit nothing is cut
-          const uint32_t keep = pend & 15u;
-          const uint32_t width = pend >= 16u ? 9u + keep : 63u;
-          low &= ~(~0ull << width);
-          pend = keep;
-        }
+        term[i] = (w[i] & lp9[i]) << nb;     // < 2^16
+        sh[i] = nb + ep[i];                  // <= 8
       }
+      const uint32_t p01 = (term[0] << sh[1]) + term[1];          // < 2^25
+      const uint64_t P = ((((uint64_t)p01 << sh[2]) + term[2]) << sh[3]) + term[3];
+      const uint32_t Ssum = sh[0] + sh[1] + sh[2] + sh[3];
+      uint64_t cut = 0, posted = 0;        // this quarter's state after and before its cut
+      uint32_t cut_pend = 0, posted_pend = 0;
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        uint64_t in = low;
+        uint32_t in_pend = pend;
+        if (r != 0) {
+          const uint32_t lo = quad_from_left((uint32_t)cut), hi = quad_from_left((uint32_t)(cut >> 32)), pp = quad_from_left(cut_pend);
+          in = q == 0 ? low : ((uint64_t)hi << 32) | lo;
+          in_pend = q == 0 ? pend : pp;
+        }
+        posted = (in << Ssum) + P;
+        posted_pend = in_pend + Ssum;
+        // whole units, and the carry above them, now belong to the post; without a whole unit nothing is cut
+        const uint32_t keep = posted_pend & 15u;
+        const uint32_t width = posted_pend >= 16u ? 9u + keep : 63u;
+        cut = posted & ~(~0ull << width);
+        cut_pend = keep;
+      }
+      // (no `if (lane < 4 * S)`: the lanes past the last substream mirror it — same fields, same values)
+      const uint32_t c = q * kQuadSubs + pr;
+      post_lo[pu][k & 1u][c] = (uint32_t)posted;
+      post_hi[pu][k & 1u][c] = (uint32_t)(posted >> 32);
+      post_pend[pu][k & 1u][c] = posted_pend;
+      low = ((uint64_t)group_bcast<4, 3>((uint32_t)(cut >> 32)) << 32) | group_bcast<4, 3>((uint32_t)cut);
+      pend = group_bcast<4, 3>(cut_pend);
     };
     __syncthreads();
     for (uint32_t k = 0; k < n_steps; k++) {
@@ -1064,7 +1092,7 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
     __syncthreads();
     __syncthreads();
   } else {
-    // ---- output waves: v5's (quad_list_units / quad_emit_units) with eight lanes per substream, two steps behind the chain ----
+    // ---- output wave: v5's (quad_list_units / quad_emit_units) with four lanes per substream, two steps behind the chain ----
     QuadEnc e;
     e.low = 0;
     e.range = 0;
@@ -1082,8 +1110,12 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
     units.store_lanes = 0;
     bool listed = false;
     auto list_step = [&](uint32_t k) {
-      units = quad_list_units<true>(e, post_lo[unit][k & 1u], post_hi[unit][k & 1u], post_pend[unit][k & 1u], row, j, live, list, lane);
+      units = quad_list_units<4>(e, post_lo[unit][k & 1u], post_hi[unit][k & 1u], post_pend[unit][k & 1u], row, j, live, list);
     };
+    // Every load of the prologue has landed before the loop.  Without this the compiler waits for one of them (a register
+    // it reuses) INSIDE the loop, with vmcnt(0) — where, from the second step on, what that waits for is the round trip of
+    // the step's own stores: the output wave was then the last at the barrier, 1 270 ticks busy for ~80 instructions.
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
     __syncthreads();
     for (uint32_t k = 0; k < n_steps; k++) {
       V5_TICK(t0);
@@ -1093,8 +1125,8 @@ __global__ __launch_bounds__(64 * (U + 2 + (U + 1) / 2)) void encode_kernel_v7(u
       V5_TICK(t1);
       __syncthreads();
       V5_TICK(t2);
-      if (unit == CABAC_V5_STAMP_UNIT) V5_ADD(6, t0, t1);
-      if (unit == CABAC_V5_STAMP_UNIT) V5_ADD(7, t1, t2);
+      V5_ADD(6, t0, t1);
+      V5_ADD(7, t1, t2);
     }
     if (listed) quad_emit_units(e, units, j, list, writer);
     if (n_steps >= 2u) {
@@ -2031,12 +2063,12 @@ hipError_t launch_encode_v6(hipStream_t st, uint32_t n_sub, const cabac_substrea
 hipError_t launch_encode_v7(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
                             uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight, const CtxSets *sets) {
   if (sets != nullptr) {
-    if (max(n_sub, in_flight) >= 1024u) hipLaunchKernelGGL((encode_kernel_v7<4, CtxSets>), dim3((n_sub + 15) / 16), dim3(512), 0, st, n_sub, desc, records, bytes, results, *sets);
+    if (max(n_sub, in_flight) >= 1024u) hipLaunchKernelGGL((encode_kernel_v7<4, CtxSets>), dim3((n_sub + 15) / 16), dim3(448), 0, st, n_sub, desc, records, bytes, results, *sets);
     else hipLaunchKernelGGL((encode_kernel_v7<1, CtxSets>), dim3((n_sub + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes, results, *sets);
     return hipGetLastError();
   }
   // sixteen substreams per workgroup once there are enough of them to give every CU one; four below that
-  if (max(n_sub, in_flight) >= 1024u) hipLaunchKernelGGL(encode_kernel_v7<4>, dim3((n_sub + 15) / 16), dim3(512), 0, st, n_sub, desc, records, bytes, results);
+  if (max(n_sub, in_flight) >= 1024u) hipLaunchKernelGGL(encode_kernel_v7<4>, dim3((n_sub + 15) / 16), dim3(448), 0, st, n_sub, desc, records, bytes, results);
   else hipLaunchKernelGGL(encode_kernel_v7<1>, dim3((n_sub + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes, results);
   return hipGetLastError();
 }

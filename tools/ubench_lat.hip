@@ -51,6 +51,42 @@ KERNEL(k_cmp_cnd, 8, R8("v_cmp_lt_u32 vcc, %0, %1\n v_cndmask_b32 %0, %0, %2, vc
   "v_add_u32 %1, %1, %2\n" \
   "v_add_u32 %2, %1, %2\n"
 KERNEL(k_dec_bin, 68, DEC_BIN DEC_BIN DEC_BIN DEC_BIN)
+// one bin of the v7 encoder's chain wave, nine instructions, four bins per block: the count-leading-zeros form (eight on the
+// dependent path), the float-exponent form (six: cabac_range_step.h), and an integer form with sub-dword operands (six)
+#define RNG_BIN_CLZ \
+  "v_bfe_u32 %3, %0, 5, 4\n" \
+  "v_mad_u32_u24 %3, %3, %1, %2\n" \
+  "v_lshrrev_b32 %3, 1, %3\n" \
+  "v_sub_u32 %5, %0, %3\n" \
+  "v_bitop3_b32 %3, %3, %5, %4 bitop3:0xe4\n" \
+  "v_ffbh_u32 %0, %3\n" \
+  "v_add_u32 %0, -23, %0\n" \
+  "v_lshl_add_u32 %5, %0, 9, %5\n" \
+  "v_lshlrev_b32 %0, %0, %3\n"
+#define RNG_BIN_F32 \
+  "v_bfe_u32 %3, %0, 20, 3\n" \
+  "v_bfe_u32 %5, %0, 15, 8\n" \
+  "v_mad_u32_u24 %3, %3, %1, %2\n" \
+  "v_or_b32 %5, 0x100, %5\n" \
+  "v_lshrrev_b32 %3, 1, %3\n" \
+  "v_sub_u32 %5, %5, %3\n" \
+  "v_bitop3_b32 %3, %3, %5, %4 bitop3:0xe4\n" \
+  "v_cvt_f32_u32 %0, %3\n" \
+  "v_or_b32 %5, %5, %0\n"
+#define RNG_BIN_SDWA \
+  "v_bfe_u32 %3, %0, 28, 3\n" \
+  "v_lshrrev_b32 %5, 23, %0\n" \
+  "v_mad_u32_u24 %3, %3, %1, %2\n" \
+  "v_cmp_ne_u32 vcc, 0, %4\n" \
+  "v_sub_u32_sdwa %5, %5, %3 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n" \
+  "v_cndmask_b32_sdwa %3, %5, %3, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n" \
+  "v_ffbh_u32 %0, %3\n" \
+  "v_lshl_add_u32 %5, %0, 9, %5\n" \
+  "v_lshlrev_b32 %0, %0, %3\n"
+KERNEL(k_cvt_f32_u32, 8, R8("v_cvt_f32_u32 %0, %0\n"))
+KERNEL(k_rng_bin_clz, 36, RNG_BIN_CLZ RNG_BIN_CLZ RNG_BIN_CLZ RNG_BIN_CLZ)
+KERNEL(k_rng_bin_f32, 36, RNG_BIN_F32 RNG_BIN_F32 RNG_BIN_F32 RNG_BIN_F32)
+KERNEL(k_rng_bin_sdwa, 36, RNG_BIN_SDWA RNG_BIN_SDWA RNG_BIN_SDWA RNG_BIN_SDWA)
 int main() {
   unsigned long long *cyc; unsigned *out; (void)hipMalloc(&cyc, 8 * 2048); (void)hipMalloc(&out, 4096);
   const int iters = 4000;
@@ -59,5 +95,6 @@ int main() {
     printf("%-16s %6.2f memtime ticks per instruction, %6.2f ns per instruction (block of %d)\n", #name, (double)h / (iters * (double)name##_n), ms * 1e6 / (iters * (double)name##_n), name##_n); }
   RUN(k_add) RUN(k_add) RUN(k_add_indep2) RUN(k_mad24) RUN(k_mul24) RUN(k_bfe) RUN(k_bfi) RUN(k_bitop3) RUN(k_ffbh) RUN(k_ashr) RUN(k_add_sdwa)
   RUN(k_pk_mad) RUN(k_pk_lshr) RUN(k_lshl64) RUN(k_dpp_nop2) RUN(k_dpp_fill2) RUN(k_cmp_cnd) RUN(k_dec_bin)
+  RUN(k_cvt_f32_u32) RUN(k_rng_bin_clz) RUN(k_rng_bin_f32) RUN(k_rng_bin_sdwa)
   return 0;
 }

@@ -22,9 +22,9 @@ int main() {
   (void)hipMemcpy(d_desc, desc.data(), desc.size() * sizeof(desc[0]), hipMemcpyHostToDevice);
   (void)hipMemcpy(d_rec, rec.data(), rec.size() * 2, hipMemcpyHostToDevice);
   for (int rep = 0; rep < 3; rep++) {
-    unsigned long long zero[16] = {};
+    unsigned long long zero[32] = {};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_v5_prof), zero, sizeof(zero));
-    hipLaunchKernelGGL(encode_kernel_v7<4>, dim3(n_sub / 16), dim3(512), 0, 0, n_sub, d_desc, d_rec, d_bytes, d_res);
+    hipLaunchKernelGGL(encode_kernel_v7<4>, dim3(n_sub / 16), dim3(448), 0, 0, n_sub, d_desc, d_rec, d_bytes, d_res);
     (void)hipDeviceSynchronize();  // the bytes the decoder reads
     const double g = n_bins / 16.0;
     {
@@ -49,7 +49,7 @@ int main() {
       (void)hipFree(d_bins);
     }
     {  // the four-wave encoder (v6), same probes
-      unsigned long long z[16] = {};
+      unsigned long long z[32] = {};
       (void)hipMemcpyToSymbol(HIP_SYMBOL(g_v5_prof), z, sizeof(z));
       hipEvent_t c, d; (void)hipEventCreate(&c); (void)hipEventCreate(&d);
       (void)hipEventRecord(c);
@@ -62,18 +62,21 @@ int main() {
              vms, q[2] / g, q[3] / g, q[4] / g, q[6] / g, q[5] / g, q[1] / g, q[7] / g, q[0] / g, q[12] / g);
     }
     for (int uu = 0; uu < 2; uu++) {  // the lane-serial encoder (v7): U = 4 (16 substreams per workgroup) and U = 1
-      unsigned long long z[16] = {};
+      unsigned long long z[32] = {};
       (void)hipMemcpyToSymbol(HIP_SYMBOL(g_v5_prof), z, sizeof(z));
       hipEvent_t c, d; (void)hipEventCreate(&c); (void)hipEventCreate(&d);
       (void)hipEventRecord(c);
-      if (uu == 0) hipLaunchKernelGGL(encode_kernel_v7<4>, dim3(n_sub / 16), dim3(512), 0, 0, n_sub, d_desc, d_rec, d_bytes, d_res);
+      if (uu == 0) hipLaunchKernelGGL(encode_kernel_v7<4>, dim3(n_sub / 16), dim3(448), 0, 0, n_sub, d_desc, d_rec, d_bytes, d_res);
       else hipLaunchKernelGGL(encode_kernel_v7<1>, dim3(n_sub / 4), dim3(256), 0, 0, n_sub, d_desc, d_rec, d_bytes, d_res);
       (void)hipEventRecord(d); (void)hipDeviceSynchronize();
       float vms; (void)hipEventElapsedTime(&vms, c, d);
-      unsigned long long q[16];
+      unsigned long long q[32];
       (void)hipMemcpyFromSymbol(q, HIP_SYMBOL(g_v5_prof), sizeof(q));
       printf("v7<%d> kernel %.3f ms; ticks per step, workgroup 0: context busy %.0f barrier %.0f | chain busy %.0f barrier %.0f | low busy %.0f barrier %.0f | output busy %.0f barrier %.0f\n",
              uu == 0 ? 4 : 1, vms, q[0] / g, q[1] / g, q[2] / g, q[3] / g, q[4] / g, q[5] / g, q[6] / g, q[7] / g);
+      printf("v7<%d> SIMD of the waves of workgroup 0 (HW_ID bits 5..4), by wave number:", uu == 0 ? 4 : 1);
+      for (int w = 0; w < 8; w++) if (q[16 + w] >> 32) printf(" %u", (unsigned)((q[16 + w] >> 4) & 3u));
+      printf("\n");
     }
   }
   return 0;
