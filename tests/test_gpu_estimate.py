@@ -78,9 +78,11 @@ def test_estimate_golden(hip):
 
 
 def test_estimate_full_size_additivity(hip):
-    """C4-sized batch: the sum over substreams equals the oracle's on a sample, and a substream split in two
-    halves (the second started from fresh contexts) is NOT additive unless contexts carry over — checked the
-    other way: bypass-only strings cost exactly one bit per bin."""
+    """The first 512 substreams of the C4 workload at their full length (128 waves: the one-wave workgroups of
+    launch_estimate, not the four-wave form a whole C4 batch takes — tests/test_gpu_estimate_geometry.py runs that one):
+    the totals equal the oracle's on a sample, and a substream split in two halves (the second started from fresh
+    contexts) is NOT additive unless contexts carry over — checked the other way: bypass-only strings cost exactly one
+    bit per bin."""
     from entropy_coding_amd.workload import CONFIGS, build_batch
     desc, records, _ = build_batch(CONFIGS["C4"], first=0, count=512)
     got, flags = hip.estimate_batch(desc, records)
