@@ -131,6 +131,12 @@ EXPORTS_PROBE = [
     "cabac_hip_written_bits_device", "cabac_hip_estimate_probes_device", "cabac_hip_encode_residual_probes_device",
     "cabac_hip_written_bits_batch", "cabac_hip_estimate_probes_batch", "cabac_hip_encode_residual_probes_batch",
 ]
+# include/cabac_hip_pieces.h (the bin codec in pieces: the coder state handed from call to call; tests/test_pieces_abi.py compares)
+EXPORTS_PIECES = ["cabac_hip_encode_pieces_device", "cabac_hip_decode_pieces_device"]
+CODER_STATE_DTYPE = np.dtype([("kind", "<u4"), ("flags", "<u4"), ("bits", "<u4"), ("bytes_final", "<u4"), ("priv", "<u4", (4,))])  # cabac_coder_state
+assert CODER_STATE_DTYPE.itemsize == 32
+CODER_FRESH, CODER_ENC, CODER_DEC, CODER_CLOSED = 0, 1, 2, 3     # CABAC_CODER_*
+RES_BAD_STATE = 0x80                                             # CABAC_RES_BAD_STATE
 REC10_STATUS_DTYPE = np.dtype([("first_bad", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])   # cabac_rec10_status
 assert REC10_STATUS_DTYPE.itemsize == 16
 REC10_BAD_BITS, REC10_OVERFLOW = 1, 2                            # CABAC_REC10_*
@@ -319,6 +325,9 @@ def load_library():
                                                  vp, vp, vp]
         L.cabac_hip_decode_wpp_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp,
                                                  ctypes.c_uint32, vp, vp, vp]
+    if hasattr(L, "cabac_hip_encode_pieces_device"):   # (a library from before cabac_hip_pieces.h: the calls then fail where they are made)
+        L.cabac_hip_encode_pieces_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp] + sets7 + [vp, vp]
+        L.cabac_hip_decode_pieces_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp] + sets7 + [vp, vp]
     L.cabac_hip_residual_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_residual_parse_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_residual_parse_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, vp, vp]
@@ -807,6 +816,26 @@ class CabacHip:
         self._check(self.L.cabac_hip_decode_sets_device(self.h, n_sub, vp(d_desc), vp(d_records), vp(d_bytes), vp(d_bins),
                                                         vp(d_results), *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set,
                                                                                     d_out_state, d_out_rate)))
+
+    def encode_pieces_device(self, n_sub, d_desc, d_records, d_bytes, d_results, n_sets=0, d_state=0, d_rate=0, d_start_set=0,
+                             d_out_set=0, d_out_state=0, d_out_rate=0, d_coder_in=0, d_coder_out=0):
+        """One piece of every substream (include/cabac_hip_pieces.h): encode_sets_device continued from the coder states
+        d_coder_in (CODER_STATE_DTYPE per substream; 0: all fresh) and leaving them in d_coder_out (0: not written; may be
+        d_coder_in).  A descriptor without SUB_FINISH flushes nothing."""
+        self._check(self.L.cabac_hip_encode_pieces_device(self.h, n_sub, vp(d_desc), vp(d_records), vp(d_bytes), vp(d_results),
+                                                          *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state,
+                                                                       d_out_rate),
+                                                          vp(d_coder_in) if d_coder_in else None,
+                                                          vp(d_coder_out) if d_coder_out else None))
+
+    def decode_pieces_device(self, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, n_sets=0, d_state=0, d_rate=0, d_start_set=0,
+                             d_out_set=0, d_out_state=0, d_out_rate=0, d_coder_in=0, d_coder_out=0):
+        """decode_sets_device in pieces: the bins of this piece's records from the decoder states d_coder_in."""
+        self._check(self.L.cabac_hip_decode_pieces_device(self.h, n_sub, vp(d_desc), vp(d_records), vp(d_bytes), vp(d_bins),
+                                                          vp(d_results), *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set,
+                                                                                      d_out_state, d_out_rate),
+                                                          vp(d_coder_in) if d_coder_in else None,
+                                                          vp(d_coder_out) if d_coder_out else None))
 
     def ctx_advance_device(self, n_sub, d_desc, d_records, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate,
                            d_flags=0):

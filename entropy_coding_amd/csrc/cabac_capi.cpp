@@ -28,6 +28,7 @@
 
 #include "cabac_hip.h"
 #include "cabac_hip_ctx_sets.h"
+#include "cabac_hip_pieces.h"
 #include "cabac_hip_estimate.h"
 #include "cabac_hip_nal.h"
 #include "cabac_hip_parse_elements.h"
@@ -3356,6 +3357,34 @@ int cabac_hip_ctx_advance_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   DeviceGuard g(c->device);
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
   return TIMED_LAUNCH(c, 32, cabac::launch_ctx_advance(c->stream, n_sub, d_desc, d_records, sets, d_flags));
+}
+
+// ---- the bin codec in pieces (cabac_hip_pieces.h): not dispatched, one geometry each ----------------------------------------------
+int cabac_hip_encode_pieces_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                   uint8_t *d_bytes, cabac_substream_result *d_results, uint32_t n_sets, const uint32_t *d_state,
+                                   const uint8_t *d_rate, const uint32_t *d_start_set, const uint32_t *d_out_set, uint32_t *d_out_state,
+                                   uint8_t *d_out_rate, const cabac_coder_state *d_coder_in, cabac_coder_state *d_coder_out) {
+  if (!c || (n_sub && (!d_desc || !d_records || !d_bytes || !d_results)) ||
+      !sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  const cabac::CtxPieces pieces{{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate}, d_coder_in, d_coder_out};
+  return TIMED_LAUNCH(c, 48, cabac::launch_encode_pieces(c->stream, n_sub, d_desc, d_records, d_bytes, d_results, pieces));
+}
+
+int cabac_hip_decode_pieces_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
+                                   const uint8_t *d_bytes, uint8_t *d_bins, cabac_substream_result *d_results, uint32_t n_sets,
+                                   const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
+                                   const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate,
+                                   const cabac_coder_state *d_coder_in, cabac_coder_state *d_coder_out) {
+  if (!c || (n_sub && (!d_desc || !d_records || !d_bytes || !d_bins || !d_results)) ||
+      !sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  const cabac::CtxPieces pieces{{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate}, d_coder_in, d_coder_out};
+  return TIMED_LAUNCH(c, 49, cabac::launch_decode_pieces(c->stream, n_sub, d_desc, d_records, d_bytes, d_bins, d_results, pieces));
 }
 
 int cabac_hip_encode_wpp_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "cabac_hip.h"
+#include "cabac_hip_pieces.h"
 #include "cabac_hip_workspace.h"
 
 struct cabac_search_log_counters;  // cabac_hip_search_emit.h
@@ -26,6 +27,14 @@ struct CtxSets {
   const uint32_t *out_set;
   uint32_t *out_state;
   uint8_t *out_rate;
+};
+
+// The sets and the coder states of the pieces calls (cabac_hip_pieces.h): everything a kernel does with sets it does with the base,
+// everything about the coder state is in the overloads that take this type (cabac_quad.h).  coder_in null: all fresh; coder_out
+// null: no state written; they may be the same array.
+struct CtxPieces : CtxSets {
+  const cabac_coder_state *coder_in;
+  cabac_coder_state *coder_out;
 };
 
 hipError_t launch_ctx_init(hipStream_t st, uint32_t n_sub, const int32_t *qp, const uint32_t *init_id, uint32_t *state,
@@ -53,6 +62,12 @@ hipError_t launch_encode_v7(hipStream_t st, uint32_t n_sub, const cabac_substrea
 hipError_t launch_decode_v4(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
                             const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight = 0,
                             int lanes_per_sub = 16, uint32_t *select = nullptr, const CtxSets *sets = nullptr);
+
+// the bin codec in pieces (cabac_hip_pieces.h): one geometry each, not dispatched
+hipError_t launch_encode_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                uint8_t *bytes, cabac_substream_result *results, const CtxPieces &pieces);
+hipError_t launch_decode_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, const CtxPieces &pieces);
 
 // bit estimator (cabac_kernels_v4.hip)
 hipError_t launch_estimate(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,

@@ -210,12 +210,22 @@ __global__ __launch_bounds__(64) void encode_kernel_v4(uint32_t n_sub, const cab
                                                        const uint16_t *__restrict__ records, uint8_t *__restrict__ bytes,
                                                        cabac_substream_result *__restrict__ results, Sets... sets) {
   constexpr bool kSets = sizeof...(Sets) != 0;
+  constexpr bool kPieces = kQuadPieces<Sets...>;  // cabac_hip_pieces.h: the coder state comes from and goes to memory
   __shared__ uint32_t ctx[kQuadSubs * kQuadCtxStride];
   const uint32_t lane = threadIdx.x, row = lane >> 4, j = lane & 15u;
   const uint32_t sub = blockIdx.x * kQuadSubs + row;
   const QuadSetUse su = quad_set_use(sub, sub < n_sub, sets...);
-  const bool live = sub < n_sub && !su.bad;  // rows beyond the batch idle with n = 0
+  bool live = sub < n_sub && !su.bad;  // rows beyond the batch idle with n = 0
   const cabac_substream_desc d = desc[live ? sub : 0];
+  // (pieces: the state is checked here, where it is loaded; a row that is refused or comes with flags codes nothing and
+  // writes no set)
+  QuadPieceUse pu{};
+  QuadSetUse su_out = su;
+  if constexpr (kPieces) {
+    pu = quad_piece_use<true>(sub, sub < n_sub, su.bad, d.byte_capacity, sets...);
+    live = live && pu.code;
+    if (pu.refuse) su_out.out = kNoSet;
+  }
   const uint32_t n = live ? d.n_records : 0u;
   const uint16_t *rec = records + d.rec_offset;
   uint32_t *rctx = ctx + row * kQuadCtxStride;
@@ -230,6 +240,14 @@ __global__ __launch_bounds__(64) void encode_kernel_v4(uint32_t n_sub, const cab
   e.buf = 0;
   e.nbuf = 0;
   e.pos = 0;
+  if constexpr (kPieces) {  // checked by quad_piece_use: pend < 16, low inside its 10 + pend bits, pos + 2 nbuf <= the capacity
+    e.low = pu.low;
+    e.range = pu.range;
+    e.pend = (int32_t)pu.pend;
+    e.buf = pu.buf;
+    e.nbuf = (int32_t)pu.nbuf;
+    e.pos = pu.pos;
+  }
   e.dst = bytes + d.byte_offset;
   e.cap = live ? d.byte_capacity : 0u;
   const bool writer = live && j == 0;
@@ -251,6 +269,30 @@ __global__ __launch_bounds__(64) void encode_kernel_v4(uint32_t n_sub, const cab
     else quad_enc_steps<true, false>(f, e, writer, QuadPost());
   }
 
+  if constexpr (kPieces) {
+    // A piece without FINISH flushes nothing: every step has run its flush checks for all sixteen places, so pend < 16 here, and
+    // what is left — low, the buffered unit, the outstanding 0xFFFF units — is the state.  All of the buffered units will be
+    // written, so a slot they do not fit into overflows now, as it will in the end.
+    const CtxPieces &cp = quad_pack_first(sets...);
+    const bool fin = (d.init_id & CABAC_SUB_FINISH) != 0;
+    const uint32_t n_bits = live ? quad_enc_finish(e, (d.init_id & CABAC_SUB_ALIGN_RBSP) != 0, writer, !fin) : 0u;
+    const uint64_t bad_mask = __ballot(bad != 0);
+    const bool row_bad = ((bad_mask >> (row * 16u)) & 0xffffull) != 0;
+    if (writer) {
+      const uint32_t ends = fin ? e.pos : e.pos + 2u * (uint32_t)e.nbuf;
+      cabac_substream_result res;
+      res.n_bits = n_bits;
+      res.flags = (ends > e.cap ? CABAC_RES_OVERFLOW : 0u) | (row_bad ? CABAC_RES_BAD_RECORD : 0u);
+      results[sub] = res;
+      if (fin) quad_piece_store(cp, sub, CABAC_CODER_CLOSED, res.flags, n_bits, e.pos, 0u, 0u, 0u, 0u);
+      else quad_piece_store(cp, sub, CABAC_CODER_ENC, res.flags, n_bits, e.pos, (uint32_t)e.low, e.range | ((uint32_t)e.pend << 16), e.buf,
+                            (uint32_t)e.nbuf);
+    }
+    quad_piece_pass(results, sub, sub < n_sub && j == 0, pu, cp);
+    __syncthreads();
+    quad_ctx_export(rctx, j, 16u, su_out, sets...);
+    return;
+  }
   const uint32_t n_bits = live ? quad_enc_finish(e, (d.init_id & CABAC_SUB_ALIGN_RBSP) != 0, writer, (d.init_id & CABAC_SUB_PROBE) != 0) : 0u;
   const uint64_t bad_mask = __ballot(bad != 0);  // row-wide OR of the bad-record flag
   const bool row_bad = ((bad_mask >> (row * 16u)) & 0xffffull) != 0;
@@ -1516,9 +1558,20 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
   uint32_t *ctx = ctx_all + wave * (kSubs * kQuadCtxStride);
   const uint32_t lane = threadIdx.x & 63u, row = lane / L, j = lane % L;
   const uint32_t sub = (blockIdx.x * W + wave) * kSubs + row;
+  constexpr bool kPieces = kQuadPieces<Sets...>;  // cabac_hip_pieces.h: the coder state comes from and goes to memory
+  static_assert(!kPieces || L == 16, "the pieces call is the quad decoder's");
   const QuadSetUse su = quad_set_use(sub, sub < n_sub, sets...);
-  const bool live = sub < n_sub && !su.bad;
+  bool live = sub < n_sub && !su.bad;
   const cabac_substream_desc d = desc[live ? sub : 0];
+  // (pieces: the state is checked here, where it is loaded; a row that is refused or comes with flags codes nothing and
+  // writes no set)
+  QuadPieceUse pu{};
+  QuadSetUse su_out = su;
+  if constexpr (kPieces) {
+    pu = quad_piece_use<false>(sub, sub < n_sub, su.bad, d.byte_capacity, sets...);
+    live = live && pu.code;
+    if (pu.refuse) su_out.out = kNoSet;
+  }
   const uint32_t n = live ? d.n_records : 0u;
   const uint16_t *rec = records + d.rec_offset;
   uint8_t *out = bins + d.rec_offset;
@@ -1588,6 +1641,44 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
   w.used = 0;
   w.npos = ~63u;
   w.range = 510;
+  if constexpr (kPieces) {
+    // A row that continues: the state is range, the sixteen bits of the value and the shifts so far, S.  The look-ahead below the
+    // value is raw stream and is read again: the window is rebuilt with the value on top and stream bits S + 16 .. S + 62 below
+    // it, as a top-up leaves it (bit cursor S + 63), over the fresh start above, which a fresh row keeps (S = 0 restages the same
+    // three blocks).  The ring is staged from the 64-byte block that holds bit S + 16.  Plain code: this runs once.
+    // (A blend over the fresh start and two opaque reads, not a second prologue beside it: hipcc ends with "illegal VGPR to SGPR
+    // copy" for this kernel when the fresh window's words have no use left or the pair of ring dwords is read as one.)
+    const uint32_t resumed = pu.fresh ? 0u : ~0u;
+    const uint32_t shifts0 = pu.bits;
+    const uint32_t block0 = ((shifts0 + 16u) >> 3) & ~63u;
+    for (uint32_t blk = 0; blk < 3u; blk++) {
+      w.filled = block0 + 64u * blk;
+      w.npos = ~0u;
+      quad_dec_stage_load<L>(w, j);
+      w.pf_mask = ~0u;
+      quad_dec_stage_store(w);
+    }
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+    w.filled = block0 + 192u;
+    w.pf_mask = 0;
+    auto stream32 = [&](uint32_t bit) {  // stream bits bit .. bit + 31 out of the ring (the pair of dwords as quad_dec_topup reads it)
+      const uint32_t *p = w.ring + (63u - ((bit >> 5) & 63u));
+      return (uint32_t)(((((uint64_t)p[1]) << 32) | p[0]) << (bit & 31u) >> 32);
+    };
+    w.hi = sel(resumed, (pu.value << 15) | (stream32(shifts0 + 16u) >> 17), w.hi);
+    w.lo = sel(resumed, stream32(shifts0 + 31u), w.lo);
+    w.npos = ~(shifts0 + 63u);
+    const uint32_t *p = w.ring + ((w.npos >> 5) & 63u);
+    uint32_t q_lo = p[0];
+    asm volatile("" : "+v"(q_lo));
+    uint32_t q_hi = p[1];
+    asm volatile("" : "+v"(q_hi));
+    w.q_lo = q_lo;
+    w.q_hi = q_hi;
+    w.range = pu.range;
+  }
   uint32_t bad = 0;
 
   // Loop bound and loads without lane conditions: an exec region or a branch on a vector compare makes the
@@ -1784,6 +1875,23 @@ __global__ __launch_bounds__(64 * W) void decode_kernel_v4(uint32_t n_sub, const
     res.n_bits = 8u * bytes_read + (uint32_t)bits_needed;
     res.flags = flags;
     results[sub] = res;
+  }
+  if constexpr (kPieces) {
+    // the state behind the piece: the value field of the window (bits 62..47), range and the shifts; behind a terminate bin 1 the
+    // value stands at or above the scaled range (quad_dec_step: it is left untouched, and range may have been raised to 511)
+    const CtxPieces &cp = quad_pack_first(sets...);
+    if (live && j == 0) {
+      const uint32_t value = (w.hi >> 15) & 0xffffu;
+      const uint32_t mark = (value >= (w.range << 7) || w.range > 510u) ? 1u : 0u;
+      if (d.init_id & CABAC_SUB_FINISH) quad_piece_store(cp, sub, CABAC_CODER_CLOSED, flags, shifts, 0u, 0u, 0u, 0u, 0u);
+      else quad_piece_store(cp, sub, CABAC_CODER_DEC, flags, shifts, 0u, w.range, value, mark, 0u);
+    }
+    quad_piece_pass(results, sub, sub < n_sub && j == 0, pu, cp);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+    quad_ctx_export(rctx, j, (uint32_t)L, su_out, sets...);
+    return;
   }
   if constexpr (kSets) {
     // Every step ends with the store of its final states (all lanes of a context hold the same word, after a pairs step too:
@@ -2043,6 +2151,21 @@ hipError_t launch_encode_v4(hipStream_t st, uint32_t n_sub, const cabac_substrea
   const dim3 grid((n_sub + kQuadSubs - 1) / kQuadSubs);
   if (sets != nullptr) hipLaunchKernelGGL(encode_kernel_v4<CtxSets>, grid, dim3(64), 0, st, n_sub, desc, records, bytes, results, *sets);
   else hipLaunchKernelGGL(encode_kernel_v4<>, grid, dim3(64), 0, st, n_sub, desc, records, bytes, results);
+  return hipGetLastError();
+}
+
+// the pieces calls (cabac_hip_pieces.h): the coder state loaded, checked and stored by the same kernels, one geometry each
+hipError_t launch_encode_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                uint8_t *bytes, cabac_substream_result *results, const CtxPieces &pieces) {
+  hipLaunchKernelGGL(encode_kernel_v4<CtxPieces>, dim3((n_sub + kQuadSubs - 1) / kQuadSubs), dim3(64), 0, st, n_sub, desc, records, bytes,
+                     results, pieces);
+  return hipGetLastError();
+}
+
+hipError_t launch_decode_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, const CtxPieces &pieces) {
+  hipLaunchKernelGGL((decode_kernel_v4<4, 16, CtxPieces>), dim3((n_sub + 15u) / 16u), dim3(256), 0, st, n_sub, desc, records, bytes, bins,
+                     results, (const uint32_t *)nullptr, 0u, pieces);
   return hipGetLastError();
 }
 

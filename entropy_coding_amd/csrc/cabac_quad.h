@@ -3,6 +3,8 @@
 // row from Ctx::init or a context set.  Shared by the kernel files that walk bin records four substreams to a wave.
 #ifndef CABAC_QUAD_H
 #define CABAC_QUAD_H
+#include <type_traits>
+
 #include "cabac_device.h"
 #include "cabac_kernels.h"
 
@@ -359,6 +361,101 @@ __device__ __forceinline__ void quad_bad_set_result(cabac_substream_result *resu
     results[sub] = res;
   }
 }
+
+// ---- the coder state of the pieces calls (cabac_hip_pieces.h) -----------------------------------------------------
+// The pieces calls instantiate the in-wave kernels with one CtxPieces in the trailing pack: the sets overloads above take its
+// base, the functions below the coder state; the kernels call them under `if constexpr`, so that the other instantiations compile
+// to the code they had.  A state is data from memory: quad_piece_use checks every condition
+// the header lists before the kernel looks at any of its values.
+template <class... Sets>
+constexpr bool kQuadPieces = (std::is_base_of_v<CtxPieces, Sets> || ...);
+
+struct QuadPieceUse {
+  bool code;        // the row codes its records
+  bool refuse;      // CABAC_RES_BAD_STATE: nothing is written but the result
+  uint32_t sticky;  // the flags the state came with (and CABAC_RES_BAD_SET of this piece): not zero — the state is copied
+  // encode: low, range, pend, buf, nbuf, pos.  decode: range, value, fresh (the value is the first 16 bits of the stream), bits
+  uint32_t low, range, pend, buf, nbuf, pos, value, fresh, bits;
+};
+template <bool kEnc>
+__device__ __forceinline__ QuadPieceUse quad_piece_use(uint32_t sub, bool in_batch, bool bad_set, uint32_t cap, const CtxPieces &cp) {
+  QuadPieceUse u{};
+  u.range = 510u;  // start(), arith_codec.cpp:329-337 / :60-66
+  u.fresh = 1u;
+  uint32_t w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  if (in_batch && cp.coder_in != nullptr) {
+    const uint32_t *p = reinterpret_cast<const uint32_t *>(cp.coder_in + sub);
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = p[k];
+  }
+  const uint32_t kind = w[0];
+  u.refuse = in_batch && !bad_set && kind != CABAC_CODER_FRESH && kind != (kEnc ? CABAC_CODER_ENC : CABAC_CODER_DEC);
+  u.sticky = u.refuse ? 0u : (w[1] | (bad_set ? 0x40u : 0u));  // CABAC_RES_BAD_SET
+  if (in_batch && !u.refuse && u.sticky == 0u && kind != CABAC_CODER_FRESH) {
+    u.fresh = 0u;
+    u.bits = w[2];
+    if (kEnc) {
+      u.low = w[4];
+      u.range = w[5] & 0xffffu;
+      u.pend = w[5] >> 16;
+      u.buf = w[6];
+      u.nbuf = w[7];
+      u.pos = w[3];
+      const uint64_t held = 8ull * u.pos + 16ull * u.nbuf + u.pend;          // what getNumWrittenBits() answers
+      u.refuse = u.range < 256u || u.range > 510u || u.pend > 15u || u.low >= (1u << (10u + (u.pend & 15u))) || (u.pos & 1u) != 0u ||
+                 held != (uint64_t)u.bits || (uint64_t)u.pos + 2ull * u.nbuf > (uint64_t)cap;
+    } else {
+      u.range = w[4];
+      u.value = w[5];
+      const uint32_t mark = w[6];  // 1: behind a terminate bin 1, where value may stand at or above the scaled range
+      u.refuse = mark > 1u || u.range < 256u || u.range > 510u + mark || u.value >= ((u.range + 2u * mark) << 7);
+    }
+  }
+  u.code = in_batch && !u.refuse && u.sticky == 0u;
+  if (!u.code) {  // a refused state's values reach nothing: the row idles as a fresh, empty one
+    u.low = u.pend = u.buf = u.nbuf = u.pos = u.value = u.bits = 0u;
+    u.range = 510u;
+    u.fresh = 1u;
+  }
+  return u;
+}
+// What a row that does not code leaves: {0, CABAC_RES_BAD_STATE} and nothing else, or {0, flags} and a copy of the state (read
+// again here: in place it is this row's own, and nobody else writes it).  first_lane: lane 0 of a row inside the batch.
+__device__ __forceinline__ void quad_piece_pass(cabac_substream_result *results, uint32_t sub, bool first_lane, const QuadPieceUse &u,
+                                                const CtxPieces &cp) {
+  if (!first_lane || u.code) return;
+  cabac_substream_result res;
+  res.n_bits = 0u;
+  res.flags = u.refuse ? 0x80u : u.sticky;  // CABAC_RES_BAD_STATE
+  results[sub] = res;
+  if (u.refuse || cp.coder_out == nullptr) return;
+  uint32_t w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  if (cp.coder_in != nullptr) {
+    const uint32_t *p = reinterpret_cast<const uint32_t *>(cp.coder_in + sub);
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = p[k];
+  }
+  w[1] = u.sticky;
+  uint32_t *q = reinterpret_cast<uint32_t *>(cp.coder_out + sub);
+#pragma unroll
+  for (int k = 0; k < 8; k++) q[k] = w[k];
+}
+// the state behind a coded piece, from the row's first lane (plain vector stores)
+__device__ __forceinline__ void quad_piece_store(const CtxPieces &cp, uint32_t sub, uint32_t kind, uint32_t flags, uint32_t bits,
+                                                 uint32_t bytes_final, uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3) {
+  if (cp.coder_out == nullptr) return;
+  uint32_t *q = reinterpret_cast<uint32_t *>(cp.coder_out + sub);
+  q[0] = kind;
+  q[1] = flags;
+  q[2] = bits;
+  q[3] = bytes_final;
+  q[4] = p0;
+  q[5] = p1;
+  q[6] = p2;
+  q[7] = p3;
+}
+template <class T, class... Rest>
+__device__ __forceinline__ const T &quad_pack_first(const T &first, const Rest &...) { return first; }
 
 // ---- probe points (cabac_hip_probe.h) ---------------------------------------------------------------------------
 // A row's cursor into its list: the next probe, the end of the list, and the clipped position of that next probe in a register
