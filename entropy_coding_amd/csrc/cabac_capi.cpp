@@ -35,6 +35,7 @@
 #include "cabac_hip_parse_plan.h"
 #include "cabac_hip_parse_unit.h"
 #include "cabac_hip_plan_rows.h"
+#include "cabac_hip_plan_resume.h"
 #include "cabac_hip_probe.h"
 #include "cabac_hip_rec10.h"
 #include "cabac_hip_search.h"
@@ -3491,6 +3492,26 @@ int cabac_hip_plan_parse_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cab
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
   return TIMED_LAUNCH(c, 34, cabac::launch_plan_parse_sets(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
                                                            coeff_bytes, d_values, d_tu_info, d_results, sets, d_out_at, n_sets, 0xFFFFFFFFu));
+}
+
+// ---- the plan parse in pieces (cabac_hip_plan_resume.h): the sets form's checks, one coder state per substream in and out --------
+int cabac_hip_plan_resume_parse_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
+                                       const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
+                                       const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
+                                       uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results, uint32_t n_sets,
+                                       const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
+                                       const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate, const void *d_coder_in,
+                                       void *d_coder_out) {
+  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results)) ||
+      !sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  const cabac::CtxPieces pieces{{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate},
+                                static_cast<const cabac_coder_state *>(d_coder_in), static_cast<cabac_coder_state *>(d_coder_out)};
+  return TIMED_LAUNCH(c, 50, cabac::launch_plan_parse_pieces(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan,
+                                                             d_coeff, coeff_bytes, d_values, d_tu_info, d_results, pieces));
 }
 
 int cabac_hip_plan_parse_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,

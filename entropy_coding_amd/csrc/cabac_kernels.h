@@ -240,6 +240,11 @@ hipError_t launch_plan_parse_sets(hipStream_t st, uint32_t n_sub, const cabac_su
                                   const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
                                   cabac_substream_result *results, const CtxSets &sets, const uint32_t *out_at, uint32_t start_bound,
                                   uint32_t slot_base);
+// the plan walk in pieces (cabac_hip_plan_resume.h): the sets form (out set behind the piece) from and into a coder state per substream
+hipError_t launch_plan_parse_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                    const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
+                                    const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
+                                    cabac_substream_result *results, const CtxPieces &pieces);
 
 // residual records spliced into host-recorded substreams (cabac_splice.hip); array sizes: pre n_splice + n_sub + 1,
 // sub_n / sub_cap / rec_base / byte_base n_sub, seen n_tu, err 1, totals 3 ({records, bytes, error})

@@ -40,6 +40,7 @@
 #include "cabac_hip_parse_elements.h"
 #include "cabac_hip_parse_plan.h"
 #include "cabac_kernels.h"
+#include "cabac_quad.h"
 #include "cabac_scan.h"
 
 namespace cabac {
@@ -783,6 +784,43 @@ __device__ __forceinline__ void parse_ctx_export(const uint4 *ctx, uint32_t lane
   }
 }
 
+// Pieces (cabac_hip_plan_resume.h): the plan walk from and into the sets AND from and into a coder state per substream — the
+// CABAC_CODER_DEC state of cabac_hip_pieces.h as cabac_hip_decode_pieces_device writes it: bits = S, the shifts so far; priv =
+// range | the value field of the window (bits 62..47) | mark | 0.  One ParsePieces in the pack; everything about the state is
+// in the functions below and behind `if constexpr (kPieces)` in the walk, so that the other instantiations keep their code.
+//  * LOAD: quad_piece_use<false> (cabac_quad.h) checks what the header lists, and one thing more: a state without flags stands
+//    inside its slot (2 + (S >> 3) <= byte_capacity; beyond it the underrun would have been flagged, and that flag is sticky).
+//    A substream that is refused, or comes with flags, leaves before anything depends on the state's values.
+//  * RESUME (in the walk, behind the fresh start, which a fresh state keeps): the look-ahead below the value is raw stream and is
+//    read again.  Stream bit S + 16 is the first look-ahead bit; it lies in 16-bit unit u = (S >> 4) + 1, of which the low
+//    16 - (S & 15) bits are still ahead: that is `look`, and rp = 2 u + 2 (8 rp - 16 - look = S).  The unit is fetched with a block
+//    load of its own: where rp is a multiple of 256 it is the last unit of the block in front of in_cur.
+//  * EXPORT: behind a terminate bin 1 pd_trm leaves range - 2 unrenormalised (254 .. 508) and the value at or above it.  The
+//    state is then written marked, with bit 8 of the range set as the bin decoder keeps it (254 / 255 -> 510 / 511, which no
+//    other range of a marked state gives: the load takes it back), value < (range + 2) << 7.  Nothing but finish() may follow.
+struct ParsePieces : ParseSets {
+  const cabac_coder_state *coder_in;
+  cabac_coder_state *coder_out;
+};
+template <class... Sets>
+constexpr bool kParsePieces = (std::is_base_of_v<ParsePieces, Sets> || ...);
+__device__ __forceinline__ QuadPieceUse parse_piece_use(uint32_t sub, bool live, bool bad_set, uint32_t cap, const ParsePieces &pp) {
+  const CtxPieces cp{pp.cs, pp.coder_in, pp.coder_out};
+  QuadPieceUse u = quad_piece_use<false>(sub, live, bad_set, cap, cp);
+  if (u.code && !u.fresh && (uint64_t)2u + (u.bits >> 3) > (uint64_t)cap) {  // no flagless decoder stands outside its slot
+    u.code = false;
+    u.refuse = true;
+  }
+  // a marked state (mark is 0 or 1 here) of range 510 / 511 is pd_trm's 254 / 255: range - 2 behind a terminate bin 1
+  if (u.code && !u.fresh && pp.coder_in[sub].priv[2] != 0u && u.range >= 510u) u.range -= 256u;
+  return u;
+}
+__device__ __forceinline__ void parse_piece_pass(cabac_substream_result *results, uint32_t sub, bool first_lane, const QuadPieceUse &u,
+                                                 const ParsePieces &pp) {
+  quad_piece_pass(results, sub, first_lane, u, CtxPieces{pp.cs, pp.coder_in, pp.coder_out});
+}
+__device__ __forceinline__ cabac_coder_state *parse_piece_out(const ParsePieces &pp) { return pp.coder_out; }
+
 template <int W, class C, int kSide, class... Sets>
 __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
                                            const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ tile_first,
@@ -822,6 +860,13 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
   int32_t *blk = blk_all + wave * kBlkWords;
   const cabac_substream_desc dsc = desc[live ? sub : 0];
   [[maybe_unused]] const ParseSetUse su = parse_set_use(sub, live, sets...);
+  constexpr bool kPieces = kParsePieces<Sets...>;
+  [[maybe_unused]] QuadPieceUse pu{};                       // the coder state the substream continues from, checked here
+  [[maybe_unused]] cabac_coder_state *piece_out = nullptr;  // where the state behind the piece goes
+  if constexpr (kPieces) {
+    pu = parse_piece_use(sub, live, su.bad, dsc.byte_capacity, sets...);
+    piece_out = parse_piece_out(sets...);
+  }
   {
     const int qp = dsc.qp < 0 ? 0 : (dsc.qp > 63 ? 63 : dsc.qp);
     const uint32_t iid = dsc.init_id & 3u;
@@ -841,6 +886,14 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
   }
   __syncthreads();
   if (!live) return;
+  if constexpr (kPieces) {
+    // a state that is refused: {0, CABAC_RES_BAD_STATE} and nothing else; one that comes with flags, or a bad set index of this
+    // piece: {0, flags} and the state copied.  No value, coefficient, info word or set either way.
+    if (rfl(pu.code ? 1u : 0u) == 0u) {
+      parse_piece_pass(results, sub, lane == 0u, pu, sets...);
+      return;
+    }
+  }
   if constexpr (kSets) {
     if (su.bad) {  // a start or out index beyond the sets: nothing is parsed, nothing is written but the result
       if (lane == 0u) {
@@ -878,10 +931,29 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
   d.look = 16;
   d.rp = 4u;
   d.range = 510u;
+  [[maybe_unused]] bool resumed = false;
+  if constexpr (kPieces) {
+    resumed = rfl(pu.fresh) == 0u;
+    if (resumed) {  // the window of a decoder that has shifted S bits (ParsePieces, above).  Plain code: this runs once.
+      const uint32_t s0 = rfl(pu.bits), value = rfl(pu.value), range = rfl(pu.range);
+      const uint32_t at = 2u * ((s0 >> 4) + 1u);           // byte offset of the unit that holds stream bit S + 16
+      const uint32_t dw = rl(pd_load_block(d, at >> 8), (at >> 2) & 63u);
+      const uint32_t unit = (at & 2u) ? (dw & 0xffffu) : (dw >> 16);
+      const uint32_t look = 16u - (s0 & 15u);              // 1 .. 16 bits of it are still ahead
+      const uint64_t win = ((uint64_t)value << 47) | ((uint64_t)(unit & (0xffffu >> (16u - look))) << (47u - look));
+      d.hi = (uint32_t)(win >> 32);
+      d.lo = (uint32_t)win;
+      d.look = (int32_t)look;
+      d.rp = at + 2u;
+      d.in_cur = pd_load_block(d, d.rp >> 8);
+      d.in_nxt = pd_load_block(d, (d.rp >> 8) + 1u);
+      d.range = range;
+    }
+  }
   // A substream that begins with the byte 0xFF is not one the arithmetic coder wrote: its first nine bits are the coder's
   // value, which is below the initial range 510.  Decoding it would leave value >= range << 7, a state in which the
   // reference's arithmetic and this one's part ways, so it is refused as a whole: no block is parsed, BAD_STOP.
-  const bool bad_start = d.cap >= 2u && (rl(d.in_cur, 0u) >> 24) == 0xffu;
+  const bool bad_start = !resumed && d.cap >= 2u && (rl(d.in_cur, 0u) >> 24) == 0xffu;
   uint32_t flags_out = bad_start ? CABAC_RES_BAD_STOP : 0u;
 
   const uint32_t t_end = bad_start ? tile_first[sub] : tile_first[sub + 1];
@@ -1207,6 +1279,24 @@ __device__ __forceinline__ void parse_walk(uint32_t n_sub, const cabac_substream
     r.flags = flags_out;
     results[sub] = r;
   }
+  if constexpr (kPieces) {
+    // the state behind the piece (ParsePieces, above): eight plain vector stores from lane 0.  CABAC_RES_RANGE is the piece's
+    // own and is not kept; every other flag is sticky (BAD_STOP can only be the refused 0xFF start here, or the last piece's).
+    if (lane == 0u && piece_out != nullptr) {
+      const uint32_t range = rfl(d.range), value = (rfl(d.hi) >> 15) & 0xffffu;
+      const uint32_t mark = (range < 256u || value >= (range << 7)) ? 1u : 0u;
+      const bool closed = (dsc.init_id & CABAC_SUB_FINISH) != 0u;
+      uint32_t *q = reinterpret_cast<uint32_t *>(piece_out + sub);
+      q[0] = closed ? CABAC_CODER_CLOSED : CABAC_CODER_DEC;
+      q[1] = flags_out & ~(uint32_t)CABAC_RES_RANGE;
+      q[2] = shifts;
+      q[3] = 0u;
+      q[4] = closed ? 0u : (range | 256u);
+      q[5] = closed ? 0u : value;
+      q[6] = closed ? 0u : mark;
+      q[7] = 0u;
+    }
+  }
   };
   if (scalar_wave) walk(std::true_type{});
   else walk(std::false_type{});
@@ -1272,6 +1362,21 @@ __global__ __launch_bounds__(64 * W) void plan_parse_sets_kernel(uint32_t n_sub,
   __shared__ uint32_t info_all[W * 17];
   parse_walk<W, C, 3>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, tu_at, nullptr, nullptr, tu_guard, plan, values,
                       ring_all + 256u * (threadIdx.x >> 6), info_all + 17u * (threadIdx.x >> 6), ps);
+}
+
+// the plan walk in pieces (cabac_hip_plan_resume.h): the sets form with a coder state per substream in and out
+template <int W, class C>
+__global__ __launch_bounds__(64 * W) void plan_parse_pieces_kernel(uint32_t n_sub, const cabac_substream_desc *__restrict__ desc,
+                                                                     const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ tile_first,
+                                                                     const cabac_tu_desc *__restrict__ tus, const uint32_t *__restrict__ tu_at,
+                                                                     const uint32_t *__restrict__ tu_guard, const uint32_t *__restrict__ plan,
+                                                                     C *__restrict__ coeff_all, uint32_t *__restrict__ values,
+                                                                     uint32_t *__restrict__ tu_info, cabac_substream_result *__restrict__ results,
+                                                                     ParsePieces pp) {
+  __shared__ uint32_t ring_all[W * 256];
+  __shared__ uint32_t info_all[W * 17];
+  parse_walk<W, C, 3>(n_sub, desc, bytes, tile_first, tus, coeff_all, tu_info, results, tu_at, nullptr, nullptr, tu_guard, plan, values,
+                      ring_all + 256u * (threadIdx.x >> 6), info_all + 17u * (threadIdx.x >> 6), pp);
 }
 
 #ifdef CABAC_PARSE_PROFILE
@@ -1407,6 +1512,40 @@ hipError_t launch_plan_parse_sets(hipStream_t st, uint32_t n_sub, const cabac_su
     return launch_plan_parse_sets_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results, ps);
   if (coeff_bytes == 4)
     return launch_plan_parse_sets_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results, ps);
+  return hipErrorInvalidValue;
+}
+
+template <class C>
+static hipError_t launch_plan_parse_pieces_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                              const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
+                                              const uint32_t *tu_guard, const uint32_t *plan, C *coeff, uint32_t *values,
+                                              uint32_t *tu_info, cabac_substream_result *results, const ParsePieces &pp) {
+  // the parser's geometry and threshold
+  if (n_sub >= 1024u)
+    hipLaunchKernelGGL((plan_parse_pieces_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus,
+                       tu_at, tu_guard, plan, coeff, values, tu_info, results, pp);
+  else
+    hipLaunchKernelGGL((plan_parse_pieces_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at,
+                       tu_guard, plan, coeff, values, tu_info, results, pp);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_parse_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
+                                    const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
+                                    const uint32_t *plan, void *coeff, int coeff_bytes, uint32_t *values, uint32_t *tu_info,
+                                    cabac_substream_result *results, const CtxPieces &pieces) {
+  if (n_sub == 0) return hipSuccess;
+  ParsePieces pp;  // the out set is behind the piece, always: no hand-over entry; start indices below n_sets; out sets as out_set says
+  pp.cs = pieces;
+  pp.out_at = nullptr;
+  pp.start_bound = pieces.n_sets;
+  pp.slot_base = 0xffffffffu;
+  pp.coder_in = pieces.coder_in;
+  pp.coder_out = pieces.coder_out;
+  if (coeff_bytes == 2)
+    return launch_plan_parse_pieces_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results, pp);
+  if (coeff_bytes == 4)
+    return launch_plan_parse_pieces_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results, pp);
   return hipErrorInvalidValue;
 }
 
