@@ -139,6 +139,8 @@ CODER_FRESH, CODER_ENC, CODER_DEC, CODER_CLOSED = 0, 1, 2, 3     # CABAC_CODER_*
 RES_BAD_STATE = 0x80                                             # CABAC_RES_BAD_STATE
 # include/cabac_hip_plan_resume.h (the plan parse in pieces: resumed from a coder state; tests/test_plan_resume_abi.py compares)
 EXPORTS_PLAN_RESUME = ["cabac_hip_plan_resume_parse_device"]
+# include/cabac_hip_plan_continue.h (the plan write in pieces: continued from a coder state; tests/test_plan_continue_abi.py compares)
+EXPORTS_PLAN_CONTINUE = ["cabac_hip_plan_continue_write_device"]
 REC10_STATUS_DTYPE = np.dtype([("first_bad", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])   # cabac_rec10_status
 assert REC10_STATUS_DTYPE.itemsize == 16
 REC10_BAD_BITS, REC10_OVERFLOW = 1, 2                            # CABAC_REC10_*
@@ -399,6 +401,10 @@ def load_library():
     # (... or from before cabac_hip_plan_resume.h — tools/bench_plan_resume.py --label parent)
     if hasattr(L, "cabac_hip_plan_resume_parse_device"):
         L.cabac_hip_plan_resume_parse_device.argtypes = L.cabac_hip_parse_plan_device.argtypes + sets7 + [vp, vp]
+    # (... or from before cabac_hip_plan_continue.h — tools/bench_plan_continue.py --label parent)
+    if hasattr(L, "cabac_hip_plan_continue_write_device"):
+        L.cabac_hip_plan_continue_write_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_int,
+                                                           vp, vp, vp, vp] + sets7 + [vp, vp]
     L.cabac_hip_resolve_plan_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_int, vp, vp,
                                                 ctypes.c_uint64, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_search_plan_round_device.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, ctypes.c_int] + \
@@ -1375,6 +1381,19 @@ class CabacHip:
             self.h, n_sub, vp(d_desc), _opt(d_plan), _opt(d_values_in), vp(d_tile_first), n_tu, _opt(d_tu), _opt(d_tu_at), _opt(d_tu_guard),
             _opt(d_coeff), 2 if int16 else 4, vp(d_payload), payload_capacity, vp(d_payload_offsets), vp(d_results), _opt(d_values_out),
             _opt(d_tu_info), *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate)))
+
+    # ---- the plan write in pieces (include/cabac_hip_plan_continue.h) ------
+    def plan_continue_write_device(self, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff,
+                                   d_bytes, d_results, d_values_out=0, d_tu_info=0, int16=False, n_sets=0, d_state=0, d_rate=0,
+                                   d_start_set=0, d_out_set=0, d_out_state=0, d_out_rate=0, d_coder_in=0, d_coder_out=0):
+        """One piece of every substream's plan: plan_write_sets_device into the caller's slots (d_bytes + the descriptor's
+        byte_offset, byte_capacity bytes) continued from the coder states d_coder_in (CODER_STATE_DTYPE per substream; 0: all
+        fresh) and leaving them in d_coder_out (0: not written; may be d_coder_in).  A descriptor without SUB_FINISH flushes
+        nothing."""
+        self._check(self.L.cabac_hip_plan_continue_write_device(
+            self.h, n_sub, vp(d_desc), _opt(d_plan), _opt(d_values_in), vp(d_tile_first), n_tu, _opt(d_tu), _opt(d_tu_at), _opt(d_tu_guard),
+            _opt(d_coeff), 2 if int16 else 4, vp(d_bytes), vp(d_results), _opt(d_values_out), _opt(d_tu_info),
+            *self._sets7(n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate), _opt(d_coder_in), _opt(d_coder_out)))
 
     def plan_write_rows_device(self, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff,
                                d_payload, payload_capacity, d_payload_offsets, d_results, level_first, d_sync_from, d_sync_at,

@@ -35,6 +35,7 @@
 #include "cabac_hip_parse_plan.h"
 #include "cabac_hip_parse_unit.h"
 #include "cabac_hip_plan_rows.h"
+#include "cabac_hip_plan_continue.h"
 #include "cabac_hip_plan_resume.h"
 #include "cabac_hip_probe.h"
 #include "cabac_hip_rec10.h"
@@ -3546,6 +3547,83 @@ int cabac_hip_plan_write_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cab
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
   return write_plan_device_impl(c, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, coeff_bytes,
                                 d_payload, payload_capacity, d_payload_offsets, d_results, d_values_out, d_tu_info, &sets, nullptr);
+}
+
+// ---- the plan write in pieces (cabac_hip_plan_continue.h): the plan write's two walks over one piece of every substream's plan,
+// the encoder in pieces on the expanded records into the caller's slots, the stops.  One wait: the expanded length sizes the
+// record scratch.  Not a call of the fixed workspace.
+int cabac_hip_plan_continue_write_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,
+                                         const uint32_t *d_values_in, const uint32_t *d_tile_first, uint32_t n_tu,
+                                         const cabac_tu_desc *d_tu, const uint32_t *d_tu_at, const uint32_t *d_tu_guard,
+                                         const void *d_coeff, int coeff_bytes, uint8_t *d_bytes, cabac_substream_result *d_results,
+                                         uint32_t *d_values_out, uint32_t *d_tu_info, uint32_t n_sets, const uint32_t *d_state,
+                                         const uint8_t *d_rate, const uint32_t *d_start_set, const uint32_t *d_out_set,
+                                         uint32_t *d_out_state, uint8_t *d_out_rate, const void *d_coder_in, void *d_coder_out) {
+  if (!c || (n_sub && (!d_desc || !d_tile_first || !d_bytes || !d_results)) || (n_tu && (!d_tu || !d_coeff)) ||
+      !sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
+    return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0 && n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "blocks without a substream");
+  if (c->ws_fixed)
+    return fail(c, CABAC_HIP_ERR_INVALID, "the workspace is fixed: the plan write in pieces waits for its sizes; call cabac_hip_workspace_release first");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  int rc;
+  const size_t n_blk = n_tu ? n_tu : 1, n_s = n_sub;
+  const size_t words = (3 * n_s + 2 + 1) & ~size_t(1);  // sub_n, sub_cap, sub_flag, err (+ pad)
+  if ((rc = ensure(c, kRowsWords, 2 * n_s * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kSpCnt, 2 * n_blk * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kResidualScratch, cabac::residual_scratch_bytes(n_tu)))) return rc;
+  if ((rc = ensure(c, kPwPlan, words * sizeof(uint32_t) + (2 * n_s + 3) * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kPwTu, n_blk * sizeof(cabac_tu_desc)))) return rc;
+  if ((rc = ensure(c, kSpDesc, n_s * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kSpTuOff, n_blk * sizeof(uint64_t)))) return rc;
+  if (!c->h_totals) HIP_TRY(c, pinned_alloc(c, &c->h_totals, 64, hipHostMallocDefault));
+  uint32_t *out_live = static_cast<uint32_t *>(c->d_buf[kRowsWords]);  // the out sets of the pieces that are coded
+  uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kSpCnt]), *d_info = d_cnt + n_blk;
+  uint32_t *sub_n = static_cast<uint32_t *>(c->d_buf[kPwPlan]), *sub_cap = sub_n + n_s, *sub_flag = sub_cap + n_s, *err = sub_flag + n_s;
+  uint64_t *rec_base = reinterpret_cast<uint64_t *>(sub_n + words), *byte_base = rec_base + n_s, *totals = byte_base + n_s;
+  auto *desc2 = static_cast<cabac_substream_desc *>(c->d_buf[kSpDesc]);
+  auto *tus2 = static_cast<cabac_tu_desc *>(c->d_buf[kPwTu]);
+  auto *tu_off = static_cast<uint64_t *>(c->d_buf[kSpTuOff]);
+  const cabac::PlanWriteIn in{d_desc, d_plan, d_values_in, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_cnt, d_info};
+  cabac::CtxPieces pieces{{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate},
+                          static_cast<const cabac_coder_state *>(d_coder_in), static_cast<cabac_coder_state *>(d_coder_out)};
+  c->timed = false;
+  {  // sizes and info words of ALL blocks of the pieces
+    Timed t(c, 5);
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[kResidualScratch]));
+  }
+  {
+    Timed t(c, 28);
+    HIP_TRY(c, cabac::launch_plan_resolve_pieces(c->stream, n_sub, in, pieces, sub_n, sub_cap, sub_flag, err));
+    HIP_TRY(c, cabac::launch_splice_scan(c->stream, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals, nullptr));
+  }
+  uint64_t *h_tot = static_cast<uint64_t *>(c->h_totals);
+  HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));  // the one wait: the expanded length decides the record scratch
+  if (h_tot[2]) return fail(c, CABAC_HIP_ERR_INVALID, "a piece outgrows 32 bits of records");
+  if ((rc = ensure(c, kSpRec, (h_tot[0] + 64) * sizeof(uint16_t)))) return rc;
+  auto *exp_rec = static_cast<uint16_t *>(c->d_buf[kSpRec]);
+  {
+    Timed t(c, 28);
+    HIP_TRY(c, cabac::launch_plan_emit_pieces(c->stream, n_sub, in, sub_n, sub_flag, rec_base, desc2, tus2, tu_off, exp_rec, d_values_out,
+                                              d_tu_info));
+    if (d_out_set) {  // a piece that is not coded writes no set
+      HIP_TRY(c, cabac::launch_plan_out_sets(c->stream, n_sub, sub_flag, d_out_set, out_live));
+      pieces.out_set = out_live;
+    }
+  }
+  {  // block records of the coded blocks, straight into the expanded pieces
+    Timed t(c, 5);
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, tus2, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[kResidualScratch]));
+  }
+  {
+    Timed t(c, 51);
+    HIP_TRY(c, cabac::launch_encode_pieces(c->stream, n_sub, desc2, exp_rec, d_bytes, d_results, pieces));
+    HIP_TRY(c, cabac::launch_plan_stops_pieces(c->stream, n_sub, sub_flag, d_results, pieces.coder_out));
+  }
+  return CABAC_HIP_OK;
 }
 
 int cabac_hip_plan_write_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,

@@ -302,6 +302,16 @@ hipError_t launch_plan_emit(hipStream_t st, uint32_t n_sub, const PlanWriteIn &i
 hipError_t launch_plan_out_sets(hipStream_t st, uint32_t n_sub, const uint32_t *sub_flag, const uint32_t *out_set, uint32_t *out_set_live);
 // a stopped substream codes nothing: results[s] = {0, sub_flag[s]} where sub_flag[s] != 0
 hipError_t launch_plan_stops(hipStream_t st, uint32_t n_sub, const uint32_t *sub_flag, cabac_substream_result *results);
+// the plan write in pieces (cabac_hip_plan_continue.h), n_sub > 0: the two walks over one piece of every substream's plan — the first
+// also checks the coder states of `cp` (sub_flag: 0, the stop, or 0x80000000 for a state that is refused or comes with flags), the
+// second writes the encode descriptors with the caller's slots — and the stops behind launch_encode_pieces
+hipError_t launch_plan_resolve_pieces(hipStream_t st, uint32_t n_sub, const PlanWriteIn &in, const CtxPieces &cp, uint32_t *sub_n,
+                                      uint32_t *sub_cap, uint32_t *sub_flag, uint32_t *err);
+hipError_t launch_plan_emit_pieces(hipStream_t st, uint32_t n_sub, const PlanWriteIn &in, const uint32_t *sub_n, const uint32_t *sub_flag,
+                                   const uint64_t *rec_base, cabac_substream_desc *desc_out, cabac_tu_desc *tus_out, uint64_t *tu_offset,
+                                   uint16_t *records, uint32_t *values_out, uint32_t *tu_info_out);
+hipError_t launch_plan_stops_pieces(hipStream_t st, uint32_t n_sub, const uint32_t *sub_flag, cabac_substream_result *results,
+                                    cabac_coder_state *coder_out);
 
 // the plan resolve of the search rounds (cabac_plan_search.hip; cabac_hip_search_plan.h): the same walk, one candidate per unit,
 // into the unit-candidate form.  What both walks read: candidate c owns the entries [ent_first[c], ent_first[c+1]) of plan /

@@ -13,6 +13,11 @@
 // The rows form (cabac_hip_plan_rows.h) runs plan_emit_rows_kernel in place of plan_emit_kernel: the same walk, which also notes
 // where in its expanded run each substream's hand-over entry lies; the WPP encode schedule takes that as its sync_at.
 //
+// The form in pieces (cabac_hip_plan_continue.h) runs plan_resolve_pieces_kernel and plan_emit_pieces_kernel: the same walk over one
+// piece of every substream's plan.  Its first walk also loads and checks the substream's coder state (cabac_quad.h), its second one
+// writes the encode descriptor with the CALLER'S slot; the encoder in pieces codes the expanded records into that slot, and
+// plan_stops_pieces_kernel gives a stopped piece its result and its flag.  No scan of byte sizes, no assembly.
+//
 // The walk itself is cabac_plan_walk.h's, one wave per substream; this file says where a substream's plan lies and where its
 // results go (one atomicOr reports a substream that outgrows 32 bits).
 #include <hip/hip_runtime.h>
@@ -23,6 +28,7 @@
 #include "cabac_hip_parse_plan.h"
 #include "cabac_kernels.h"
 #include "cabac_plan_walk.h"
+#include "cabac_quad.h"
 
 namespace cabac {
 
@@ -107,6 +113,45 @@ struct PwRowsIo : PwIo {
   __device__ __forceinline__ void emit_sync(uint32_t sub, uint64_t off) const { sync_rec[sub] = (uint32_t)off; }
 };
 
+// the form in pieces (cabac_hip_plan_continue.h): the same unit, coded into the caller's slot from a coder state.  sub_flag says
+// what becomes of the piece: 0 it is walked and coded; CABAC_RES_BAD_RECORD / CABAC_RES_BAD_VALUE its walk stops; kPcPass its
+// state is refused or comes with flags, so that the encoder in pieces answers for it and nothing else of it is written.
+constexpr uint32_t kPcPass = 0x80000000u;
+
+struct PcIo : PwIo {
+  CtxPieces cp;
+  __device__ __forceinline__ void count_end(uint32_t sub, bool bad_rec, bool bad_val, uint64_t off) const {
+    // the state is data from memory: checked here, where it is loaded, before the second walk writes anything.  (A bad set index
+    // is the encoder's to report: the walk writes what the one-call form writes for such a substream.)
+    const QuadPieceUse pu = quad_piece_use<true>(sub, true, false, desc[sub].byte_capacity, cp);
+    const uint32_t flag = !pu.code ? kPcPass : bad_rec ? CABAC_RES_BAD_RECORD : bad_val ? CABAC_RES_BAD_VALUE : 0u;
+    const uint64_t expanded = flag ? 0u : off;
+    if (expanded > 0xfffffff0ull) atomicOr(err, 1u);
+    sub_flag[sub] = flag;
+    sub_n[sub] = (uint32_t)expanded;
+    sub_cap[sub] = 0u;  // (the slot is the caller's)
+  }
+  __device__ __forceinline__ bool emit_begin(uint32_t sub, const PlanWalkUnit &u, uint32_t lane, uint64_t &base) const {
+    base = out.rec_base[sub];
+    const uint32_t flag = out.sub_flag[sub];
+    if (lane == 0u) {
+      cabac_substream_desc o = desc[sub];  // byte_offset, byte_capacity, qp and init_id are the caller's
+      o.rec_offset = base;
+      o.n_records = out.sub_n[sub];
+      if (flag != 0u) o.init_id &= ~(uint32_t)CABAC_SUB_FINISH;  // a stopped piece is not finished: it passes its state through
+      out.desc_out[sub] = o;
+    }
+    if (flag == 0u) return true;
+    cabac_tu_desc rejected{};  // none of its blocks is coded, nothing else of it is written
+    rejected.log2_width = rejected.log2_height = 7;
+    for (uint32_t t = u.t0 + lane; t < u.t1; t += 64u) {
+      out.tus_out[t] = rejected;
+      out.tu_offset[t] = base;
+    }
+    return false;
+  }
+};
+
 __device__ __forceinline__ PwIo pw_io(uint32_t n_sub, const PlanWriteIn &in, uint32_t *sub_n, uint32_t *sub_cap, uint32_t *sub_flag,
                                       uint32_t *err, const PwOut &out) {
   return PwIo{n_sub, in.desc, in.plan, in.values, in.tile_first, in.tus, in.tu_at, in.tu_guard, in.tu_n_records, in.tu_info,
@@ -129,6 +174,32 @@ __global__ __launch_bounds__(64 * kPwWaves) void plan_emit_rows_kernel(uint32_t 
                                                                         const uint32_t *__restrict__ sync_entry,
                                                                         uint32_t *__restrict__ sync_rec) {
   plan_walk<true, true>(PwRowsIo{pw_io(n_sub, in, nullptr, nullptr, nullptr, nullptr, out), sync_entry, sync_rec});
+}
+
+__global__ __launch_bounds__(64 * kPwWaves) void plan_resolve_pieces_kernel(uint32_t n_sub, PlanWriteIn in, CtxPieces cp,
+                                                                             uint32_t *__restrict__ sub_n, uint32_t *__restrict__ sub_cap,
+                                                                             uint32_t *__restrict__ sub_flag, uint32_t *__restrict__ err) {
+  plan_walk<false>(PcIo{pw_io(n_sub, in, sub_n, sub_cap, sub_flag, err, PwOut{}), cp});
+}
+
+__global__ __launch_bounds__(64 * kPwWaves) void plan_emit_pieces_kernel(uint32_t n_sub, PlanWriteIn in, PwOut out) {
+  plan_walk<true>(PcIo{pw_io(n_sub, in, nullptr, nullptr, nullptr, nullptr, out), CtxPieces{}});
+}
+
+// the stops of the form in pieces, behind the encoder: a stopped piece has passed its state through (a fresh one as the state of
+// start()); it returns {0, flag} and the flag is added to the state.  A piece that was passed to the encoder has its answer.
+__global__ __launch_bounds__(256) void plan_stops_pieces_kernel(uint32_t n_sub, const uint32_t *__restrict__ sub_flag,
+                                                                cabac_substream_result *__restrict__ results,
+                                                                cabac_coder_state *__restrict__ coder_out) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= n_sub) return;
+  const uint32_t flag = sub_flag[s];
+  if (flag == 0u || flag == kPcPass) return;
+  cabac_substream_result r;
+  r.n_bits = 0u;
+  r.flags = flag;
+  results[s] = r;
+  if (coder_out != nullptr) coder_out[s].flags |= flag;
 }
 
 // the out sets of a plan write from sets: a stopped substream writes none
@@ -169,6 +240,29 @@ hipError_t launch_plan_emit(hipStream_t st, uint32_t n_sub, const PlanWriteIn &i
   const dim3 grid((n_sub + kPwWaves - 1u) / kPwWaves), block(64 * kPwWaves);
   if (n_sub && sync_entry) hipLaunchKernelGGL(plan_emit_rows_kernel, grid, block, 0, st, n_sub, in, out, sync_entry, sync_rec);
   else if (n_sub) hipLaunchKernelGGL(plan_emit_kernel, grid, block, 0, st, n_sub, in, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_resolve_pieces(hipStream_t st, uint32_t n_sub, const PlanWriteIn &in, const CtxPieces &cp, uint32_t *sub_n,
+                                      uint32_t *sub_cap, uint32_t *sub_flag, uint32_t *err) {
+  hipError_t e = hipMemsetAsync(err, 0, sizeof(uint32_t), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(plan_resolve_pieces_kernel, dim3((n_sub + kPwWaves - 1u) / kPwWaves), dim3(64 * kPwWaves), 0, st, n_sub, in, cp, sub_n,
+                     sub_cap, sub_flag, err);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_emit_pieces(hipStream_t st, uint32_t n_sub, const PlanWriteIn &in, const uint32_t *sub_n, const uint32_t *sub_flag,
+                                   const uint64_t *rec_base, cabac_substream_desc *desc_out, cabac_tu_desc *tus_out, uint64_t *tu_offset,
+                                   uint16_t *records, uint32_t *values_out, uint32_t *tu_info_out) {
+  const PwOut out{sub_n, nullptr, sub_flag, rec_base, nullptr, desc_out, tus_out, tu_offset, records, values_out, tu_info_out};
+  hipLaunchKernelGGL(plan_emit_pieces_kernel, dim3((n_sub + kPwWaves - 1u) / kPwWaves), dim3(64 * kPwWaves), 0, st, n_sub, in, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_stops_pieces(hipStream_t st, uint32_t n_sub, const uint32_t *sub_flag, cabac_substream_result *results,
+                                    cabac_coder_state *coder_out) {
+  hipLaunchKernelGGL(plan_stops_pieces_kernel, dim3((n_sub + 255u) / 256u), dim3(256), 0, st, n_sub, sub_flag, results, coder_out);
   return hipGetLastError();
 }
 
