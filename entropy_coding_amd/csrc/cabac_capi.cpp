@@ -9,7 +9,9 @@
 // section uses (fail / ensure, the event brackets Bracket, TIMED_LAUNCH and Timed, the PCIe path, the level / link checks and the
 // WPP and rows schedules); then one section per header.  The single-launch device calls go through TIMED_LAUNCH.  The four
 // host-pointer forms of the parser family (residual, unit, element and plan parse, the rows parse included) share their host
-// checks (check_substream_host, check_plan_host, check_coeff_ranges_host) and their staging (ParseStage); the pipelined
+// checks (check_substream_host, check_plan_host, check_coeff_ranges_host) and their staging (ParseStage), the family's device calls
+// their operands (cabac::ParseIn) and their prelude (parse_device_call); the device pipelines of the plan write share their
+// tables and the one wait (plan_write_tables, wait_for_totals); the pipelined
 // host-pointer forms each keep their own stream choreography.  The blocking runtime calls go through counting helpers (wait_stream,
 // device_alloc, ...: cabac_hip_workspace_waits); on a ctx with a fixed workspace (cabac_hip_workspace.h) the three pipelines that wait
 // in the middle take a branch that queues a gate kernel instead.
@@ -730,13 +732,10 @@ int wpp_device_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const cabac_s
 // The schedule of a rows parse on the ctx stream: for every non-empty level ONE launch of the sets kernel over that level's
 // substreams.  A substream starts from the slot of its link (checked on the device against the level: it must lie below the
 // level's first substream) and writes its own slot at its hand-over entry; the last level writes none.
-int parse_rows_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
-                           const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at, const uint32_t *d_tu_guard,
-                           const uint32_t *d_plan, void *d_coeff, int coeff_bytes, uint32_t *d_values, uint32_t *d_tu_info,
-                           cabac_substream_result *d_results, const Rows &rows) {
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results || !rows.d_sync_from || !rows.d_sync_at)))
+int parse_rows_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac::ParseIn &in, const Rows &rows) {
+  if (!c || (n_sub && (!in.desc || !in.bytes || !in.tile_first || !in.results || !rows.d_sync_from || !rows.d_sync_at)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (in.coeff_bytes != 4 && in.coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (n_sub == 0) return CABAC_HIP_OK;
   int rc = check_levels(c, n_sub, rows.n_level, rows.level_first);
   if (rc) return rc;
@@ -754,10 +753,12 @@ int parse_rows_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substre
     if (n == 0) continue;
     const bool hands_over = l + 1 < last;
     const cabac::CtxSets sets{n_sub, slot_state, slot_rate, rows.d_sync_from + first, nullptr, slot_state, slot_rate};
+    cabac::ParseIn level = in;  // what is per substream starts at the level's first
+    level.desc += first;
+    level.tile_first += first;
+    level.results += first;
     Timed t(c, 35);
-    HIP_TRY(c, cabac::launch_plan_parse_sets(c->stream, n, d_desc + first, d_bytes, d_tile_first + first, d_tu, d_tu_at, d_tu_guard, d_plan,
-                                             d_coeff, coeff_bytes, d_values, d_tu_info, d_results + first, sets, rows.d_sync_at + first,
-                                             first, hands_over ? first : 0xFFFFFFFFu));
+    HIP_TRY(c, cabac::launch_plan_parse_sets(c->stream, n, level, sets, rows.d_sync_at + first, first, hands_over ? first : 0xFFFFFFFFu));
   }
   return CABAC_HIP_OK;
 }
@@ -833,13 +834,7 @@ struct ParseStage {
   int coeff_bytes;
   uint64_t n_coeff_total;
   bool blocks;  // the coefficients go up (int32) or are cleared (int16), and come back
-  const cabac_substream_desc *d_desc = nullptr;
-  const uint8_t *d_bytes = nullptr;
-  const uint32_t *d_tile_first = nullptr;
-  const cabac_tu_desc *d_tu = nullptr;
-  void *d_coeff = nullptr;
-  uint32_t *d_tu_info = nullptr;
-  cabac_substream_result *d_results = nullptr;
+  cabac::ParseIn in{};  // the common operands on the device; the form adds its own members
 
   size_t tu_word_bytes() const { return size_t(n_tu) * sizeof(uint32_t); }  // one word per block: info words, positions, guards
 
@@ -856,30 +851,26 @@ struct ParseStage {
     if ((rc = ensure(c, kParseResults, n_sub * sizeof(cabac_substream_result)))) return rc;
     if ((rc = ensure(c, kTuInfo, tu_word_bytes()))) return rc;
     uint8_t *d_first = static_cast<uint8_t *>(c->d_buf[kFirstTus]);
-    d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[kDesc]);
-    d_bytes = static_cast<const uint8_t *>(c->d_buf[kBytes]);
-    d_tile_first = reinterpret_cast<const uint32_t *>(d_first);
-    d_tu = reinterpret_cast<const cabac_tu_desc *>(d_first + first_pad);
-    d_coeff = c->d_buf[kCoeff];
-    d_tu_info = static_cast<uint32_t *>(c->d_buf[kTuInfo]);
-    d_results = static_cast<cabac_substream_result *>(c->d_buf[kParseResults]);
+    in = {static_cast<const cabac_substream_desc *>(c->d_buf[kDesc]), static_cast<const uint8_t *>(c->d_buf[kBytes]),
+          reinterpret_cast<const uint32_t *>(d_first), reinterpret_cast<const cabac_tu_desc *>(d_first + first_pad), c->d_buf[kCoeff],
+          coeff_bytes, static_cast<uint32_t *>(c->d_buf[kTuInfo]), static_cast<cabac_substream_result *>(c->d_buf[kParseResults])};
     HIP_TRY(c, up(c, c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc)));
     HIP_TRY(c, up(c, c->d_buf[kBytes], bytes, bytes_total));
     HIP_TRY(c, up(c, d_first, tile_first, first_bytes));
     HIP_TRY(c, up(c, d_first + first_pad, tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
-    if (tu_info_in) HIP_TRY(c, up(c, d_tu_info, tu_info_in, tu_word_bytes()));
+    if (tu_info_in) HIP_TRY(c, up(c, in.tu_info, tu_info_in, tu_word_bytes()));
     // int32: what the walk does not write (outside the coded region of 64-wide blocks, the blocks of a stopped substream) keeps
     // the caller's values; int16: output only, zero where nothing is written
-    if (blocks && coeff_bytes == 4) HIP_TRY(c, up(c, d_coeff, coeff, n_coeff_total * sizeof(int32_t)));
-    if (blocks && n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(d_coeff, 0, n_coeff_total * sizeof(int16_t), c->stream));
+    if (blocks && coeff_bytes == 4) HIP_TRY(c, up(c, in.coeff, coeff, n_coeff_total * sizeof(int32_t)));
+    if (blocks && n_coeff_total && coeff_bytes == 2) HIP_TRY(c, hipMemsetAsync(in.coeff, 0, n_coeff_total * sizeof(int16_t), c->stream));
     return CABAC_HIP_OK;
   }
 
   // info words (where the caller wants them), coefficients and results back, the wait, and the flags as the status
   int finish(void *coeff, uint32_t *tu_info, cabac_substream_result *results) {
-    if (tu_info) HIP_TRY(c, down(c, tu_info, d_tu_info, tu_word_bytes()));
-    if (blocks) HIP_TRY(c, down(c, coeff, d_coeff, n_coeff_total * size_t(coeff_bytes)));
-    HIP_TRY(c, down(c, results, d_results, n_sub * sizeof(cabac_substream_result)));
+    if (tu_info) HIP_TRY(c, down(c, tu_info, in.tu_info, tu_word_bytes()));
+    if (blocks) HIP_TRY(c, down(c, coeff, in.coeff, n_coeff_total * size_t(coeff_bytes)));
+    HIP_TRY(c, down(c, results, in.results, n_sub * sizeof(cabac_substream_result)));
     HIP_TRY(c, wait_stream(c, c->stream));
     int status = CABAC_HIP_OK;
     for (uint32_t s = 0; s < n_sub; s++)
@@ -888,6 +879,73 @@ struct ParseStage {
     return status;
   }
 };
+
+// ---- what the device pipelines of the plan write (the whole write and the write in pieces) set up alike: the sizes and info words of
+// the blocks (kSpCnt), the tables of the two walks and their scan (kPwPlan), the expanded descriptors (kSpDesc), the blocks as they
+// are coded (kPwTu), their destinations (kSpTuOff); words: two per substream for hand-over records and live out sets (kRowsWords),
+// null where the call has no use for them
+struct PlanWriteTables {
+  uint32_t *cnt, *info;
+  uint32_t *sub_n, *sub_cap, *sub_flag, *err;
+  uint64_t *rec_base, *byte_base, *totals;
+  cabac_substream_desc *desc2;
+  cabac_tu_desc *tus2;
+  uint64_t *tu_off;
+  uint32_t *words;
+};
+int plan_write_tables(cabac_hip_ctx *c, uint32_t n_sub, uint32_t n_tu, bool with_words, PlanWriteTables *t) {
+  int rc;
+  const size_t n_blk = n_tu ? n_tu : 1, n_s = n_sub ? n_sub : 1;
+  const size_t words = (3 * n_s + 2 + 1) & ~size_t(1);  // sub_n, sub_cap, sub_flag, err (+ pad)
+  if (with_words && (rc = ensure(c, kRowsWords, 2 * n_s * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kSpCnt, 2 * n_blk * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c, kResidualScratch, cabac::residual_scratch_bytes(n_tu)))) return rc;
+  if ((rc = ensure(c, kPwPlan, words * sizeof(uint32_t) + (2 * n_s + 3) * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(c, kPwTu, n_blk * sizeof(cabac_tu_desc)))) return rc;
+  if ((rc = ensure(c, kSpDesc, n_s * sizeof(cabac_substream_desc)))) return rc;
+  if ((rc = ensure(c, kSpTuOff, n_blk * sizeof(uint64_t)))) return rc;
+  if (!c->ws_fixed && !c->h_totals) HIP_TRY(c, pinned_alloc(c, &c->h_totals, 64, hipHostMallocDefault));
+  uint32_t *cnt = static_cast<uint32_t *>(c->d_buf[kSpCnt]);
+  uint32_t *sub_n = static_cast<uint32_t *>(c->d_buf[kPwPlan]), *sub_cap = sub_n + n_s, *sub_flag = sub_cap + n_s, *err = sub_flag + n_s;
+  uint64_t *rec_base = reinterpret_cast<uint64_t *>(sub_n + words), *byte_base = rec_base + n_s, *totals = byte_base + n_s;
+  *t = {cnt, cnt + n_blk, sub_n, sub_cap, sub_flag, err, rec_base, byte_base, totals,
+        static_cast<cabac_substream_desc *>(c->d_buf[kSpDesc]), static_cast<cabac_tu_desc *>(c->d_buf[kPwTu]),
+        static_cast<uint64_t *>(c->d_buf[kSpTuOff]), with_words ? static_cast<uint32_t *>(c->d_buf[kRowsWords]) : nullptr};
+  return CABAC_HIP_OK;
+}
+
+// THE ONE WAIT of a pipeline whose sizes decide the buffers of its second half: totals = {records, bytes, refused} as the scan
+// left them; refused: the call's message for it.  Then the expanded records (kSpRec) and, where asked, the byte slots (kSpBytes).
+int wait_for_totals(cabac_hip_ctx *c, const uint64_t *totals, const char *refused, bool byte_slots) {
+  uint64_t *h_tot = static_cast<uint64_t *>(c->h_totals);
+  HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, wait_stream(c, c->stream));
+  if (h_tot[2]) return fail(c, CABAC_HIP_ERR_INVALID, refused);
+  int rc;
+  if ((rc = ensure(c, kSpRec, (h_tot[0] + 64) * sizeof(uint16_t)))) return rc;
+  if (byte_slots && (rc = ensure(c, kSpBytes, h_tot[1] + 64))) return rc;
+  return CABAC_HIP_OK;
+}
+
+// ---- the device calls of the parser family take their operands as a cabac::ParseIn, whose first eight members every walk has.
+// The prelude of all but the residual parse (which demands the blocks and has its own): the refusals (args_ok: what the form
+// checks beside the common pointers), the empty call, the device, and the launch between its events.  tus / coeff belong to the
+// blocks, records / side_bins or plan / values to the runs or plans: either kind may be absent altogether
+template <class F>
+int parse_device_call(cabac_hip_ctx *c, uint32_t n_sub, const cabac::ParseIn &in, bool args_ok, int kind, const char *what, F &&launch) {
+  if (!c || (n_sub && (!in.desc || !in.bytes || !in.tile_first || !in.results)) || !args_ok) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (in.coeff_bytes != 4 && in.coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
+  if (n_sub == 0) return CABAC_HIP_OK;
+  DeviceGuard g(c->device);
+  return timed_launch(c, kind, what, launch);
+}
+#define PARSE_DEVICE_CALL(c, n_sub, in, args_ok, kind, expr) \
+  parse_device_call((c), (n_sub), (in), (args_ok), (kind), #expr, [&] { return (expr); })
+
+// the unit, element and plan walk: one launch, told apart by the walk and its profile kind (25, 26, 27)
+int parse_walk_device(cabac_hip_ctx *c, cabac::ParseWalk walk, int kind, uint32_t n_sub, const cabac::ParseIn &in) {
+  return PARSE_DEVICE_CALL(c, n_sub, in, true, kind, cabac::launch_parse(c->stream, walk, n_sub, in));
+}
 
 }  // namespace
 
@@ -1415,26 +1473,24 @@ int cabac_hip_residual_batch(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_des
   return status;
 }
 
-static int residual_parse_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
-                                      const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, void *d_coeff, int coeff_bytes,
-                                      uint32_t *d_tu_info, cabac_substream_result *d_results) {
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_tu || !d_coeff || !d_results)))
+// this one demands the blocks; the others' prelude is parse_device_call
+static int residual_parse_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac::ParseIn &in) {
+  if (!c || (n_sub && (!in.desc || !in.bytes || !in.tile_first || !in.tus || !in.coeff || !in.results)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
-  return TIMED_LAUNCH(c, 9, cabac::launch_residual_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_coeff, coeff_bytes, d_tu_info,
-                                                         d_results));
+  return TIMED_LAUNCH(c, 9, cabac::launch_parse(c->stream, cabac::ParseWalk::kResidual, n_sub, in));
 }
 
 int cabac_hip_residual_parse_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
                                     const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, int32_t *d_coeff, uint32_t *d_tu_info,
                                     cabac_substream_result *d_results) {
-  return residual_parse_device_impl(c, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_coeff, 4, d_tu_info, d_results);
+  return residual_parse_device_impl(c, n_sub, {d_desc, d_bytes, d_tile_first, d_tu, d_coeff, 4, d_tu_info, d_results});
 }
 
 int cabac_hip_residual_parse16_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
                                       const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, int16_t *d_coeff, uint32_t *d_tu_info,
                                       cabac_substream_result *d_results) {
-  return residual_parse_device_impl(c, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_coeff, 2, d_tu_info, d_results);
+  return residual_parse_device_impl(c, n_sub, {d_desc, d_bytes, d_tile_first, d_tu, d_coeff, 2, d_tu_info, d_results});
 }
 
 static int residual_parse_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
@@ -1451,9 +1507,7 @@ static int residual_parse_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cab
   ParseStage st{c, n_sub, n_tu, coeff_bytes, n_coeff_total, n_coeff_total != 0};
   int rc;
   if ((rc = st.stage(desc, bytes, bytes_total, tile_first, tus, coeff, nullptr))) return rc;
-  if ((rc = residual_parse_device_impl(c, n_sub, st.d_desc, st.d_bytes, st.d_tile_first, st.d_tu, st.d_coeff, coeff_bytes, st.d_tu_info,
-                                       st.d_results)))
-    return rc;
+  if ((rc = residual_parse_device_impl(c, n_sub, st.in))) return rc;
   return st.finish(coeff, tu_info, results);
 }
 
@@ -1474,13 +1528,9 @@ int cabac_hip_parse_unit_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_su
                                 const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
                                 const uint16_t *d_records, void *d_coeff, int coeff_bytes, uint8_t *d_side_bins, uint32_t *d_tu_info,
                                 cabac_substream_result *d_results) {
-  // d_tu / d_coeff belong to the blocks, d_records / d_side_bins to the runs: either kind may be absent altogether
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  DeviceGuard g(c->device);
-  return TIMED_LAUNCH(c, 25, cabac::launch_unit_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_records, d_coeff, coeff_bytes,
-                                                      d_side_bins, d_tu_info, d_results));
+  return parse_walk_device(c, cabac::ParseWalk::kUnit, 25, n_sub,
+                           {d_desc, d_bytes, d_tile_first, d_tu, d_coeff, coeff_bytes, d_tu_info, d_results, d_tu_at, nullptr, nullptr,
+                            nullptr, d_records, d_side_bins});
 }
 
 int cabac_hip_parse_unit_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
@@ -1526,10 +1576,10 @@ int cabac_hip_parse_unit_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
   HIP_TRY(c, up(c, c->d_buf[kUnitRecords], records, rec_bytes));
   if (tu_at) HIP_TRY(c, up(c, c->d_buf[kUnitTuAt], tu_at, st.tu_word_bytes()));
   HIP_TRY(c, up(c, c->d_buf[kUnitBins], side_bins, bin_bytes));  // what the walk does not write keeps the caller's values
-  rc = cabac_hip_parse_unit_device(c, n_sub, st.d_desc, st.d_bytes, st.d_tile_first, st.d_tu,
-                                   tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr, (const uint16_t *)c->d_buf[kUnitRecords],
-                                   st.d_coeff, coeff_bytes, (uint8_t *)c->d_buf[kUnitBins], st.d_tu_info, st.d_results);
-  if (rc) return rc;
+  st.in.tu_at = tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr;
+  st.in.records = (const uint16_t *)c->d_buf[kUnitRecords];
+  st.in.side_bins = (uint8_t *)c->d_buf[kUnitBins];
+  if ((rc = parse_walk_device(c, cabac::ParseWalk::kUnit, 25, n_sub, st.in))) return rc;
   HIP_TRY(c, down(c, side_bins, c->d_buf[kUnitBins], bin_bytes));
   return st.finish(coeff, tu_info, results);
 }
@@ -1539,13 +1589,8 @@ int cabac_hip_parse_elements_device(cabac_hip_ctx *c, uint32_t n_sub, const caba
                                     const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
                                     const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
                                     uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results) {
-  // d_tu / d_coeff belong to the blocks, d_plan / d_values to the plans: either kind may be absent altogether
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  DeviceGuard g(c->device);
-  return TIMED_LAUNCH(c, 26, cabac::launch_element_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
-                                                         coeff_bytes, d_values, d_tu_info, d_results));
+  return parse_walk_device(c, cabac::ParseWalk::kElement, 26, n_sub,
+                           {d_desc, d_bytes, d_tile_first, d_tu, d_coeff, coeff_bytes, d_tu_info, d_results, d_tu_at, d_tu_guard, d_plan, d_values});
 }
 
 // ---- a whole transform unit in one walk (declared in cabac_hip_parse_plan.h; the plan-walking instantiation) ----
@@ -1553,12 +1598,8 @@ int cabac_hip_parse_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_su
                                 const uint32_t *d_tile_first, const cabac_tu_desc *d_tu, const uint32_t *d_tu_at,
                                 const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
                                 uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results) {
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  DeviceGuard g(c->device);
-  return TIMED_LAUNCH(c, 27, cabac::launch_plan_parse(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
-                                                      coeff_bytes, d_values, d_tu_info, d_results));
+  return parse_walk_device(c, cabac::ParseWalk::kPlan, 27, n_sub,
+                           {d_desc, d_bytes, d_tile_first, d_tu, d_coeff, coeff_bytes, d_tu_info, d_results, d_tu_at, d_tu_guard, d_plan, d_values});
 }
 
 // what the host-pointer forms of the two refuse about a plan (the plan write and the plan round of the search use it too)
@@ -1708,23 +1749,22 @@ static int parse_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   if (tu_at) HIP_TRY(c, up(c, c->d_buf[kUnitTuAt], tu_at, st.tu_word_bytes()));
   if (tu_guard) HIP_TRY(c, up(c, c->d_buf[kElemGuard], tu_guard, st.tu_word_bytes()));
   HIP_TRY(c, up(c, c->d_buf[kElemValues], values, value_bytes));
-  const uint32_t *d_tu_at = tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr;
-  const uint32_t *d_tu_guard = tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr;
-  const uint32_t *d_plan = (const uint32_t *)c->d_buf[kElemPlan];
-  uint32_t *d_values = (uint32_t *)c->d_buf[kElemValues];
+  st.in.tu_at = tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr;
+  st.in.tu_guard = tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr;
+  st.in.plan = (const uint32_t *)c->d_buf[kElemPlan];
+  st.in.values = (uint32_t *)c->d_buf[kElemValues];
   if (rows) {
     HIP_TRY(c, up(c, c->d_buf[kWppFrom], rows->d_sync_from, link_bytes));
     HIP_TRY(c, up(c, c->d_buf[kWppAt], rows->d_sync_at, link_bytes));
     const Rows d_rows{rows->n_level, rows->level_first, (const uint32_t *)c->d_buf[kWppFrom], (const uint32_t *)c->d_buf[kWppAt]};
-    rc = parse_rows_device_impl(c, n_sub, st.d_desc, st.d_bytes, st.d_tile_first, st.d_tu, d_tu_at, d_tu_guard, d_plan, st.d_coeff,
-                                coeff_bytes, d_values, st.d_tu_info, st.d_results, d_rows);
+    rc = parse_rows_device_impl(c, n_sub, st.in, d_rows);
+  } else if (rules.computed) {
+    rc = parse_walk_device(c, cabac::ParseWalk::kPlan, 27, n_sub, st.in);
   } else {
-    rc = (rules.computed ? cabac_hip_parse_plan_device : cabac_hip_parse_elements_device)(
-        c, n_sub, st.d_desc, st.d_bytes, st.d_tile_first, st.d_tu, d_tu_at, d_tu_guard, d_plan, st.d_coeff, coeff_bytes, d_values,
-        st.d_tu_info, st.d_results);
+    rc = parse_walk_device(c, cabac::ParseWalk::kElement, 26, n_sub, st.in);
   }
   if (rc) return rc;
-  HIP_TRY(c, down(c, values, d_values, value_bytes));
+  HIP_TRY(c, down(c, values, st.in.values, value_bytes));
   return st.finish(coeff, tu_info, results);
 }
 
@@ -1806,14 +1846,8 @@ static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const c
     HIP_TRY(c, cabac::launch_splice_plan(c->stream, n_sub, n_tu, d_desc, d_splice_first, d_splices, n_splice, d_cnt, pre, sub_n, sub_cap, seen, err,
                                          rec_base, byte_base, totals, d_n_live, fixed ? &gate : nullptr));
   }
-  if (!fixed) {
-    uint64_t *h_tot = static_cast<uint64_t *>(c->h_totals);
-    HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, wait_stream(c, c->stream));  // the one wait: sizes decide the buffers of the second half
-    if (h_tot[2]) return fail(c, CABAC_HIP_ERR_INVALID, "splice list: not sorted, outside its substream, or a block not spliced exactly once");
-    if ((rc = ensure(c, kSpRec, (h_tot[0] + 64) * sizeof(uint16_t)))) return rc;
-    if ((rc = ensure(c, kSpBytes, h_tot[1] + 64))) return rc;
-  }
+  if (!fixed && (rc = wait_for_totals(c, totals, "splice list: not sorted, outside its substream, or a block not spliced exactly once", true)))
+    return rc;
   auto *exp_rec = static_cast<uint16_t *>(c->d_buf[kSpRec]);
   auto *slots = static_cast<uint8_t *>(c->d_buf[kSpBytes]);
   {
@@ -2103,64 +2137,40 @@ static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_
     if (int bad = check_workspace(c, n_sub, n_tu, rows != nullptr)) return bad;
   DeviceGuard g(c->device);
   int rc;
-  if ((sets || rows) && (rc = ensure(c, kRowsWords, 2 * size_t(n_sub ? n_sub : 1) * sizeof(uint32_t)))) return rc;
-  uint32_t *sync_rec = nullptr, *out_live = nullptr;  // the hand-over records of a rows call; the out sets of the rows that did not stop
-  if (sets || rows) {
-    sync_rec = static_cast<uint32_t *>(c->d_buf[kRowsWords]);
-    out_live = sync_rec + (n_sub ? n_sub : 1);
-  }
-  const size_t n_blk = n_tu ? n_tu : 1, n_s = n_sub ? n_sub : 1;
-  const size_t words = (3 * n_s + 2 + 1) & ~size_t(1);  // sub_n, sub_cap, sub_flag, err (+ pad)
-  if ((rc = ensure(c, kSpCnt, 2 * n_blk * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kResidualScratch, cabac::residual_scratch_bytes(n_tu)))) return rc;
-  if ((rc = ensure(c, kPwPlan, words * sizeof(uint32_t) + (2 * n_s + 3) * sizeof(uint64_t)))) return rc;
-  if ((rc = ensure(c, kPwTu, n_blk * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, kSpDesc, n_s * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, kSpTuOff, n_blk * sizeof(uint64_t)))) return rc;
-  if (!fixed && !c->h_totals) HIP_TRY(c, pinned_alloc(c, &c->h_totals, 64, hipHostMallocDefault));
-  uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kSpCnt]), *d_info = d_cnt + n_blk;
-  uint32_t *sub_n = static_cast<uint32_t *>(c->d_buf[kPwPlan]), *sub_cap = sub_n + n_s, *sub_flag = sub_cap + n_s, *err = sub_flag + n_s;
-  uint64_t *rec_base = reinterpret_cast<uint64_t *>(sub_n + words), *byte_base = rec_base + n_s, *totals = byte_base + n_s;
-  auto *desc2 = static_cast<cabac_substream_desc *>(c->d_buf[kSpDesc]);
-  auto *tus2 = static_cast<cabac_tu_desc *>(c->d_buf[kPwTu]);
-  auto *tu_off = static_cast<uint64_t *>(c->d_buf[kSpTuOff]);
-  const cabac::PlanWriteIn in{d_desc, d_plan, d_values_in, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_cnt, d_info};
+  PlanWriteTables w;
+  if ((rc = plan_write_tables(c, n_sub, n_tu, sets || rows, &w))) return rc;
+  // the hand-over records of a rows call; the out sets of the rows that did not stop
+  uint32_t *sync_rec = w.words, *out_live = w.words ? w.words + (n_sub ? n_sub : 1) : nullptr;
+  const cabac::PlanWriteIn in{d_desc, d_plan, d_values_in, d_tile_first, d_tu, d_tu_at, d_tu_guard, w.cnt, w.info};
   c->timed = false;
   {  // sizes and info words of ALL blocks: they do not depend on the guards, the guards depend on them
     Timed t(c, 5);
-    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[kResidualScratch]));
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, w.cnt, w.info, nullptr, c->d_buf[kResidualScratch]));
   }
   {
     Timed t(c, 28);
-    HIP_TRY(c, cabac::launch_plan_resolve(c->stream, n_sub, in, sub_n, sub_cap, sub_flag, err));
+    HIP_TRY(c, cabac::launch_plan_resolve(c->stream, n_sub, in, w.sub_n, w.sub_cap, w.sub_flag, w.err));
     // fixed: the scan ends in the gate; a voided call's substreams all become stopped ones (CABAC_RES_OVERFLOW) of length 0,
     // which the emit walk, the out sets, the records pass and the stops below already treat as the contract asks
-    const cabac::WsGate gate{c->d_ws, CABAC_WS_RECORDS_32BIT, sub_flag, nullptr, 0};
-    HIP_TRY(c, cabac::launch_splice_scan(c->stream, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals, fixed ? &gate : nullptr));
+    const cabac::WsGate gate{c->d_ws, CABAC_WS_RECORDS_32BIT, w.sub_flag, nullptr, 0};
+    HIP_TRY(c, cabac::launch_splice_scan(c->stream, n_sub, w.sub_n, w.sub_cap, w.rec_base, w.byte_base, w.err, w.totals, fixed ? &gate : nullptr));
   }
-  if (!fixed) {
-    uint64_t *h_tot = static_cast<uint64_t *>(c->h_totals);
-    HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, wait_stream(c, c->stream));  // the one wait: sizes decide the buffers of the second half
-    if (h_tot[2]) return fail(c, CABAC_HIP_ERR_INVALID, "a substream outgrows 32 bits of records");
-    if ((rc = ensure(c, kSpRec, (h_tot[0] + 64) * sizeof(uint16_t)))) return rc;
-    if ((rc = ensure(c, kSpBytes, h_tot[1] + 64))) return rc;
-  }
+  if (!fixed && (rc = wait_for_totals(c, w.totals, "a substream outgrows 32 bits of records", true))) return rc;
   auto *exp_rec = static_cast<uint16_t *>(c->d_buf[kSpRec]);
   auto *slots = static_cast<uint8_t *>(c->d_buf[kSpBytes]);
   {
     Timed t(c, 28);
-    HIP_TRY(c, cabac::launch_plan_emit(c->stream, n_sub, in, sub_n, sub_cap, sub_flag, rec_base, byte_base, desc2, tus2, tu_off, exp_rec,
-                                       d_values_out, d_tu_info, rows ? rows->d_sync_at : nullptr, rows ? sync_rec : nullptr));
-    if (sets && sets->out_set) HIP_TRY(c, cabac::launch_plan_out_sets(c->stream, n_sub, sub_flag, sets->out_set, out_live));
+    HIP_TRY(c, cabac::launch_plan_emit(c->stream, n_sub, in, w.sub_n, w.sub_cap, w.sub_flag, w.rec_base, w.byte_base, w.desc2, w.tus2, w.tu_off,
+                                       exp_rec, d_values_out, d_tu_info, rows ? rows->d_sync_at : nullptr, rows ? sync_rec : nullptr));
+    if (sets && sets->out_set) HIP_TRY(c, cabac::launch_plan_out_sets(c->stream, n_sub, w.sub_flag, sets->out_set, out_live));
   }
   {  // block records of the coded blocks, straight into the expanded substreams: in tus2 a skipped block is one the binariser
      // rejects, so it writes nothing whatever its coefficients hold (another list: the block order is made again)
     Timed t(c, 5);
-    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, tus2, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[kResidualScratch]));
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, w.tus2, d_coeff, coeff_bytes, w.tu_off, w.cnt, w.info, exp_rec, c->d_buf[kResidualScratch]));
   }
   if (rows) {  // the context-advance prefix passes per level, then one encode launch from the slots
-    if (n_sub && (rc = wpp_device_impl(c, false, n_sub, desc2, exp_rec, slots, nullptr, d_results, rows->n_level, rows->level_first,
+    if (n_sub && (rc = wpp_device_impl(c, false, n_sub, w.desc2, exp_rec, slots, nullptr, d_results, rows->n_level, rows->level_first,
                                        rows->d_sync_from, sync_rec)))
       return rc;
     c->timed = false;
@@ -2168,18 +2178,18 @@ static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_
     cabac::CtxSets live = *sets;  // a stopped substream has an empty run: it would write a copy of its start set
     if (live.out_set) live.out_set = out_live;
     Timed t(c, 36);
-    HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, desc2, exp_rec, slots, d_results, 0, &live));
+    HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, w.desc2, exp_rec, slots, d_results, 0, &live));
   } else {
     Timed t(c, 0);
-    HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, desc2, exp_rec, slots, d_results));
+    HIP_TRY(c, cabac::launch_encode(c->stream, c->enc_variant, n_sub, w.desc2, exp_rec, slots, d_results));
   }
   {
     Timed t(c, 28);
-    HIP_TRY(c, cabac::launch_plan_stops(c->stream, n_sub, sub_flag, d_results));
+    HIP_TRY(c, cabac::launch_plan_stops(c->stream, n_sub, w.sub_flag, d_results));
   }
   {
     Timed t(c, 6);
-    HIP_TRY(c, cabac::launch_assemble(c->stream, n_sub, desc2, d_results, slots, d_payload, payload_capacity, d_payload_offsets));
+    HIP_TRY(c, cabac::launch_assemble(c->stream, n_sub, w.desc2, d_results, slots, d_payload, payload_capacity, d_payload_offsets));
   }
   return CABAC_HIP_OK;
 }
@@ -3484,15 +3494,10 @@ int cabac_hip_plan_parse_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cab
                                      uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results, uint32_t n_sets,
                                      const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
                                      const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate, const uint32_t *d_out_at) {
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results)) ||
-      !sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
-    return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  DeviceGuard g(c->device);
+  const cabac::ParseIn in{d_desc, d_bytes, d_tile_first, d_tu, d_coeff, coeff_bytes, d_tu_info, d_results, d_tu_at, d_tu_guard, d_plan, d_values};
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
-  return TIMED_LAUNCH(c, 34, cabac::launch_plan_parse_sets(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff,
-                                                           coeff_bytes, d_values, d_tu_info, d_results, sets, d_out_at, n_sets, 0xFFFFFFFFu));
+  return PARSE_DEVICE_CALL(c, n_sub, in, sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate), 34,
+                           cabac::launch_plan_parse_sets(c->stream, n_sub, in, sets, d_out_at, n_sets, 0xFFFFFFFFu));
 }
 
 // ---- the plan parse in pieces (cabac_hip_plan_resume.h): the sets form's checks, one coder state per substream in and out --------
@@ -3503,16 +3508,11 @@ int cabac_hip_plan_resume_parse_device(cabac_hip_ctx *c, uint32_t n_sub, const c
                                        const uint32_t *d_state, const uint8_t *d_rate, const uint32_t *d_start_set,
                                        const uint32_t *d_out_set, uint32_t *d_out_state, uint8_t *d_out_rate, const void *d_coder_in,
                                        void *d_coder_out) {
-  if (!c || (n_sub && (!d_desc || !d_bytes || !d_tile_first || !d_results)) ||
-      !sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
-    return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  if (n_sub == 0) return CABAC_HIP_OK;
-  DeviceGuard g(c->device);
+  const cabac::ParseIn in{d_desc, d_bytes, d_tile_first, d_tu, d_coeff, coeff_bytes, d_tu_info, d_results, d_tu_at, d_tu_guard, d_plan, d_values};
   const cabac::CtxPieces pieces{{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate},
                                 static_cast<const cabac_coder_state *>(d_coder_in), static_cast<cabac_coder_state *>(d_coder_out)};
-  return TIMED_LAUNCH(c, 50, cabac::launch_plan_parse_pieces(c->stream, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan,
-                                                             d_coeff, coeff_bytes, d_values, d_tu_info, d_results, pieces));
+  return PARSE_DEVICE_CALL(c, n_sub, in, sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate), 50,
+                           cabac::launch_plan_parse_pieces(c->stream, n_sub, in, pieces));
 }
 
 int cabac_hip_plan_parse_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint8_t *d_bytes,
@@ -3520,8 +3520,9 @@ int cabac_hip_plan_parse_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cab
                                      const uint32_t *d_tu_guard, const uint32_t *d_plan, void *d_coeff, int coeff_bytes,
                                      uint32_t *d_values, uint32_t *d_tu_info, cabac_substream_result *d_results, uint32_t n_level,
                                      const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
-  return parse_rows_device_impl(c, n_sub, d_desc, d_bytes, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_plan, d_coeff, coeff_bytes, d_values,
-                                d_tu_info, d_results, Rows{n_level, level_first, d_sync_from, d_sync_at});
+  return parse_rows_device_impl(c, n_sub, {d_desc, d_bytes, d_tile_first, d_tu, d_coeff, coeff_bytes, d_tu_info, d_results, d_tu_at, d_tu_guard,
+                                           d_plan, d_values},
+                                Rows{n_level, level_first, d_sync_from, d_sync_at});
 }
 
 int cabac_hip_plan_parse_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
@@ -3569,59 +3570,42 @@ int cabac_hip_plan_continue_write_device(cabac_hip_ctx *c, uint32_t n_sub, const
   if (n_sub == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
   int rc;
-  const size_t n_blk = n_tu ? n_tu : 1, n_s = n_sub;
-  const size_t words = (3 * n_s + 2 + 1) & ~size_t(1);  // sub_n, sub_cap, sub_flag, err (+ pad)
-  if ((rc = ensure(c, kRowsWords, 2 * n_s * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kSpCnt, 2 * n_blk * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kResidualScratch, cabac::residual_scratch_bytes(n_tu)))) return rc;
-  if ((rc = ensure(c, kPwPlan, words * sizeof(uint32_t) + (2 * n_s + 3) * sizeof(uint64_t)))) return rc;
-  if ((rc = ensure(c, kPwTu, n_blk * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, kSpDesc, n_s * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, kSpTuOff, n_blk * sizeof(uint64_t)))) return rc;
-  if (!c->h_totals) HIP_TRY(c, pinned_alloc(c, &c->h_totals, 64, hipHostMallocDefault));
-  uint32_t *out_live = static_cast<uint32_t *>(c->d_buf[kRowsWords]);  // the out sets of the pieces that are coded
-  uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kSpCnt]), *d_info = d_cnt + n_blk;
-  uint32_t *sub_n = static_cast<uint32_t *>(c->d_buf[kPwPlan]), *sub_cap = sub_n + n_s, *sub_flag = sub_cap + n_s, *err = sub_flag + n_s;
-  uint64_t *rec_base = reinterpret_cast<uint64_t *>(sub_n + words), *byte_base = rec_base + n_s, *totals = byte_base + n_s;
-  auto *desc2 = static_cast<cabac_substream_desc *>(c->d_buf[kSpDesc]);
-  auto *tus2 = static_cast<cabac_tu_desc *>(c->d_buf[kPwTu]);
-  auto *tu_off = static_cast<uint64_t *>(c->d_buf[kSpTuOff]);
-  const cabac::PlanWriteIn in{d_desc, d_plan, d_values_in, d_tile_first, d_tu, d_tu_at, d_tu_guard, d_cnt, d_info};
+  PlanWriteTables w;
+  if ((rc = plan_write_tables(c, n_sub, n_tu, true, &w))) return rc;
+  uint32_t *out_live = w.words;  // the out sets of the pieces that are coded
+  const cabac::PlanWriteIn in{d_desc, d_plan, d_values_in, d_tile_first, d_tu, d_tu_at, d_tu_guard, w.cnt, w.info};
   cabac::CtxPieces pieces{{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate},
                           static_cast<const cabac_coder_state *>(d_coder_in), static_cast<cabac_coder_state *>(d_coder_out)};
   c->timed = false;
   {  // sizes and info words of ALL blocks of the pieces
     Timed t(c, 5);
-    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, d_cnt, d_info, nullptr, c->d_buf[kResidualScratch]));
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, d_tu, d_coeff, coeff_bytes, nullptr, w.cnt, w.info, nullptr, c->d_buf[kResidualScratch]));
   }
   {
     Timed t(c, 28);
-    HIP_TRY(c, cabac::launch_plan_resolve_pieces(c->stream, n_sub, in, pieces, sub_n, sub_cap, sub_flag, err));
-    HIP_TRY(c, cabac::launch_splice_scan(c->stream, n_sub, sub_n, sub_cap, rec_base, byte_base, err, totals, nullptr));
+    HIP_TRY(c, cabac::launch_plan_resolve_pieces(c->stream, n_sub, in, pieces, w.sub_n, w.sub_cap, w.sub_flag, w.err));
+    HIP_TRY(c, cabac::launch_splice_scan(c->stream, n_sub, w.sub_n, w.sub_cap, w.rec_base, w.byte_base, w.err, w.totals, nullptr));
   }
-  uint64_t *h_tot = static_cast<uint64_t *>(c->h_totals);
-  HIP_TRY(c, hipMemcpyAsync(h_tot, totals, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, wait_stream(c, c->stream));  // the one wait: the expanded length decides the record scratch
-  if (h_tot[2]) return fail(c, CABAC_HIP_ERR_INVALID, "a piece outgrows 32 bits of records");
-  if ((rc = ensure(c, kSpRec, (h_tot[0] + 64) * sizeof(uint16_t)))) return rc;
+  // (the caller's slots take the bytes: the expanded length decides the record scratch alone)
+  if ((rc = wait_for_totals(c, w.totals, "a piece outgrows 32 bits of records", false))) return rc;
   auto *exp_rec = static_cast<uint16_t *>(c->d_buf[kSpRec]);
   {
     Timed t(c, 28);
-    HIP_TRY(c, cabac::launch_plan_emit_pieces(c->stream, n_sub, in, sub_n, sub_flag, rec_base, desc2, tus2, tu_off, exp_rec, d_values_out,
-                                              d_tu_info));
+    HIP_TRY(c, cabac::launch_plan_emit_pieces(c->stream, n_sub, in, w.sub_n, w.sub_flag, w.rec_base, w.desc2, w.tus2, w.tu_off, exp_rec,
+                                              d_values_out, d_tu_info));
     if (d_out_set) {  // a piece that is not coded writes no set
-      HIP_TRY(c, cabac::launch_plan_out_sets(c->stream, n_sub, sub_flag, d_out_set, out_live));
+      HIP_TRY(c, cabac::launch_plan_out_sets(c->stream, n_sub, w.sub_flag, d_out_set, out_live));
       pieces.out_set = out_live;
     }
   }
   {  // block records of the coded blocks, straight into the expanded pieces
     Timed t(c, 5);
-    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, tus2, d_coeff, coeff_bytes, tu_off, d_cnt, d_info, exp_rec, c->d_buf[kResidualScratch]));
+    HIP_TRY(c, cabac::launch_residual(c->stream, n_tu, w.tus2, d_coeff, coeff_bytes, w.tu_off, w.cnt, w.info, exp_rec, c->d_buf[kResidualScratch]));
   }
   {
     Timed t(c, 51);
-    HIP_TRY(c, cabac::launch_encode_pieces(c->stream, n_sub, desc2, exp_rec, d_bytes, d_results, pieces));
-    HIP_TRY(c, cabac::launch_plan_stops_pieces(c->stream, n_sub, sub_flag, d_results, pieces.coder_out));
+    HIP_TRY(c, cabac::launch_encode_pieces(c->stream, n_sub, w.desc2, exp_rec, d_bytes, d_results, pieces));
+    HIP_TRY(c, cabac::launch_plan_stops_pieces(c->stream, n_sub, w.sub_flag, d_results, pieces.coder_out));
   }
   return CABAC_HIP_OK;
 }
@@ -3796,9 +3780,8 @@ int cabac_hip_sparse_parse_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   if ((rc = ensure(c, kSparseFirst, first_bytes)) || (rc = ensure(c, kSparseEnt, cap * sizeof(uint32_t))) ||
       (rc = ensure(c, kSparseScratch, cabac::sparse_scratch_bytes(n_tu))) || (rc = ensure(c, kSparseStatus, sizeof(cabac_sparse_status))))
     return rc;
-  if ((rc = residual_parse_device_impl(c, n_sub, st.d_desc, st.d_bytes, st.d_tile_first, st.d_tu, st.d_coeff, 2, st.d_tu_info, st.d_results)))
-    return rc;
-  if ((rc = TIMED_LAUNCH(c, 42, cabac::launch_sparse_compact(c->stream, n_tu, st.d_tu, st.d_coeff, 2, n_coeff_total,
+  if ((rc = residual_parse_device_impl(c, n_sub, st.in))) return rc;
+  if ((rc = TIMED_LAUNCH(c, 42, cabac::launch_sparse_compact(c->stream, n_tu, st.in.tus, st.in.coeff, 2, n_coeff_total,
                                                              static_cast<uint32_t *>(c->d_buf[kSparseFirst]),
                                                              static_cast<uint32_t *>(c->d_buf[kSparseEnt]), cap,
                                                              static_cast<cabac_sparse_status *>(c->d_buf[kSparseStatus]),

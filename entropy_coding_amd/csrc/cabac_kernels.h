@@ -208,43 +208,36 @@ hipError_t launch_search_log_place(hipStream_t st, const SearchLogArrays &log, c
                                    uint64_t n_record, uint32_t n_tu, cabac_substream_desc *desc_out, uint32_t *splice_first,
                                    uint16_t *records, cabac_splice *splices);
 
-// residual parser (cabac_residual.hip): bytes -> coefficient blocks, one substream = blocks [tile_first[s], tile_first[s+1])
-// (cabac_residual_parse.hip); tu_info (may be null): per block scanPosLast | CABAC_TU_INFO_*
-hipError_t launch_residual_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                 const uint32_t *tile_first, const cabac_tu_desc *tus, void *coeff, int coeff_bytes /* 4 or 2 */,
-                                 uint32_t *tu_info, cabac_substream_result *results);
-// its side-walking instantiation (cabac_hip_parse_unit.h): substream s = the side records records[desc[s].rec_offset .. +
-// n_records) with block t spliced in front of index tu_at[t] of that run (tu_at null: behind the run), all on one context store;
-// side_bins[rec_offset + i] receives the bin of side record i
-hipError_t launch_unit_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                             const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint16_t *records,
-                             void *coeff, int coeff_bytes /* 4 or 2 */, uint8_t *side_bins, uint32_t *tu_info,
-                             cabac_substream_result *results);
-// its element-walking instantiation (cabac_hip_parse_elements.h): the run is a plan of syntax elements (2 words each: the
-// binariser's word0, a guard word), values[rec_offset + i] receives the value of element i; tu_guard (may be null): one guard word
-// per block
-hipError_t launch_element_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
-                                const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
-                                cabac_substream_result *results);
-// the plan walk (cabac_hip_parse_plan.h): the element walk with the two computed entry kinds, on the same operands
-hipError_t launch_plan_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                             const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
-                             const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
-                             cabac_substream_result *results);
+// residual parser family (cabac_residual_parse.hip): bytes -> coefficient blocks, one substream = blocks [tile_first[s],
+// tile_first[s+1]).  What the walks read and write; members a walk does not read are null.  The first eight are every walk's.
+struct ParseIn {
+  const cabac_substream_desc *desc;
+  const uint8_t *bytes;
+  const uint32_t *tile_first;
+  const cabac_tu_desc *tus;
+  void *coeff;
+  int coeff_bytes;    // 4 or 2
+  uint32_t *tu_info;  // may be null: per block scanPosLast | CABAC_TU_INFO_*
+  cabac_substream_result *results;
+  const uint32_t *tu_at;     // block t goes in front of index tu_at[t] of its substream's run (null: behind the run)
+  const uint32_t *tu_guard;  // may be null: one guard word per block
+  const uint32_t *plan;      // 2 words per entry: the binariser's word0, a guard word
+  uint32_t *values;          // values[rec_offset + i] receives the value of entry i
+  const uint16_t *records;   // the side records of the unit walk ...
+  uint8_t *side_bins;        // ... and side_bins[rec_offset + i] the bin of side record i
+};
+// kResidual: blocks alone.  kUnit (cabac_hip_parse_unit.h): substream s = the side records records[desc[s].rec_offset .. +
+// n_records) with the blocks spliced in, all on one context store.  kElement (cabac_hip_parse_elements.h): the run is a plan of
+// syntax elements.  kPlan (cabac_hip_parse_plan.h): the element walk with the two computed entry kinds, on the same operands.
+enum class ParseWalk { kResidual, kUnit, kElement, kPlan };
+hipError_t launch_parse(hipStream_t st, ParseWalk walk, uint32_t n_sub, const ParseIn &in);
 // the plan walk from and into context sets (cabac_hip_plan_rows.h): substream s hands its contexts over when the walk arrives at
 // entry out_at[s] (out_at null: behind the substream).  A start index at or above start_bound is a bad one.  slot_base
 // 0xffffffff: the out sets are sets.out_set's; otherwise substream s writes set slot_base + s and sets.out_set is not read
-hipError_t launch_plan_parse_sets(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                  const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
-                                  const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
-                                  cabac_substream_result *results, const CtxSets &sets, const uint32_t *out_at, uint32_t start_bound,
-                                  uint32_t slot_base);
+hipError_t launch_plan_parse_sets(hipStream_t st, uint32_t n_sub, const ParseIn &in, const CtxSets &sets, const uint32_t *out_at,
+                                  uint32_t start_bound, uint32_t slot_base);
 // the plan walk in pieces (cabac_hip_plan_resume.h): the sets form (out set behind the piece) from and into a coder state per substream
-hipError_t launch_plan_parse_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                    const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
-                                    const uint32_t *plan, void *coeff, int coeff_bytes /* 4 or 2 */, uint32_t *values, uint32_t *tu_info,
-                                    cabac_substream_result *results, const CtxPieces &pieces);
+hipError_t launch_plan_parse_pieces(hipStream_t st, uint32_t n_sub, const ParseIn &in, const CtxPieces &pieces);
 
 // residual records spliced into host-recorded substreams (cabac_splice.hip); array sizes: pre n_splice + n_sub + 1,
 // sub_n / sub_cap / rec_base / byte_base n_sub, seen n_tu, err 1, totals 3 ({records, bytes, error})

@@ -2146,12 +2146,20 @@ hipError_t launch_wpp_level(hipStream_t st, uint32_t first, uint32_t n, const ca
 }
 
 // ---------------------------------------------------------------------------------------------
+// Each dispatch below is written once, over the pack: `sets` is one CtxSets (the instantiations that start from and write context
+// sets) or nothing (the plain ones); the public functions call it with *sets or without.
+template <class F>
+static hipError_t with_sets(const CtxSets *sets, F dispatch) {
+  return sets != nullptr ? dispatch(*sets) : dispatch();
+}
+
 hipError_t launch_encode_v4(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
                             uint8_t *bytes, cabac_substream_result *results, const CtxSets *sets) {
-  const dim3 grid((n_sub + kQuadSubs - 1) / kQuadSubs);
-  if (sets != nullptr) hipLaunchKernelGGL(encode_kernel_v4<CtxSets>, grid, dim3(64), 0, st, n_sub, desc, records, bytes, results, *sets);
-  else hipLaunchKernelGGL(encode_kernel_v4<>, grid, dim3(64), 0, st, n_sub, desc, records, bytes, results);
-  return hipGetLastError();
+  return with_sets(sets, [&](auto... s) {
+    hipLaunchKernelGGL(encode_kernel_v4<decltype(s)...>, dim3((n_sub + kQuadSubs - 1) / kQuadSubs), dim3(64), 0, st, n_sub, desc, records,
+                       bytes, results, s...);
+    return hipGetLastError();
+  });
 }
 
 // the pieces calls (cabac_hip_pieces.h): the coder state loaded, checked and stored by the same kernels, one geometry each
@@ -2173,27 +2181,28 @@ hipError_t launch_encode_v6(hipStream_t st, uint32_t n_sub, const cabac_substrea
                             uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight, const CtxSets *sets) {
   const uint32_t units = (n_sub + kQuadSubs - 1) / kQuadSubs;
   const uint32_t units_on_chip = (max(n_sub, in_flight) + kQuadSubs - 1) / kQuadSubs;
-  if (sets != nullptr) {  // the same geometries, from / into context sets
-    if (units_on_chip >= 1024u) hipLaunchKernelGGL((encode_kernel_v6<4, 1, CtxSets>), dim3((units + 3) / 4), dim3(1024), 0, st, n_sub, desc, records, bytes, results, *sets);
-    else hipLaunchKernelGGL((encode_kernel_v6<1, 2, CtxSets>), dim3(units), dim3(256), 0, st, n_sub, desc, records, bytes, results, *sets);
+  return with_sets(sets, [&](auto... s) {
+    if (units_on_chip >= 1024u)
+      hipLaunchKernelGGL((encode_kernel_v6<4, 1, decltype(s)...>), dim3((units + 3) / 4), dim3(1024), 0, st, n_sub, desc, records, bytes,
+                         results, s...);
+    else
+      hipLaunchKernelGGL((encode_kernel_v6<1, 2, decltype(s)...>), dim3(units), dim3(256), 0, st, n_sub, desc, records, bytes, results, s...);
     return hipGetLastError();
-  }
-  if (units_on_chip >= 1024u) hipLaunchKernelGGL((encode_kernel_v6<4, 1>), dim3((units + 3) / 4), dim3(1024), 0, st, n_sub, desc, records, bytes, results);
-  else hipLaunchKernelGGL((encode_kernel_v6<1, 2>), dim3(units), dim3(256), 0, st, n_sub, desc, records, bytes, results);
-  return hipGetLastError();
+  });
 }
 
 hipError_t launch_encode_v7(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
                             uint8_t *bytes, cabac_substream_result *results, uint32_t in_flight, const CtxSets *sets) {
-  if (sets != nullptr) {
-    if (max(n_sub, in_flight) >= 1024u) hipLaunchKernelGGL((encode_kernel_v7<4, CtxSets>), dim3((n_sub + 15) / 16), dim3(448), 0, st, n_sub, desc, records, bytes, results, *sets);
-    else hipLaunchKernelGGL((encode_kernel_v7<1, CtxSets>), dim3((n_sub + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes, results, *sets);
+  return with_sets(sets, [&](auto... s) {
+    // sixteen substreams per workgroup once there are enough of them to give every CU one; four below that
+    if (max(n_sub, in_flight) >= 1024u)
+      hipLaunchKernelGGL((encode_kernel_v7<4, decltype(s)...>), dim3((n_sub + 15) / 16), dim3(448), 0, st, n_sub, desc, records, bytes,
+                         results, s...);
+    else
+      hipLaunchKernelGGL((encode_kernel_v7<1, decltype(s)...>), dim3((n_sub + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes,
+                         results, s...);
     return hipGetLastError();
-  }
-  // sixteen substreams per workgroup once there are enough of them to give every CU one; four below that
-  if (max(n_sub, in_flight) >= 1024u) hipLaunchKernelGGL(encode_kernel_v7<4>, dim3((n_sub + 15) / 16), dim3(448), 0, st, n_sub, desc, records, bytes, results);
-  else hipLaunchKernelGGL(encode_kernel_v7<1>, dim3((n_sub + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes, results);
-  return hipGetLastError();
+  });
 }
 
 // How many substreams of the longest one's length the batch is worth: sum of n_records / max n_records.  The sixteen-per-wave
@@ -2261,92 +2270,62 @@ __global__ __launch_bounds__(1024) void decode_select_solo_kernel(uint32_t n_sub
   if (threadIdx.x == 0) *select = (longest != 0u && past <= max_long) ? 2u : 0u;
 }
 
-static hipError_t launch_decode_v4_sets(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                                        const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight,
-                                        int lanes_per_sub, uint32_t *select, const CtxSets &sets);
-
-constexpr uint32_t kSoloUpTo = 1024;
-constexpr uint32_t kSoloAskUpTo = 3072;  // ... and up to here the batch is looked at on the device (below the headline's 4 096)  // substreams in flight up to which each gets a wave (and a SIMD) of its own
+constexpr uint32_t kSoloUpTo = 1024;     // substreams in flight up to which each gets a wave (and a SIMD) of its own ...
+constexpr uint32_t kSoloAskUpTo = 3072;  // ... and up to here the batch is looked at on the device (below the headline's 4 096)
 constexpr uint32_t kHexFrom = 9216;  // measured (tools/batch_scaling.py): 8 192 equal substreams 2.12 ms quad / 2.23 ms hex, 12 288: 3.14 / 2.23
 
-hipError_t launch_decode_v4(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                            const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight, int lanes_per_sub,
-                            uint32_t *select, const CtxSets *sets) {
-  if (sets != nullptr) return launch_decode_v4_sets(st, n_sub, desc, records, bytes, bins, results, in_flight, lanes_per_sub, select, *sets);
+// The decoder's dispatch, over the same pack.  A geometry is decode_kernel_v4<W, L> in workgroups of 64 * W threads that hold
+// W * 64 / L substreams; one that the device chooses (`chosen`: the device word) returns at once unless the word holds its `mine`.
+template <class... Sets>
+static hipError_t decode_v4_dispatch(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                                     const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight,
+                                     int lanes_per_sub, uint32_t *select, const Sets &...sets) {
+  const uint32_t on_chip = max(n_sub, in_flight);
+  auto launch = [&](auto kernel, uint32_t W, uint32_t L, const uint32_t *chosen = nullptr, uint32_t mine = 0u) {
+    const uint32_t per_group = W * 64u / L;
+    hipLaunchKernelGGL(kernel, dim3((n_sub + per_group - 1u) / per_group), dim3(64u * W), 0, st, n_sub, desc, records, bytes, bins, results,
+                       chosen, mine, sets...);
+  };
   if (lanes_per_sub == 0) {  // auto
-    // up to one substream per SIMD: a wave each, 64 bins a step (16 ... 1 024 C4-type substreams 1.13-1.16 ms against 1.30)
-    if (max(n_sub, in_flight) <= kSoloUpTo) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 64);
-    if (select != nullptr && max(n_sub, in_flight) <= kSoloAskUpTo && in_flight <= n_sub) {  // (not for chunks of a bigger batch)
+    if (on_chip <= kSoloUpTo) {
+      // up to one substream per SIMD: a wave each, 64 bins a step (16 ... 1 024 C4-type substreams 1.13-1.16 ms against 1.30)
+      lanes_per_sub = 64;
+    } else if (select != nullptr && on_chip <= kSoloAskUpTo && in_flight <= n_sub) {  // (not for chunks of a bigger batch)
       hipLaunchKernelGGL(decode_select_solo_kernel, dim3(1), dim3(1024), 0, st, n_sub, desc, kSoloUpTo, select);
-      hipLaunchKernelGGL((decode_kernel_v4<4, 64>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 2u);
-      hipLaunchKernelGGL((decode_kernel_v4<4, 16>), dim3((n_sub + 15u) / 16u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 0u);
+      launch(decode_kernel_v4<4, 64, Sets...>, 4, 64, select, 2u);
+      launch(decode_kernel_v4<4, 16, Sets...>, 4, 16, select, 0u);
+      return hipGetLastError();
+    } else if (on_chip < kHexFrom || select == nullptr) {
+      lanes_per_sub = 16;
+    } else {
+      // enough substreams for the sixteen-per-wave geometry IF they are about equally long: asked on the device, both
+      // geometries launched, the one not chosen returns at once
+      // (a chunk of a bigger batch in flight is judged by its share of the threshold)
+      const uint32_t thr = (uint32_t)((uint64_t)kHexFrom * n_sub / on_chip);
+      hipLaunchKernelGGL(decode_select_kernel, dim3(1), dim3(1024), 0, st, n_sub, desc, thr, select);
+      launch(decode_kernel_v4<4, 4, Sets...>, 4, 4, select, 1u);
+      launch(decode_kernel_v4<4, 16, Sets...>, 4, 16, select, 0u);
       return hipGetLastError();
     }
-    if (max(n_sub, in_flight) < kHexFrom || select == nullptr) return launch_decode_v4(st, n_sub, desc, records, bytes, bins, results, in_flight, 16);
-    // enough substreams for the sixteen-per-wave geometry IF they are about equally long: asked on the device, both
-    // geometries launched, the one not chosen returns at once
-    // (a chunk of a bigger batch in flight is judged by its share of the threshold)
-    const uint32_t thr = (uint32_t)((uint64_t)kHexFrom * n_sub / max(n_sub, in_flight));
-    hipLaunchKernelGGL(decode_select_kernel, dim3(1), dim3(1024), 0, st, n_sub, desc, thr, select);
-    hipLaunchKernelGGL((decode_kernel_v4<4, 4>), dim3((n_sub + 63u) / 64u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 1u);
-    hipLaunchKernelGGL((decode_kernel_v4<4, 16>), dim3((n_sub + 15u) / 16u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 0u);
-    return hipGetLastError();
   }
-  const uint32_t waves = (n_sub + kQuadSubs - 1) / kQuadSubs;
   if (lanes_per_sub == 64) {  // one substream per wave, 64 bins per step: the per-step work around the chain is spread over 64 bins
-    if (max(n_sub, in_flight) >= 1024u)
-      hipLaunchKernelGGL((decode_kernel_v4<4, 64>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results,
-                         (const uint32_t *)nullptr, 0u);
-    else
-      hipLaunchKernelGGL((decode_kernel_v4<1, 64>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, records, bytes, bins, results,
-                         (const uint32_t *)nullptr, 0u);
+    if (on_chip >= 1024u) launch(decode_kernel_v4<4, 64, Sets...>, 4, 64);
+    else launch(decode_kernel_v4<1, 64, Sets...>, 1, 64);
   } else if (lanes_per_sub == 4) {  // sixteen substreams per wave, 64 per workgroup (one workgroup's LDS fills most of a CU)
-    hipLaunchKernelGGL((decode_kernel_v4<4, 4>), dim3((n_sub + 63u) / 64u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results,
-                       (const uint32_t *)nullptr, 0u);
-  } else if ((max(n_sub, in_flight) + kQuadSubs - 1) / kQuadSubs >= 1024u) {
-    hipLaunchKernelGGL(decode_kernel_v4<4>, dim3((waves + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes, bins,
-                       results, (const uint32_t *)nullptr, 0u);
+    launch(decode_kernel_v4<4, 4, Sets...>, 4, 4);
+  } else if ((on_chip + kQuadSubs - 1) / kQuadSubs >= 1024u) {  // four substreams per wave: four-wave workgroups pin one wave per SIMD
+    launch(decode_kernel_v4<4, 16, Sets...>, 4, 16);
   } else {
-    hipLaunchKernelGGL(decode_kernel_v4<1>, dim3(waves), dim3(64), 0, st, n_sub, desc, records, bytes, bins, results,
-                       (const uint32_t *)nullptr, 0u);
+    launch(decode_kernel_v4<1, 16, Sets...>, 1, 16);
   }
   return hipGetLastError();
 }
 
-// the dispatch above, geometry for geometry, with the instantiations that start from and write context sets
-static hipError_t launch_decode_v4_sets(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                                        const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight,
-                                        int lanes_per_sub, uint32_t *select, const CtxSets &sets) {
-  const uint32_t *const no_select = nullptr;
-  if (lanes_per_sub == 0) {  // auto
-    if (max(n_sub, in_flight) <= kSoloUpTo) return launch_decode_v4_sets(st, n_sub, desc, records, bytes, bins, results, in_flight, 64, select, sets);
-    if (select != nullptr && max(n_sub, in_flight) <= kSoloAskUpTo && in_flight <= n_sub) {
-      hipLaunchKernelGGL(decode_select_solo_kernel, dim3(1), dim3(1024), 0, st, n_sub, desc, kSoloUpTo, select);
-      hipLaunchKernelGGL((decode_kernel_v4<4, 64, CtxSets>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 2u, sets);
-      hipLaunchKernelGGL((decode_kernel_v4<4, 16, CtxSets>), dim3((n_sub + 15u) / 16u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 0u, sets);
-      return hipGetLastError();
-    }
-    if (max(n_sub, in_flight) < kHexFrom || select == nullptr) return launch_decode_v4_sets(st, n_sub, desc, records, bytes, bins, results, in_flight, 16, select, sets);
-    const uint32_t thr = (uint32_t)((uint64_t)kHexFrom * n_sub / max(n_sub, in_flight));
-    hipLaunchKernelGGL(decode_select_kernel, dim3(1), dim3(1024), 0, st, n_sub, desc, thr, select);
-    hipLaunchKernelGGL((decode_kernel_v4<4, 4, CtxSets>), dim3((n_sub + 63u) / 64u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 1u, sets);
-    hipLaunchKernelGGL((decode_kernel_v4<4, 16, CtxSets>), dim3((n_sub + 15u) / 16u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, select, 0u, sets);
-    return hipGetLastError();
-  }
-  const uint32_t waves = (n_sub + kQuadSubs - 1) / kQuadSubs;
-  if (lanes_per_sub == 64) {
-    if (max(n_sub, in_flight) >= 1024u)
-      hipLaunchKernelGGL((decode_kernel_v4<4, 64, CtxSets>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, no_select, 0u, sets);
-    else
-      hipLaunchKernelGGL((decode_kernel_v4<1, 64, CtxSets>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, records, bytes, bins, results, no_select, 0u, sets);
-  } else if (lanes_per_sub == 4) {
-    hipLaunchKernelGGL((decode_kernel_v4<4, 4, CtxSets>), dim3((n_sub + 63u) / 64u), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, no_select, 0u, sets);
-  } else if ((max(n_sub, in_flight) + kQuadSubs - 1) / kQuadSubs >= 1024u) {
-    hipLaunchKernelGGL((decode_kernel_v4<4, 16, CtxSets>), dim3((waves + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes, bins, results, no_select, 0u, sets);
-  } else {
-    hipLaunchKernelGGL((decode_kernel_v4<1, 16, CtxSets>), dim3(waves), dim3(64), 0, st, n_sub, desc, records, bytes, bins, results, no_select, 0u, sets);
-  }
-  return hipGetLastError();
+hipError_t launch_decode_v4(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
+                            const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight, int lanes_per_sub,
+                            uint32_t *select, const CtxSets *sets) {
+  if (sets == nullptr) return decode_v4_dispatch(st, n_sub, desc, records, bytes, bins, results, in_flight, lanes_per_sub, select);
+  return decode_v4_dispatch(st, n_sub, desc, records, bytes, bins, results, in_flight, lanes_per_sub, select, *sets);
 }
 
 }  // namespace cabac

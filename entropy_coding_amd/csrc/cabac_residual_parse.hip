@@ -1392,148 +1392,58 @@ hipError_t debug_read_parse_prof(unsigned long long *out) {
 }
 #endif
 
-template <class C>
-static hipError_t launch_residual_parse_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                           const uint32_t *tile_first, const cabac_tu_desc *tus, C *coeff, uint32_t *tu_info,
-                                           cabac_substream_result *results) {
-  // four waves per workgroup, one per SIMD of the CU; small batches spread single waves over the chip
-  if (n_sub >= 1024u)
-    hipLaunchKernelGGL((residual_parse_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus,
-                       coeff, tu_info, results);
-  else
-    hipLaunchKernelGGL((residual_parse_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, coeff, tu_info,
-                       results);
-  return hipGetLastError();
-}
-
-template <class C>
-static hipError_t launch_unit_parse_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                       const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
-                                       const uint16_t *records, C *coeff, uint8_t *side_bins, uint32_t *tu_info,
-                                       cabac_substream_result *results) {
-  // the parser's geometry and threshold
-  if (n_sub >= 1024u)
-    hipLaunchKernelGGL((unit_parse_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at,
-                       records, coeff, side_bins, tu_info, results);
-  else
-    hipLaunchKernelGGL((unit_parse_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at, records,
-                       coeff, side_bins, tu_info, results);
-  return hipGetLastError();
-}
-
-hipError_t launch_unit_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                             const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint16_t *records,
-                             void *coeff, int coeff_bytes, uint8_t *side_bins, uint32_t *tu_info, cabac_substream_result *results) {
-  if (n_sub == 0) return hipSuccess;
-  if (coeff_bytes == 2)
-    return launch_unit_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, records, static_cast<int16_t *>(coeff), side_bins, tu_info, results);
-  if (coeff_bytes == 4)
-    return launch_unit_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, records, static_cast<int32_t *>(coeff), side_bins, tu_info, results);
+// The family's two host choices, each made once: int16_t or int32_t coefficients, and one wave per workgroup or four.  `launch`
+// receives the waves as a std::integral_constant, the typed coefficients, the grid and the workgroup, and launches its kernel.
+template <class F>
+static hipError_t parse_dispatch(uint32_t n_sub, const ParseIn &in, F launch) {
+  auto as = [&](auto *coeff) {
+    // four waves per workgroup, one per SIMD of the CU; small batches spread single waves over the chip
+    if (n_sub >= 1024u) launch(std::integral_constant<int, 4>{}, coeff, dim3((n_sub + 3u) / 4u), dim3(256));
+    else launch(std::integral_constant<int, 1>{}, coeff, dim3(n_sub), dim3(64));
+    return hipGetLastError();
+  };
+  if (in.coeff_bytes == 2) return as(static_cast<int16_t *>(in.coeff));
+  if (in.coeff_bytes == 4) return as(static_cast<int32_t *>(in.coeff));
   return hipErrorInvalidValue;
 }
 
-template <class C>
-static hipError_t launch_element_parse_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                          const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
-                                          const uint32_t *tu_guard, const uint32_t *plan, C *coeff, uint32_t *values, uint32_t *tu_info,
-                                          cabac_substream_result *results) {
-  // the parser's geometry and threshold
-  if (n_sub >= 1024u)
-    hipLaunchKernelGGL((element_parse_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at,
-                       tu_guard, plan, coeff, values, tu_info, results);
-  else
-    hipLaunchKernelGGL((element_parse_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard,
-                       plan, coeff, values, tu_info, results);
-  return hipGetLastError();
+// What a launch lambda is given, as the kernels' template arguments
+#define PARSE_W decltype(w)::value
+#define PARSE_C std::remove_pointer_t<decltype(coeff)>
+
+// The forms, in the order their kernels have in the code object.
+static hipError_t unit_walk(hipStream_t st, uint32_t n_sub, const ParseIn &in) {
+  return parse_dispatch(n_sub, in, [&](auto w, auto *coeff, dim3 grid, dim3 group) {
+    hipLaunchKernelGGL((unit_parse_kernel<PARSE_W, PARSE_C>), grid, group, 0, st, n_sub, in.desc, in.bytes, in.tile_first, in.tus, in.tu_at,
+                       in.records, coeff, in.side_bins, in.tu_info, in.results);
+  });
 }
 
-hipError_t launch_element_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
-                                const uint32_t *plan, void *coeff, int coeff_bytes, uint32_t *values, uint32_t *tu_info,
-                                cabac_substream_result *results) {
-  if (n_sub == 0) return hipSuccess;
-  if (coeff_bytes == 2)
-    return launch_element_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results);
-  if (coeff_bytes == 4)
-    return launch_element_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results);
-  return hipErrorInvalidValue;
+static hipError_t element_walk(hipStream_t st, uint32_t n_sub, const ParseIn &in) {
+  return parse_dispatch(n_sub, in, [&](auto w, auto *coeff, dim3 grid, dim3 group) {
+    hipLaunchKernelGGL((element_parse_kernel<PARSE_W, PARSE_C>), grid, group, 0, st, n_sub, in.desc, in.bytes, in.tile_first, in.tus,
+                       in.tu_at, in.tu_guard, in.plan, coeff, in.values, in.tu_info, in.results);
+  });
 }
 
-template <class C>
-static hipError_t launch_plan_parse_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                       const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
-                                       const uint32_t *tu_guard, const uint32_t *plan, C *coeff, uint32_t *values, uint32_t *tu_info,
-                                       cabac_substream_result *results) {
-  // the parser's geometry and threshold
-  if (n_sub >= 1024u)
-    hipLaunchKernelGGL((plan_parse_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at,
-                       tu_guard, plan, coeff, values, tu_info, results);
-  else
-    hipLaunchKernelGGL((plan_parse_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard,
-                       plan, coeff, values, tu_info, results);
-  return hipGetLastError();
+static hipError_t plan_walk(hipStream_t st, uint32_t n_sub, const ParseIn &in) {
+  return parse_dispatch(n_sub, in, [&](auto w, auto *coeff, dim3 grid, dim3 group) {
+    hipLaunchKernelGGL((plan_parse_kernel<PARSE_W, PARSE_C>), grid, group, 0, st, n_sub, in.desc, in.bytes, in.tile_first, in.tus, in.tu_at,
+                       in.tu_guard, in.plan, coeff, in.values, in.tu_info, in.results);
+  });
 }
 
-hipError_t launch_plan_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                             const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
-                             const uint32_t *plan, void *coeff, int coeff_bytes, uint32_t *values, uint32_t *tu_info,
-                             cabac_substream_result *results) {
-  if (n_sub == 0) return hipSuccess;
-  if (coeff_bytes == 2)
-    return launch_plan_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results);
-  if (coeff_bytes == 4)
-    return launch_plan_parse_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results);
-  return hipErrorInvalidValue;
-}
-
-template <class C>
-static hipError_t launch_plan_parse_sets_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                            const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
-                                            const uint32_t *tu_guard, const uint32_t *plan, C *coeff, uint32_t *values, uint32_t *tu_info,
-                                            cabac_substream_result *results, const ParseSets &ps) {
-  // the parser's geometry and threshold
-  if (n_sub >= 1024u)
-    hipLaunchKernelGGL((plan_parse_sets_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus,
-                       tu_at, tu_guard, plan, coeff, values, tu_info, results, ps);
-  else
-    hipLaunchKernelGGL((plan_parse_sets_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at,
-                       tu_guard, plan, coeff, values, tu_info, results, ps);
-  return hipGetLastError();
-}
-
-hipError_t launch_plan_parse_sets(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                  const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
-                                  const uint32_t *plan, void *coeff, int coeff_bytes, uint32_t *values, uint32_t *tu_info,
-                                  cabac_substream_result *results, const CtxSets &sets, const uint32_t *out_at, uint32_t start_bound,
-                                  uint32_t slot_base) {
+hipError_t launch_plan_parse_sets(hipStream_t st, uint32_t n_sub, const ParseIn &in, const CtxSets &sets, const uint32_t *out_at,
+                                  uint32_t start_bound, uint32_t slot_base) {
   if (n_sub == 0) return hipSuccess;
   const ParseSets ps{sets, out_at, start_bound, slot_base};
-  if (coeff_bytes == 2)
-    return launch_plan_parse_sets_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results, ps);
-  if (coeff_bytes == 4)
-    return launch_plan_parse_sets_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results, ps);
-  return hipErrorInvalidValue;
+  return parse_dispatch(n_sub, in, [&](auto w, auto *coeff, dim3 grid, dim3 group) {
+    hipLaunchKernelGGL((plan_parse_sets_kernel<PARSE_W, PARSE_C>), grid, group, 0, st, n_sub, in.desc, in.bytes, in.tile_first, in.tus,
+                       in.tu_at, in.tu_guard, in.plan, coeff, in.values, in.tu_info, in.results, ps);
+  });
 }
 
-template <class C>
-static hipError_t launch_plan_parse_pieces_as(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                              const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at,
-                                              const uint32_t *tu_guard, const uint32_t *plan, C *coeff, uint32_t *values,
-                                              uint32_t *tu_info, cabac_substream_result *results, const ParsePieces &pp) {
-  // the parser's geometry and threshold
-  if (n_sub >= 1024u)
-    hipLaunchKernelGGL((plan_parse_pieces_kernel<4, C>), dim3((n_sub + 3u) / 4u), dim3(256), 0, st, n_sub, desc, bytes, tile_first, tus,
-                       tu_at, tu_guard, plan, coeff, values, tu_info, results, pp);
-  else
-    hipLaunchKernelGGL((plan_parse_pieces_kernel<1, C>), dim3(n_sub), dim3(64), 0, st, n_sub, desc, bytes, tile_first, tus, tu_at,
-                       tu_guard, plan, coeff, values, tu_info, results, pp);
-  return hipGetLastError();
-}
-
-hipError_t launch_plan_parse_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                    const uint32_t *tile_first, const cabac_tu_desc *tus, const uint32_t *tu_at, const uint32_t *tu_guard,
-                                    const uint32_t *plan, void *coeff, int coeff_bytes, uint32_t *values, uint32_t *tu_info,
-                                    cabac_substream_result *results, const CtxPieces &pieces) {
+hipError_t launch_plan_parse_pieces(hipStream_t st, uint32_t n_sub, const ParseIn &in, const CtxPieces &pieces) {
   if (n_sub == 0) return hipSuccess;
   ParsePieces pp;  // the out set is behind the piece, always: no hand-over entry; start indices below n_sets; out sets as out_set says
   pp.cs = pieces;
@@ -1542,19 +1452,27 @@ hipError_t launch_plan_parse_pieces(hipStream_t st, uint32_t n_sub, const cabac_
   pp.slot_base = 0xffffffffu;
   pp.coder_in = pieces.coder_in;
   pp.coder_out = pieces.coder_out;
-  if (coeff_bytes == 2)
-    return launch_plan_parse_pieces_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int16_t *>(coeff), values, tu_info, results, pp);
-  if (coeff_bytes == 4)
-    return launch_plan_parse_pieces_as(st, n_sub, desc, bytes, tile_first, tus, tu_at, tu_guard, plan, static_cast<int32_t *>(coeff), values, tu_info, results, pp);
-  return hipErrorInvalidValue;
+  return parse_dispatch(n_sub, in, [&](auto w, auto *coeff, dim3 grid, dim3 group) {
+    hipLaunchKernelGGL((plan_parse_pieces_kernel<PARSE_W, PARSE_C>), grid, group, 0, st, n_sub, in.desc, in.bytes, in.tile_first, in.tus,
+                       in.tu_at, in.tu_guard, in.plan, coeff, in.values, in.tu_info, in.results, pp);
+  });
 }
 
-hipError_t launch_residual_parse(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint8_t *bytes,
-                                 const uint32_t *tile_first, const cabac_tu_desc *tus, void *coeff, int coeff_bytes, uint32_t *tu_info,
-                                 cabac_substream_result *results) {
+static hipError_t residual_walk(hipStream_t st, uint32_t n_sub, const ParseIn &in) {
+  return parse_dispatch(n_sub, in, [&](auto w, auto *coeff, dim3 grid, dim3 group) {
+    hipLaunchKernelGGL((residual_parse_kernel<PARSE_W, PARSE_C>), grid, group, 0, st, n_sub, in.desc, in.bytes, in.tile_first, in.tus, coeff,
+                       in.tu_info, in.results);
+  });
+}
+
+hipError_t launch_parse(hipStream_t st, ParseWalk walk, uint32_t n_sub, const ParseIn &in) {
   if (n_sub == 0) return hipSuccess;
-  if (coeff_bytes == 2) return launch_residual_parse_as(st, n_sub, desc, bytes, tile_first, tus, static_cast<int16_t *>(coeff), tu_info, results);
-  if (coeff_bytes == 4) return launch_residual_parse_as(st, n_sub, desc, bytes, tile_first, tus, static_cast<int32_t *>(coeff), tu_info, results);
+  switch (walk) {
+  case ParseWalk::kResidual: return residual_walk(st, n_sub, in);
+  case ParseWalk::kUnit: return unit_walk(st, n_sub, in);
+  case ParseWalk::kElement: return element_walk(st, n_sub, in);
+  case ParseWalk::kPlan: return plan_walk(st, n_sub, in);
+  }
   return hipErrorInvalidValue;
 }
 

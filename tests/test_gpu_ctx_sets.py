@@ -437,3 +437,71 @@ def test_a_batch_large_enough_for_the_big_geometries(hip):
     assert np.array_equal(bins[:len(records)], records >> 15) and np.array_equal(dres["n_bits"], M.decode_sets(desc, records, ref_b, sets, start)[1]["n_bits"])
     assert not dres["flags"].any() and np.array_equal(host(os_, np.uint32), want_state)
     assert np.array_equal(host(or_, np.uint8), np.concatenate([M.pack(c)[1] for c in left]))
+
+
+@functools.lru_cache(None)
+def short_batch(n_sub, seed, lo, hi, first=None):
+    """n_sub substreams of lo .. hi - 1 records, the closing terminate bin counted (first: substream 0's number instead), start
+    sets mixed with NO_SET -> (desc, records, total, start, and the model's bytes, results and contexts left)"""
+    sets, _, _ = start_sets()
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(lo, hi, size=n_sub)
+    if first is not None:
+        lens[0] = first
+    recs = [H.random_records(rng, int(n) - 1, ctx_frac=0.85, ctx_pool=np.arange(86, 292)) if n else np.zeros(0, np.uint16) for n in lens]
+    desc, total = H.make_desc([len(r) for r in recs], rng.integers(0, 64, size=n_sub), rng.integers(0, 3, size=n_sub), FIN)
+    assert desc["n_records"].tolist() == lens.tolist()
+    records = np.concatenate(recs).astype(np.uint16)
+    start = np.where(rng.random(n_sub) < 0.3, M.NO_SET, rng.integers(0, N_SETS, size=n_sub)).astype(np.uint32)
+    return (desc, records, total, start) + M.encode_sets(desc, records, total, sets, start)
+
+
+def check_decode_from_sets(c, desc, records, start, ref_b, left):
+    """Decode from sets, every substream into its own out set, against the model: bins, results, out sets"""
+    sets, _, _ = start_sets()
+    n_sub = len(desc)
+    state, rate = padded(n_sub)
+    os_, or_ = sentinel_sets(n_sub)
+    bins, dres = run_decode(c, desc, records, ref_b, state, rate, start, np.arange(n_sub, dtype=np.uint32), os_, or_)
+    want_bins, want_res, want_left = M.decode_sets(desc, records, ref_b, sets, start)
+    assert np.array_equal(bins[:len(records)], want_bins) and np.array_equal(want_bins, records >> 15)
+    assert np.array_equal(dres, want_res) and not dres["flags"][desc["n_records"] != 0].any()   # (an empty one has no stop bit)
+    assert np.array_equal(host(os_, np.uint32), np.concatenate([M.pack(x)[0] for x in want_left]).astype(np.uint32))
+    assert np.array_equal(host(or_, np.uint8), np.concatenate([M.pack(x)[1] for x in want_left]))
+    assert np.array_equal(host(os_, np.uint32), np.concatenate([M.pack(x)[0] for x in left]).astype(np.uint32))
+
+
+def test_sets_in_four_wave_workgroups_of_the_forced_variants():
+    """4 100 substreams of 0 .. 20 records under the forced variants (6, 4): 1 025 units, so encode_kernel_v6 and the quad decoder
+    run their sets instantiations in four-unit / four-wave workgroups, the last of which holds one live unit."""
+    c = H.gpu_ctx()
+    try:
+        c.set_variant(6, 4)
+        n_sub = 4100
+        desc, records, total, start, ref_b, ref_r, left = short_batch(n_sub, 9500, 0, 21)
+        state, rate = padded(n_sub)
+        os_, or_ = sentinel_sets(n_sub)
+        got_b, got_r = run_encode(c, desc, records, total, state, rate, start, np.arange(n_sub, dtype=np.uint32), os_, or_)
+        assert np.array_equal(got_r, ref_r)
+        same_coded_bytes(desc, got_b, ref_b, ref_r)
+        assert np.array_equal(host(os_, np.uint32), np.concatenate([M.pack(x)[0] for x in left]).astype(np.uint32))
+        assert np.array_equal(host(or_, np.uint8), np.concatenate([M.pack(x)[1] for x in left]))
+        check_decode_from_sets(c, desc, records, start, ref_b, left)
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("longest", [8, 2000], ids=["equal-sixteen-per-wave", "one-long-quad"])
+def test_sets_under_the_device_side_choice_of_the_dispatch(longest):
+    """9 300 substreams (from 9 216 the dispatch asks on the device) of 8 records each: the batch is worth 9 300 of its longest, so
+    the device takes sixteen per wave; with substream 0 at 2 000 records it is worth 38 of them and the quad decoder runs.  Both
+    geometries are launched with sets either way; the one not chosen must write nothing."""
+    c = H.gpu_ctx()
+    try:
+        n_sub = 9300
+        desc, records, total, start, ref_b, ref_r, left = short_batch(n_sub, 9600, 8, 9, first=longest)
+        worth = int(desc["n_records"].sum()) // int(desc["n_records"].max())   # substreams of the longest one's length
+        assert (worth >= 9216) == (longest == 8)
+        check_decode_from_sets(c, desc, records, start, ref_b, left)
+    finally:
+        c.close()

@@ -333,6 +333,42 @@ def test_rows_parse_of_one_level_is_the_plain_call(hip):
         assert np.array_equal(a[key], b[key]), key
 
 
+@functools.lru_cache(maxsize=None)
+def wide_level():
+    """1 027 rows of one transform unit each in level 0 — one launch of four-wave workgroups whose last one has three live waves —
+    and five rows in level 1 that start from slots of level 0, the first and the last among them, and from Ctx::init.  Level 0
+    repeats twelve rows (every row of it starts from Ctx::init, so the model codes each once); sync_at differs with the row."""
+    rng = np.random.default_rng(0x9B04)
+    n0, froms = 1027, [0, 511, 1026, NO, 1024]
+    pool = [R.tu_row(rng, [(0, 0, 1, 0, 0, 0)]) for _ in range(12)]          # luma alone is coded: one small block per row
+    ats = [5, 0, PM.TU_LEN, PM.TU_LEN + 1, 10 ** 6, 12]
+    pool_w = [R.write_row(r, CS.init_set(r["qp"], 2), ats[k % len(ats)]) for k, r in enumerate(pool)]
+    rows = [pool[s % 12] for s in range(n0)] + [R.tu_row(rng, [OUTCOMES3[k % 3]]) for k in range(len(froms))]
+    sync_at = [ats[(s % 12) % len(ats)] for s in range(n0)] + [0] * len(froms)
+    written = [pool_w[s % 12] for s in range(n0)]
+    for k, f in enumerate(froms):
+        row = rows[n0 + k]
+        written.append(R.write_row(row, CS.init_set(row["qp"], 2) if f == NO else written[f]["handed"], 0))
+    no_skips(pool + rows[n0:])
+    return rows, [0, n0, n0 + len(froms)], [NO] * n0 + froms, sync_at, written
+
+
+@pytest.mark.parametrize("int16", [False, True], ids=["int32", "int16"])
+def test_rows_parse_across_the_four_wave_switch(hip, int16):
+    """Levels [0, 1027, 1032]: level 0 is at the parser's switch to four waves per workgroup (1 024 substreams in one launch), and
+    level 1's pointers start 1 027 substreams into every per-substream array."""
+    rows, level_first, sync_from, sync_at, written = wide_level()
+    units = [unit_of(r, w) for r, w in zip(rows, written)]
+    r = parse(hip, units, int16, entry="rows", rows=(level_first, sync_from, sync_at))
+    r["int16"] = int16
+    for s, (row, w) in enumerate(zip(rows, written)):
+        assert_row(r, s, row, w, "wide level")
+    # the links count: a linked row read from Ctx::init is not what was written
+    linked = [s for s in range(level_first[1], level_first[2]) if sync_from[s] != NO and sync_at[sync_from[s]] != 0]
+    plain = run_plain(hip, [units[s] for s in linked], int16)
+    assert any(plain["values"][k].tolist() != written[s]["values"] or int(plain["res"]["flags"][k]) != 0 for k, s in enumerate(linked))
+
+
 def _host_buffers(P, int16=False):
     return (np.full(P["total"], sentinel(int16), np.int16 if int16 else np.int32), np.full(len(P["plan"]), VAL_GUARD, np.uint32),
             np.full(P["n_tu"], WORD_GUARD_U, np.uint32))
