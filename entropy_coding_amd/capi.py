@@ -137,6 +137,8 @@ CODER_STATE_DTYPE = np.dtype([("kind", "<u4"), ("flags", "<u4"), ("bits", "<u4")
 assert CODER_STATE_DTYPE.itemsize == 32
 CODER_FRESH, CODER_ENC, CODER_DEC, CODER_CLOSED = 0, 1, 2, 3     # CABAC_CODER_*
 RES_BAD_STATE = 0x80                                             # CABAC_RES_BAD_STATE
+# include/cabac_hip_piece_encoder.h (which encoder codes the pieces: a per-ctx setting; tests/test_piece_encoder_abi.py compares)
+EXPORTS_PIECE_ENCODER = ["cabac_hip_piece_encoder_set", "cabac_hip_piece_encoder_get"]
 # include/cabac_hip_plan_resume.h (the plan parse in pieces: resumed from a coder state; tests/test_plan_resume_abi.py compares)
 EXPORTS_PLAN_RESUME = ["cabac_hip_plan_resume_parse_device"]
 # include/cabac_hip_plan_continue.h (the plan write in pieces: continued from a coder state; tests/test_plan_continue_abi.py compares)
@@ -332,6 +334,9 @@ def load_library():
     if hasattr(L, "cabac_hip_encode_pieces_device"):   # (a library from before cabac_hip_pieces.h: the calls then fail where they are made)
         L.cabac_hip_encode_pieces_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp] + sets7 + [vp, vp]
         L.cabac_hip_decode_pieces_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp] + sets7 + [vp, vp]
+    if hasattr(L, "cabac_hip_piece_encoder_set"):      # (a library from before cabac_hip_piece_encoder.h: the calls then fail where they are made)
+        L.cabac_hip_piece_encoder_set.argtypes = [vp, ctypes.c_int]
+        L.cabac_hip_piece_encoder_get.argtypes = [vp]
     L.cabac_hip_residual_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_residual_parse_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp]
     L.cabac_hip_residual_parse_batch.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, vp, vp]
@@ -684,6 +689,14 @@ class CabacHip:
 
     def set_variant(self, enc=0, dec=0):
         self._check(self.L.cabac_hip_set_variant(self.h, enc, dec))
+
+    def piece_encoder_set(self, variant):
+        """cabac_hip_piece_encoder.h: the encoder of encode_pieces_device and of plan_continue_write_device's encode leg —
+        4 (the default), 7 or 0 = by the batch.  Any other value raises CabacHipError (status ERR_INVALID); the setting stays."""
+        self._check(self.L.cabac_hip_piece_encoder_set(self.h, variant))
+
+    def piece_encoder_get(self):
+        return int(self.L.cabac_hip_piece_encoder_get(self.h))
 
     def synchronize(self):
         self._check(self.L.cabac_hip_synchronize(self.h))

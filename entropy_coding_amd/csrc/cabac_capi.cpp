@@ -31,6 +31,7 @@
 #include "cabac_hip.h"
 #include "cabac_hip_ctx_sets.h"
 #include "cabac_hip_pieces.h"
+#include "cabac_hip_piece_encoder.h"
 #include "cabac_hip_estimate.h"
 #include "cabac_hip_nal.h"
 #include "cabac_hip_parse_elements.h"
@@ -119,6 +120,7 @@ struct cabac_hip_ctx {
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   bool timed = false;
   int enc_variant = 0, dec_variant = 0;
+  int piece_encoder = 4;  // cabac_hip_piece_encoder.h: the encoder of the pieces calls (4, 7, 0 = by the batch)
   std::string last_error;
   // per-launch profiling ring (cabac_hip_profile_enable)
   std::vector<hipEvent_t> prof_ev;  // 2 per slot
@@ -3371,6 +3373,27 @@ int cabac_hip_ctx_advance_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   return TIMED_LAUNCH(c, 32, cabac::launch_ctx_advance(c->stream, n_sub, d_desc, d_records, sets, d_flags));
 }
 
+// ---- the encoder of the pieces calls (cabac_hip_piece_encoder.h) -----------------------------------------------------------------
+// Setting 0: the lane-serial encoder from this many substreams in the call, the in-wave one below.  Measured (tools/bench_piece_encoder.py,
+// profiles/piece_encoder.json: four pieces of substreams of 16 384 records, the first N of the 1080p batch, setting 4 / setting 7):
+// N = 256 1.563 / 0.500 ms, 1 024 1.575 / 0.568, 2 048 1.691 / 0.575, 4 096 1.636 / 0.602 — 7 never loses, so the threshold is 0
+// and setting 0 is setting 7 on every batch measured.  Results never depend on it.
+static constexpr uint32_t kPieceEncoderV7From = 0;
+
+static int piece_encoder_for(const cabac_hip_ctx *c, uint32_t n_sub) {
+  if (c->piece_encoder != 0) return c->piece_encoder;
+  return (kPieceEncoderV7From == 0u || n_sub >= kPieceEncoderV7From) ? 7 : 4;
+}
+
+int cabac_hip_piece_encoder_set(cabac_hip_ctx *c, int variant) {
+  if (!c) return CABAC_HIP_ERR_INVALID;
+  if (variant != 4 && variant != 7 && variant != 0) return fail(c, CABAC_HIP_ERR_INVALID, "piece encoder: 4, 7 or 0");
+  c->piece_encoder = variant;
+  return CABAC_HIP_OK;
+}
+
+int cabac_hip_piece_encoder_get(const cabac_hip_ctx *c) { return c ? c->piece_encoder : CABAC_HIP_ERR_INVALID; }
+
 // ---- the bin codec in pieces (cabac_hip_pieces.h): not dispatched, one geometry each ----------------------------------------------
 int cabac_hip_encode_pieces_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
                                    uint8_t *d_bytes, cabac_substream_result *d_results, uint32_t n_sets, const uint32_t *d_state,
@@ -3382,7 +3405,8 @@ int cabac_hip_encode_pieces_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac
   if (n_sub == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
   const cabac::CtxPieces pieces{{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate}, d_coder_in, d_coder_out};
-  return TIMED_LAUNCH(c, 48, cabac::launch_encode_pieces(c->stream, n_sub, d_desc, d_records, d_bytes, d_results, pieces));
+  return TIMED_LAUNCH(c, 48, cabac::launch_encode_pieces(c->stream, n_sub, d_desc, d_records, d_bytes, d_results, pieces,
+                                                         piece_encoder_for(c, n_sub)));
 }
 
 int cabac_hip_decode_pieces_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
@@ -3604,7 +3628,7 @@ int cabac_hip_plan_continue_write_device(cabac_hip_ctx *c, uint32_t n_sub, const
   }
   {
     Timed t(c, 51);
-    HIP_TRY(c, cabac::launch_encode_pieces(c->stream, n_sub, w.desc2, exp_rec, d_bytes, d_results, pieces));
+    HIP_TRY(c, cabac::launch_encode_pieces(c->stream, n_sub, w.desc2, exp_rec, d_bytes, d_results, pieces, piece_encoder_for(c, n_sub)));
     HIP_TRY(c, cabac::launch_plan_stops_pieces(c->stream, n_sub, w.sub_flag, d_results, pieces.coder_out));
   }
   return CABAC_HIP_OK;

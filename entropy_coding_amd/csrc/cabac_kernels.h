@@ -63,9 +63,11 @@ hipError_t launch_decode_v4(hipStream_t st, uint32_t n_sub, const cabac_substrea
                             const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, uint32_t in_flight = 0,
                             int lanes_per_sub = 16, uint32_t *select = nullptr, const CtxSets *sets = nullptr);
 
-// the bin codec in pieces (cabac_hip_pieces.h): one geometry each, not dispatched
+// the bin codec in pieces (cabac_hip_pieces.h): not dispatched.  The decoder has one geometry; the encoder the caller's choice
+// (cabac_hip_piece_encoder.h), variant 4: one wave per four substreams, 7: the lane-serial encoder, sixteen substreams per
+// workgroup from 1 024 substreams and four below — everything they write is the same
 hipError_t launch_encode_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                                uint8_t *bytes, cabac_substream_result *results, const CtxPieces &pieces);
+                                uint8_t *bytes, cabac_substream_result *results, const CtxPieces &pieces, int variant);
 hipError_t launch_decode_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
                                 const uint8_t *bytes, uint8_t *bins, cabac_substream_result *results, const CtxPieces &pieces);
 

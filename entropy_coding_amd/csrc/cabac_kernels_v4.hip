@@ -897,6 +897,7 @@ __global__ __launch_bounds__(64 * (U + 3)) void encode_kernel_v7(uint32_t n_sub,
                                                                       uint8_t *__restrict__ bytes,
                                                                       cabac_substream_result *__restrict__ results, Sets... sets) {
   constexpr bool kSets = sizeof...(Sets) != 0;
+  constexpr bool kPieces = kQuadPieces<Sets...>;  // cabac_hip_piece_encoder.h: the coder state comes from and goes to memory
   constexpr uint32_t S = U * kQuadSubs;
   __shared__ uint32_t ctx_all[S * kQuadCtxStride];
   __shared__ __attribute__((aligned(16))) uint32_t fld[4][kV7Fields][S * kV7Pad];  // context waves -> chain / low wave
@@ -905,6 +906,7 @@ __global__ __launch_bounds__(64 * (U + 3)) void encode_kernel_v7(uint32_t n_sub,
   __shared__ __attribute__((aligned(16))) uint32_t wpost[2][(S + 1) * kV7Pad];
   __shared__ uint32_t post_lo[U][2][4 * kQuadSubs], post_hi[U][2][4 * kQuadSubs], post_pend[U][2][4 * kQuadSubs];  // low -> output (v5's posts)
   __shared__ uint32_t fin_lo[S], fin_hi[S], fin_pend[S];
+  __shared__ uint32_t fin_range[S];  // pieces only (64 bytes at U = 4; no other instantiation refers to it, so none of them holds it)
   __shared__ uint32_t unit_list[U][kQuadSubs][kUnitSlots];
   // What a record id means comes from a table (quad_resolve<.., kKindTab>) where context waves share a SIMD with the chain
   // and the low wave, U = 4: 22 of the context wave's 137 instructions per step less, 4 096 substreams 0.530 -> 0.514 ms
@@ -962,9 +964,22 @@ __global__ __launch_bounds__(64 * (U + 3)) void encode_kernel_v7(uint32_t n_sub,
   }
   const uint32_t sub = blockIdx.x * S + local;
   const QuadSetUse su = quad_set_use(sub, sub < n_sub, sets...);
-  const bool in_batch = sub < n_sub && !su.bad;
-  const bool live = in_batch && in_range;
+  bool in_batch = sub < n_sub && !su.bad;
   const cabac_substream_desc d = desc[in_batch ? sub : 0];
+  // Pieces: every role loads and checks the state of its substream here (32 bytes, the same for all lanes of a substream) and
+  // takes from it what it owns — the chain wave the range, the low wave low and pend, the output wave the buffered unit, the
+  // count and the position.  A substream that is refused or comes with flags idles with n = 0: it keeps every barrier count,
+  // writes no byte and no set (refused) and its n = 0 is what enters wg_max_n.  IN PLACE (coder_out == coder_in): these are
+  // the only reads of coder_in in front of the last barrier, and they stand before the first one; the store, and the
+  // re-read inside quad_piece_pass, come behind the last one, from the one lane that owns the substream (output wave).
+  QuadPieceUse piece{};
+  QuadSetUse su_out = su;
+  if constexpr (kPieces) {
+    piece = quad_piece_use<true>(sub, sub < n_sub, su.bad, d.byte_capacity, sets...);
+    in_batch = in_batch && piece.code;
+    if (piece.refuse) su_out.out = kNoSet;
+  }
+  const bool live = in_batch && in_range;
   const uint32_t n = in_batch ? d.n_records : 0u;
 
   if (threadIdx.x == 0) wg_max_n = 0;
@@ -1023,7 +1038,7 @@ __global__ __launch_bounds__(64 * (U + 3)) void encode_kernel_v7(uint32_t n_sub,
       asm volatile("" ::: "memory");
       __builtin_amdgcn_wave_barrier();
       asm volatile("" ::: "memory");
-      quad_ctx_export(rctx, j, 16u, su, sets...);
+      quad_ctx_export(rctx, j, 16u, su_out, sets...);  // (su_out is su but for a refused piece: no set written)
     }
     __syncthreads();
     __syncthreads();
@@ -1031,6 +1046,7 @@ __global__ __launch_bounds__(64 * (U + 3)) void encode_kernel_v7(uint32_t n_sub,
     // ---- chain wave: lane = substream ------------------------------------------------------------------------
     __builtin_amdgcn_s_setprio(3);
     uint32_t range = 510;  // start(), arith_codec.cpp:329-337
+    if constexpr (kPieces) range = piece.range;  // checked by quad_piece_use: 256..510
     __syncthreads();
     for (uint32_t k = 0; k < n_steps; k++) {
       V5_TICK(t0);
@@ -1054,6 +1070,7 @@ __global__ __launch_bounds__(64 * (U + 3)) void encode_kernel_v7(uint32_t n_sub,
       V5_ADD(2, t0, t1);
       V5_ADD(3, t1, t2);
     }
+    if constexpr (kPieces) fin_range[local] = range;  // (lanes past the last substream mirror it: the same value)
     __syncthreads();
     __syncthreads();
   } else if (is_low) {
@@ -1068,6 +1085,10 @@ __global__ __launch_bounds__(64 * (U + 3)) void encode_kernel_v7(uint32_t n_sub,
     // quad_enc_step).  low < 2^58 before a cut, as there. ----
     uint64_t low = 0;       // the state behind the last quarter, in all four lanes of a substream
     uint32_t pend = 0;
+    if constexpr (kPieces) {  // checked by quad_piece_use: pend < 16, low inside its 10 + pend bits — the state behind a cut (below)
+      low = piece.low;
+      pend = piece.pend;
+    }
     const uint32_t pu = local >> 2, pr = local & 3u, q = j;
     auto quad_from_left = [](uint32_t v) {   // lane q of a quad gets lane q - 1 (quad_perm:[0,0,1,2]; quarter 0 does not use it)
       return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x90, 0xf, 0xf, true);
@@ -1142,6 +1163,11 @@ __global__ __launch_bounds__(64 * (U + 3)) void encode_kernel_v7(uint32_t n_sub,
     e.buf = 0;
     e.nbuf = 0;
     e.pos = 0;
+    if constexpr (kPieces) {  // checked by quad_piece_use: pos even, pos + 2 nbuf <= the capacity
+      e.buf = piece.buf;
+      e.nbuf = (int32_t)piece.nbuf;
+      e.pos = piece.pos;
+    }
     e.dst = bytes + d.byte_offset;
     e.cap = live ? d.byte_capacity : 0u;
     const bool writer = live && j == 0;
@@ -1182,6 +1208,28 @@ __global__ __launch_bounds__(64 * (U + 3)) void encode_kernel_v7(uint32_t n_sub,
     }
     e.low = ((uint64_t)fin_hi[local] << 32) | fin_lo[local];
     e.pend = (int32_t)fin_pend[local];
+    if constexpr (kPieces) {
+      // The tail of encode_kernel_v4's pieces form, from the substream's first lane.  A piece without FINISH flushes nothing:
+      // the low wave has cut whole units after bins 3, 7, 11, 15 of every step, so pend < 16, and what is left — low, the
+      // buffered unit, the outstanding 0xFFFF units, the chain wave's range — is the state.  Behind the LAST barrier (in place,
+      // see where the state is loaded): nothing reads coder_in any more but quad_piece_pass, this lane, its own substream.
+      __syncthreads();
+      const CtxPieces &cp = quad_pack_first(sets...);
+      const bool fin = (d.init_id & CABAC_SUB_FINISH) != 0;
+      const uint32_t n_bits = live ? quad_enc_finish(e, (d.init_id & CABAC_SUB_ALIGN_RBSP) != 0, writer, !fin) : 0u;
+      if (writer) {
+        const uint32_t ends = fin ? e.pos : e.pos + 2u * (uint32_t)e.nbuf;
+        cabac_substream_result res;
+        res.n_bits = n_bits;
+        res.flags = (ends > e.cap ? CABAC_RES_OVERFLOW : 0u) | (((bad_rows[unit] >> row) & 1u) ? CABAC_RES_BAD_RECORD : 0u);
+        results[sub] = res;
+        if (fin) quad_piece_store(cp, sub, CABAC_CODER_CLOSED, res.flags, n_bits, e.pos, 0u, 0u, 0u, 0u);
+        else quad_piece_store(cp, sub, CABAC_CODER_ENC, res.flags, n_bits, e.pos, (uint32_t)e.low, fin_range[local] | ((uint32_t)e.pend << 16),
+                              e.buf, (uint32_t)e.nbuf);
+      }
+      quad_piece_pass(results, sub, sub < n_sub && in_range && j == 0, piece, cp);
+      return;
+    }
     const uint32_t n_bits = live ? quad_enc_finish(e, (d.init_id & CABAC_SUB_ALIGN_RBSP) != 0, writer, (d.init_id & CABAC_SUB_PROBE) != 0) : 0u;
     if (writer) {
       cabac_substream_result res;
@@ -2162,9 +2210,21 @@ hipError_t launch_encode_v4(hipStream_t st, uint32_t n_sub, const cabac_substrea
   });
 }
 
-// the pieces calls (cabac_hip_pieces.h): the coder state loaded, checked and stored by the same kernels, one geometry each
+// the pieces calls (cabac_hip_pieces.h): the coder state loaded, checked and stored by the same kernels.  The encoder in one of two
+// geometries (cabac_hip_piece_encoder.h), same bytes, results, sets and states: variant 4 the in-wave one, 7 the lane-serial one
+// with launch_encode_v7's rule for its two sizes (in_flight = 0)
 hipError_t launch_encode_pieces(hipStream_t st, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
-                                uint8_t *bytes, cabac_substream_result *results, const CtxPieces &pieces) {
+                                uint8_t *bytes, cabac_substream_result *results, const CtxPieces &pieces, int variant) {
+  if (variant == 7) {
+    if (n_sub >= 1024u)
+      hipLaunchKernelGGL((encode_kernel_v7<4, CtxPieces>), dim3((n_sub + 15) / 16), dim3(448), 0, st, n_sub, desc, records, bytes, results,
+                         pieces);
+    else
+      hipLaunchKernelGGL((encode_kernel_v7<1, CtxPieces>), dim3((n_sub + 3) / 4), dim3(256), 0, st, n_sub, desc, records, bytes, results,
+                         pieces);
+    return hipGetLastError();
+  }
+  if (variant != 4) return hipErrorInvalidValue;
   hipLaunchKernelGGL(encode_kernel_v4<CtxPieces>, dim3((n_sub + kQuadSubs - 1) / kQuadSubs), dim3(64), 0, st, n_sub, desc, records, bytes,
                      results, pieces);
   return hipGetLastError();

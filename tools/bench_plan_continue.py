@@ -11,6 +11,8 @@ bin.  Device buffers resident.  Legs, ALTERNATING in one run (rep by rep):
   pieces_4         the same substreams in 4 equal pieces (100 cbfs and their blocks each; the terminate bin in the last): 4 calls,
                    state and contexts handed over in place
   pieces_16        in 16 equal pieces (25 blocks: the "CTU" of tools/bench_plan_rows.py)
+  pieces_K_enc7    (--piece-encoder 7) the three pieces legs again under cabac_hip_piece_encoder_set(ctx, 7): the encode leg on
+                   the lane-serial encoder, the one the one call's dispatch picks (include/cabac_hip_piece_encoder.h)
 Before anything is timed every leg runs once and its bytes, results, values, info words and out sets are compared with the one
 call's.  Two times per leg and round, 2 warm-up + R timed rounds, median / minimum / maximum:
   device   the sum of the HIP events of cabac_hip_profile_enable around the launches of the leg
@@ -21,14 +23,14 @@ leg's time, reported per leg.
 
 EXPECTATION, stated before the run: ONE piece costs at most 1.10 x the one-call form of the parent's build, device time, same run
 (the standing bound of profiles/pieces.json and profiles/plan_resume.json).  Reported as met / MISSED with the 4- and 16-piece
-ratios; the bound is no gate.  Without --parent-library the ratio is taken against this build's one_call and says so.
+ratios; the bound is no gate.  With --piece-encoder 7 the same is reported for pieces_1_enc7 ("expectation_enc7").  Without --parent-library the ratio is taken against this build's one_call and says so.
 
 --label parent (with CABAC_HIP_LIBRARY naming a build of the parent): only the one_call leg, which the parent has too, is run and
 stored under "parent"; a later run under another label reports its legs over that one as well.
 
 Writes one JSON object (--out, default profiles/plan_continue.json; merged with what the file holds under other labels).
 
-  python tools/bench_plan_continue.py [--tiles 4096] [--reps 7] [--parent-library FILE] [--label NAME] [--out FILE]
+  python tools/bench_plan_continue.py [--tiles 4096] [--reps 7] [--parent-library FILE] [--piece-encoder 7] [--label NAME] [--out FILE]
 """
 import argparse
 import json
@@ -80,6 +82,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--parent-library", default=None)
     ap.add_argument("--label", default="this")
+    ap.add_argument("--piece-encoder", type=int, default=4, choices=(4, 7), help="7: the pieces legs under setting 7 as well")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plan_continue.json"))
     a = ap.parse_args()
     assert a.reps >= 3
@@ -161,7 +164,8 @@ def main():
                 ls.append((dev(dp), t_first_p, t_tu_p, t_at_p, t_info_p, p, L))
             launches[P] = ls
 
-    def pieces(P):
+    def pieces(P, setting=4):
+        hip.piece_encoder_set(setting)
         for t_dp, t_first_p, t_tu_p, t_at_p, t_info_p, p, L in launches[P]:
             hip.plan_continue_write_device(n_sub, t_dp.data_ptr(), t_plan.data_ptr(), t_vin.data_ptr(), t_first_p.data_ptr(), n_sub * L,
                                            t_tu_p.data_ptr(), t_at_p.data_ptr(), t_gd.data_ptr(), t_co.data_ptr(), t_slots.data_ptr(),
@@ -174,6 +178,8 @@ def main():
         legs.insert(0, ("parent_one_call", lambda: one_call(parent)))
     if not only_plain:
         legs += [("pieces_%d" % P, (lambda P=P: pieces(P))) for P in PIECES]
+        if a.piece_encoder == 7:
+            legs += [("pieces_%d_enc7" % P, (lambda P=P: pieces(P, 7))) for P in PIECES]
     owner = {name: (parent if name == "parent_one_call" else hip) for name, _ in legs}
 
     def clear():
@@ -254,7 +260,18 @@ def main():
                               "ratio": ratio, "verdict": "met" if ratio <= BOUND else "MISSED"}
         print("expectation %s: pieces_1 / parent one_call = %.3f (pieces_4 %.3f, pieces_16 %.3f); host wait share of pieces_1 %.2f" %
               (out["expectation"]["verdict"], ratio, out["pieces_4_over_parent"], out["pieces_16_over_parent"], out["pieces_1"]["host_wait_share"]))
+        if a.piece_encoder == 7:
+            for P in PIECES:
+                out["pieces_%d_enc7_over_parent" % P] = out["pieces_%d_enc7" % P]["device"]["ms_median"] / base["ms_median"]
+                out["pieces_%d_enc7_over_one_call" % P] = out["pieces_%d_enc7" % P]["device"]["ms_median"] / out["one_call"]["device"]["ms_median"]
+            ratio = out["pieces_1_enc7_over_parent"]
+            out["expectation_enc7"] = {"text": "pieces_1_enc7 <= %.2f x one_call (device time), against %s" % (BOUND, against), "bound": BOUND,
+                                       "ratio": ratio, "verdict": "met" if ratio <= BOUND else "MISSED"}
+            print("expectation under setting 7 %s: pieces_1_enc7 / one_call = %.3f (pieces_4_enc7 %.3f, pieces_16_enc7 %.3f)" %
+                  (out["expectation_enc7"]["verdict"], ratio, out["pieces_4_enc7_over_parent"], out["pieces_16_enc7_over_parent"]))
     merged[a.label] = out
+    if not only_plain:
+        hip.piece_encoder_set(4)
     hip.close()
     if parent is not None:
         parent.close()
