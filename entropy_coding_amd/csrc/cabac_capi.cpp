@@ -11,8 +11,10 @@
 // host-pointer forms of the parser family (residual, unit, element and plan parse, the rows parse included) share their host
 // checks (check_substream_host, check_plan_host, check_coeff_ranges_host) and their staging (ParseStage), the family's device calls
 // their operands (cabac::ParseIn) and their prelude (parse_device_call); the device pipelines of the plan write share their
-// tables and the one wait (plan_write_tables, wait_for_totals); the pipelined
-// host-pointer forms each keep their own stream choreography.  The blocking runtime calls go through counting helpers (wait_stream,
+// tables and the one wait (plan_write_tables, wait_for_totals).  Every other host-pointer form but the chunked codec pipeline stages
+// through Stage (a slot, the copy, the typed pointer; plain or through the bounce ring) and shares what it has in common with another:
+// stage_rows, CandStage, PayloadReturn, check_records_host, flags_status; the device pipelines take operand structs (SpliceIn,
+// cabac::PlanWriteIn, PayloadOut).  The pipelined forms keep their own stream choreography.  The blocking runtime calls go through counting helpers (wait_stream,
 // device_alloc, ...: cabac_hip_workspace_waits); on a ctx with a fixed workspace (cabac_hip_workspace.h) the three pipelines that wait
 // in the middle take a branch that queues a gate kernel instead.
 #include <hip/hip_runtime.h>
@@ -304,6 +306,33 @@ int check_desc_host(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc
   return CABAC_HIP_OK;
 }
 
+// What a form that takes bin records and no byte ranges refuses about substream s: its record range, its init_id, then `more` (the
+// form's own finding about s, or null).  named: the message begins "substream s: " (the rows form of the spliced call), else it is bare
+int check_records_host(cabac_hip_ctx *c, uint32_t s, const cabac_substream_desc &d, uint64_t n_records_total, const char *more = nullptr,
+                       bool named = false) {
+  const char *what = more;
+  if (d.rec_offset > n_records_total || d.n_records > n_records_total - d.rec_offset) what = "records out of range";
+  else if ((d.init_id & 3u) > 2u) what = "init_id must be 0..2";
+  if (!what) return CABAC_HIP_OK;
+  char buf[96];
+  snprintf(buf, sizeof buf, "substream %u: %s", s, what);
+  return fail(c, CABAC_HIP_ERR_INVALID, named ? buf : what);
+}
+
+// The flags (or results) a call fetched, to the caller's array where there is one (out null, or got itself: nothing to copy); any of
+// them set: CABAC_HIP_ERR_SUBSTREAM and the form's message.  status: what the form has found so far
+inline uint32_t flag_of(uint32_t f) { return f; }
+inline uint32_t flag_of(const cabac_substream_result &r) { return r.flags; }
+template <class T>
+int flags_status(cabac_hip_ctx *c, uint32_t n, const T *got, T *out, const char *message, int status = CABAC_HIP_OK) {
+  for (uint32_t i = 0; i < n; i++) {
+    if (out && out != got) out[i] = got[i];
+    if (flag_of(got[i])) status = CABAC_HIP_ERR_SUBSTREAM;
+  }
+  if (status) c->last_error = message;
+  return status;
+}
+
 // ---- the host checks of the parser family's host-pointer forms, in the order every form runs them: per substream the three
 // checks below and then the form's own, and behind all substreams the blocks' coefficient ranges -------------------------------
 // bytes_total: null where the descriptors' byte ranges are not input (the plan write, the plan round)
@@ -519,6 +548,116 @@ int d2h_drain(cabac_hip_ctx *c) {
   return CABAC_HIP_OK;
 }
 
+// ---- the staging of every host-pointer form but the chunked codec pipeline (encode_batch_impl / decode_batch_impl, which moves
+// pieces of its arrays on several streams): room for `count` elements of T in a slot, the caller's array copied into it, the typed
+// device pointer back.  Two transports: the plain copy on the ctx stream (up), or with `ring` h2d on `st` (pinned memory DMA'd where
+// it lies, pageable memory through the bounce ring).  The first failure sticks: every later call does nothing and returns null, so
+// a form stages all it needs in the order the copies are to run and asks once (rc).
+struct Stage {
+  cabac_hip_ctx *c;
+  bool ring = false;
+  hipStream_t st = nullptr;
+  int rc = CABAC_HIP_OK;
+
+  // room bytes in the slot; n of them from src where there is something to copy (n 0: nothing is issued)
+  void *bytes(int slot, size_t room, const void *src, size_t n) {
+    if (rc || (rc = ensure(c, slot, room))) return nullptr;
+    void *d = c->d_buf[slot];
+    if (ring) rc = h2d(c, d, src, n, st);
+    else if (hipError_t e = up(c, d, src, n); e != hipSuccess) rc = fail_hip(c, e, "up(c, d, src, n)");
+    return rc ? nullptr : d;
+  }
+  // room for count + pad elements, the first count of them from src
+  template <class T>
+  T *put(int slot, size_t count, const T *src, size_t pad = 0) {
+    return static_cast<T *>(bytes(slot, (count + pad) * sizeof(T), src, count * sizeof(T)));
+  }
+  template <class T>
+  T *room(int slot, size_t count) { return static_cast<T *>(bytes(slot, count * sizeof(T), nullptr, 0)); }
+  // an array the caller may leave out: the slot all the same, a null pointer for the kernels
+  template <class T>
+  T *opt(int slot, size_t count, const T *src) {
+    T *d = src ? put(slot, count, src) : room<T>(slot, count);
+    return src ? d : nullptr;
+  }
+};
+
+// What every payload-producing device pipeline writes (the spliced encode, the plan write, the log's emit): the compacted payload,
+// its offsets, the results, and the blocks' info words (may be null)
+struct PayloadOut {
+  uint8_t *d_payload;
+  uint64_t payload_capacity;
+  uint64_t *d_payload_offsets;
+  cabac_substream_result *d_results;
+  uint32_t *d_tu_info;
+};
+
+// What the spliced encode reads: side records per substream and the blocks spliced into them
+struct SpliceIn {
+  const cabac_substream_desc *d_desc;
+  const uint16_t *d_records;
+  const uint32_t *d_splice_first;
+  const cabac_splice *d_splices;
+  uint32_t n_splice, n_tu;
+  const cabac_tu_desc *d_tu;
+  const void *d_coeff;
+  int coeff_bytes;
+};
+
+// The way back of the two pipelined writer forms (the spliced encode, the plan write): results and offsets come back through the
+// pinned block h_pin[0] on the ctx stream, behind them one word the form may add; the payload follows on s_out once its size is
+// known.  prepare() before the uploads, fetch() behind the device pipeline (then the form's own d2h copies on s_out), finish() last.
+struct PayloadReturn {
+  cabac_hip_ctx *c;
+  uint32_t n_sub;
+  uint8_t *payload;
+  uint64_t payload_capacity;
+  uint64_t *payload_offsets;
+  cabac_substream_result *results;
+  PayloadOut d{};
+  cabac_substream_result *h_res = nullptr;
+  uint64_t *h_off = nullptr;
+  uint32_t *h_word = nullptr;
+
+  size_t res_bytes() const { return size_t(n_sub) * sizeof(cabac_substream_result); }
+  size_t off_bytes() const { return (size_t(n_sub) + 1) * sizeof(uint64_t); }
+
+  // the device side (d_tu_info: room for n_info words) and the pinned block
+  int prepare(Stage &st, size_t n_info) {
+    d = {st.room<uint8_t>(kPayload, payload_capacity ? payload_capacity : 16), payload_capacity,
+         st.room<uint64_t>(kPayloadOffsets, size_t(n_sub) + 1), st.room<cabac_substream_result>(kSpOutRes, n_sub),
+         st.room<uint32_t>(kSpOutInfo, n_info ? n_info : 1)};
+    if (st.rc) return st.rc;
+    if (int rc = ensure_pinned(c, 0, res_bytes() + off_bytes() + 64)) return rc;
+    h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
+    h_off = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(c->h_pin[0]) + res_bytes());
+    h_word = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(h_off) + off_bytes());
+    return CABAC_HIP_OK;
+  }
+
+  // d_word (may be null): a device word that comes back with the results, into *h_word.  Waits for them, refuses a payload that does
+  // not fit, queues the payload's copy
+  int fetch(const uint32_t *d_word) {
+    HIP_TRY(c, hipMemcpyAsync(h_res, d.d_results, res_bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_off, d.d_payload_offsets, off_bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (d_word) HIP_TRY(c, hipMemcpyAsync(h_word, d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_k[1], c->stream));
+    // the big things leave on the outgoing copy stream once the offsets are known
+    HIP_TRY(c, wait_event(c, c->ev_k[1]));
+    if (h_off[n_sub] > payload_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "payload_capacity too small");
+    return d2h(c, payload, d.d_payload, h_off[n_sub], c->s_out);
+  }
+
+  // everything queued on s_out has arrived; results and offsets to the caller; the flags (and what the form found: status) as the status
+  int finish(int status, const char *message) {
+    if (int rc = d2h_drain(c)) return rc;
+    HIP_TRY(c, wait_stream(c, c->s_out));
+    payload_offsets[0] = 0;
+    for (uint32_t s = 0; s < n_sub; s++) payload_offsets[s + 1] = h_off[s + 1];
+    return flags_status(c, n_sub, h_res, results, message, status);
+  }
+};
+
 // A batch cut at substream boundaries into chunks of about equal record counts.  Chunks need the substreams' record
 // and byte slots in ascending, non-overlapping order (what every packer produces); otherwise the batch is one chunk.
 struct Chunk {
@@ -658,6 +797,13 @@ int check_probes_host(cabac_hip_ctx *c, uint32_t n_sub, const uint32_t *probe_fi
 int check_rows_host(cabac_hip_ctx *c, uint32_t n_sub, const Rows &rows) {
   if (int bad = check_levels(c, n_sub, rows.n_level, rows.level_first)) return bad;
   return check_links_host(c, n_sub, rows.n_level, rows.level_first, rows.d_sync_from);
+}
+
+// the rows of a host-pointer form, staged: links and hand-over positions on the device, the levels where they are.  spliced: the form
+// of cabac_hip_splice_rows.h, which has a slot for the hand-over splice counts (the caller may still leave them out)
+Rows stage_rows(Stage &st, uint32_t n_sub, const Rows &rows, bool spliced) {
+  const uint32_t *from = st.put(kWppFrom, n_sub, rows.d_sync_from), *at = st.put(kWppAt, n_sub, rows.d_sync_at);
+  return Rows{rows.n_level, rows.level_first, from, at, spliced ? st.opt(kSpInSync, n_sub, rows.d_sync_splice) : nullptr};
 }
 
 // what a call on a fixed workspace (cabac_hip_workspace.h) may not exceed; checked before anything is queued.  (n_splice needs no
@@ -1297,34 +1443,21 @@ int cabac_hip_estimate_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_subst
                              uint64_t n_records_total, uint64_t *frac_bits, uint32_t *flags) {
   if (!c || (n_sub && (!desc || !frac_bits))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (n_sub == 0) return CABAC_HIP_OK;
-  for (uint32_t s = 0; s < n_sub; s++) {
-    if (desc[s].rec_offset > n_records_total || desc[s].n_records > n_records_total - desc[s].rec_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "records out of range");
-    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
-  }
+  for (uint32_t s = 0; s < n_sub; s++)
+    if (int bad = check_records_host(c, s, desc[s], n_records_total)) return bad;
   DeviceGuard g(c->device);
-  int rc;
-  if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
-  if ((rc = ensure(c, kFracBits, n_sub * sizeof(uint64_t)))) return rc;
-  if ((rc = ensure(c, kFlags, n_sub * sizeof(uint32_t)))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc), hipMemcpyHostToDevice, c->stream));
-  if (n_records_total)
-    HIP_TRY(c, hipMemcpyAsync(c->d_buf[kRecords], records, n_records_total * 2, hipMemcpyHostToDevice, c->stream));
-  rc = cabac_hip_estimate_device(c, n_sub, (const cabac_substream_desc *)c->d_buf[kDesc], (const uint16_t *)c->d_buf[kRecords],
-                                 (uint64_t *)c->d_buf[kFracBits], (uint32_t *)c->d_buf[kFlags]);
-  if (rc) return rc;
+  Stage st{c};
+  auto *d_desc = st.put(kDesc, n_sub, desc);
+  auto *d_rec = st.put(kRecords, n_records_total, records);
+  auto *d_bits = st.room<uint64_t>(kFracBits, n_sub);
+  auto *d_flags = st.room<uint32_t>(kFlags, n_sub);
+  if (st.rc) return st.rc;
+  if (int rc = cabac_hip_estimate_device(c, n_sub, d_desc, d_rec, d_bits, d_flags)) return rc;
   std::vector<uint32_t> fl(n_sub);
-  HIP_TRY(c, hipMemcpyAsync(frac_bits, c->d_buf[kFracBits], n_sub * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(fl.data(), c->d_buf[kFlags], n_sub * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, down(c, frac_bits, d_bits, n_sub * sizeof(uint64_t)));
+  HIP_TRY(c, down(c, fl.data(), d_flags, n_sub * sizeof(uint32_t)));
   HIP_TRY(c, wait_stream(c, c->stream));
-  int status = CABAC_HIP_OK;
-  for (uint32_t s = 0; s < n_sub; s++) {
-    if (flags) flags[s] = fl[s];
-    if (fl[s]) status = CABAC_HIP_ERR_SUBSTREAM;
-  }
-  if (status) c->last_error = "substream flag set (see flags[])";
-  return status;
+  return flags_status(c, n_sub, fl.data(), flags, "substream flag set (see flags[])");
 }
 
 // packed: `bins` receives (n_records_total + 7) / 8 bytes, bit (r & 7) of byte r >> 3 = the bin of record r
@@ -1433,27 +1566,20 @@ int cabac_hip_residual_batch(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_des
   if (!c || !offsets || (n_tu && (!tus || !coeff))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   offsets[0] = 0;
   if (n_tu == 0) return CABAC_HIP_OK;
-  for (uint32_t t = 0; t < n_tu; t++) {
-    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, reads nothing
-    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
-    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
-  }
+  if (int bad = check_coeff_ranges_host(c, n_tu, tus, n_coeff_total)) return bad;
   DeviceGuard g(c->device);
   int rc;
   // staging: kCounts holds the counts, then the info words
-  if ((rc = ensure(c, kDesc, n_tu * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, kCoeff, n_coeff_total * sizeof(int32_t)))) return rc;
-  if ((rc = ensure(c, kRecOffsets, n_tu * sizeof(uint64_t)))) return rc;
-  if ((rc = ensure(c, kCounts, 2 * size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  uint32_t *d_cnt = static_cast<uint32_t *>(c->d_buf[kCounts]), *d_info = d_cnt + n_tu;
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kDesc], tus, n_tu * sizeof(cabac_tu_desc), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kCoeff], coeff, n_coeff_total * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  rc = cabac_hip_residual_device(c, n_tu, (const cabac_tu_desc *)c->d_buf[kDesc], (const int32_t *)c->d_buf[kCoeff], nullptr, d_cnt,
-                                 d_info, nullptr);
-  if (rc) return rc;
+  Stage st{c};
+  auto *d_tu = st.put(kDesc, n_tu, tus);
+  auto *d_coeff = st.put(kCoeff, n_coeff_total, coeff);
+  auto *d_off = st.room<uint64_t>(kRecOffsets, n_tu);
+  uint32_t *d_cnt = st.room<uint32_t>(kCounts, 2 * size_t(n_tu));
+  if (st.rc) return st.rc;
+  uint32_t *d_info = d_cnt + n_tu;
+  if ((rc = cabac_hip_residual_device(c, n_tu, d_tu, d_coeff, nullptr, d_cnt, d_info, nullptr))) return rc;
   std::vector<uint32_t> cnt(2 * size_t(n_tu));
-  HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, down(c, cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t)));
   HIP_TRY(c, wait_stream(c, c->stream));
   int status = CABAC_HIP_OK;
   for (uint32_t t = 0; t < n_tu; t++) {
@@ -1465,12 +1591,11 @@ int cabac_hip_residual_batch(cabac_hip_ctx *c, uint32_t n_tu, const cabac_tu_des
   if (!records) return status;
   if (records_capacity < offsets[n_tu]) return fail(c, CABAC_HIP_ERR_INVALID, "records_capacity too small");
   if (offsets[n_tu] == 0) return status;
-  if ((rc = ensure(c, kOutRecords, offsets[n_tu] * sizeof(uint16_t)))) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kRecOffsets], offsets, n_tu * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-  rc = cabac_hip_residual_device(c, n_tu, (const cabac_tu_desc *)c->d_buf[kDesc], (const int32_t *)c->d_buf[kCoeff],
-                                 (const uint64_t *)c->d_buf[kRecOffsets], d_cnt, d_info, (uint16_t *)c->d_buf[kOutRecords]);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(records, c->d_buf[kOutRecords], offsets[n_tu] * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+  auto *d_rec = st.room<uint16_t>(kOutRecords, offsets[n_tu]);
+  st.put(kRecOffsets, n_tu, offsets);
+  if (st.rc) return st.rc;
+  if ((rc = cabac_hip_residual_device(c, n_tu, d_tu, d_coeff, d_off, d_cnt, d_info, d_rec))) return rc;
+  HIP_TRY(c, down(c, records, d_rec, offsets[n_tu] * sizeof(uint16_t)));
   HIP_TRY(c, wait_stream(c, c->stream));
   return status;
 }
@@ -1571,18 +1696,13 @@ int cabac_hip_parse_unit_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
   ParseStage st{c, n_sub, n_tu, coeff_bytes, n_coeff_total, n_tu != 0};
   int rc;
   if ((rc = st.stage(desc, bytes, bytes_total, tile_first, tus, coeff, nullptr))) return rc;
-  const size_t rec_bytes = size_t(n_records_total) * sizeof(uint16_t), bin_bytes = size_t(n_records_total);
-  if ((rc = ensure(c, kUnitRecords, rec_bytes))) return rc;
-  if ((rc = ensure(c, kUnitTuAt, st.tu_word_bytes()))) return rc;
-  if ((rc = ensure(c, kUnitBins, bin_bytes))) return rc;
-  HIP_TRY(c, up(c, c->d_buf[kUnitRecords], records, rec_bytes));
-  if (tu_at) HIP_TRY(c, up(c, c->d_buf[kUnitTuAt], tu_at, st.tu_word_bytes()));
-  HIP_TRY(c, up(c, c->d_buf[kUnitBins], side_bins, bin_bytes));  // what the walk does not write keeps the caller's values
-  st.in.tu_at = tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr;
-  st.in.records = (const uint16_t *)c->d_buf[kUnitRecords];
-  st.in.side_bins = (uint8_t *)c->d_buf[kUnitBins];
+  Stage own{c};
+  st.in.records = own.put(kUnitRecords, n_records_total, records);
+  st.in.tu_at = own.opt(kUnitTuAt, n_tu, tu_at);
+  st.in.side_bins = own.put(kUnitBins, n_records_total, side_bins);  // what the walk does not write keeps the caller's values
+  if (own.rc) return own.rc;
   if ((rc = parse_walk_device(c, cabac::ParseWalk::kUnit, 25, n_sub, st.in))) return rc;
-  HIP_TRY(c, down(c, side_bins, c->d_buf[kUnitBins], bin_bytes));
+  HIP_TRY(c, down(c, side_bins, st.in.side_bins, n_records_total));
   return st.finish(coeff, tu_info, results);
 }
 
@@ -1740,25 +1860,16 @@ static int parse_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   ParseStage st{c, n_sub, n_tu, coeff_bytes, n_coeff_total, n_tu != 0};
   int rc;
   if ((rc = st.stage(desc, bytes, bytes_total, tile_first, tus, coeff, tu_info))) return rc;
-  const size_t plan_bytes = size_t(n_elements_total) * 2 * sizeof(uint32_t), value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
-  const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
-  if ((rc = ensure(c, kUnitTuAt, st.tu_word_bytes()))) return rc;
-  if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
-  if ((rc = ensure(c, kElemGuard, st.tu_word_bytes()))) return rc;
-  if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
-  if (rows && ((rc = ensure(c, kWppFrom, link_bytes)) || (rc = ensure(c, kWppAt, link_bytes)))) return rc;
-  HIP_TRY(c, up(c, c->d_buf[kElemPlan], plan, plan_bytes));
-  if (tu_at) HIP_TRY(c, up(c, c->d_buf[kUnitTuAt], tu_at, st.tu_word_bytes()));
-  if (tu_guard) HIP_TRY(c, up(c, c->d_buf[kElemGuard], tu_guard, st.tu_word_bytes()));
-  HIP_TRY(c, up(c, c->d_buf[kElemValues], values, value_bytes));
-  st.in.tu_at = tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr;
-  st.in.tu_guard = tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr;
-  st.in.plan = (const uint32_t *)c->d_buf[kElemPlan];
-  st.in.values = (uint32_t *)c->d_buf[kElemValues];
+  const size_t value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
+  Stage own{c};
+  st.in.plan = own.put(kElemPlan, size_t(n_elements_total) * 2, plan);
+  st.in.tu_at = own.opt(kUnitTuAt, n_tu, tu_at);
+  st.in.tu_guard = own.opt(kElemGuard, n_tu, tu_guard);
+  st.in.values = own.put(kElemValues, n_elements_total, values);
+  Rows d_rows{};
+  if (rows) d_rows = stage_rows(own, n_sub, *rows, false);
+  if (own.rc) return own.rc;
   if (rows) {
-    HIP_TRY(c, up(c, c->d_buf[kWppFrom], rows->d_sync_from, link_bytes));
-    HIP_TRY(c, up(c, c->d_buf[kWppAt], rows->d_sync_at, link_bytes));
-    const Rows d_rows{rows->n_level, rows->level_first, (const uint32_t *)c->d_buf[kWppFrom], (const uint32_t *)c->d_buf[kWppAt]};
     rc = parse_rows_device_impl(c, n_sub, st.in, d_rows);
   } else if (rules.computed) {
     rc = parse_walk_device(c, cabac::ParseWalk::kPlan, 27, n_sub, st.in);
@@ -1793,13 +1904,11 @@ int cabac_hip_parse_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
 // becomes an index into its expanded string and the WPP encode schedule takes the encode launch's place.  Not both.  The plain
 // calls pass neither.  d_n_live (the log's emit on a fixed workspace; else null): the device word that says how many of the n_tu
 // blocks and n_splice splices count.
-static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
-                                       const uint32_t *d_splice_first, const cabac_splice *d_splices, uint32_t n_splice, uint32_t n_tu,
-                                       const cabac_tu_desc *d_tu, const void *d_coeff, int coeff_bytes, uint8_t *d_payload,
-                                       uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
-                                       uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets = nullptr,
-                                       const Rows *rows = nullptr, const uint64_t *d_n_live = nullptr,
+static int encode_residual_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const SpliceIn &in, const PayloadOut &out, uint32_t *d_bin_counts,
+                                       const cabac::CtxSets *sets = nullptr, const Rows *rows = nullptr, const uint64_t *d_n_live = nullptr,
                                        const SpliceProbes *probes = nullptr) {
+  const auto [d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes] = in;
+  const auto [d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info] = out;
   if (!c || !d_payload_offsets || (n_sub && (!d_desc || !d_records || !d_splice_first || !d_payload || !d_results)) ||
       (n_splice && !d_splices) || (n_tu && (!d_tu || !d_coeff)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
@@ -1926,8 +2035,8 @@ int cabac_hip_encode_residual_device(cabac_hip_ctx *c, uint32_t n_sub, const cab
                                      const cabac_tu_desc *d_tu, const int32_t *d_coeff, uint8_t *d_payload, uint64_t payload_capacity,
                                      uint64_t *d_payload_offsets, cabac_substream_result *d_results, uint32_t *d_tu_info,
                                      uint32_t *d_bin_counts) {
-  return encode_residual_device_impl(c, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, 4, d_payload,
-                                     payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts);
+  return encode_residual_device_impl(c, n_sub, {d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, 4},
+                                     {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_bin_counts);
 }
 
 int cabac_hip_encode_residual16_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
@@ -1935,8 +2044,8 @@ int cabac_hip_encode_residual16_device(cabac_hip_ctx *c, uint32_t n_sub, const c
                                        const cabac_tu_desc *d_tu, const int16_t *d_coeff, uint8_t *d_payload, uint64_t payload_capacity,
                                        uint64_t *d_payload_offsets, cabac_substream_result *d_results, uint32_t *d_tu_info,
                                        uint32_t *d_bin_counts) {
-  return encode_residual_device_impl(c, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, 2, d_payload,
-                                     payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts);
+  return encode_residual_device_impl(c, n_sub, {d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, 2},
+                                     {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_bin_counts);
 }
 
 static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
@@ -1953,148 +2062,80 @@ static int encode_batch_residual_impl(cabac_hip_ctx *c, uint32_t n_sub, const ca
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (probes)  // refused before anything is touched, payload_offsets[0] included
     if (int bad = check_probes_host(c, n_sub, probes->first, probes->at, probes->n)) return bad;
-  if (rows && n_sub) {  // refused before anything is touched, payload_offsets[0] included
+  if (rows && n_sub)
     if (int bad = check_rows_host(c, n_sub, *rows)) return bad;
-    for (uint32_t s = 0; s < n_sub; s++) {
-      const char *what = nullptr;
-      if (desc[s].rec_offset > n_records_total || desc[s].n_records > n_records_total - desc[s].rec_offset) what = "records out of range";
-      else if ((desc[s].init_id & 3u) > 2u) what = "init_id must be 0..2";
-      else if (splice_first[s] > splice_first[s + 1]) what = "splice_first must not decrease";
-      if (what) {
-        char buf[96];
-        snprintf(buf, sizeof buf, "substream %u: %s", s, what);
-        return fail(c, CABAC_HIP_ERR_INVALID, buf);
-      }
-    }
-    if (splice_first[0] != 0 || splice_first[n_sub] != n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "every block must be spliced exactly once");
-  }
   if ((!rows && !sparse) || n_sub == 0) payload_offsets[0] = 0;  // (the rows and the sparse form write no output before they have run)
   if (n_sub == 0) return n_tu ? fail(c, CABAC_HIP_ERR_INVALID, "blocks without a substream") : CABAC_HIP_OK;
-  for (uint32_t s = 0; s < n_sub; s++) {
-    if (desc[s].rec_offset > n_records_total || desc[s].n_records > n_records_total - desc[s].rec_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "records out of range");
-    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
-    if (splice_first[s] > splice_first[s + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "splice_first must not decrease");
-  }
+  for (uint32_t s = 0; s < n_sub; s++)  // (the rows form names the substream)
+    if (int bad = check_records_host(c, s, desc[s], n_records_total,
+                                     splice_first[s] > splice_first[s + 1] ? "splice_first must not decrease" : nullptr, rows != nullptr))
+      return bad;
   const uint32_t n_splice = splice_first[n_sub];
   if (splice_first[0] != 0 || n_splice != n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "every block must be spliced exactly once");
   DeviceGuard g(c->device);
   int rc;
   if ((rc = pipe_init(c))) return rc;
-  const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t);
-  if ((rc = ensure(c, kSpInDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, kSpInRec, (n_records_total + 8) * sizeof(uint16_t)))) return rc;
-  if ((rc = ensure(c, kSpInFirst, first_bytes))) return rc;
-  if ((rc = ensure(c, kSpInSplice, size_t(n_splice ? n_splice : 1) * sizeof(cabac_splice)))) return rc;
-  if ((rc = ensure(c, kSpInTu, size_t(n_tu ? n_tu : 1) * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, kSpInCoeff, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
-  if ((rc = ensure(c, kSpOutRes, n_sub * sizeof(cabac_substream_result)))) return rc;
-  if ((rc = ensure(c, kSpOutInfo, size_t(n_tu ? n_tu : 1) * sizeof(uint32_t)))) return rc;
-  if (bin_counts && (rc = ensure(c, kSpOutCnt, size_t(n_sub) * CABAC_BIN_COUNT_WORDS * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kPayload, payload_capacity ? payload_capacity : 16))) return rc;
-  if ((rc = ensure(c, kPayloadOffsets, (size_t(n_sub) + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = ensure(c, kSpFlag, 64))) return rc;
-  const size_t ent_first_bytes = (size_t(n_tu) + 1) * sizeof(uint32_t);
-  if (sparse && ((rc = ensure(c, kSparseFirst, ent_first_bytes)) || (rc = ensure(c, kSparseEnt, sparse->n_entries * sizeof(uint32_t))) ||
-                 (rc = ensure(c, kSparseScratch, cabac::sparse_scratch_bytes(n_tu))) ||
-                 (rc = ensure(c, kSparseStatus, sizeof(cabac_sparse_status)))))
-    return rc;
-  const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
-  if (rows && ((rc = ensure(c, kWppFrom, link_bytes)) || (rc = ensure(c, kWppAt, link_bytes)) || (rc = ensure(c, kSpInSync, link_bytes))))
-    return rc;
-  const size_t probe_bytes = probes ? size_t(probes->n) * sizeof(uint32_t) : 0;
-  if (probes && ((rc = ensure(c, kProbeFirst, first_bytes)) || (rc = ensure(c, kProbeAt, probe_bytes)) ||
-                 (rc = ensure(c, kProbeSplice, probe_bytes)) || (rc = ensure(c, kProbeOut, probe_bytes))))
-    return rc;
-  const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result), off_bytes = (size_t(n_sub) + 1) * sizeof(uint64_t);
-  if ((rc = ensure_pinned(c, 0, res_bytes + off_bytes + 64))) return rc;
-  auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
-  auto *h_off = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(c->h_pin[0]) + res_bytes);
-  auto *h_flag = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(h_off) + off_bytes);
-  uint32_t *d_flag = static_cast<uint32_t *>(c->d_buf[kSpFlag]);  // [0] descriptor range check, [1] empty / bad block
+  Stage st{c, true, c->s_in};
+  PayloadReturn back{c, n_sub, payload, payload_capacity, payload_offsets, results};
+  if ((rc = back.prepare(st, n_tu))) return rc;
+  uint32_t *d_counts = bin_counts ? st.room<uint32_t>(kSpOutCnt, size_t(n_sub) * CABAC_BIN_COUNT_WORDS) : nullptr;
+  uint32_t *d_flag = st.room<uint32_t>(kSpFlag, 16);  // [0] descriptor range check, [1] empty / bad block
+  void *d_sparse_scratch = sparse ? st.bytes(kSparseScratch, cabac::sparse_scratch_bytes(n_tu), nullptr, 0) : nullptr;
+  auto *d_sparse_status = sparse ? st.room<cabac_sparse_status>(kSparseStatus, 1) : nullptr;
+  if (st.rc) return st.rc;
 
   // what came before on the caller's stream is finished first; uploads run on the copy stream, the kernels on the ctx's
   HIP_TRY(c, wait_stream(c, c->stream));
   // small things first: the block descriptors are checked on the device while the coefficients are still on the wire
-  if ((rc = h2d(c, c->d_buf[kSpInTu], tus, size_t(n_tu) * sizeof(cabac_tu_desc), c->s_in))) return rc;
+  SpliceIn in{};
+  in.d_tu = st.put(kSpInTu, n_tu, tus);
+  if (st.rc) return st.rc;
   HIP_TRY(c, hipEventRecord(c->ev_in[0], c->s_in));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in[0], 0));
-  HIP_TRY(c, cabac::launch_tu_range_check(c->stream, n_tu, static_cast<const cabac_tu_desc *>(c->d_buf[kSpInTu]), n_coeff_total, d_flag));
-  HIP_TRY(c, hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, cabac::launch_tu_range_check(c->stream, n_tu, in.d_tu, n_coeff_total, d_flag));
+  HIP_TRY(c, hipMemcpyAsync(back.h_word, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev_k[0], c->stream));
-  if ((rc = h2d(c, c->d_buf[kSpInDesc], desc, n_sub * sizeof(cabac_substream_desc), c->s_in))) return rc;
-  if ((rc = h2d(c, c->d_buf[kSpInFirst], splice_first, first_bytes, c->s_in))) return rc;
-  if ((rc = h2d(c, c->d_buf[kSpInSplice], splices, size_t(n_splice) * sizeof(cabac_splice), c->s_in))) return rc;
-  if ((rc = h2d(c, c->d_buf[kSpInRec], records, n_records_total * sizeof(uint16_t), c->s_in))) return rc;
+  in.d_desc = st.put(kSpInDesc, n_sub, desc);
+  in.d_splice_first = st.put(kSpInFirst, size_t(n_sub) + 1, splice_first);
+  in.d_splices = st.put(kSpInSplice, n_splice, splices);
+  in.d_records = st.put(kSpInRec, n_records_total, records, 8);
+  in.n_splice = n_splice, in.n_tu = n_tu, in.coeff_bytes = coeff_bytes;
+  const uint32_t *d_ent_first = nullptr, *d_entries = nullptr;
+  const size_t coeff_room = (n_coeff_total + 4) * size_t(coeff_bytes);
   if (sparse) {  // the lists go up in the coefficients' place
-    if ((rc = h2d(c, c->d_buf[kSparseFirst], sparse->ent_first, ent_first_bytes, c->s_in))) return rc;
-    if ((rc = h2d(c, c->d_buf[kSparseEnt], sparse->entries, sparse->n_entries * sizeof(uint32_t), c->s_in))) return rc;
-  } else if ((rc = h2d(c, c->d_buf[kSpInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), c->s_in))) return rc;
+    d_ent_first = st.put(kSparseFirst, size_t(n_tu) + 1, sparse->ent_first);
+    d_entries = st.put(kSparseEnt, sparse->n_entries, sparse->entries);
+    in.d_coeff = st.bytes(kSpInCoeff, coeff_room, nullptr, 0);
+  } else {
+    in.d_coeff = st.bytes(kSpInCoeff, coeff_room, coeff, n_coeff_total * size_t(coeff_bytes));
+  }
   Rows d_rows{};
-  if (rows) {
-    if ((rc = h2d(c, c->d_buf[kWppFrom], rows->d_sync_from, link_bytes, c->s_in))) return rc;
-    if ((rc = h2d(c, c->d_buf[kWppAt], rows->d_sync_at, link_bytes, c->s_in))) return rc;
-    if (rows->d_sync_splice && (rc = h2d(c, c->d_buf[kSpInSync], rows->d_sync_splice, link_bytes, c->s_in))) return rc;
-    d_rows = Rows{rows->n_level, rows->level_first, static_cast<const uint32_t *>(c->d_buf[kWppFrom]),
-                        static_cast<const uint32_t *>(c->d_buf[kWppAt]),
-                        rows->d_sync_splice ? static_cast<const uint32_t *>(c->d_buf[kSpInSync]) : nullptr};
-  }
+  if (rows) d_rows = stage_rows(st, n_sub, *rows, true);
   SpliceProbes d_probes{};
-  if (probes) {
-    if ((rc = h2d(c, c->d_buf[kProbeFirst], probes->first, first_bytes, c->s_in))) return rc;
-    if ((rc = h2d(c, c->d_buf[kProbeAt], probes->at, probe_bytes, c->s_in))) return rc;
-    if (probes->splice && (rc = h2d(c, c->d_buf[kProbeSplice], probes->splice, probe_bytes, c->s_in))) return rc;
-    d_probes = SpliceProbes{static_cast<const uint32_t *>(c->d_buf[kProbeFirst]), static_cast<const uint32_t *>(c->d_buf[kProbeAt]),
-                            probes->splice ? static_cast<const uint32_t *>(c->d_buf[kProbeSplice]) : nullptr, probes->n,
-                            static_cast<uint32_t *>(c->d_buf[kProbeOut])};
-  }
+  if (probes)
+    d_probes = SpliceProbes{st.put(kProbeFirst, size_t(n_sub) + 1, probes->first), st.put(kProbeAt, probes->n, probes->at),
+                            st.opt(kProbeSplice, probes->n, probes->splice), probes->n, st.room<uint32_t>(kProbeOut, probes->n)};
+  if (st.rc) return st.rc;
   HIP_TRY(c, hipEventRecord(c->ev_in[1], c->s_in));
   // the lists are checked while they are on the wire: nothing of the pipeline has run and no output is touched when they are refused
   if (sparse && (rc = check_sparse_host(c, n_tu, tus, *sparse))) return rc;
   HIP_TRY(c, wait_event(c, c->ev_k[0]));
-  if (*h_flag) return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
+  if (*back.h_word) return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
   HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in[1], 0));
   if (sparse) {  // every block that lies inside the buffer (checked above) is written whole: zeros, then its entries
     Timed t(c, 41);
-    HIP_TRY(c, cabac::launch_sparse_expand(c->stream, n_tu, static_cast<const cabac_tu_desc *>(c->d_buf[kSpInTu]),
-                                           static_cast<const uint32_t *>(c->d_buf[kSparseFirst]),
-                                           static_cast<const uint32_t *>(c->d_buf[kSparseEnt]), sparse->n_entries, c->d_buf[kSpInCoeff],
-                                           coeff_bytes, n_coeff_total, static_cast<cabac_sparse_status *>(c->d_buf[kSparseStatus]),
-                                           c->d_buf[kSparseScratch]));
+    HIP_TRY(c, cabac::launch_sparse_expand(c->stream, n_tu, in.d_tu, d_ent_first, d_entries, sparse->n_entries, const_cast<void *>(in.d_coeff),
+                                           coeff_bytes, n_coeff_total, d_sparse_status, d_sparse_scratch));
   }
-  rc = encode_residual_device_impl(c, n_sub, static_cast<const cabac_substream_desc *>(c->d_buf[kSpInDesc]),
-                                        static_cast<const uint16_t *>(c->d_buf[kSpInRec]), static_cast<const uint32_t *>(c->d_buf[kSpInFirst]),
-                                        static_cast<const cabac_splice *>(c->d_buf[kSpInSplice]), n_splice, n_tu,
-                                        static_cast<const cabac_tu_desc *>(c->d_buf[kSpInTu]), c->d_buf[kSpInCoeff], coeff_bytes,
-                                        static_cast<uint8_t *>(c->d_buf[kPayload]), payload_capacity, static_cast<uint64_t *>(c->d_buf[kPayloadOffsets]),
-                                        static_cast<cabac_substream_result *>(c->d_buf[kSpOutRes]), static_cast<uint32_t *>(c->d_buf[kSpOutInfo]),
-                                        bin_counts ? static_cast<uint32_t *>(c->d_buf[kSpOutCnt]) : nullptr, nullptr,
-                                        rows ? &d_rows : nullptr, nullptr, probes ? &d_probes : nullptr);
-  if (rc) return rc;
-  HIP_TRY(c, cabac::launch_tu_info_any(c->stream, n_tu, static_cast<const uint32_t *>(c->d_buf[kSpOutInfo]), d_flag + 1));
-  HIP_TRY(c, hipMemcpyAsync(h_res, c->d_buf[kSpOutRes], res_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h_off, c->d_buf[kPayloadOffsets], off_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h_flag, d_flag + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipEventRecord(c->ev_k[1], c->stream));
-  // the big things leave on the outgoing copy stream once the offsets are known
-  HIP_TRY(c, wait_event(c, c->ev_k[1]));
-  const uint64_t n_pay = h_off[n_sub];
-  if (n_pay > payload_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "payload_capacity too small");
-  if ((rc = d2h(c, payload, c->d_buf[kPayload], n_pay, c->s_out))) return rc;
-  if (tu_info && (rc = d2h(c, tu_info, c->d_buf[kSpOutInfo], size_t(n_tu) * sizeof(uint32_t), c->s_out))) return rc;
-  if (bin_counts && (rc = d2h(c, bin_counts, c->d_buf[kSpOutCnt], size_t(n_sub) * CABAC_BIN_COUNT_WORDS * sizeof(uint32_t), c->s_out))) return rc;
-  if (probes && (rc = d2h(c, probes->bits, c->d_buf[kProbeOut], size_t(probes->first[n_sub]) * sizeof(uint32_t), c->s_out))) return rc;
-  if ((rc = d2h_drain(c))) return rc;
-  HIP_TRY(c, wait_stream(c, c->s_out));
-  int status = *h_flag ? CABAC_HIP_ERR_SUBSTREAM : CABAC_HIP_OK;
-  payload_offsets[0] = 0;
-  for (uint32_t s = 0; s < n_sub; s++) {
-    results[s] = h_res[s];
-    payload_offsets[s + 1] = h_off[s + 1];
-    if (h_res[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
-  }
-  if (status) c->last_error = "substream flag set, or an empty / badly described block (see results[].flags, tu_info[])";
-  return status;
+  if ((rc = encode_residual_device_impl(c, n_sub, in, back.d, d_counts, nullptr, rows ? &d_rows : nullptr, nullptr, probes ? &d_probes : nullptr)))
+    return rc;
+  HIP_TRY(c, cabac::launch_tu_info_any(c->stream, n_tu, back.d.d_tu_info, d_flag + 1));
+  if ((rc = back.fetch(d_flag + 1))) return rc;
+  if (tu_info && (rc = d2h(c, tu_info, back.d.d_tu_info, size_t(n_tu) * sizeof(uint32_t), c->s_out))) return rc;
+  if (bin_counts && (rc = d2h(c, bin_counts, d_counts, size_t(n_sub) * CABAC_BIN_COUNT_WORDS * sizeof(uint32_t), c->s_out))) return rc;
+  if (probes && (rc = d2h(c, probes->bits, d_probes.bits, size_t(probes->first[n_sub]) * sizeof(uint32_t), c->s_out))) return rc;
+  return back.finish(*back.h_word ? CABAC_HIP_ERR_SUBSTREAM : CABAC_HIP_OK,
+                     "substream flag set, or an empty / badly described block (see results[].flags, tu_info[])");
 }
 
 int cabac_hip_encode_batch_residual(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
@@ -2120,13 +2161,12 @@ int cabac_hip_encode_batch_residual16(cabac_hip_ctx *c, uint32_t n_sub, const ca
 // ---- plan + values -> bytes (cabac_plan_write.hip; declared in cabac_hip_write_plan.h) --------------------------------------
 // sets (may be null): the encode launch starts from and writes context sets; rows (may be null): the emit walk notes each
 // substream's hand-over record and the WPP encode schedule takes the encode launch's place.  Not both.
-static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint32_t *d_plan,
-                                  const uint32_t *d_values_in, const uint32_t *d_tile_first, uint32_t n_tu, const cabac_tu_desc *d_tu,
-                                  const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes,
-                                  uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_payload_offsets,
-                                  cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info,
-                                  const cabac::CtxSets *sets, const Rows *rows) {
-  if (!c || !d_payload_offsets || (n_sub && (!d_desc || !d_tile_first || !d_payload || !d_results)) || (n_tu && (!d_tu || !d_coeff)))
+// in: the plan write's operands as the kernels take them (cabac::PlanWriteIn; its last two members are filled in here)
+static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, cabac::PlanWriteIn in, uint32_t n_tu, const void *d_coeff, int coeff_bytes,
+                                  const PayloadOut &out, uint32_t *d_values_out, const cabac::CtxSets *sets, const Rows *rows) {
+  const auto [d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info] = out;
+  const cabac_tu_desc *d_tu = in.tus;
+  if (!c || !d_payload_offsets || (n_sub && (!in.desc || !in.tile_first || !d_payload || !d_results)) || (n_tu && (!d_tu || !d_coeff)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (n_sub == 0 && n_tu) return fail(c, CABAC_HIP_ERR_INVALID, "blocks without a substream");
@@ -2143,7 +2183,7 @@ static int write_plan_device_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_
   if ((rc = plan_write_tables(c, n_sub, n_tu, sets || rows, &w))) return rc;
   // the hand-over records of a rows call; the out sets of the rows that did not stop
   uint32_t *sync_rec = w.words, *out_live = w.words ? w.words + (n_sub ? n_sub : 1) : nullptr;
-  const cabac::PlanWriteIn in{d_desc, d_plan, d_values_in, d_tile_first, d_tu, d_tu_at, d_tu_guard, w.cnt, w.info};
+  in.tu_n_records = w.cnt, in.tu_info = w.info;
   c->timed = false;
   {  // sizes and info words of ALL blocks: they do not depend on the guards, the guards depend on them
     Timed t(c, 5);
@@ -2201,8 +2241,8 @@ int cabac_hip_write_plan_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_su
                                 const uint32_t *d_tu_at, const uint32_t *d_tu_guard, const void *d_coeff, int coeff_bytes,
                                 uint8_t *d_payload, uint64_t payload_capacity, uint64_t *d_payload_offsets,
                                 cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info) {
-  return write_plan_device_impl(c, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, coeff_bytes,
-                                d_payload, payload_capacity, d_payload_offsets, d_results, d_values_out, d_tu_info, nullptr, nullptr);
+  return write_plan_device_impl(c, n_sub, {d_desc, d_plan, d_values_in, d_tile_first, d_tu, d_tu_at, d_tu_guard}, n_tu, d_coeff, coeff_bytes,
+                                {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_values_out, nullptr, nullptr);
 }
 
 // rows (may be null): the levels and the links, all in HOST memory here
@@ -2230,88 +2270,44 @@ static int write_plan_batch_impl(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   DeviceGuard g(c->device);
   int rc;
   if ((rc = pipe_init(c))) return rc;
-  const size_t first_bytes = (size_t(n_sub) + 1) * sizeof(uint32_t), at_bytes = size_t(n_tu) * sizeof(uint32_t);
-  const size_t link_bytes = size_t(n_sub) * sizeof(uint32_t);
-  if (rows && ((rc = ensure(c, kWppFrom, link_bytes)) || (rc = ensure(c, kWppAt, link_bytes)))) return rc;
-  const size_t plan_bytes = size_t(n_elements_total) * 2 * sizeof(uint32_t), value_bytes = size_t(n_elements_total) * sizeof(uint32_t);
-  if ((rc = ensure(c, kSpInDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, kSpInFirst, first_bytes))) return rc;
-  if ((rc = ensure(c, kSpInTu, size_t(n_tu ? n_tu : 1) * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, kSpInCoeff, (n_coeff_total + 4) * size_t(coeff_bytes)))) return rc;
-  if ((rc = ensure(c, kSpOutRes, n_sub * sizeof(cabac_substream_result)))) return rc;
-  if ((rc = ensure(c, kSpOutInfo, size_t(n_tu ? n_tu : 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kUnitTuAt, at_bytes))) return rc;
-  if ((rc = ensure(c, kElemGuard, at_bytes))) return rc;
-  if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
-  if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
-  if ((rc = ensure(c, kPayload, payload_capacity ? payload_capacity : 16))) return rc;
-  if ((rc = ensure(c, kPayloadOffsets, (size_t(n_sub) + 1) * sizeof(uint64_t)))) return rc;
-  const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result), off_bytes = (size_t(n_sub) + 1) * sizeof(uint64_t);
-  if ((rc = ensure_pinned(c, 0, res_bytes + off_bytes + 64))) return rc;
-  auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
-  auto *h_off = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(c->h_pin[0]) + res_bytes);
-  uint32_t *d_values = static_cast<uint32_t *>(c->d_buf[kElemValues]);
+  Stage st{c, true, c->s_in};
+  PayloadReturn back{c, n_sub, payload, payload_capacity, payload_offsets, results};
+  if ((rc = back.prepare(st, n_tu))) return rc;
 
   // what came before on the caller's stream is finished first; uploads run on the copy stream, the kernels on the ctx's
   HIP_TRY(c, wait_stream(c, c->stream));
-  if ((rc = h2d(c, c->d_buf[kSpInTu], tus, size_t(n_tu) * sizeof(cabac_tu_desc), c->s_in))) return rc;
-  if ((rc = h2d(c, c->d_buf[kSpInDesc], desc, n_sub * sizeof(cabac_substream_desc), c->s_in))) return rc;
-  if ((rc = h2d(c, c->d_buf[kSpInFirst], tile_first, first_bytes, c->s_in))) return rc;
-  if (tu_at && (rc = h2d(c, c->d_buf[kUnitTuAt], tu_at, at_bytes, c->s_in))) return rc;
-  if (tu_guard && (rc = h2d(c, c->d_buf[kElemGuard], tu_guard, at_bytes, c->s_in))) return rc;
-  if ((rc = h2d(c, c->d_buf[kElemPlan], plan, plan_bytes, c->s_in))) return rc;
-  if ((rc = h2d(c, d_values, values_in, value_bytes, c->s_in))) return rc;
-  if ((rc = h2d(c, c->d_buf[kSpInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), c->s_in))) return rc;
+  cabac::PlanWriteIn in{};
+  in.tus = st.put(kSpInTu, n_tu, tus);
+  in.desc = st.put(kSpInDesc, n_sub, desc);
+  in.tile_first = st.put(kSpInFirst, size_t(n_sub) + 1, tile_first);
+  in.tu_at = st.opt(kUnitTuAt, n_tu, tu_at);
+  in.tu_guard = st.opt(kElemGuard, n_tu, tu_guard);
+  in.plan = st.put(kElemPlan, size_t(n_elements_total) * 2, plan);
+  uint32_t *d_values = st.put(kElemValues, n_elements_total, const_cast<uint32_t *>(values_in));
+  in.values = d_values;
+  const void *d_coeff = st.bytes(kSpInCoeff, (n_coeff_total + 4) * size_t(coeff_bytes), coeff, n_coeff_total * size_t(coeff_bytes));
   Rows d_rows{};
-  if (rows) {
-    if ((rc = h2d(c, c->d_buf[kWppFrom], rows->d_sync_from, link_bytes, c->s_in))) return rc;
-    if ((rc = h2d(c, c->d_buf[kWppAt], rows->d_sync_at, link_bytes, c->s_in))) return rc;
-    d_rows = Rows{rows->n_level, rows->level_first, static_cast<const uint32_t *>(c->d_buf[kWppFrom]),
-                      static_cast<const uint32_t *>(c->d_buf[kWppAt])};
-  }
+  if (rows) d_rows = stage_rows(st, n_sub, *rows, false);
+  if (st.rc) return st.rc;
   HIP_TRY(c, hipEventRecord(c->ev_in[0], c->s_in));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in[0], 0));
-  rc = write_plan_device_impl(c, n_sub, static_cast<const cabac_substream_desc *>(c->d_buf[kSpInDesc]),
-                                   static_cast<const uint32_t *>(c->d_buf[kElemPlan]), d_values,
-                                   static_cast<const uint32_t *>(c->d_buf[kSpInFirst]), n_tu,
-                                   static_cast<const cabac_tu_desc *>(c->d_buf[kSpInTu]),
-                                   tu_at ? static_cast<const uint32_t *>(c->d_buf[kUnitTuAt]) : nullptr,
-                                   tu_guard ? static_cast<const uint32_t *>(c->d_buf[kElemGuard]) : nullptr, c->d_buf[kSpInCoeff],
-                                   coeff_bytes, static_cast<uint8_t *>(c->d_buf[kPayload]), payload_capacity,
-                                   static_cast<uint64_t *>(c->d_buf[kPayloadOffsets]),
-                                   static_cast<cabac_substream_result *>(c->d_buf[kSpOutRes]), values_out ? d_values : nullptr,
-                                   tu_info ? static_cast<uint32_t *>(c->d_buf[kSpOutInfo]) : nullptr, nullptr, rows ? &d_rows : nullptr);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h_res, c->d_buf[kSpOutRes], res_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h_off, c->d_buf[kPayloadOffsets], off_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipEventRecord(c->ev_k[1], c->stream));
-  // the big things leave on the outgoing copy stream once the offsets are known
-  HIP_TRY(c, wait_event(c, c->ev_k[1]));
-  const uint64_t n_pay = h_off[n_sub];
-  if (n_pay > payload_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "payload_capacity too small");
-  if ((rc = d2h(c, payload, c->d_buf[kPayload], n_pay, c->s_out))) return rc;
+  PayloadOut out = back.d;
+  if (!tu_info) out.d_tu_info = nullptr;
+  if ((rc = write_plan_device_impl(c, n_sub, in, n_tu, d_coeff, coeff_bytes, out, values_out ? d_values : nullptr, nullptr, rows ? &d_rows : nullptr)))
+    return rc;
+  if ((rc = back.fetch(nullptr))) return rc;
   // a stopped substream's values and info words are unspecified on the device: the caller's stay what they were
-  int status = CABAC_HIP_OK;
   for (uint32_t s = 0; s < n_sub; s++) {
-    if (h_res[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
-    if (h_res[s].flags & (CABAC_RES_BAD_RECORD | CABAC_RES_BAD_VALUE)) continue;
+    if (back.h_res[s].flags & (CABAC_RES_BAD_RECORD | CABAC_RES_BAD_VALUE)) continue;
     if (values_out && desc[s].n_records &&
         (rc = d2h(c, values_out + desc[s].rec_offset, d_values + desc[s].rec_offset, size_t(desc[s].n_records) * sizeof(uint32_t), c->s_out)))
       return rc;
     if (tu_info && tile_first[s + 1] > tile_first[s] &&
-        (rc = d2h(c, tu_info + tile_first[s], static_cast<uint32_t *>(c->d_buf[kSpOutInfo]) + tile_first[s],
-                  size_t(tile_first[s + 1] - tile_first[s]) * sizeof(uint32_t), c->s_out)))
+        (rc = d2h(c, tu_info + tile_first[s], back.d.d_tu_info + tile_first[s], size_t(tile_first[s + 1] - tile_first[s]) * sizeof(uint32_t),
+                  c->s_out)))
       return rc;
   }
-  if ((rc = d2h_drain(c))) return rc;
-  HIP_TRY(c, wait_stream(c, c->s_out));
-  for (uint32_t s = 0; s < n_sub; s++) {
-    results[s] = h_res[s];
-    payload_offsets[s + 1] = h_off[s + 1];
-  }
-  payload_offsets[0] = 0;
-  if (status) c->last_error = "substream flag set (see results[].flags)";
-  return status;
+  return back.finish(CABAC_HIP_OK, "substream flag set (see results[].flags)");
 }
 
 int cabac_hip_write_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint32_t *plan,
@@ -2325,6 +2321,82 @@ int cabac_hip_write_plan_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
 }
 
 // ---- pinned host memory for the caller's buffers ------------------------------------------------------------
+// ---- the candidates of cabac_hip_estimate_residual_batch and of the search rounds' host-pointer forms: the host checks both run,
+// their staging (kEstIn* / kEstOut*, plain copies on the ctx stream) and the way back of what every such call returns
+namespace {
+struct CandStage {
+  cabac_hip_ctx *c;
+  uint32_t n_cand;
+  const uint32_t *cand_first;
+  const cabac_tu_desc *tus;
+  const void *coeff;
+  int coeff_bytes;
+  uint64_t n_coeff_total;
+  uint32_t n_sets;
+  const uint32_t *set;
+  uint32_t n_tu = 0;
+  // the device side
+  const uint32_t *d_first = nullptr, *d_set = nullptr;
+  const cabac_tu_desc *d_tu = nullptr;
+  void *d_coeff = nullptr;
+  uint32_t *d_state = nullptr, *d_info = nullptr;
+  uint8_t *d_rate = nullptr;
+  uint64_t *d_bits = nullptr, *d_tu_bits = nullptr;
+  std::vector<uint32_t> info;  // the info words as they came back
+
+  int check_lists() const {
+    for (uint32_t k = 0; k < n_cand; k++) {
+      if (cand_first[k] > cand_first[k + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "cand_first is not non-decreasing");
+      if (set[k] >= n_sets) return fail(c, CABAC_HIP_ERR_INVALID, "set out of range");
+    }
+    return CABAC_HIP_OK;
+  }
+  // (the lists are through) the blocks the candidates own: there, and inside the coefficients
+  int check_blocks() {
+    n_tu = cand_first[n_cand];
+    if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+    return check_coeff_ranges_host(c, n_tu - cand_first[0], tus + cand_first[0], n_coeff_total);
+  }
+  // coeff_up: the bytes of the coefficients that go up
+  int stage(Stage &st, const uint32_t *state, const uint8_t *rate, size_t coeff_up) {
+    const size_t set_words = size_t(n_sets) * CABAC_NUM_CONTEXTS;
+    d_first = st.put(kEstInFirst, size_t(n_cand) + 1, cand_first);
+    d_tu = st.put(kEstInTu, n_tu, tus);
+    d_coeff = st.bytes(kEstInCoeff, n_coeff_total * size_t(coeff_bytes), coeff, coeff_up);
+    d_state = static_cast<uint32_t *>(st.bytes(kEstInState, set_words * sizeof(uint32_t), state, n_cand ? set_words * sizeof(uint32_t) : 0));
+    d_rate = static_cast<uint8_t *>(st.bytes(kEstInRate, set_words, rate, n_cand ? set_words : 0));
+    d_set = st.put(kEstInSet, n_cand, set);
+    d_bits = st.room<uint64_t>(kEstOutBits, size_t(n_cand) + n_tu);
+    d_info = st.room<uint32_t>(kEstOutInfo, n_tu);
+    if (st.rc) return st.rc;
+    d_tu_bits = d_bits + n_cand;
+    if (n_tu) {  // blocks no candidate owns keep a defined value
+      HIP_TRY(c, hipMemsetAsync(d_tu_bits, 0, size_t(n_tu) * sizeof(uint64_t), c->stream));
+      HIP_TRY(c, hipMemsetAsync(d_info, 0, size_t(n_tu) * sizeof(uint32_t), c->stream));
+    }
+    return CABAC_HIP_OK;
+  }
+  // queues the way back of the bits and the info words (tu_frac_bits may be null); the caller waits
+  int fetch(uint64_t *frac_bits, uint64_t *tu_frac_bits) {
+    info = std::vector<uint32_t>(n_tu);
+    HIP_TRY(c, down(c, frac_bits, d_bits, size_t(n_cand) * sizeof(uint64_t)));
+    if (tu_frac_bits) HIP_TRY(c, down(c, tu_frac_bits, d_tu_bits, size_t(n_tu) * sizeof(uint64_t)));
+    HIP_TRY(c, down(c, info.data(), d_info, size_t(n_tu) * sizeof(uint32_t)));
+    return CABAC_HIP_OK;
+  }
+  // (after the wait) the info words to the caller where wanted; judged: an empty or badly described block is the status
+  int info_status(uint32_t *tu_info, bool judged) {
+    int status = CABAC_HIP_OK;
+    for (uint32_t t = 0; t < n_tu; t++) {
+      if (tu_info) tu_info[t] = info[t];
+      if (judged && (info[t] & (CABAC_TU_INFO_EMPTY | CABAC_TU_INFO_BAD_DESC))) status = CABAC_HIP_ERR_SUBSTREAM;
+    }
+    if (status) c->last_error = "empty block or bad descriptor (see tu_info[])";
+    return status;
+  }
+};
+}  // namespace
+
 // ---- fused residual estimator (cabac_residual_estimate.hip) -------------------------------------------------------
 static int estimate_residual_device_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
                                          const void *d_coeff, int coeff_bytes, const uint32_t *d_state, const uint8_t *d_rate,
@@ -2359,60 +2431,19 @@ int cabac_hip_estimate_residual_batch(cabac_hip_ctx *c, uint32_t n_cand, const u
   if (!c || (n_cand && (!cand_first || !state || !rate || !set || !frac_bits))) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
   if (n_cand == 0) return CABAC_HIP_OK;
-  for (uint32_t k = 0; k < n_cand; k++) {
-    if (cand_first[k] > cand_first[k + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "cand_first is not non-decreasing");
-    if (set[k] >= n_sets) return fail(c, CABAC_HIP_ERR_INVALID, "set out of range");
-  }
-  const uint32_t n_tu = cand_first[n_cand];
-  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  for (uint32_t t = cand_first[0]; t < n_tu; t++) {
-    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, reads nothing
-    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
-    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
-  }
+  CandStage cs{c, n_cand, cand_first, tus, coeff, coeff_bytes, n_coeff_total, n_sets, set};
+  if (int bad = cs.check_lists()) return bad;
+  if (int bad = cs.check_blocks()) return bad;
   DeviceGuard g(c->device);
   int rc;
-  const size_t set_words = size_t(n_sets) * CABAC_NUM_CONTEXTS;
-  if ((rc = ensure(c, kEstInFirst, (size_t(n_cand) + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kEstInTu, size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, kEstInCoeff, n_coeff_total * size_t(coeff_bytes)))) return rc;
-  if ((rc = ensure(c, kEstInState, set_words * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kEstInRate, set_words))) return rc;
-  if ((rc = ensure(c, kEstInSet, size_t(n_cand) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kEstOutBits, (size_t(n_cand) + n_tu) * sizeof(uint64_t)))) return rc;
-  if ((rc = ensure(c, kEstOutInfo, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  uint64_t *d_bits = static_cast<uint64_t *>(c->d_buf[kEstOutBits]), *d_tu_bits = d_bits + n_cand;
-  uint32_t *d_info = static_cast<uint32_t *>(c->d_buf[kEstOutInfo]);
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInFirst], cand_first, (size_t(n_cand) + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  if (n_tu) HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInTu], tus, size_t(n_tu) * sizeof(cabac_tu_desc), hipMemcpyHostToDevice, c->stream));
-  if (n_coeff_total)
-    HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInCoeff], coeff, n_coeff_total * size_t(coeff_bytes), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInState], state, set_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInRate], rate, set_words, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kEstInSet], set, size_t(n_cand) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  if (n_tu) {  // blocks no candidate owns keep a defined value
-    HIP_TRY(c, hipMemsetAsync(d_tu_bits, 0, size_t(n_tu) * sizeof(uint64_t), c->stream));
-    HIP_TRY(c, hipMemsetAsync(d_info, 0, size_t(n_tu) * sizeof(uint32_t), c->stream));
-  }
-  rc = estimate_residual_device_impl(c, n_cand, (const uint32_t *)c->d_buf[kEstInFirst], (const cabac_tu_desc *)c->d_buf[kEstInTu],
-                                     c->d_buf[kEstInCoeff], coeff_bytes, (const uint32_t *)c->d_buf[kEstInState],
-                                     (const uint8_t *)c->d_buf[kEstInRate], (const uint32_t *)c->d_buf[kEstInSet], d_bits, d_tu_bits,
-                                     d_info);
-  if (rc) return rc;
-  std::vector<uint32_t> info(n_tu);
-  HIP_TRY(c, hipMemcpyAsync(frac_bits, d_bits, size_t(n_cand) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  if (n_tu && tu_frac_bits)
-    HIP_TRY(c, hipMemcpyAsync(tu_frac_bits, d_tu_bits, size_t(n_tu) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  if (n_tu) HIP_TRY(c, hipMemcpyAsync(info.data(), d_info, size_t(n_tu) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  Stage st{c};
+  if ((rc = cs.stage(st, state, rate, n_coeff_total * size_t(coeff_bytes)))) return rc;
+  if ((rc = estimate_residual_device_impl(c, n_cand, cs.d_first, cs.d_tu, cs.d_coeff, coeff_bytes, cs.d_state, cs.d_rate, cs.d_set, cs.d_bits,
+                                          cs.d_tu_bits, cs.d_info)))
+    return rc;
+  if ((rc = cs.fetch(frac_bits, tu_frac_bits))) return rc;
   HIP_TRY(c, wait_stream(c, c->stream));
-  int status = CABAC_HIP_OK;
-  for (uint32_t t = 0; t < n_tu; t++) {
-    if (tu_info) tu_info[t] = info[t];
-    if (info[t] & (CABAC_TU_INFO_EMPTY | CABAC_TU_INFO_BAD_DESC)) status = CABAC_HIP_ERR_SUBSTREAM;
-  }
-  if (status) c->last_error = "empty block or bad descriptor (see tu_info[])";
-  return status;
+  return cs.info_status(tu_info, true);
 }
 
 // ---- emulation prevention (cabac_nal.hip; declared in cabac_hip_nal.h) ---------------------------------------------------
@@ -2469,22 +2500,18 @@ int cabac_hip_nal_escape_batch(cabac_hip_ctx *c, uint32_t n_seg, const uint64_t 
   int rc;
   const uint64_t cap = std::min<uint64_t>(nal_capacity, cabac_hip_nal_escape_bound(n));   // no result is longer
   const size_t off_bytes = (size_t(n_seg) + 1) * sizeof(uint64_t);
-  if ((rc = ensure(c, kNalIn, n))) return rc;
-  if ((rc = ensure(c, kNalInOff, off_bytes))) return rc;
-  if ((rc = ensure(c, kNalOut, cap))) return rc;
-  if ((rc = ensure(c, kNalOutOff, off_bytes))) return rc;
-  if ((rc = ensure(c, kNalStatus, sizeof(cabac_nal_status)))) return rc;
-  auto *d_status = static_cast<cabac_nal_status *>(c->d_buf[kNalStatus]);
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kNalInOff], offsets, off_bytes, hipMemcpyHostToDevice, c->stream));
-  if (n) HIP_TRY(c, hipMemcpyAsync(c->d_buf[kNalIn], payload, n, hipMemcpyHostToDevice, c->stream));
-  rc = cabac_hip_nal_escape_device(c, n_seg, (const uint64_t *)c->d_buf[kNalInOff], (const uint8_t *)c->d_buf[kNalIn], n,
-                                   (uint8_t *)c->d_buf[kNalOut], cap, (uint64_t *)c->d_buf[kNalOutOff], d_status);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(status, d_status, sizeof(cabac_nal_status), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(nal_offsets, c->d_buf[kNalOutOff], off_bytes, hipMemcpyDeviceToHost, c->stream));
+  Stage st{c};
+  auto *d_off = st.put(kNalInOff, size_t(n_seg) + 1, offsets);
+  auto *d_in = st.put(kNalIn, n, payload);
+  auto *d_out = st.room<uint8_t>(kNalOut, cap);
+  auto *d_out_off = st.room<uint64_t>(kNalOutOff, size_t(n_seg) + 1);
+  auto *d_status = st.room<cabac_nal_status>(kNalStatus, 1);
+  if (st.rc) return st.rc;
+  if ((rc = cabac_hip_nal_escape_device(c, n_seg, d_off, d_in, n, d_out, cap, d_out_off, d_status))) return rc;
+  HIP_TRY(c, down(c, status, d_status, sizeof(cabac_nal_status)));
+  HIP_TRY(c, down(c, nal_offsets, d_out_off, off_bytes));
   HIP_TRY(c, wait_stream(c, c->stream));
-  const uint64_t got = std::min<uint64_t>(status->out_bytes, cap);
-  if (got) HIP_TRY(c, hipMemcpyAsync(nal, c->d_buf[kNalOut], got, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, down(c, nal, d_out, std::min<uint64_t>(status->out_bytes, cap)));
   HIP_TRY(c, wait_stream(c, c->stream));
   return CABAC_HIP_OK;
 }
@@ -2503,27 +2530,23 @@ int cabac_hip_nal_unescape_batch(cabac_hip_ctx *c, uint32_t n_seg, const uint64_
   const uint64_t cap = std::min<uint64_t>(payload_capacity, n);
   const uint64_t loc_cap = locations ? std::min<uint64_t>(loc_capacity, n / 3) : 0;   // a removal needs two zeros in front of it
   const size_t off_bytes = (size_t(n_seg) + 1) * sizeof(uint64_t);
-  if ((rc = ensure(c, kNalIn, n))) return rc;
-  if ((rc = ensure(c, kNalInOff, off_bytes))) return rc;
-  if ((rc = ensure(c, kNalOut, cap))) return rc;
-  if ((rc = ensure(c, kNalOutOff, off_bytes))) return rc;
-  if ((rc = ensure(c, kNalLoc, loc_cap * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kNalStatus, sizeof(cabac_nal_status)))) return rc;
-  auto *d_status = static_cast<cabac_nal_status *>(c->d_buf[kNalStatus]);
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kNalInOff], nal_offsets, off_bytes, hipMemcpyHostToDevice, c->stream));
-  if (n) HIP_TRY(c, hipMemcpyAsync(c->d_buf[kNalIn], nal, n, hipMemcpyHostToDevice, c->stream));
+  Stage st{c};
+  auto *d_in_off = st.put(kNalInOff, size_t(n_seg) + 1, nal_offsets);
+  auto *d_in = st.put(kNalIn, n, nal);
+  auto *d_out = st.room<uint8_t>(kNalOut, cap);
+  auto *d_out_off = st.room<uint64_t>(kNalOutOff, size_t(n_seg) + 1);
+  auto *d_loc = st.room<uint32_t>(kNalLoc, loc_cap);
+  auto *d_status = st.room<cabac_nal_status>(kNalStatus, 1);
+  if (st.rc) return st.rc;
   // (loc_capacity as the caller gave it: CABAC_NAL_LOC_OVERFLOW is judged against that; no more than loc_cap can occur)
-  rc = cabac_hip_nal_unescape_device(c, n_seg, (const uint64_t *)c->d_buf[kNalInOff], (const uint8_t *)c->d_buf[kNalIn], n,
-                                     (uint8_t *)c->d_buf[kNalOut], cap, (uint64_t *)c->d_buf[kNalOutOff],
-                                     locations ? (uint32_t *)c->d_buf[kNalLoc] : nullptr, locations ? loc_capacity : 0, loc_base,
-                                     d_status);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(status, d_status, sizeof(cabac_nal_status), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(offsets, c->d_buf[kNalOutOff], off_bytes, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = cabac_hip_nal_unescape_device(c, n_seg, d_in_off, d_in, n, d_out, cap, d_out_off, locations ? d_loc : nullptr,
+                                          locations ? loc_capacity : 0, loc_base, d_status)))
+    return rc;
+  HIP_TRY(c, down(c, status, d_status, sizeof(cabac_nal_status)));
+  HIP_TRY(c, down(c, offsets, d_out_off, off_bytes));
   HIP_TRY(c, wait_stream(c, c->stream));
-  const uint64_t got = std::min<uint64_t>(status->out_bytes, cap), got_loc = std::min<uint64_t>(status->n_changed, loc_cap);
-  if (got) HIP_TRY(c, hipMemcpyAsync(payload, c->d_buf[kNalOut], got, hipMemcpyDeviceToHost, c->stream));
-  if (got_loc) HIP_TRY(c, hipMemcpyAsync(locations, c->d_buf[kNalLoc], got_loc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, down(c, payload, d_out, std::min<uint64_t>(status->out_bytes, cap)));
+  HIP_TRY(c, down(c, locations, d_loc, std::min<uint64_t>(status->n_changed, loc_cap) * sizeof(uint32_t)));
   HIP_TRY(c, wait_stream(c, c->stream));
   return CABAC_HIP_OK;
 }
@@ -2544,37 +2567,28 @@ int cabac_hip_encode_batch_nal(cabac_hip_ctx *c, uint32_t n_sub, const cabac_sub
   // device: the slots of cabac_hip_encode_batch, then the escape's own
   const size_t off_bytes = (size_t(n_sub) + 1) * sizeof(uint64_t), res_bytes = size_t(n_sub) * sizeof(cabac_substream_result);
   const uint64_t cap = std::min<uint64_t>(nal_capacity, cabac_hip_nal_escape_bound(slots_end));
-  if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
-  if ((rc = ensure(c, kBytes, slots_end))) return rc;
-  if ((rc = ensure(c, kResults, res_bytes))) return rc;
-  if ((rc = ensure(c, kPayload, slots_end))) return rc;
-  if ((rc = ensure(c, kPayloadOffsets, off_bytes))) return rc;
-  if ((rc = ensure(c, kNalOut, cap))) return rc;
-  if ((rc = ensure(c, kNalOutOff, off_bytes))) return rc;
-  if ((rc = ensure(c, kNalStatus, sizeof(cabac_nal_status)))) return rc;
-  auto *d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[kDesc]);
-  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[kResults]);
-  auto *d_status = static_cast<cabac_nal_status *>(c->d_buf[kNalStatus]);
-  HIP_TRY(c, hipMemcpyAsync(c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc), hipMemcpyHostToDevice, c->stream));
-  if (n_records_total) HIP_TRY(c, hipMemcpyAsync(c->d_buf[kRecords], records, n_records_total * 2, hipMemcpyHostToDevice, c->stream));
-  if ((rc = cabac_hip_encode_device(c, n_sub, d_desc, (const uint16_t *)c->d_buf[kRecords], (uint8_t *)c->d_buf[kBytes], d_res))) return rc;
-  if ((rc = cabac_hip_assemble_device(c, n_sub, d_desc, d_res, (const uint8_t *)c->d_buf[kBytes], (uint8_t *)c->d_buf[kPayload], slots_end,
-                                      (uint64_t *)c->d_buf[kPayloadOffsets])))
-    return rc;
-  if ((rc = cabac_hip_nal_escape_device(c, n_sub, (const uint64_t *)c->d_buf[kPayloadOffsets], (const uint8_t *)c->d_buf[kPayload], slots_end,
-                                        (uint8_t *)c->d_buf[kNalOut], cap, (uint64_t *)c->d_buf[kNalOutOff], d_status)))
-    return rc;
-  HIP_TRY(c, hipMemcpyAsync(status, d_status, sizeof(cabac_nal_status), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(nal_offsets, c->d_buf[kNalOutOff], off_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(results, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+  Stage st{c};
+  auto *d_desc = st.put(kDesc, n_sub, desc);
+  auto *d_rec = st.put(kRecords, n_records_total, records);
+  auto *d_slots = st.room<uint8_t>(kBytes, slots_end);
+  auto *d_res = st.room<cabac_substream_result>(kResults, n_sub);
+  auto *d_pay = st.room<uint8_t>(kPayload, slots_end);
+  auto *d_off = st.room<uint64_t>(kPayloadOffsets, size_t(n_sub) + 1);
+  auto *d_nal = st.room<uint8_t>(kNalOut, cap);
+  auto *d_nal_off = st.room<uint64_t>(kNalOutOff, size_t(n_sub) + 1);
+  auto *d_status = st.room<cabac_nal_status>(kNalStatus, 1);
+  if (st.rc) return st.rc;
+  if ((rc = cabac_hip_encode_device(c, n_sub, d_desc, d_rec, d_slots, d_res))) return rc;
+  if ((rc = cabac_hip_assemble_device(c, n_sub, d_desc, d_res, d_slots, d_pay, slots_end, d_off))) return rc;
+  if ((rc = cabac_hip_nal_escape_device(c, n_sub, d_off, d_pay, slots_end, d_nal, cap, d_nal_off, d_status))) return rc;
+  HIP_TRY(c, down(c, status, d_status, sizeof(cabac_nal_status)));
+  HIP_TRY(c, down(c, nal_offsets, d_nal_off, off_bytes));
+  HIP_TRY(c, down(c, results, d_res, res_bytes));
   HIP_TRY(c, wait_stream(c, c->stream));
   if (status->out_bytes > nal_capacity) return fail(c, CABAC_HIP_ERR_INVALID, "nal_capacity too small (status->out_bytes is the size needed)");
-  if (status->out_bytes) HIP_TRY(c, hipMemcpyAsync(nal, c->d_buf[kNalOut], status->out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, down(c, nal, d_nal, status->out_bytes));
   HIP_TRY(c, wait_stream(c, c->stream));
-  for (uint32_t s = 0; s < n_sub; s++)
-    if (results[s].flags) return fail(c, CABAC_HIP_ERR_SUBSTREAM, "substream flag set (see results[].flags)");
-  return CABAC_HIP_OK;
+  return flags_status(c, n_sub, results, results, "substream flag set (see results[].flags)");
 }
 
 // ---- search rounds (cabac_search.hip, cabac_residual_estimate.hip; declared in cabac_hip_search.h) -----------------------------
@@ -2651,55 +2665,46 @@ int check_search_plan_host(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *ca
   return CABAC_HIP_OK;
 }
 
+// what the search rounds' host-pointer forms stage beside the candidates: the groups, their out sets and the distortions (either may
+// be left out), and where the picks and their costs land
+struct SearchStage {
+  const uint32_t *group_first, *out_set;
+  const uint64_t *dist;
+  uint32_t *pick;
+  uint64_t *cost;
+};
+
 // the plan inputs staged behind what search_round_batch_impl has staged, the resolved form in the library's own buffers (the
 // record buffer sized from the bound), and the round
-int search_plan_stage_and_run(cabac_hip_ctx *c, uint32_t n_group, uint32_t n_cand, uint32_t n_tu, int coeff_bytes, const HostPlan &hp,
-                              uint64_t record_bound, bool has_out_set, bool has_dist, uint64_t lambda_q16, uint64_t *d_bits,
-                              uint64_t *d_tu_bits, uint32_t *d_info) {
-  int rc;
-  const size_t at_bytes = size_t(n_tu) * sizeof(uint32_t), ent_bytes = (size_t(n_cand) + 1) * sizeof(uint64_t);
-  const size_t plan_bytes = size_t(hp.n_entries_total) * 2 * sizeof(uint32_t), value_bytes = size_t(hp.n_entries_total) * sizeof(uint32_t);
-  if ((rc = ensure(c, kElemPlan, plan_bytes))) return rc;
-  if ((rc = ensure(c, kElemValues, value_bytes))) return rc;
-  if ((rc = ensure(c, kUnitTuAt, at_bytes))) return rc;
-  if ((rc = ensure(c, kElemGuard, at_bytes))) return rc;
-  if ((rc = ensure(c, kPsEnt, ent_bytes))) return rc;
-  if ((rc = ensure(c, kPsFlags, size_t(n_cand ? n_cand : 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kSearchInRecords, size_t(record_bound) * sizeof(uint16_t)))) return rc;
-  if ((rc = ensure(c, kSearchInRecFirst, ent_bytes))) return rc;
-  if ((rc = ensure(c, kSearchInTuAt, at_bytes))) return rc;
-  if ((rc = ensure(c, kPwTu, size_t(n_tu ? n_tu : 1) * sizeof(cabac_tu_desc)))) return rc;
-  HIP_TRY(c, up(c, c->d_buf[kElemPlan], hp.plan, plan_bytes));
-  HIP_TRY(c, up(c, c->d_buf[kElemValues], hp.values_in, value_bytes));
-  HIP_TRY(c, up(c, c->d_buf[kPsEnt], hp.ent_first, ent_bytes));
-  if (hp.tu_at) HIP_TRY(c, up(c, c->d_buf[kUnitTuAt], hp.tu_at, at_bytes));
-  if (hp.tu_guard) HIP_TRY(c, up(c, c->d_buf[kElemGuard], hp.tu_guard, at_bytes));
-  return cabac_hip_search_plan_round_device(
-      c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand, (const uint32_t *)c->d_buf[kEstInFirst], n_tu,
-      (const cabac_tu_desc *)c->d_buf[kEstInTu], c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState],
-      (uint8_t *)c->d_buf[kEstInRate], (const uint32_t *)c->d_buf[kEstInSet], (const uint64_t *)c->d_buf[kPsEnt],
-      (const uint32_t *)c->d_buf[kElemPlan], (const uint32_t *)c->d_buf[kElemValues],
-      hp.tu_at ? (const uint32_t *)c->d_buf[kUnitTuAt] : nullptr, hp.tu_guard ? (const uint32_t *)c->d_buf[kElemGuard] : nullptr,
-      has_out_set ? (const uint32_t *)c->d_buf[kSearchInOutSet] : nullptr, has_dist ? (const uint64_t *)c->d_buf[kSearchInDist] : nullptr,
-      lambda_q16, d_bits, (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info,
-      (uint32_t *)c->d_buf[kPsFlags], (uint64_t *)c->d_buf[kSearchInRecFirst], (uint16_t *)c->d_buf[kSearchInRecords], record_bound,
-      (uint32_t *)c->d_buf[kSearchInTuAt], (cabac_tu_desc *)c->d_buf[kPwTu], hp.values_out ? (uint32_t *)c->d_buf[kElemValues] : nullptr,
-      nullptr);
+int search_plan_stage_and_run(const CandStage &cs, const SearchStage &ss, uint32_t n_group, const HostPlan &hp, uint64_t record_bound,
+                              uint64_t lambda_q16) {
+  cabac_hip_ctx *c = cs.c;
+  const uint32_t n_cand = cs.n_cand, n_tu = cs.n_tu;
+  Stage st{c};
+  auto *d_plan = st.put(kElemPlan, size_t(hp.n_entries_total) * 2, hp.plan);
+  auto *d_values = st.put(kElemValues, hp.n_entries_total, const_cast<uint32_t *>(hp.values_in));
+  auto *d_ent = st.put(kPsEnt, size_t(n_cand) + 1, hp.ent_first);
+  auto *d_at = st.opt(kUnitTuAt, n_tu, hp.tu_at);
+  auto *d_guard = st.opt(kElemGuard, n_tu, hp.tu_guard);
+  auto *d_flags = st.room<uint32_t>(kPsFlags, n_cand ? n_cand : 1);
+  auto *d_rec = st.room<uint16_t>(kSearchInRecords, record_bound);
+  auto *d_rec_first = st.room<uint64_t>(kSearchInRecFirst, size_t(n_cand) + 1);
+  auto *d_at_out = st.room<uint32_t>(kSearchInTuAt, n_tu);
+  auto *d_tu_out = st.room<cabac_tu_desc>(kPwTu, n_tu ? n_tu : 1);
+  if (st.rc) return st.rc;
+  return cabac_hip_search_plan_round_device(c, n_group, ss.group_first, n_cand, cs.d_first, n_tu, cs.d_tu, cs.d_coeff, cs.coeff_bytes, cs.d_state,
+                                            cs.d_rate, cs.d_set, d_ent, d_plan, d_values, d_at, d_guard, ss.out_set, ss.dist, lambda_q16,
+                                            cs.d_bits, ss.pick, ss.cost, cs.d_tu_bits, cs.d_info, d_flags, d_rec_first, d_rec, record_bound,
+                                            d_at_out, d_tu_out, hp.values_out ? d_values : nullptr, nullptr);
 }
 
-// the flags and the filled values back; *status: CABAC_HIP_ERR_SUBSTREAM when a candidate has a flag
-int search_plan_fetch(cabac_hip_ctx *c, uint32_t n_cand, const HostPlan &hp, int *status) {
+// the flags and the filled values back; a candidate with a flag is the status
+int search_plan_fetch(cabac_hip_ctx *c, uint32_t n_cand, const HostPlan &hp) {
   std::vector<uint32_t> fl(n_cand);
-  if (n_cand) HIP_TRY(c, hipMemcpyAsync(fl.data(), c->d_buf[kPsFlags], size_t(n_cand) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  if (hp.values_out && hp.n_entries_total)
-    HIP_TRY(c, hipMemcpyAsync(hp.values_out, c->d_buf[kElemValues], size_t(hp.n_entries_total) * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                              c->stream));
+  HIP_TRY(c, down(c, fl.data(), c->d_buf[kPsFlags], size_t(n_cand) * sizeof(uint32_t)));
+  if (hp.values_out) HIP_TRY(c, down(c, hp.values_out, c->d_buf[kElemValues], size_t(hp.n_entries_total) * sizeof(uint32_t)));
   HIP_TRY(c, wait_stream(c, c->stream));
-  for (uint32_t k = 0; k < n_cand; k++) {
-    if (hp.flags) hp.flags[k] = fl[k];
-    if (fl[k]) *status = CABAC_HIP_ERR_SUBSTREAM;
-  }
-  return CABAC_HIP_OK;
+  return flags_status(c, n_cand, fl.data(), hp.flags, "a candidate has a flag set (see flags[])");
 }
 
 int estimate_residual_ctx_device_impl(cabac_hip_ctx *c, uint32_t n_cand, const uint32_t *d_cand_first, const cabac_tu_desc *d_tu,
@@ -2789,21 +2794,13 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
   if (!c || !group_first || !cand_first || (n_cand && (!state || !rate || !set || !frac_bits)) || (n_group && (!pick || !cost)))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   if (coeff_bytes != 4 && coeff_bytes != 2) return fail(c, CABAC_HIP_ERR_INVALID, "coeff_bytes must be 4 or 2");
-  for (uint32_t k = 0; k < n_cand; k++) {
-    if (cand_first[k] > cand_first[k + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "cand_first is not non-decreasing");
-    if (set[k] >= n_sets) return fail(c, CABAC_HIP_ERR_INVALID, "set out of range");
-  }
+  CandStage cs{c, n_cand, cand_first, tus, coeff, coeff_bytes, n_coeff_total, n_sets, set};
+  if (int bad = cs.check_lists()) return bad;
   for (uint32_t g = 0; g < n_group; g++)
     if (group_first[g] > group_first[g + 1]) return fail(c, CABAC_HIP_ERR_INVALID, "group_first is not non-decreasing");
   if (group_first[n_group] != n_cand) return fail(c, CABAC_HIP_ERR_INVALID, "group_first[n_group] must be n_cand");
-  const uint32_t n_tu = cand_first[n_cand];
-  if (n_tu && (!tus || !coeff)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
-  for (uint32_t t = cand_first[0]; t < n_tu; t++) {
-    if (tus[t].log2_width > 6 || tus[t].log2_height > 6) continue;  // flagged by the kernel, reads nothing
-    const uint64_t n = uint64_t(1) << (tus[t].log2_width + tus[t].log2_height);
-    if (tus[t].coeff_offset > n_coeff_total || n > n_coeff_total - tus[t].coeff_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "coefficients out of range");
-  }
+  if (int bad = cs.check_blocks()) return bad;
+  const uint32_t n_tu = cs.n_tu;
   if (group_out_set) {  // the in-place rule of cabac_hip_search.h
     std::vector<uint32_t> owner(n_sets, CABAC_SEARCH_NONE);  // set -> the group that writes it
     for (uint32_t g = 0; g < n_group; g++) {
@@ -2857,69 +2854,36 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
   if (n_cand == 0 && n_group == 0) return CABAC_HIP_OK;
   DeviceGuard g(c->device);
   int rc;
-  const size_t set_words = size_t(n_sets) * CABAC_NUM_CONTEXTS;
-  if ((rc = ensure(c, kEstInFirst, (size_t(n_cand) + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kEstInTu, size_t(n_tu) * sizeof(cabac_tu_desc)))) return rc;
-  if ((rc = ensure(c, kEstInCoeff, n_coeff_total * size_t(coeff_bytes)))) return rc;
-  if ((rc = ensure(c, kEstInState, set_words * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kEstInRate, set_words))) return rc;
-  if ((rc = ensure(c, kEstInSet, size_t(n_cand) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kEstOutBits, (size_t(n_cand) + n_tu) * sizeof(uint64_t)))) return rc;
-  if ((rc = ensure(c, kEstOutInfo, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kSearchInGroupFirst, (size_t(n_group) + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kSearchInOutSet, size_t(n_group) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kSearchInDist, size_t(n_cand) * sizeof(uint64_t)))) return rc;
-  if ((rc = ensure(c, kSearchOutPick, size_t(n_group) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kSearchOutCost, size_t(n_group) * sizeof(uint64_t)))) return rc;
-  uint64_t *d_bits = static_cast<uint64_t *>(c->d_buf[kEstOutBits]), *d_tu_bits = d_bits + n_cand;
-  uint32_t *d_info = static_cast<uint32_t *>(c->d_buf[kEstOutInfo]);
-  HIP_TRY(c, up(c, c->d_buf[kEstInFirst], cand_first, (size_t(n_cand) + 1) * sizeof(uint32_t)));
-  HIP_TRY(c, up(c, c->d_buf[kEstInTu], tus, size_t(n_tu) * sizeof(cabac_tu_desc)));
-  HIP_TRY(c, up(c, c->d_buf[kEstInCoeff], coeff, n_tu ? n_coeff_total * size_t(coeff_bytes) : 0));
-  HIP_TRY(c, up(c, c->d_buf[kEstInState], state, n_cand ? set_words * sizeof(uint32_t) : 0));
-  HIP_TRY(c, up(c, c->d_buf[kEstInRate], rate, n_cand ? set_words : 0));
-  HIP_TRY(c, up(c, c->d_buf[kEstInSet], set, size_t(n_cand) * sizeof(uint32_t)));
-  HIP_TRY(c, up(c, c->d_buf[kSearchInGroupFirst], group_first, (size_t(n_group) + 1) * sizeof(uint32_t)));
-  if (group_out_set) HIP_TRY(c, up(c, c->d_buf[kSearchInOutSet], group_out_set, size_t(n_group) * sizeof(uint32_t)));
-  if (dist) HIP_TRY(c, up(c, c->d_buf[kSearchInDist], dist, size_t(n_cand) * sizeof(uint64_t)));
+  Stage st{c};
+  if ((rc = cs.stage(st, state, rate, n_tu ? n_coeff_total * size_t(coeff_bytes) : 0))) return rc;
+  SearchStage ss{};
+  ss.group_first = st.put(kSearchInGroupFirst, size_t(n_group) + 1, group_first);
+  ss.out_set = st.opt(kSearchInOutSet, n_group, group_out_set);
+  ss.dist = st.opt(kSearchInDist, n_cand, dist);
+  ss.pick = st.room<uint32_t>(kSearchOutPick, n_group);
+  ss.cost = st.room<uint64_t>(kSearchOutCost, n_group);
+  const uint16_t *d_side = nullptr;
+  const uint64_t *d_rec_first = nullptr;
+  const uint32_t *d_side_at = nullptr;
   if (side) {
-    if ((rc = ensure(c, kSearchInRecords, size_t(side->n_records_total) * sizeof(uint16_t)))) return rc;
-    if ((rc = ensure(c, kSearchInRecFirst, (size_t(n_cand) + 1) * sizeof(uint64_t)))) return rc;
-    if ((rc = ensure(c, kSearchInTuAt, size_t(n_tu) * sizeof(uint32_t)))) return rc;
-    HIP_TRY(c, up(c, c->d_buf[kSearchInRecords], side->records, size_t(side->n_records_total) * sizeof(uint16_t)));
-    HIP_TRY(c, up(c, c->d_buf[kSearchInRecFirst], side->rec_first, (size_t(n_cand) + 1) * sizeof(uint64_t)));
-    if (side->tu_at) HIP_TRY(c, up(c, c->d_buf[kSearchInTuAt], side->tu_at, size_t(n_tu) * sizeof(uint32_t)));
+    d_side = st.put(kSearchInRecords, side->n_records_total, side->records);
+    d_rec_first = st.put(kSearchInRecFirst, size_t(n_cand) + 1, side->rec_first);
+    d_side_at = st.opt(kSearchInTuAt, n_tu, side->tu_at);
   }
-  if (n_tu) {  // blocks no candidate owns keep a defined value
-    HIP_TRY(c, hipMemsetAsync(d_tu_bits, 0, size_t(n_tu) * sizeof(uint64_t), c->stream));
-    HIP_TRY(c, hipMemsetAsync(d_info, 0, size_t(n_tu) * sizeof(uint32_t), c->stream));
-  }
+  if (st.rc) return st.rc;
   if (hp)
-    rc = search_plan_stage_and_run(c, n_group, n_cand, n_tu, coeff_bytes, *hp, record_bound, group_out_set != nullptr, dist != nullptr,
-                                   lambda_q16, d_bits, d_tu_bits, d_info);
+    rc = search_plan_stage_and_run(cs, ss, n_group, *hp, record_bound, lambda_q16);
   else if (side)
-    rc = cabac_hip_search_unit_round_device(
-        c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand, (const uint32_t *)c->d_buf[kEstInFirst],
-        (const cabac_tu_desc *)c->d_buf[kEstInTu], c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState],
-        (uint8_t *)c->d_buf[kEstInRate], (const uint32_t *)c->d_buf[kEstInSet], (const uint64_t *)c->d_buf[kSearchInRecFirst],
-        (const uint16_t *)c->d_buf[kSearchInRecords], side->tu_at ? (const uint32_t *)c->d_buf[kSearchInTuAt] : nullptr,
-        group_out_set ? (const uint32_t *)c->d_buf[kSearchInOutSet] : nullptr, dist ? (const uint64_t *)c->d_buf[kSearchInDist] : nullptr,
-        lambda_q16, d_bits, (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info, nullptr);
+    rc = cabac_hip_search_unit_round_device(c, n_group, ss.group_first, n_cand, cs.d_first, cs.d_tu, cs.d_coeff, coeff_bytes, cs.d_state, cs.d_rate,
+                                            cs.d_set, d_rec_first, d_side, d_side_at, ss.out_set, ss.dist, lambda_q16, cs.d_bits, ss.pick,
+                                            ss.cost, cs.d_tu_bits, cs.d_info, nullptr);
   else
-    rc = cabac_hip_search_round_device(c, n_group, (const uint32_t *)c->d_buf[kSearchInGroupFirst], n_cand,
-                                       (const uint32_t *)c->d_buf[kEstInFirst], (const cabac_tu_desc *)c->d_buf[kEstInTu],
-                                       c->d_buf[kEstInCoeff], coeff_bytes, (uint32_t *)c->d_buf[kEstInState], (uint8_t *)c->d_buf[kEstInRate],
-                                       (const uint32_t *)c->d_buf[kEstInSet],
-                                       group_out_set ? (const uint32_t *)c->d_buf[kSearchInOutSet] : nullptr,
-                                       dist ? (const uint64_t *)c->d_buf[kSearchInDist] : nullptr, lambda_q16, d_bits,
-                                       (uint32_t *)c->d_buf[kSearchOutPick], (uint64_t *)c->d_buf[kSearchOutCost], d_tu_bits, d_info);
+    rc = cabac_hip_search_round_device(c, n_group, ss.group_first, n_cand, cs.d_first, cs.d_tu, cs.d_coeff, coeff_bytes, cs.d_state, cs.d_rate,
+                                       cs.d_set, ss.out_set, ss.dist, lambda_q16, cs.d_bits, ss.pick, ss.cost, cs.d_tu_bits, cs.d_info);
   if (rc) return rc;
-  std::vector<uint32_t> info(n_tu);
-  HIP_TRY(c, down(c, frac_bits, d_bits, size_t(n_cand) * sizeof(uint64_t)));
-  if (tu_frac_bits) HIP_TRY(c, down(c, tu_frac_bits, d_tu_bits, size_t(n_tu) * sizeof(uint64_t)));
-  HIP_TRY(c, down(c, info.data(), d_info, size_t(n_tu) * sizeof(uint32_t)));
-  HIP_TRY(c, down(c, pick, c->d_buf[kSearchOutPick], size_t(n_group) * sizeof(uint32_t)));
-  HIP_TRY(c, down(c, cost, c->d_buf[kSearchOutCost], size_t(n_group) * sizeof(uint64_t)));
+  if ((rc = cs.fetch(frac_bits, tu_frac_bits))) return rc;
+  HIP_TRY(c, down(c, pick, ss.pick, size_t(n_group) * sizeof(uint32_t)));
+  HIP_TRY(c, down(c, cost, ss.cost, size_t(n_group) * sizeof(uint64_t)));
   HIP_TRY(c, wait_stream(c, c->stream));
   // the written sets: those of the groups that picked a candidate
   if (group_out_set && n_cand) {
@@ -2927,24 +2891,15 @@ static int search_round_batch_impl(cabac_hip_ctx *c, uint32_t n_group, const uin
       const uint32_t o = group_out_set[k];
       if (o == CABAC_SEARCH_NO_SET || pick[k] == CABAC_SEARCH_NONE) continue;
       const size_t at = size_t(o) * CABAC_NUM_CONTEXTS;
-      HIP_TRY(c, down(c, state + at, (const uint32_t *)c->d_buf[kEstInState] + at, CABAC_NUM_CONTEXTS * sizeof(uint32_t)));
-      HIP_TRY(c, down(c, rate + at, (const uint8_t *)c->d_buf[kEstInRate] + at, CABAC_NUM_CONTEXTS));
+      HIP_TRY(c, down(c, state + at, cs.d_state + at, CABAC_NUM_CONTEXTS * sizeof(uint32_t)));
+      HIP_TRY(c, down(c, rate + at, cs.d_rate + at, CABAC_NUM_CONTEXTS));
     }
     HIP_TRY(c, wait_stream(c, c->stream));
   }
-  int status = CABAC_HIP_OK;
-  if (hp) {  // the plan's info words: a block without records stops its candidate only where it is coded (see flags[])
-    for (uint32_t t = 0; t < n_tu && tu_info; t++) tu_info[t] = info[t];
-    if ((rc = search_plan_fetch(c, n_cand, *hp, &status))) return rc;
-    if (status) c->last_error = "a candidate has a flag set (see flags[])";
-    return status;
-  }
-  for (uint32_t t = 0; t < n_tu; t++) {
-    if (tu_info) tu_info[t] = info[t];
-    if (info[t] & (CABAC_TU_INFO_EMPTY | CABAC_TU_INFO_BAD_DESC)) status = CABAC_HIP_ERR_SUBSTREAM;
-  }
-  if (status) c->last_error = "empty block or bad descriptor (see tu_info[])";
-  return status;
+  if (!hp) return cs.info_status(tu_info, true);
+  // the plan's info words: a block without records stops its candidate only where it is coded (see flags[])
+  (void)cs.info_status(tu_info, false);
+  return search_plan_fetch(c, n_cand, *hp);
 }
 
 int cabac_hip_search_round_batch(cabac_hip_ctx *c, uint32_t n_group, const uint32_t *group_first, uint32_t n_cand,
@@ -3244,9 +3199,8 @@ int cabac_hip_search_log_view(const cabac_search_log *log, cabac_search_log_view
 // The emit on a fixed workspace (cabac_hip_workspace.h): the counters stay on the device and every launch is sized from the log's
 // capacities; the place pass hands the binariser tu_cap descriptors, the unused ones rejected, and the splice kernels count the
 // logged blocks by the device's word.
-static int search_log_encode_fixed(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
-                                   uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
-                                   uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets, const Rows *rows) {
+static int search_log_encode_fixed(cabac_search_log *log, const cabac_substream_desc *d_desc, const PayloadOut &out, uint32_t *d_bin_counts,
+                                   const cabac::CtxSets *sets, const Rows *rows) {
   cabac_hip_ctx *c = log->ctx;
   const cabac::SearchLogArrays &a = log->a;
   if (int bad = check_workspace(c, a.n_chain, a.tu_cap, rows != nullptr)) return bad;
@@ -3269,11 +3223,12 @@ static int search_log_encode_fixed(cabac_search_log *log, const cabac_substream_
   }
   Rows marked{};
   if (rows) marked = Rows{rows->n_level, rows->level_first, rows->d_sync_from, a.mark_rec, a.mark_tu};
-  if ((rc = encode_residual_device_impl(c, a.n_chain, desc2, rec, first, splices, a.tu_cap, a.tu_cap, tus, a.coeff, log->coeff_bytes,
-                                        d_payload, payload_capacity, d_payload_offsets, d_results, nullptr, d_bin_counts, sets,
-                                        rows ? &marked : nullptr, &c->d_ws->log_tu)))
+  PayloadOut no_info = out;  // (the binariser's words are per descriptor handed over, used or not)
+  no_info.d_tu_info = nullptr;
+  if ((rc = encode_residual_device_impl(c, a.n_chain, {desc2, rec, first, splices, a.tu_cap, a.tu_cap, tus, a.coeff, log->coeff_bytes}, no_info,
+                                        d_bin_counts, sets, rows ? &marked : nullptr, &c->d_ws->log_tu)))
     return rc;
-  if (d_tu_info) {  // one word per LOGGED block: the count is the device's
+  if (uint32_t *d_tu_info = out.d_tu_info) {  // one word per LOGGED block: the count is the device's
     Timed t(c, 40);
     HIP_TRY(c, cabac::launch_ws_log_info(c->stream, c->d_ws, a.tu_cap, static_cast<uint32_t *>(c->d_buf[kSpCnt]) + (a.tu_cap ? a.tu_cap : 1),
                                          d_tu_info));
@@ -3283,16 +3238,14 @@ static int search_log_encode_fixed(cabac_search_log *log, const cabac_substream_
 
 // sets / rows (may be null, not both): handed on to the spliced encode; a rows call takes the chains' marks as the hand-over pairs
 // (its d_sync_at and d_sync_splice are not read)
-static int search_log_encode_impl(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
-                                  uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
-                                  uint32_t *d_tu_info, uint32_t *d_bin_counts, const cabac::CtxSets *sets, const Rows *rows) {
+static int search_log_encode_impl(cabac_search_log *log, const cabac_substream_desc *d_desc, const PayloadOut &out, uint32_t *d_bin_counts,
+                                  const cabac::CtxSets *sets, const Rows *rows) {
   if (!log) return CABAC_HIP_ERR_INVALID;
   cabac_hip_ctx *c = log->ctx;
-  if (!d_desc || !d_payload || !d_payload_offsets || !d_results) return fail(c, CABAC_HIP_ERR_INVALID, "null");
+  if (!d_desc || !out.d_payload || !out.d_payload_offsets || !out.d_results) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   DeviceGuard g(c->device);
   const cabac::SearchLogArrays &a = log->a;
-  if (c->ws_fixed) return search_log_encode_fixed(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info,
-                                                  d_bin_counts, sets, rows);
+  if (c->ws_fixed) return search_log_encode_fixed(log, d_desc, out, d_bin_counts, sets, rows);
   if (!c->h_totals) HIP_TRY(c, pinned_alloc(c, &c->h_totals, 64, hipHostMallocDefault));
   static_assert(sizeof(cabac_search_log_counters) <= 64, "the pinned block of the ctx holds the counters");
   HIP_TRY(c, hipMemcpyAsync(c->h_totals, a.counters, sizeof(cabac_search_log_counters), hipMemcpyDeviceToHost, c->stream));
@@ -3325,15 +3278,14 @@ static int search_log_encode_impl(cabac_search_log *log, const cabac_substream_d
   }
   Rows marked{};
   if (rows) marked = Rows{rows->n_level, rows->level_first, rows->d_sync_from, a.mark_rec, a.mark_tu};
-  return encode_residual_device_impl(c, a.n_chain, desc2, rec, first, splices, n_tu, n_tu, a.tu, a.coeff, log->coeff_bytes, d_payload,
-                                     payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, sets,
-                                     rows ? &marked : nullptr);
+  return encode_residual_device_impl(c, a.n_chain, {desc2, rec, first, splices, n_tu, n_tu, a.tu, a.coeff, log->coeff_bytes}, out, d_bin_counts,
+                                     sets, rows ? &marked : nullptr);
 }
 
 int cabac_hip_search_log_encode_device(cabac_search_log *log, const cabac_substream_desc *d_desc, uint8_t *d_payload,
                                        uint64_t payload_capacity, uint64_t *d_payload_offsets, cabac_substream_result *d_results,
                                        uint32_t *d_tu_info, uint32_t *d_bin_counts) {
-  return search_log_encode_impl(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr,
+  return search_log_encode_impl(log, d_desc, {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_bin_counts, nullptr,
                                 nullptr);
 }
 
@@ -3451,49 +3403,27 @@ static int wpp_batch_impl(cabac_hip_ctx *c, bool decode, uint32_t n_sub, const c
   DeviceGuard g(c->device);
   if ((rc = pipe_init(c))) return rc;
   const size_t res_bytes = size_t(n_sub) * sizeof(cabac_substream_result);
-  if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
-  if ((rc = ensure(c, kBytes, bytes_total + 4))) return rc;
-  if ((rc = ensure(c, kResults, res_bytes))) return rc;
-  if (decode && (rc = ensure(c, kBins, n_records_total + 8))) return rc;
-  if ((rc = ensure(c, kWppFrom, size_t(n_sub) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kWppAt, size_t(n_sub) * sizeof(uint32_t)))) return rc;
   if ((rc = ensure_pinned(c, 0, res_bytes))) return rc;
-  auto *d_desc = static_cast<cabac_substream_desc *>(c->d_buf[kDesc]);
-  auto *d_rec = static_cast<uint16_t *>(c->d_buf[kRecords]);
-  auto *d_slots = static_cast<uint8_t *>(c->d_buf[kBytes]);
-  auto *d_res = static_cast<cabac_substream_result *>(c->d_buf[kResults]);
-  auto *d_bins = static_cast<uint8_t *>(c->d_buf[kBins]);
   auto *h_res = static_cast<cabac_substream_result *>(c->h_pin[0]);
-  hipStream_t st = c->stream;
-  HIP_TRY(c, wait_stream(c, st));
-  if ((rc = h2d(c, d_desc, desc, n_sub * sizeof(cabac_substream_desc), st))) return rc;
-  if ((rc = h2d(c, d_rec, records, n_records_total * 2, st))) return rc;
-  if ((rc = h2d(c, c->d_buf[kWppFrom], sync_from, size_t(n_sub) * sizeof(uint32_t), st))) return rc;
-  if ((rc = h2d(c, c->d_buf[kWppAt], sync_at, size_t(n_sub) * sizeof(uint32_t), st))) return rc;
-  if (decode) {
-    if ((rc = h2d(c, d_slots, bytes, bytes_total, st))) return rc;
-  } else {
-    HIP_TRY(c, hipMemsetAsync(d_slots, 0, bytes_total, st));  // the whole range goes back: what no substream writes stays zero
-  }
-  if ((rc = wpp_device_impl(c, decode, n_sub, d_desc, d_rec, d_slots, decode ? d_bins : nullptr, d_res, n_level, level_first,
-                            static_cast<const uint32_t *>(c->d_buf[kWppFrom]), static_cast<const uint32_t *>(c->d_buf[kWppAt]))))
+  hipStream_t stream = c->stream;
+  HIP_TRY(c, wait_stream(c, stream));
+  Stage st{c, true, stream};
+  auto *d_desc = st.put(kDesc, n_sub, desc);
+  auto *d_rec = st.put(kRecords, n_records_total, records);
+  const Rows d_rows = stage_rows(st, n_sub, Rows{n_level, level_first, sync_from, sync_at}, false);
+  // decode: the bytes go up; encode: the whole range goes back, so what no substream writes stays zero
+  auto *d_slots = static_cast<uint8_t *>(st.bytes(kBytes, bytes_total + 4, bytes, decode ? bytes_total : 0));
+  auto *d_res = st.room<cabac_substream_result>(kResults, n_sub);
+  auto *d_bins = decode ? st.room<uint8_t>(kBins, n_records_total + 8) : nullptr;
+  if (st.rc) return st.rc;
+  if (!decode) HIP_TRY(c, hipMemsetAsync(d_slots, 0, bytes_total, stream));
+  if ((rc = wpp_device_impl(c, decode, n_sub, d_desc, d_rec, d_slots, d_bins, d_res, n_level, level_first, d_rows.d_sync_from, d_rows.d_sync_at)))
     return rc;
-  HIP_TRY(c, hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, st));
-  if (decode) {
-    if ((rc = d2h(c, bins, d_bins, n_records_total, st))) return rc;
-  } else {
-    if ((rc = d2h(c, bytes, d_slots, bytes_total, st))) return rc;
-  }
+  HIP_TRY(c, hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, stream));
+  if ((rc = d2h(c, decode ? bins : bytes, decode ? d_bins : d_slots, decode ? n_records_total : bytes_total, stream))) return rc;
   if ((rc = d2h_drain(c))) return rc;
-  HIP_TRY(c, wait_stream(c, st));
-  int status = CABAC_HIP_OK;
-  for (uint32_t s = 0; s < n_sub; s++) {
-    results[s] = h_res[s];
-    if (h_res[s].flags) status = CABAC_HIP_ERR_SUBSTREAM;
-  }
-  if (status) c->last_error = "substream flag set (see results[].flags)";
-  return status;
+  HIP_TRY(c, wait_stream(c, stream));
+  return flags_status(c, n_sub, h_res, results, "substream flag set (see results[].flags)");
 }
 
 int cabac_hip_encode_wpp_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
@@ -3570,8 +3500,8 @@ int cabac_hip_plan_write_sets_device(cabac_hip_ctx *c, uint32_t n_sub, const cab
   if (!sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
-  return write_plan_device_impl(c, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, coeff_bytes,
-                                d_payload, payload_capacity, d_payload_offsets, d_results, d_values_out, d_tu_info, &sets, nullptr);
+  return write_plan_device_impl(c, n_sub, {d_desc, d_plan, d_values_in, d_tile_first, d_tu, d_tu_at, d_tu_guard}, n_tu, d_coeff, coeff_bytes,
+                                {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_values_out, &sets, nullptr);
 }
 
 // ---- the plan write in pieces (cabac_hip_plan_continue.h): the plan write's two walks over one piece of every substream's plan,
@@ -3641,8 +3571,8 @@ int cabac_hip_plan_write_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cab
                                      cabac_substream_result *d_results, uint32_t *d_values_out, uint32_t *d_tu_info, uint32_t n_level,
                                      const uint32_t *level_first, const uint32_t *d_sync_from, const uint32_t *d_sync_at) {
   const Rows rows{n_level, level_first, d_sync_from, d_sync_at};
-  return write_plan_device_impl(c, n_sub, d_desc, d_plan, d_values_in, d_tile_first, n_tu, d_tu, d_tu_at, d_tu_guard, d_coeff, coeff_bytes,
-                                d_payload, payload_capacity, d_payload_offsets, d_results, d_values_out, d_tu_info, nullptr, &rows);
+  return write_plan_device_impl(c, n_sub, {d_desc, d_plan, d_values_in, d_tile_first, d_tu, d_tu_at, d_tu_guard}, n_tu, d_coeff, coeff_bytes,
+                                {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_values_out, nullptr, &rows);
 }
 
 int cabac_hip_plan_write_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint32_t *plan,
@@ -3668,8 +3598,8 @@ int cabac_hip_encode_residual_sets_device(cabac_hip_ctx *c, uint32_t n_sub, cons
   if (!sets_args_ok(n_sub, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
     return fail(c, CABAC_HIP_ERR_INVALID, "null");
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
-  return encode_residual_device_impl(c, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes,
-                                     d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, &sets, nullptr);
+  return encode_residual_device_impl(c, n_sub, {d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes},
+                                     {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_bin_counts, &sets, nullptr);
 }
 
 int cabac_hip_encode_residual_rows_device(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *d_desc, const uint16_t *d_records,
@@ -3679,8 +3609,8 @@ int cabac_hip_encode_residual_rows_device(cabac_hip_ctx *c, uint32_t n_sub, cons
                                           uint32_t *d_tu_info, uint32_t *d_bin_counts, uint32_t n_level, const uint32_t *level_first,
                                           const uint32_t *d_sync_from, const uint32_t *d_sync_at, const uint32_t *d_sync_splice) {
   const Rows rows{n_level, level_first, d_sync_from, d_sync_at, d_sync_splice};
-  return encode_residual_device_impl(c, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes,
-                                     d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr, &rows);
+  return encode_residual_device_impl(c, n_sub, {d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes},
+                                     {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_bin_counts, nullptr, &rows);
 }
 
 int cabac_hip_encode_residual_rows_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_substream_desc *desc, const uint16_t *records,
@@ -3717,7 +3647,7 @@ int cabac_hip_search_log_encode_sets_device(cabac_search_log *log, const cabac_s
   if (!sets_args_ok(log->a.n_chain, n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate))
     return fail(log->ctx, CABAC_HIP_ERR_INVALID, "null");
   const cabac::CtxSets sets{n_sets, d_state, d_rate, d_start_set, d_out_set, d_out_state, d_out_rate};
-  return search_log_encode_impl(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, &sets,
+  return search_log_encode_impl(log, d_desc, {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_bin_counts, &sets,
                                 nullptr);
 }
 
@@ -3729,7 +3659,7 @@ int cabac_hip_search_log_encode_rows_device(cabac_search_log *log, const cabac_s
   if (!d_sync_from) return fail(log->ctx, CABAC_HIP_ERR_INVALID, "null");
   if (int bad = check_levels(log->ctx, log->a.n_chain, n_level, level_first)) return bad;  // before the first wait
   const Rows rows{n_level, level_first, d_sync_from, nullptr, nullptr};
-  return search_log_encode_impl(log, d_desc, d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr,
+  return search_log_encode_impl(log, d_desc, {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_bin_counts, nullptr,
                                 &rows);
 }
 
@@ -3801,25 +3731,25 @@ int cabac_hip_sparse_parse_batch(cabac_hip_ctx *c, uint32_t n_sub, const cabac_s
   int rc;
   if ((rc = st.stage(desc, bytes, bytes_total, tile_first, tus, nullptr, nullptr))) return rc;  // 16-bit blocks: cleared, nothing goes up
   const size_t first_bytes = (size_t(n_tu) + 1) * sizeof(uint32_t);
-  if ((rc = ensure(c, kSparseFirst, first_bytes)) || (rc = ensure(c, kSparseEnt, cap * sizeof(uint32_t))) ||
-      (rc = ensure(c, kSparseScratch, cabac::sparse_scratch_bytes(n_tu))) || (rc = ensure(c, kSparseStatus, sizeof(cabac_sparse_status))))
-    return rc;
+  Stage own{c};
+  auto *d_ent_first = own.room<uint32_t>(kSparseFirst, size_t(n_tu) + 1);
+  auto *d_entries = own.room<uint32_t>(kSparseEnt, cap);
+  void *d_scratch = own.bytes(kSparseScratch, cabac::sparse_scratch_bytes(n_tu), nullptr, 0);
+  auto *d_status = own.room<cabac_sparse_status>(kSparseStatus, 1);
+  if (own.rc) return own.rc;
   if ((rc = residual_parse_device_impl(c, n_sub, st.in))) return rc;
-  if ((rc = TIMED_LAUNCH(c, 42, cabac::launch_sparse_compact(c->stream, n_tu, st.in.tus, st.in.coeff, 2, n_coeff_total,
-                                                             static_cast<uint32_t *>(c->d_buf[kSparseFirst]),
-                                                             static_cast<uint32_t *>(c->d_buf[kSparseEnt]), cap,
-                                                             static_cast<cabac_sparse_status *>(c->d_buf[kSparseStatus]),
-                                                             c->d_buf[kSparseScratch]))))
+  if ((rc = TIMED_LAUNCH(c, 42, cabac::launch_sparse_compact(c->stream, n_tu, st.in.tus, st.in.coeff, 2, n_coeff_total, d_ent_first, d_entries, cap,
+                                                             d_status, d_scratch))))
     return rc;
-  HIP_TRY(c, down(c, status, c->d_buf[kSparseStatus], sizeof(cabac_sparse_status)));
-  HIP_TRY(c, down(c, ent_first, c->d_buf[kSparseFirst], first_bytes));
+  HIP_TRY(c, down(c, status, d_status, sizeof(cabac_sparse_status)));
+  HIP_TRY(c, down(c, ent_first, d_ent_first, first_bytes));
   st.blocks = false;  // the blocks stay on the device: the entries leave in their place, once their number is known
   const int flagged = st.finish(nullptr, tu_info, results);  // the first wait
   if (flagged != CABAC_HIP_OK && flagged != CABAC_HIP_ERR_SUBSTREAM) return flagged;
   if (status->n_entries > entry_capacity)
     return fail(c, CABAC_HIP_ERR_INVALID, "entry_capacity too small (status->n_entries is the size needed)");
   if (status->n_entries > cap) return fail(c, CABAC_HIP_ERR_INVALID, "more entries than coefficients: blocks overlap");
-  HIP_TRY(c, down(c, entries, c->d_buf[kSparseEnt], status->n_entries * sizeof(uint32_t)));
+  HIP_TRY(c, down(c, entries, d_entries, status->n_entries * sizeof(uint32_t)));
   HIP_TRY(c, wait_stream(c, c->stream));  // the second
   return flagged;
 }
@@ -4014,9 +3944,7 @@ int probes_batch_impl(cabac_hip_ctx *c, bool estimate, uint32_t n_sub, const cab
   if (n_sub == 0) return CABAC_HIP_OK;
   if (start_set && n_sets && (!state || !rate)) return fail(c, CABAC_HIP_ERR_INVALID, "null");
   for (uint32_t s = 0; s < n_sub; s++) {
-    if (desc[s].rec_offset > n_records_total || desc[s].n_records > n_records_total - desc[s].rec_offset)
-      return fail(c, CABAC_HIP_ERR_INVALID, "records out of range");
-    if ((desc[s].init_id & 3u) > 2u) return fail(c, CABAC_HIP_ERR_INVALID, "init_id must be 0..2");
+    if (int bad = check_records_host(c, s, desc[s], n_records_total)) return bad;
     if (start_set && start_set[s] != CABAC_CTX_NO_SET && start_set[s] >= n_sets) {
       char buf[96];
       snprintf(buf, sizeof buf, "substream %u: start set >= n_sets", s);
@@ -4026,54 +3954,37 @@ int probes_batch_impl(cabac_hip_ctx *c, bool estimate, uint32_t n_sub, const cab
   if (int bad = check_probes_host(c, n_sub, probe_first, probe_at, n_probe)) return bad;
   DeviceGuard g(c->device);
   int rc;
-  const size_t set_entries = size_t(n_sets) * CABAC_NUM_CONTEXTS, out_bytes = size_t(n_probe) * (estimate ? sizeof(uint64_t) : sizeof(uint32_t));
-  if ((rc = ensure(c, kDesc, n_sub * sizeof(cabac_substream_desc)))) return rc;
-  if ((rc = ensure(c, kRecords, n_records_total * 2))) return rc;
-  if ((rc = ensure(c, kFlags, n_sub * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kProbeFirst, (size_t(n_sub) + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kProbeAt, size_t(n_probe) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(c, kProbeOut, out_bytes))) return rc;
-  if (start_set && ((rc = ensure(c, kEstInState, set_entries * sizeof(uint32_t))) || (rc = ensure(c, kEstInRate, set_entries)) ||
-                    (rc = ensure(c, kEstInSet, n_sub * sizeof(uint32_t)))))
-    return rc;
-  HIP_TRY(c, up(c, c->d_buf[kDesc], desc, n_sub * sizeof(cabac_substream_desc)));
-  HIP_TRY(c, up(c, c->d_buf[kRecords], records, n_records_total * 2));
-  HIP_TRY(c, up(c, c->d_buf[kProbeFirst], probe_first, (size_t(n_sub) + 1) * sizeof(uint32_t)));
-  HIP_TRY(c, up(c, c->d_buf[kProbeAt], probe_at, size_t(n_probe) * sizeof(uint32_t)));
+  const size_t set_entries = size_t(n_sets) * CABAC_NUM_CONTEXTS, each = estimate ? sizeof(uint64_t) : sizeof(uint32_t);
+  Stage st{c};
+  auto *d_desc = st.put(kDesc, n_sub, desc);
+  auto *d_rec = st.put(kRecords, n_records_total, records);
+  auto *d_first = st.put(kProbeFirst, size_t(n_sub) + 1, probe_first);
+  auto *d_at = st.put(kProbeAt, n_probe, probe_at);
+  const uint32_t *d_state = nullptr, *d_set = nullptr;
+  const uint8_t *d_rate = nullptr;
   if (start_set) {
-    HIP_TRY(c, up(c, c->d_buf[kEstInState], state, set_entries * sizeof(uint32_t)));
-    HIP_TRY(c, up(c, c->d_buf[kEstInRate], rate, set_entries));
-    HIP_TRY(c, up(c, c->d_buf[kEstInSet], start_set, n_sub * sizeof(uint32_t)));
+    d_state = st.put(kEstInState, set_entries, state);
+    d_rate = st.put(kEstInRate, set_entries, rate);
+    d_set = st.put(kEstInSet, n_sub, start_set);
   }
-  auto *d_desc = static_cast<const cabac_substream_desc *>(c->d_buf[kDesc]);
-  auto *d_rec = static_cast<const uint16_t *>(c->d_buf[kRecords]);
-  auto *d_first = static_cast<const uint32_t *>(c->d_buf[kProbeFirst]), *d_at = static_cast<const uint32_t *>(c->d_buf[kProbeAt]);
-  auto *d_state = start_set ? static_cast<const uint32_t *>(c->d_buf[kEstInState]) : nullptr;
-  auto *d_rate = start_set ? static_cast<const uint8_t *>(c->d_buf[kEstInRate]) : nullptr;
-  auto *d_set = start_set ? static_cast<const uint32_t *>(c->d_buf[kEstInSet]) : nullptr;
-  auto *d_flags = static_cast<uint32_t *>(c->d_buf[kFlags]);
+  auto *d_flags = st.room<uint32_t>(kFlags, n_sub);
+  void *d_out = st.bytes(kProbeOut, size_t(n_probe) * each, nullptr, 0);
+  if (st.rc) return st.rc;
   if (estimate)
     rc = cabac_hip_estimate_probes_device(c, n_sub, d_desc, d_rec, d_first, d_at, n_probe, n_sets, d_state, d_rate, d_set,
-                                          static_cast<uint64_t *>(c->d_buf[kProbeOut]), d_flags);
+                                          static_cast<uint64_t *>(d_out), d_flags);
   else
     rc = cabac_hip_written_bits_device(c, n_sub, d_desc, d_rec, d_first, d_at, n_probe, n_sets, d_state, d_rate, d_set,
-                                       static_cast<uint32_t *>(c->d_buf[kProbeOut]), d_flags);
+                                       static_cast<uint32_t *>(d_out), d_flags);
   if (rc) return rc;
   // the values come back into the ctx's own memory first: a caller's array holds only what the list's probes own
   std::vector<uint32_t> fl(n_sub);
-  std::vector<uint8_t> vals(out_bytes);
-  HIP_TRY(c, down(c, vals.data(), c->d_buf[kProbeOut], out_bytes));
+  std::vector<uint8_t> vals(size_t(n_probe) * each);
+  HIP_TRY(c, down(c, vals.data(), d_out, vals.size()));
   HIP_TRY(c, down(c, fl.data(), d_flags, n_sub * sizeof(uint32_t)));
   HIP_TRY(c, wait_stream(c, c->stream));
-  const size_t each = estimate ? sizeof(uint64_t) : sizeof(uint32_t);
   std::memcpy(out, vals.data(), size_t(probe_first[n_sub]) * each);
-  int status = CABAC_HIP_OK;
-  for (uint32_t s = 0; s < n_sub; s++) {
-    if (flags) flags[s] = fl[s];
-    if (fl[s]) status = CABAC_HIP_ERR_SUBSTREAM;
-  }
-  if (status) c->last_error = "substream flag set (see flags[])";
-  return status;
+  return flags_status(c, n_sub, fl.data(), flags, "substream flag set (see flags[])");
 }
 }  // namespace
 
@@ -4123,8 +4034,8 @@ int cabac_hip_encode_residual_probes_device(cabac_hip_ctx *c, uint32_t n_sub, co
                                             uint32_t *d_tu_info, uint32_t *d_bin_counts, const uint32_t *d_probe_first,
                                             const uint32_t *d_probe_at, const uint32_t *d_probe_splice, uint32_t n_probe, uint32_t *d_bits) {
   const SpliceProbes probes{d_probe_first, d_probe_at, d_probe_splice, n_probe, d_bits};
-  return encode_residual_device_impl(c, n_sub, d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes,
-                                     d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info, d_bin_counts, nullptr, nullptr,
+  return encode_residual_device_impl(c, n_sub, {d_desc, d_records, d_splice_first, d_splices, n_splice, n_tu, d_tu, d_coeff, coeff_bytes},
+                                     {d_payload, payload_capacity, d_payload_offsets, d_results, d_tu_info}, d_bin_counts, nullptr, nullptr,
                                      nullptr, &probes);
 }
 
